@@ -32,6 +32,12 @@ Workloads (BASELINE.json configs):
 
 `--dry-run` (CPU, backend gloo; used by tests/test_shard.py with world size 2) runs the same sharding, planning,
 barrier and reduction code without a GPU: frames are not rendered and the line says so ("dry_run": true).
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.  `--full` adds, behind the timed
+region, what takes runs of its own: the one-frame-at-a-time rate, the per-kernel and per-stage event times with the roofline
+blocks, the CPU baseline, the device-side in-flight trace and (default workload, one GPU) the secondary c3 measurement.
+`--dump-outputs DIR` writes the image the timed path drew in its last step as DIR/image.npy (float32, h x w x 4; beyond
+64 MB a fixed, seeded sample of pixels: image_sample.npy + image_sample_pixels.npy), so that two builds can be compared.
 """
 import argparse
 import json
@@ -459,13 +465,19 @@ def main():
     ap.add_argument("--streams", type=int, default=int(os.environ.get("WS_BENCH_STREAMS", "4")),
                     help="frames in flight per GPU: one renderer (private scratch) + one HIP stream each "
                          "(the views of a batch are independent; 1 = strictly one frame at a time)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what takes runs of its own: single-stream rate, per-kernel / "
+                         "per-stage times and roofline, CPU baseline, in-flight trace, the secondary c3 block (default workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image the timed path drew in its last step to DIR/*.npy (float32; a seeded sample of "
+                         "pixels when the image is larger than 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="the default run (hd1m, one GPU) also times c3 -- the largest single-GPU configuration, where the "
+                    help="(--full) the default run (hd1m, one GPU) also times c3 -- the largest single-GPU configuration, where the "
                          "HBM fractions of the sort and K1 mean something -- for ~200 frames and reports it under "
                          "\"secondary\"; this switch leaves it out")
     ap.add_argument("--no-dist", action="store_true", help="skip the one-rank RCCL communicator at N = 1")
-    ap.add_argument("--no-inflight", action="store_true", help="skip the device-side in-flight trace behind the timed region (the 'inflight' block)")
+    ap.add_argument("--no-inflight", action="store_true", help="(--full) skip the device-side in-flight trace behind the timed region (the 'inflight' block)")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="gloo: the collectives run on host tensors (tests: several ranks sharing ONE GPU, where RCCL refuses "
                          "two ranks on a device); the rendering path is unchanged")
@@ -587,8 +599,9 @@ def main():
         else:
             bar_t.update(sync1=tb - ta, host_barrier=0.0, sync2=0.0)
 
-    if not a.dry_run:
-        # one more renderer on the default stream: the one-frame-at-a-time rate and the per-kernel times (rank 0)
+    frame = None
+    if not a.dry_run and (a.full or a.check_shard_determinism):
+        # one more renderer on the default stream: the one-frame-at-a-time rate and the per-kernel times (rank 0, --full)
         r = ws.GaussianRenderer(ctx, a.format, gpc.sh_deg, gpc.compressed)
         target1 = targets[0]
 
@@ -596,6 +609,7 @@ def main():
             r.prepare(pc, my_views[i % len(my_views)])
             r.render(pc, target_ptr=target1.data_ptr())
 
+    if not a.dry_run:
         # Building the synthetic scene keeps the host busy for seconds while the GPU idles at low clocks: bring it to
         # its steady-state clock with ~0.3 s of (untimed, uncounted) frames before the W warm-up steps.
         t_pre = time.perf_counter()
@@ -613,11 +627,13 @@ def main():
             submit(plan(i_pre, 2 * nstreams))
             i_pre += 2 * nstreams
             torch.cuda.synchronize()
-        frame(0)
-        if r.errors(reset=True)[0] & 1:
+        if frame is not None:
             frame(0)
+            if r.errors(reset=True)[0] & 1:
+                frame(0)
     if a.warmup:
         submit(plan(0, a.warmup))
+    last_target = (planned[0] + a.steps - 1) % nstreams   # the target the last timed frame is drawn into
     timed = plan(a.warmup, a.steps)
     # The timed region.  Opening bracket: every rank's device idle, then the host barrier, then device synchronize: all ranks
     # start together.  Closing bracket: THIS rank's device synchronize, the clock, then the host barrier.  A rank's interval
@@ -656,6 +672,12 @@ def main():
     if err_bits:
         raise SystemExit(f"[bench] INVALID RUN: device-side error bits 0x{err_bits:x} in the timed frames (bit 0 = tile-entry "
                          "list overflow: entries were dropped; bits 1-3 = look-back time-out) -- no result line is printed")
+
+    if a.dump_outputs and rank == 0:
+        if a.dry_run:
+            print("[bench] --dump-outputs: a dry run draws no frames, nothing written", file=sys.stderr)
+        else:
+            dump_outputs(a.dump_outputs, targets[last_target])
 
     out = None
     if rank == 0:
@@ -712,7 +734,7 @@ def main():
             out["config"]["shard_determinism"] = {"views": probe, "ranks": world,
                                                   "identical": all(g == got[0] for g in got),
                                                   "distinct_images": len(set(got[0]))}
-    if rank == 0 and not a.dry_run:
+    if rank == 0 and not a.dry_run and a.full:
         analyse(a, ws, ctx, pc, gpc, r, frame, my_views, views, viewport, out, world)
         if nstreams > 1 and not a.no_inflight:
             try:
@@ -751,7 +773,8 @@ def main():
                 raise SystemExit(f"[bench] host partition INVALID: overlapping rank shares {overlap}, sum of OMP teams {omp_sum} "
                                  f"against a quota of {quota}")
     if not a.dry_run:
-        r.close()
+        if frame is not None:
+            r.close()
         batch.close()
         pc.close()
         ctx.close()
@@ -760,6 +783,25 @@ def main():
     if out is not None:
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     os.close(result_fd)
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, target):
+    """--dump-outputs: the image of the timed path's last frame, as the caller of the path receives it (the target texture),
+    in float32.  An image beyond DUMP_LIMIT_BYTES is sampled: a fixed set of pixels drawn with a seeded generator, stored with
+    their linear indices (y * width + x)."""
+    img = target.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    h, w, c = img.shape
+    pix = np.sort(np.random.default_rng(0).choice(h * w, size=min(DUMP_SAMPLE_PIXELS, h * w), replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), img.reshape(h * w, c)[pix])
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), pix.astype(np.float64))
 
 
 def inflight_trace(ws, batch, pc, plan, submit, device_sync, nstreams, frames):

@@ -11,7 +11,7 @@ print(round(j['value'],1), 'single', round(c.get('single_stream_fps',0)), 'busy'
 run() {  # name dir steps [env...] -- [args...]
   local N=$1 D=$2 S=$3; shift 3
   local envs=(); while [[ $# -gt 0 && $1 != -- ]]; do envs+=("$1"); shift; done; shift
-  ( cd $D && env "${envs[@]}" timeout 300 python bench.py --gpus 1 --steps $S --warmup $([[ $S == 20 ]] && echo 5 || echo 50) --no-secondary --no-cpu-baseline "$@" ) > $OUT/${N}_$S.json 2> $OUT/${N}_$S.err
+  ( cd $D && env "${envs[@]}" timeout 300 python bench.py --full --gpus 1 --steps $S --warmup $([[ $S == 20 ]] && echo 5 || echo 50) --no-secondary --no-cpu-baseline "$@" ) > $OUT/${N}_$S.json 2> $OUT/${N}_$S.err
   echo "$N steps$S: $(val $OUT/${N}_$S.json)" >> $OUT/summary.txt
 }
 for k in 1 2 3; do

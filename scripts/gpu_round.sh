@@ -30,7 +30,7 @@ if [[ $WHAT == *valu* ]]; then
   cp $OUT/valu_$WORKLOAD.json profiles/valu_$WORKLOAD.json 2>/dev/null  # bench.py reads it
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 900 python bench.py --steps $STEPS --warmup 20 --workload $WORKLOAD > $OUT/bench_$WORKLOAD.json 2> $OUT/bench_$WORKLOAD.err; echo "bench exit=$?" >> $OUT/summary.txt
+  timeout 900 python bench.py --full --steps $STEPS --warmup 20 --workload $WORKLOAD > $OUT/bench_$WORKLOAD.json 2> $OUT/bench_$WORKLOAD.err; echo "bench exit=$?" >> $OUT/summary.txt
 fi
 if [[ $WHAT == *prof* ]]; then
   rm -rf $OUT/prof_$WORKLOAD

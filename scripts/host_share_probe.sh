@@ -37,7 +37,7 @@ echo "mine: $MINE" >> $R
 one() {  # label, prefix command..., env via ENVV
   local label=$1; shift
   local line
-  line=$(env ${ENVV:-} "$@" python bench.py --steps ${STEPS:-1000} --warmup 50 --no-cpu-baseline --no-secondary ${BARGS:-} 2> $OUT/host_$label.err | tail -1)
+  line=$(env ${ENVV:-} "$@" python bench.py --full --steps ${STEPS:-1000} --warmup 50 --no-cpu-baseline --no-secondary ${BARGS:-} 2> $OUT/host_$label.err | tail -1)
   python - "$label" "$line" >> $R <<'PY'
 import json, sys
 try:

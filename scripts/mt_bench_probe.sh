@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_fullsize.py tests/test_gpu_drivers.p
 for a in "10000 800 600" "250000 800 600"; do python scripts/mt_enqueue_probe.py $a 2>/dev/null | grep "^N" >> $R; done
 for W in c1 hd1m c2; do
   for T in 0 -1 0 -1; do
-    line=$(WS_BATCH_THREADS=$T timeout 600 python bench.py --steps 2000 --warmup 50 --workload $W --no-cpu-baseline --no-secondary 2>/dev/null | tail -1)
+    line=$(WS_BATCH_THREADS=$T timeout 600 python bench.py --full --steps 2000 --warmup 50 --workload $W --no-cpu-baseline --no-secondary 2>/dev/null | tail -1)
     python -c "
 import json,sys
 try:
