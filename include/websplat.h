@@ -436,6 +436,15 @@ int ws_debug_binning_decision(uint32_t request, const uint32_t* sums, const uint
  * fourth pass is the identity (skip), and the span class the next frame's digit width is chosen by (0 unknown, 1 = < 2^24, 2 = not) */
 int ws_debug_depth_range(uint32_t key_min, uint32_t key_max, int have_keys, uint32_t digits, uint32_t* base, uint32_t* skip,
                          uint32_t* span_class);
+/* host twin of the whole fold (CPU unit test): keys[0, count) in sort tiles of tile_n keys, each tile reported by the rule the
+ * depth sort's first histogram kernels share (ws_internal.h depth_tile_reports) into slot t & 15, then depth_range_decide ->
+ * the same (base, skip, span_class) as ws_debug_depth_range gives from the keys' true min and max. */
+int ws_debug_depth_fold(const uint32_t* keys, uint32_t count, uint32_t tile_n, uint32_t digits, uint32_t* base, uint32_t* skip,
+                        uint32_t* span_class);
+/* what the device decided in the last ws_sorter_sort_depth of this sorter (syncs on that call's stream): the base of passes
+ * 1..3, whether the fourth pass was skipped, the span class.  WS_ERR_STATE when that call did not fold its key range (the
+ * context's depth_skip_top is 0, the fat-tile form ran, or the sorter's last sort was not a ws_sorter_sort_depth). */
+int ws_sorter_depth_range(ws_sorter* s, uint32_t* base, uint32_t* skip, uint32_t* span_class);
 /* tuning / analysis read-back: per tile LIST (one per binning tile, ws_renderer_binning_tile; row-major over
  * ceil(viewport / binning tile)), the length of the depth-ordered splat list and (capture mode, where the binning tile is
  * the compositing tile) how deep into it the compositing pass read: the position, counted from the near end, of the deepest
@@ -557,9 +566,12 @@ void ws_sorter_destroy(ws_sorter* s);
  * clamped to n): ascending, stable, in place in d_keys / d_payload (gpu_rs.rs:865-884). */
 int ws_sorter_sort(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, const uint32_t* d_count, uint32_t n,
                    void* stream);
-/* The same contract (record_sort / record_sort_indirect) through the kernels a frame's depth sort runs: four 8-bit
- * passes of the generic sorter -- or, in a context created with WS_DEPTH_SORT=onesweep | coop, the fat-tile one-sweep --
- * with d_aux (may be NULL), a 4-byte companion that travels with the payload.  In place.
+/* The same contract (record_sort / record_sort_indirect) through the kernels a frame's depth sort runs: the generic sorter
+ * at the context's digit width (8 or 9 bits) and 9-bit tile size, with the frame's key-range fold unless the context's
+ * depth_skip_top is 0 -- passes 1..3 sort key - base, and the fourth pass is skipped when the keys span less than three
+ * digits above the base (ws_sorter_depth_range reads the decision back) -- or, in a context created with
+ * WS_DEPTH_SORT=onesweep | coop, the fat-tile one-sweep; d_aux (may be NULL) is a 4-byte companion that travels with the
+ * payload.  In place: after three passes a copy kernel brings [0, count) back; nothing past count is touched.
  * d_keys must be 16-byte aligned (both entry points: the histogram kernels read the keys four at a time);
  * WS_ERR_INVALID otherwise. */
 int ws_sorter_sort_depth(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, uint32_t* d_aux, const uint32_t* d_count,

@@ -5,36 +5,51 @@ import os
 import numpy as np
 import pytest
 
+from depth_fold_cases import CASES, FF, FF_TILE_CASES, fold_reference, hostile_keys
 from variants import env_param, exp_param  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=["generic", "depth", "depth9", "depth9k8", exp_param("depth:onesweep", id="depth_fat_onesweep"),
-                                        exp_param("depth:coop", id="depth_fat_coop")],
-                ids=lambda p: {"generic": "reduce_scan", "depth": "depth_scan_companion", "depth9": "depth_9bit_digits",
-                               "depth9k8": "depth_9bit_digits_2048_tiles"}.get(p))
+def _context(ws, env):
+    """a context created under the WS_* switches `env` (the process environment is restored at once)"""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return ws.Context(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+@pytest.fixture(scope="module", params=["generic", "depth", "depth_noskip", "depth9", "depth9k8",
+                                        exp_param("depth:onesweep", id="depth_fat_onesweep"), exp_param("depth:coop", id="depth_fat_coop")],
+                ids=lambda p: {"generic": "reduce_scan", "depth": "depth_scan_companion", "depth_noskip": "depth_noskip",
+                               "depth9": "depth_9bit_digits", "depth9k8": "depth_9bit_digits_2048_tiles"}.get(p))
 def sort_ctx(ws, request):
     """Four paths to the same contract: the generic sorter (per-tile histograms -> column scan -> scatter), and the
-    renderer's depth sorts behind ws_sorter_sort_depth -- the generic sorter carrying a companion value, and the fat-tile
-    one-sweep (round 4) as per-pass launches and as ONE launch with device-wide barriers (WS_DEPTH_SORT selects; inputs
-    beyond the fat form's 2 M pairs take the generic sorter)."""
+    renderer's depth sorts behind ws_sorter_sort_depth -- the generic sorter carrying a companion value in the frame's form
+    (the key-range fold: passes 1..3 over key - base, the fourth skipped on a narrow range) at 8 and 9 bits, and with the fold
+    off (WS_DEPTH_SKIP_TOP=0: four plain passes); and the fat-tile one-sweep (round 4) as per-pass launches and as ONE launch
+    with device-wide barriers (WS_DEPTH_SORT selects; inputs beyond the fat form's 2 M pairs take the generic sorter)."""
     depth = request.param != "generic"
-    env = {"WS_DEPTH_DIGIT_BITS": "8", "WS_DEPTH_TILE_KPT": "0"}
+    env = {"WS_DEPTH_DIGIT_BITS": "8", "WS_DEPTH_TILE_KPT": "0", "WS_DEPTH_SKIP_TOP": "1"}
     if depth and ":" in request.param:
         env["WS_DEPTH_SORT"] = request.param.split(":")[1]
+    if request.param == "depth_noskip":
+        env["WS_DEPTH_SKIP_TOP"] = "0"
     if request.param.startswith("depth9"):   # round 6: 9-bit digits (k_dsort9_*), at both tile sizes
         env["WS_DEPTH_DIGIT_BITS"] = "9"
         env["WS_DEPTH_TILE_KPT"] = "8" if request.param.endswith("k8") else "4"
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    c = ws.Context(0)
+    c = _context(ws, env)
     c.depth_mode = depth
-    for k, v in old.items():
-        if v is None:
-            del os.environ[k]
-        else:
-            os.environ[k] = v
+    # the radix of the fold the sort reports (ws_sorter_depth_range); None: no fold to check -- four plain passes (depth_noskip:
+    # the read-back must refuse) or the fat-tile one-sweep (it hands only the inputs beyond its capacity to the folded sort)
+    c.fold_digits = {"depth": 256, "depth9": 512, "depth9k8": 512}.get(request.param)
+    c.fold_absent = request.param == "depth_noskip"
     yield c
     c.close()
 
@@ -46,19 +61,23 @@ def test_sort_known_answer(sort_ctx):
 
 def _check(ws, ctx, oracle, keys, count=None):
     n = len(keys)
+    m = n if count is None else min(count, n)
     sorter = ws.GPURSSorter(ctx, max(n, 1))
     try:
         if getattr(ctx, "depth_mode", False):  # a companion value rides along: must arrive with its pair
             aux_in = (np.arange(n, dtype=np.uint32) * np.uint32(2654435761)) ^ np.uint32(0x5BD1E995)
             k, p, ax = sorter.sort_host(keys, np.arange(n, dtype=np.uint32), count=count, depth=True, aux=aux_in)
-            mm = n if count is None else min(count, n)
-            assert np.array_equal(ax[:mm], aux_in[p[:mm]]), "companion values separated from their pairs"
-            assert np.array_equal(ax[mm:], aux_in[mm:])
+            assert np.array_equal(ax[:m], aux_in[p[:m]]), "companion values separated from their pairs"
+            assert np.array_equal(ax[m:], aux_in[m:])
+            if getattr(ctx, "fold_digits", None):  # what the device decided from keys[:count]: base, skip, span class
+                assert sorter.depth_range() == fold_reference(keys[:m], ctx.fold_digits), "key-range fold differs from the reference"
+            elif getattr(ctx, "fold_absent", False):
+                with pytest.raises(ws.WebSplatError):
+                    sorter.depth_range()
         else:
             k, p = sorter.sort_host(keys, np.arange(n, dtype=np.uint32), count=count)
     finally:
         sorter.close()
-    m = n if count is None else min(count, n)
     ok, op = oracle.sort_pairs(keys[:m], np.arange(m, dtype=np.uint32))
     assert np.array_equal(k[:m], ok), "keys differ from the stable reference sort"
     assert np.array_equal(p[:m], op), "payload differs (stability or permutation broken)"
@@ -136,7 +155,8 @@ def test_sort_large_sortedness(ws, sort_ctx):
 def test_depth_sort_key_ranges(ws, oracle, nbits, digit_bits, monkeypatch):
     """Keys confined to a range of nbits bits that starts anywhere (a frame's depth keys are: bits of zfar - z), from a
     single value to the full 32 bits: passes whose digit is the same for every key are the degenerate case of every
-    histogram and scan in the sorter."""
+    histogram and scan in the sorter.  The sort folds the key range as a frame's does; the decision it reports shows the rows
+    up to 24 (8-bit) / 27 (9-bit) bits above the base sorted by three passes, the others by four."""
     n = 300_001
     rng = np.random.default_rng(1000 + nbits)
     span = (1 << nbits) - 1 if nbits else 0
@@ -149,8 +169,65 @@ def test_depth_sort_key_ranges(ws, oracle, nbits, digit_bits, monkeypatch):
     sorter = ws.GPURSSorter(ctx, n)
     try:
         k, p = sorter.sort_host(keys, np.arange(n, dtype=np.uint32), depth=True)
+        fold = sorter.depth_range()
     finally:
         sorter.close()
         ctx.close()
     ok, op = oracle.sort_pairs(keys, np.arange(n, dtype=np.uint32))
     assert np.array_equal(k, ok) and np.array_equal(p, op)
+    assert fold == fold_reference(keys, 1 << int(digit_bits))
+
+
+@pytest.fixture(scope="module", params=["8", "9k4", "9k8"], ids=["8bit", "9bit_1024_tiles", "9bit_2048_tiles"])
+def fold_ctx(ws, request):
+    """The renderer's folded depth sort behind ws_sorter_sort_depth: 8-bit digits, and 9-bit digits over 1024-key tiles (up to
+    SORT_SMALL_MAX keys, 2048 beyond) and 2048-key tiles."""
+    nine = request.param != "8"
+    c = _context(ws, {"WS_DEPTH_DIGIT_BITS": "9" if nine else "8", "WS_DEPTH_TILE_KPT": request.param[-1] if nine else "0",
+                      "WS_DEPTH_SKIP_TOP": "1"})
+    c.digits = 512 if nine else 256
+    yield c
+    c.close()
+
+
+SMALL_MAX = 2_097_152  # ws_internal.h SORT_SMALL_MAX: where the 8-bit form's tile (and the 9-bit form's at 4 keys per thread) grows
+FOLD_BIG = ("ff_tile_middle", "ff_tile_last", "span_below", "span_at")
+FOLD_PARAMS = ([(c, n, cm) for c in CASES for n in (8192, 12_289) for cm in ("all", "count_stale0", "count_staleff")] +
+               [(c, n, cm) for c in FOLD_BIG for n in (SMALL_MAX, SMALL_MAX + 1) for cm in ("all", "count_staleff")])
+
+
+@pytest.mark.parametrize("case,n,count_mode", FOLD_PARAMS)
+def test_depth_sort_range_fold(ws, oracle, fold_ctx, case, n, count_mode):
+    """The depth sort's key-range fold on hostile keys (tests/depth_fold_cases.py): a whole 2048-aligned tile of 0xFFFFFFFF
+    among keys that span < 2^20 (first, middle, partial last tile), scattered 0xFFFFFFFF, a maximum of 0xFFFFFFFE, only
+    0xFFFFFFFF, minima at the digit edges, max - base at radix^3 - 1 and at radix^3, NaN bit patterns -- at tile multiples and
+    at SORT_SMALL_MAX / + 1, with the count in device memory below n and stale keys of 0 / 0xFFFFFFFF past it, which must not
+    move the decision (the renderer's key buffer holds stale keys past num_visible).  (a) keys and payload are the stable
+    reference sort's, the companion stays with its pair, nothing past the count is touched; (b) the decision read back from
+    the device is the Python-integer reference's on keys[:count]; (c) so the fourth pass is skipped exactly where the reference
+    says, and there the result came through three passes and the copy back."""
+    count = n if count_mode == "all" else n - 1500
+    keys = hostile_keys(case, count, fold_ctx.digits, seed=n)
+    if count < n:
+        keys = np.concatenate([keys, np.full(n - count, 0 if count_mode == "count_stale0" else FF, dtype=np.uint32)])
+    aux_in = (np.arange(n, dtype=np.uint32) * np.uint32(2654435761)) ^ np.uint32(0x5BD1E995)
+    sorter = ws.GPURSSorter(fold_ctx, n)
+    try:
+        k, p, ax = sorter.sort_host(keys, np.arange(n, dtype=np.uint32), count=None if count_mode == "all" else count, depth=True,
+                                    aux=aux_in)
+        fold = sorter.depth_range()
+    finally:
+        sorter.close()
+    ok, op = oracle.sort_pairs(keys[:count], np.arange(count, dtype=np.uint32))
+    assert np.array_equal(k[:count], ok), "keys differ from the stable reference sort"
+    assert np.array_equal(p[:count], op), "payload differs (stability or permutation broken)"
+    assert np.array_equal(ax[:count], aux_in[p[:count]]), "companion values separated from their pairs"
+    assert np.array_equal(k[count:], keys[count:]) and np.array_equal(p[count:], np.arange(count, n, dtype=np.uint32))
+    assert np.array_equal(ax[count:], aux_in[count:])
+    want = fold_reference(keys[:count], fold_ctx.digits)
+    assert fold == want, f"device fold {fold} != reference {want}"
+    # (c) both outcomes of the skip are reached: the cases that hold a 0xFFFFFFFF or span radix^3 run four passes, the others three
+    if case in FF_TILE_CASES or case in ("ff_scattered", "all_ff", "span_at", "nan_mix"):
+        assert fold[1] == 0
+    else:
+        assert fold[1] == 1

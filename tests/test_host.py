@@ -364,8 +364,8 @@ def test_depth_sort_range_decision(ws):
     """ws_internal.h depth_range_decide through its host twin: base = min(key) with the first digit's bits cleared (the first pass runs
     before anybody knows the base), the fourth pass is the identity iff max - base < radix^3 (2^24 at 8 bits, 2^27 at 9), the span class
     the next frame's digit width follows is taken on the 8-bit base whatever the radix, no key -> nothing decided, and a frame that
-    holds a key of 0xFFFFFFFF keeps base 0 (the scatter kernels exempt that value -- also their padding key -- from the subtraction,
-    the histogram kernels do not: ADVICE r05)."""
+    holds a key of 0xFFFFFFFF keeps base 0 (every depth kernel exempts that value -- also the scatter kernels' padding key -- from
+    the subtraction: ws_internal.h depth_digit)."""
     def decide(lo, hi, digits, have=1):
         b, s, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
         assert ws.lib.ws_debug_depth_range(lo, hi, have, digits, C.byref(b), C.byref(s), C.byref(c)) == 0
@@ -382,3 +382,89 @@ def test_depth_sort_range_decision(ws):
     assert decide(0xFFFFFF00, 0xFFFFFFFE, 256) == (0xFFFFFF00, 1, 1)
     with pytest.raises(ws.WebSplatError):
         ws.check(ws.lib.ws_debug_depth_range(1, 2, 1, 300, C.byref(C.c_uint32()), C.byref(C.c_uint32()), C.byref(C.c_uint32())))
+
+
+def _fold(ws, keys, count, tile_n, digits):
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    b, s, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    kp = keys.ctypes.data_as(C.POINTER(C.c_uint32)) if keys.size else None
+    assert ws.lib.ws_debug_depth_fold(kp, count, tile_n, digits, C.byref(b), C.byref(s), C.byref(c)) == 0, ws.lib.ws_last_error()
+    return b.value, s.value, c.value
+
+
+@pytest.mark.parametrize("digits", [256, 512])
+@pytest.mark.parametrize("tile_n", [1024, 2048])
+def test_depth_fold_named_key_sets(ws, tile_n, digits):
+    """The whole fold of the depth sort's first histogram kernels through its host twin (ws_debug_depth_fold: per tile of tile_n
+    keys the report rule the kernels share, a max into slot t & 15, depth_range_decide) equals the Python-integer reference
+    taken from min and max of keys[:count].  The ff_tile cases -- a whole tile of 0xFFFFFFFF among keys that span < 2^20, at the
+    first, a middle and the partial last tile -- are the ones the old rule (a tile reported only if max(~key) != 0) decided
+    wrongly: base != 0 with a key of 0xFFFFFFFF in the frame."""
+    from depth_fold_cases import CASES, FF_TILE_CASES, fold_reference, hostile_keys
+    count = 5 * tile_n + 77
+    for name in CASES:
+        keys = hostile_keys(name, count, digits, seed=tile_n + digits, run=tile_n)
+        want = fold_reference(keys, digits)
+        assert _fold(ws, keys, count, tile_n, digits) == want, name
+        if name in FF_TILE_CASES:
+            assert want[0] == 0 and want[1] == 0 and want[2] == 2, name  # the frame keeps base 0 and runs four passes
+        # keys past the count -- the renderer's stale keys past num_visible -- do not move the decision
+        for stale in (0, 0xFFFFFFFF):
+            padded = np.concatenate([keys, np.full(tile_n + 5, stale, dtype=np.uint32)])
+            assert _fold(ws, padded, count, tile_n, digits) == want, (name, stale)
+    lo = 0x40A01234
+    band = (lo + np.arange(3 * tile_n, dtype=np.uint64) * 97 % (1 << 20)).astype(np.uint32)
+    for c in (0, 1, tile_n, tile_n + 1):  # counts at and around one tile
+        assert _fold(ws, band, c, tile_n, digits) == fold_reference(band[:c], digits), c
+        ff_last = band.copy()
+        if c:
+            ff_last[c - 1] = 0xFFFFFFFF  # tile_n + 1: a last tile of ONE key, 0xFFFFFFFF
+            assert _fold(ws, ff_last, c, tile_n, digits) == fold_reference(ff_last[:c], digits), c
+    assert _fold(ws, band, tile_n + 1, tile_n, digits)[0] == lo & ~(digits - 1)
+    ff_last = band.copy()
+    ff_last[tile_n] = 0xFFFFFFFF
+    assert _fold(ws, ff_last, tile_n + 1, tile_n, digits) == (0, 0, 2)
+    assert _fold(ws, np.zeros(0, dtype=np.uint32), 0, tile_n, digits) == (0, 0, 0)
+    assert _fold(ws, np.full(3 * tile_n, 0xFFFFFFFF, dtype=np.uint32), 3 * tile_n, tile_n, digits) == (0, 0, 0)
+
+
+def test_depth_fold_edges_of_the_decision(ws):
+    """Exact values at the edges the reference names: the minimum's low byte / low nine bits, max - base one below and at
+    digits^3, the largest key short of 0xFFFFFFFF."""
+    from depth_fold_cases import hostile_keys
+    for tile_n in (1024, 2048):
+        for digits in (256, 512):
+            f = lambda name: _fold(ws, hostile_keys(name, 3 * tile_n + 9, digits), 3 * tile_n + 9, tile_n, digits)
+            assert f("min_low_00") == (0x3F123400 & ~(digits - 1), 1, 1)
+            assert f("min_low_ff") == (0x3F123400 & ~(digits - 1), 1, 1)
+            assert f("min_low_1ff") == (0x3F1235FF & ~(digits - 1), 1, 1)
+            base = 0x20000000 + 0x12345 * digits
+            assert f("span_below") == (base, 1, 1 if digits == 256 else 2)
+            assert f("span_at") == (base, 0, 2)
+            assert f("max_fffffffe") == ((0xFFFFFFFE - (1 << 20) + 1) & ~(digits - 1), 1, 1)
+            assert f("all_ff") == (0, 0, 0)
+            assert f("ff_tile_middle") == (0, 0, 2)
+
+
+def test_depth_fold_random_key_sets(ws):
+    """Seeded property sweep: the host twin of the fold equals the Python-integer reference on a few hundred key sets -- depth-like
+    f32 bits, negative-float bits, narrow integer bands, full-range keys, NaN patterns (0x7FC00000, 0xFFC00000, 0xFFFFFFFF) and
+    runs of 0xFFFFFFFF of random length and offset -- at random counts, tile sizes and radixes."""
+    from depth_fold_cases import fold_reference, random_keys
+    rng = np.random.default_rng(20261016)
+    for it in range(400):
+        tile_n = int(rng.choice([64, 1024, 2048]))
+        digits = int(rng.choice([256, 512]))
+        count = int(rng.integers(0, 40 * tile_n))
+        keys = random_keys(rng, count)
+        assert _fold(ws, keys, count, tile_n, digits) == fold_reference(keys, digits), (it, tile_n, digits, count)
+    with pytest.raises(ws.WebSplatError):
+        ws.check(_fold_rc(ws, 0))
+    with pytest.raises(ws.WebSplatError):
+        ws.check(ws.lib.ws_debug_depth_fold(None, 0, 1024, 300, C.byref(C.c_uint32()), C.byref(C.c_uint32()), C.byref(C.c_uint32())))
+
+
+def _fold_rc(ws, tile_n):
+    k = np.zeros(4, dtype=np.uint32)
+    return ws.lib.ws_debug_depth_fold(k.ctypes.data_as(C.POINTER(C.c_uint32)), 4, tile_n, 256, C.byref(C.c_uint32()),
+                                      C.byref(C.c_uint32()), C.byref(C.c_uint32()))

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_tile_hist(const uint32_t*
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
             const uint32_t pos = base + j * SORT_THREADS + threadIdx.x;
-            if (pos < count) atomicAdd(&sh[(((k[j] - kbase) >> shift) & mask) * HIST_COPIES + copy], 1u);
+            if (pos < count) atomicAdd(&sh[depth_digit(k[j], kbase, shift, mask) * HIST_COPIES + copy], 1u);
         }
         if (!KEY16 && fold) {
             // The depth sort's first kernel reads every key anyway: it also leaves their range -- max(~key) and max(key), two
@@ -148,8 +148,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_tile_hist(const uint32_t*
                 knmin = max(knmin, s_rng[0][w]);
                 kmax = max(kmax, s_rng[1][w]);
             }
-            if (knmin) {
-                uint32_t* ts = fold->tile_sums + (t & (TILE_SUM_SLOTS - 1)) * TILE_SUM_STRIDE;
+            if (depth_tile_reports(knmin, kmax)) {  // (an all-0xFFFFFFFF tile too: ws_internal.h)
+                uint32_t* ts = depth_range_slot(fold, t);
                 atomicMax(ts + 2, knmin);
                 atomicMax(ts + 3, kmax);
             }
@@ -231,9 +231,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    // (base and skip belong to the depth sort of a frame, the CARRY instantiation: every other one compiles to what it was)
-    if (CARRY && skip && *skip) return;  // (block-uniform) a pass over a constant digit moves nothing
-    const uint32_t kbase = (CARRY && key_base) ? *key_base : 0u;
+    // (base and skip belong to the depth sort: 32-bit keys, with or without a companion.  The 16-bit instantiations -- the
+    // tile-id sort -- compile to exactly what they were without them.)
+    if (!KEY16 && skip && *skip) return;  // (block-uniform) a pass over a constant digit moves nothing
+    const uint32_t kbase = (!KEY16 && key_base) ? *key_base : 0u;
 
     const uint32_t count = device_count(d_count, n);
     // first output position of every digit: the same for all tiles of this pass
@@ -257,8 +258,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_scatter(
                              : 0xFFFFFFFFu;
     }
     // The digit of a key is taken from key - base (the subtraction sits where the digit is computed, not behind the loads:
-    // there it made every load wait for its own data).  Padding keys (0xFFFFFFFF) keep the top digit.
-    auto digit_of = [&](uint32_t k) -> uint32_t { return ((k == 0xFFFFFFFFu ? k : k - kbase) >> shift) & DMASK; };
+    // there it made every load wait for its own data).  Padding keys (0xFFFFFFFF) keep the top digit (depth_digit).
+    auto digit_of = [&](uint32_t k) -> uint32_t { return depth_digit(k, kbase, shift, DMASK); };
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
         const uint32_t pos = wave_base + j * 64;
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_dsort9_tile_hist(const uint32_
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
             const uint32_t pos = base + j * SORT_THREADS + threadIdx.x;
-            if (pos < count) atomicAdd(&sh[(((k[j] - kbase) >> shift) & (RADIX9 - 1)) * COPIES + copy], 1u);
+            if (pos < count) atomicAdd(&sh[depth_digit(k[j], kbase, shift, RADIX9 - 1) * COPIES + copy], 1u);
         }
         if (fold) {  // the frame's key range, as k_sort_tile_hist leaves it (first pass only)
             uint32_t knmin = 0u, kmax = 0u;
@@ -443,8 +444,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_dsort9_tile_hist(const uint32_
                 knmin = max(knmin, s_rng[0][w]);
                 kmax = max(kmax, s_rng[1][w]);
             }
-            if (knmin) {
-                uint32_t* ts = fold->tile_sums + (t & (TILE_SUM_SLOTS - 1)) * TILE_SUM_STRIDE;
+            if (depth_tile_reports(knmin, kmax)) {  // (an all-0xFFFFFFFF tile too: ws_internal.h)
+                uint32_t* ts = depth_range_slot(fold, t);
                 atomicMax(ts + 2, knmin);
                 atomicMax(ts + 3, kmax);
             }
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_dsort9_scatter(
         const uint32_t pos = wave_base + j * 64;
         key[j] = pos < count ? keys_in[pos] : 0xFFFFFFFFu;
     }
-    auto digit_of = [&](uint32_t k) -> uint32_t { return ((k == 0xFFFFFFFFu ? k : k - kbase) >> shift) & DMASK; };
+    auto digit_of = [&](uint32_t k) -> uint32_t { return depth_digit(k, kbase, shift, DMASK); };
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
         const uint32_t pos = wave_base + j * 64;
@@ -603,6 +604,22 @@ __global__ __launch_bounds__(SORT_THREADS) void k_dsort9_scatter(
     }
 }
 
+// The stand-alone depth sort's last step (ws_sorter_sort_depth): when the fold skipped the fourth pass, the result is where
+// pass 2 left it, in the scratch partners -- copy [0, count) back to the caller's arrays.  Nothing past count is touched.
+__global__ __launch_bounds__(SORT_THREADS) void k_dsort_copy_back(const uint32_t* __restrict__ skip, const uint32_t* __restrict__ d_count,
+                                                                 uint32_t n, const uint32_t* __restrict__ keys_src,
+                                                                 const uint32_t* __restrict__ vals_src, const uint32_t* __restrict__ aux_src,
+                                                                 uint32_t* __restrict__ keys_dst, uint32_t* __restrict__ vals_dst,
+                                                                 uint32_t* __restrict__ aux_dst) {
+    if (*skip == 0u) return;  // four passes ran: the result is in place already
+    const uint32_t count = device_count(d_count, n);
+    for (uint32_t i = blockIdx.x * SORT_THREADS + threadIdx.x; i < count; i += gridDim.x * SORT_THREADS) {
+        keys_dst[i] = keys_src[i];
+        vals_dst[i] = vals_src[i];
+        if (aux_dst) aux_dst[i] = aux_src[i];
+    }
+}
+
 template <int KPT, int BITS, bool KEY16>
 int run_passes_scan(const SortScratch& sc, uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, uint32_t* ain,
                     uint32_t* aout,
@@ -689,6 +706,17 @@ uint32_t sort_grid(uint32_t tiles) {
 }
 
 uint32_t sort_tile_size(uint32_t n) { return n <= SORT_SMALL_MAX ? SORT_THREADS * SORT_KPT_SMALL : SORT_TILE; }
+
+int launch_depth_copy_back(const uint32_t* skip, const uint32_t* d_count, uint32_t n, const uint32_t* keys_src, const uint32_t* vals_src,
+                           const uint32_t* aux_src, uint32_t* keys_dst, uint32_t* vals_dst, uint32_t* aux_dst, hipStream_t stream) {
+    if (n == 0) return WS_OK;
+    if (aux_dst && !aux_src) return fail(WS_ERR_INVALID, "sort: copy-back of a companion without its source");
+    const uint32_t blocks = sort_grid((n + SORT_THREADS - 1) / SORT_THREADS);
+    hipLaunchKernelGGL(k_dsort_copy_back, dim3(blocks), dim3(SORT_THREADS), 0, stream, skip, d_count, n, keys_src, vals_src, aux_src,
+                       keys_dst, vals_dst, aux_dst);
+    WS_HIP(hipGetLastError());
+    return WS_OK;
+}
 
 #ifdef WS_EXPERIMENTAL  // measured-and-lost variants: compiled by `make experimental` only
 #include "experimental/sort_variants_host.hip"

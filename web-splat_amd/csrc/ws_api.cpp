@@ -5,6 +5,7 @@
 // GPURSSorter + PointCloudSortStuff (gpu_rs.rs:23-175, 865-884) -> ws_sorter.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -86,13 +87,14 @@ using namespace ws;
 #define WS_DEPTH_SORT_DEFAULT DS_SCAN
 #endif
 
-// small per-sort zero arena of a stand-alone sorter: tickets, error word, digit histograms
+// small per-sort zero arena of a stand-alone sorter: tickets, error word, digit histograms, the depth sort's key-range fold
 struct SorterZero {
     uint32_t tickets[4];
     uint32_t error;
     uint32_t _pad[3];
     uint32_t hist[4 * 512];                                  // (rows of 512: 9-bit digits; 8-bit digits use the first 256)
     uint32_t fat_barrier[9 * 16];                            // single-launch depth sort: barrier state
+    FrameCounters counters;                                  // ws_sorter_sort_depth: the range report and decision (depth_range_decide)
 };
 
 struct ws_sorter {
@@ -102,6 +104,8 @@ struct ws_sorter {
     uint32_t* aux_alt = nullptr;
     SorterZero* zero = nullptr;
     uint32_t epoch = 0;
+    bool folded = false;              // the last ws_sorter_sort_depth folded the key range (ws_sorter_depth_range)
+    hipStream_t last_stream = nullptr;
 };
 
 struct ws_renderer {
@@ -564,6 +568,34 @@ int ws_debug_depth_range(uint32_t key_min, uint32_t key_max, int have_keys, uint
     if (have_keys) {  // what the sort's first histogram kernel leaves in one slot: max(~key) and max(key)
         fc.tile_sums[5 * TILE_SUM_STRIDE + 2] = ~key_min;
         fc.tile_sums[5 * TILE_SUM_STRIDE + 3] = key_max;
+    }
+    depth_range_decide(&fc, digits);
+    *base = fc.depth_key_base;
+    *skip = fc.depth_skip_top;
+    *span_class = fc.depth_span_class;
+    return WS_OK;
+}
+
+int ws_debug_depth_fold(const uint32_t* keys, uint32_t count, uint32_t tile_n, uint32_t digits, uint32_t* base, uint32_t* skip,
+                        uint32_t* span_class) {
+    if (!base || !skip || !span_class || (count && !keys) || tile_n == 0 || (digits != 256u && digits != 512u))
+        return fail(WS_ERR_INVALID, "ws_debug_depth_fold: null argument, a tile of no keys, or a radix other than 256 / 512");
+    FrameCounters fc;
+    std::memset(&fc, 0, sizeof fc);
+    // what the depth sort's first histogram kernel does per sort tile: max(~key) and max(key) over its valid keys, reported by
+    // the shared rule into slot t & 15 (k_sort_tile_hist, k_dsort9_tile_hist)
+    for (uint32_t t = 0; (uint64_t)t * tile_n < count; ++t) {
+        const uint32_t b = t * tile_n, e = (uint64_t)b + tile_n < count ? b + tile_n : count;
+        uint32_t knmin = 0u, kmax = 0u;
+        for (uint32_t i = b; i < e; ++i) {
+            knmin = std::max(knmin, ~keys[i]);
+            kmax = std::max(kmax, keys[i]);
+        }
+        if (depth_tile_reports(knmin, kmax)) {
+            uint32_t* ts = depth_range_slot(&fc, t);
+            ts[2] = std::max(ts[2], knmin);
+            ts[3] = std::max(ts[3], kmax);
+        }
     }
     depth_range_decide(&fc, digits);
     *base = fc.depth_key_base;
@@ -1840,6 +1872,7 @@ int ws_sorter_sort(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, const ui
                    void* stream_v) {
     if (!s || !d_keys || !d_payload) return fail(WS_ERR_INVALID, "ws_sorter_sort: null argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    s->folded = false;  // (the memset below clears what a ws_sorter_sort_depth decided)
     WS_HIP(hipMemsetAsync(s->zero, 0, sizeof(SorterZero), stream));
     uint32_t *ok = nullptr, *ov = nullptr;
     int rc = launch_sort_pairs(s->sc, d_keys, d_payload, d_count, n, 0, 32, false, false, stream, &ok, &ov);
@@ -1865,17 +1898,46 @@ int ws_sorter_sort_depth(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, ui
         if (s->fat.status) WS_HIP(hipMemsetAsync(s->fat.status, 0, fat_sort_status_words() * sizeof(uint64_t), stream));
         s->epoch = 1;
     }
+    s->folded = false;
+    s->last_stream = stream;
     WS_HIP(hipMemsetAsync(s->zero, 0, sizeof(SorterZero), stream));
+    const bool fat = n != 0 && s->fat.status && fat_sort_grid(n, s->ctx->num_cus, s->fat.grid_request) != 0u;
+    // the frame's form (ws_renderer_prepare): the first histogram kernel reports the key range, the column scan behind it decides
+    // the base of passes 1..3 and whether the fourth pass runs (depth_range_decide)
+    FrameCounters* skip_top = (s->ctx->depth_skip_top && !fat) ? &s->zero->counters : nullptr;
+    s->folded = skip_top != nullptr;
     if (n == 0) return WS_OK;
-    if (s->fat.status && fat_sort_grid(n, s->ctx->num_cus, s->fat.grid_request) != 0u)
+    if (fat)
         return launch_depth_sort_fat(s->fat, d_keys, d_payload, d_aux, d_count, n, false, s->ctx->depth_sort_mode == DS_COOP,
                                      s->epoch, s->ctx->num_cus, stream, nullptr);
-    uint32_t *ok = nullptr, *ov = nullptr;
+    uint32_t *ok = nullptr, *ov = nullptr, *sk = nullptr, *sv = nullptr;
     int rc = launch_sort_pairs(s->sc, d_keys, d_payload, d_count, n, 0, 32, false, false, stream, &ok, &ov, nullptr, "depth:",
-                               nullptr, 0, depth_digit_bits(s->ctx), false, d_aux, d_aux ? s->aux_alt : nullptr, nullptr, nullptr, nullptr,
-                               s->ctx->depth_tile_kpt);
+                               nullptr, 0, depth_digit_bits(s->ctx), false, d_aux, d_aux ? s->aux_alt : nullptr, skip_top, &sk, &sv,
+                               s->ctx->depth_tile_kpt ? s->ctx->depth_tile_kpt : 8);
     if (rc) return rc;
     if (ok != d_keys) return fail(WS_ERR_STATE, "ws_sorter_sort_depth: internal ping-pong parity error");
+    if (skip_top) {  // three passes when the fourth was skipped: the result is in the scratch partners -> back in place
+        if (sk != s->sc.keys_alt || sv != s->sc.vals_alt)
+            return fail(WS_ERR_STATE, "ws_sorter_sort_depth: internal ping-pong parity error (skipped pass)");
+        rc = launch_depth_copy_back(&skip_top->depth_skip_top, d_count, n, sk, sv, d_aux ? s->aux_alt : nullptr, d_keys, d_payload, d_aux,
+                                    stream);
+    }
+    return rc;
+}
+
+int ws_sorter_depth_range(ws_sorter* s, uint32_t* base, uint32_t* skip, uint32_t* span_class) {
+    if (!s || !base || !skip || !span_class) return fail(WS_ERR_INVALID, "ws_sorter_depth_range: null argument");
+    if (!s->folded)
+        return fail(WS_ERR_STATE, "ws_sorter_depth_range: the last ws_sorter_sort_depth did not fold its key range "
+                                  "(the context's depth_skip_top is 0, the fat-tile form ran, or no such call)");
+    uint32_t w[3];  // depth_skip_top, depth_key_base, depth_span_class: adjacent words of the counters' second line
+    static_assert(offsetof(FrameCounters, depth_key_base) == offsetof(FrameCounters, depth_skip_top) + 4 &&
+                      offsetof(FrameCounters, depth_span_class) == offsetof(FrameCounters, depth_skip_top) + 8,
+                  "FrameCounters layout");
+    { int rc_ = copy_d2h(w, &s->zero->counters.depth_skip_top, sizeof w, s->last_stream); if (rc_) return rc_; }
+    *skip = w[0];
+    *base = w[1];
+    *span_class = w[2];
     return WS_OK;
 }
 

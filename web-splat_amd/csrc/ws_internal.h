@@ -210,8 +210,24 @@ __host__ __device__ inline uint32_t rect_coarse(uint32_t r) {
 // `digits` = 2^b, the radix of the sort: b = 8 is the reference's shape (four passes, the fourth skipped below 2^24); b = 9
 // (round 6) is three passes over key - base whenever the frame's keys span less than 2^27 -- every frame of every BASELINE
 // workload -- with a fourth pass over bits 27..31 enqueued for the frames that do not, which leaves at once on all others.
-// A frame that holds a key of 0xFFFFFFFF (the compressed path's saturating u32(f32), bits(NaN)) keeps base = 0: the scatter
-// kernels exempt that value from the subtraction (it is also their padding key), the histogram kernels do not.
+// A frame that holds a key of 0xFFFFFFFF (the compressed path's saturating u32(f32), bits(NaN)) keeps base = 0.  Every depth
+// kernel takes its digit through depth_digit, which exempts that value from the subtraction (it is also the scatter kernels'
+// padding key), so histogram and scatter agree whatever the base; and every tile that holds a key reports, an all-0xFFFFFFFF
+// tile included (depth_tile_reports), so such a key is never missing from the fold.
+//
+// The report rule of one sort tile, shared by both pass-0 histogram kernels and the host twin (ws_debug_depth_fold): a tile
+// with at least one valid key reports (max(~key), max(key)) -- (0, 0) only for a tile without keys.  An all-0xFFFFFFFF tile
+// reports (0, 0xFFFFFFFF): it does not move the minimum, and it gives the frame mx == 0xFFFFFFFF, hence base = 0.
+__host__ __device__ inline bool depth_tile_reports(uint32_t knmin, uint32_t kmax) { return (knmin | kmax) != 0u; }
+// the slotted line tile t's report goes to (max into words [2], [3])
+__host__ __device__ inline uint32_t* depth_range_slot(FrameCounters* c, uint32_t t) {
+    return c->tile_sums + (t & (TILE_SUM_SLOTS - 1)) * TILE_SUM_STRIDE;
+}
+// The digit of a depth key in every depth-sort kernel, histogram and scatter alike: from key - base, except for 0xFFFFFFFF,
+// which keeps its own digits (the top digit of every pass).  With base == 0 -- passes 0, the tile-id sort -- it is the plain digit.
+__host__ __device__ inline uint32_t depth_digit(uint32_t k, uint32_t base, int shift, uint32_t mask) {
+    return ((k == 0xFFFFFFFFu ? k : k - base) >> shift) & mask;
+}
 __host__ __device__ inline void depth_range_decide(FrameCounters* c, uint32_t digits = 256u) {
     uint32_t not_min = 0u, mx = 0u;
 #pragma unroll
@@ -336,6 +352,11 @@ int launch_sort_pairs(const SortScratch& sc, uint32_t* keys, uint32_t* vals, con
 //     result is what pass 2 wrote: *out_keys_skipped / *out_vals_skipped (the companion values next to the payload).
 //   aux / aux_alt: a 4-byte companion value per pair travels with the payload; the result lands where
 //     the payload lands (aux for an even pass count, aux_alt for an odd one).
+// After a skip_top sort, for callers that need the result in place (ws_sorter_sort_depth): when *skip is set, copy [0, count)
+// of (keys, vals, aux) from where pass 2 left them (the scratch partners) to the caller's arrays; a no-op otherwise.  aux_dst
+// may be null (no companion).
+int launch_depth_copy_back(const uint32_t* skip, const uint32_t* d_count, uint32_t n, const uint32_t* keys_src, const uint32_t* vals_src,
+                           const uint32_t* aux_src, uint32_t* keys_dst, uint32_t* vals_dst, uint32_t* aux_dst, hipStream_t stream);
 
 // ---- single-pass tile-id sort (sort.hip) ---------------------------------------------------------------------------
 // Stable counting sort of n (16-bit tile id, value) pairs whose ids are below `bins` = 2^bits <= 2048, in TWO launches:

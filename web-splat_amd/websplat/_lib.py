@@ -178,6 +178,7 @@ SIGNATURES = {
     "ws_debug_packed_rect": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p]),
     "ws_debug_binning_decision": (C.c_int, [C.c_uint32, _u32p, _u32p, C.c_uint32, _u32p]),
     "ws_debug_depth_range": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _u32p, _u32p, _u32p]),
+    "ws_debug_depth_fold": (C.c_int, [_u32p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
     "ws_debug_footprint": (C.c_int, [_u32p, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     "ws_sync": (C.c_int, [_P, _P]),
     "ws_context_set_host_wait": (C.c_int, [_P, C.c_int]),
@@ -259,6 +260,7 @@ SIGNATURES = {
     "ws_sorter_destroy": (None, [_P]),
     "ws_sorter_sort": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "ws_sorter_sort_depth": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P]),
+    "ws_sorter_depth_range": (C.c_int, [_P, _u32p, _u32p, _u32p]),
     "ws_sort_selftest": (C.c_int, [_P, C.POINTER(C.c_int)]),
 }
 

@@ -896,6 +896,13 @@ class GPURSSorter:
                                        C.c_void_p(d_aux) if d_aux else None, C.c_void_p(d_count) if d_count else None,
                                        int(n), C.c_void_p(stream or 0)))
 
+    def depth_range(self):
+        """(base, skip, span_class) the device decided in the last sort_depth (ws_sorter_depth_range); raises when that sort did
+        not fold its key range (WS_DEPTH_SKIP_TOP=0, the fat-tile form)."""
+        b, s, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib.ws_sorter_depth_range(self.handle, C.byref(b), C.byref(s), C.byref(c)))
+        return b.value, s.value, c.value
+
     def sort_host(self, keys: np.ndarray, payload: np.ndarray, count: int = None, depth: bool = False, aux: np.ndarray = None):
         """Convenience for tests: upload, sort, download. `count` exercises the device-side count path; `depth`
         selects the depth-sort specialisation, `aux` its companion values (returned as a third array)."""
