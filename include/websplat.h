@@ -339,6 +339,33 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
  * premultiplied RGBA over `background` (the clear colour, bin/render.rs:113-116). */
 int ws_renderer_render(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
                        size_t row_pitch_bytes, void* stream);
+/* ---- Auxiliary planes: where the image is (no counterpart in the reference) ------------------------------------------
+ * All planes are f32, one value per pixel, rows of *_pitch bytes (at least 4 x viewport width, multiples of 4; 4-B aligned
+ * pointers).  z_i is the view-space depth of splat i, (view * [x, y, z, 1]).z -- the f32 value the preprocess kernel computes,
+ * positive in front of the camera.  w_i is the exact weight the FAST blend gives splat i at the pixel and T the
+ * transmittance it ends with, both including the early termination at T < 2^-14:
+ *   depth         expected depth sum(w_i z_i) / sum(w_i); 0 where nothing is drawn
+ *   median_depth  z_i of the first splat, front to back, after which T <= 0.5; 0 where T never reaches 0.5
+ *   alpha         coverage 1 - T, whatever the background; 0 where nothing is drawn
+ * depth and median_depth need the frame's z plane: ws_renderer_enable_depth(r, 1) before prepare() (K1 then also writes
+ * 4 B per visible splat).  Toggling it takes effect at the next prepare(). */
+int ws_renderer_enable_depth(ws_renderer* r, int enable);
+typedef struct ws_aux_targets {
+    float* depth;              /* device pointers; any may be NULL */
+    size_t depth_pitch;        /* bytes */
+    float* median_depth;
+    size_t median_depth_pitch;
+    float* alpha;
+    size_t alpha_pitch;
+    uint32_t reserved[4];      /* must be zero */
+} ws_aux_targets;
+/* ws_renderer_render plus the auxiliary planes.  aux == NULL, or all three pointers NULL: exactly ws_renderer_render (same
+ * launch, same bytes); the colour image is bit-identical to ws_renderer_render's in every case.  Errors: WS_ERR_STATE when
+ * depth or median_depth is asked for but the prepared frame has no z plane; WS_ERR_INVALID for a pitch below 4 x width, a
+ * pitch or pointer not 4-B aligned, or a non-zero reserved word; WS_ERR_UNSUPPORTED with any plane under
+ * WS_BLEND_TARGET_PRECISION or WS_BLEND_FAST_EXACT_CUT (not built yet: a later change), capture mode or blend timing. */
+int ws_renderer_render_aux(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
+                           size_t row_pitch_bytes, const ws_aux_targets* aux, void* stream);
 /* GaussianRenderer::num_visible_points (syncs) */
 int ws_renderer_num_visible(ws_renderer* r, uint32_t* out);
 int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out); /* syncs */
@@ -385,6 +412,9 @@ int ws_renderer_set_tile_entry_capacity(ws_renderer* r, uint64_t entries);
  * (far -> near).  Any pointer may be NULL.  capacity = number of elements each array can hold. Syncs. */
 int ws_renderer_download_frame(ws_renderer* r, uint32_t capacity, void* splats, uint32_t* keys,
                                uint32_t* src_index, uint32_t* sorted, uint32_t* num_visible);
+/* The prepared frame's z plane: V view-space depths in store order (the order of ws_renderer_download_frame's splats; z may be
+ * NULL to read num_visible only).  WS_ERR_STATE when depth was off at prepare().  Syncs. */
+int ws_renderer_download_depths(ws_renderer* r, uint32_t capacity, float* z, uint32_t* num_visible);
 /* The binning tile the LAST prepared frame used: the context's tile (ws_context_tile_size) or, when the frame's splats span
  * several tiles, 2 x 2 blocks of it -- decided per frame on the device from the tile counts K1 sums for both sizes (a pure
  * function of the frame; WS_BIN_SHIFT=0 / 1 forces it off / on; frames in capture mode always use the context's tile).

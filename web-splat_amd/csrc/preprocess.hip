@@ -532,8 +532,14 @@ __device__ __forceinline__ void k1_back_compressed(const K1Params& p, const K1Bu
 #ifndef WS_K1_MINWAVES
 #define WS_K1_MINWAVES 1
 #endif
-template <bool COMPRESSED, int FPMODE>
-__global__ __launch_bounds__(K1_THREADS, WS_K1_MINWAVES) void k_preprocess(const K1Params p, const K1Buffers b) {
+// DEPTH (ws_renderer_enable_depth): also store the splat's view-space depth camspace[2] -- the value the front end has already
+// computed -- at its store slot of the z plane, the third kernel argument `depths` of this form only (Z = float*: the other
+// forms keep their argument layout, hidden arguments included).  The blend's depth planes are built from it.
+__device__ __forceinline__ void k1_store_depth(uint32_t, float) {}
+__device__ __forceinline__ void k1_store_depth(uint32_t slot, float z, float* depths) { depths[slot] = z; }
+template <bool COMPRESSED, int FPMODE, bool DEPTH = false, typename... Z>
+__global__ __launch_bounds__(K1_THREADS, WS_K1_MINWAVES) void k_preprocess(const K1Params p, const K1Buffers b, Z... depths) {
+    static_assert(DEPTH == (sizeof...(Z) == 1), "the DEPTH form takes the z plane, the others nothing");
     WS_SETPRIO_K1();
     ws_trace_begin(b.trace);
     __shared__ uint32_t s_bid;
@@ -563,6 +569,7 @@ __global__ __launch_bounds__(K1_THREADS, WS_K1_MINWAVES) void k_preprocess(const
     Front fr[K1_ITEMS];
     bool vis[K1_ITEMS];
     uint32_t lane_rank[K1_ITEMS];
+    float zcam[DEPTH ? K1_ITEMS : 1];
 #pragma unroll
     for (int it = 0; it < K1_ITEMS; ++it) {
         // unconditional (index clamped): four position loads in flight per lane, no vmcnt drain at a branch join
@@ -574,6 +581,7 @@ __global__ __launch_bounds__(K1_THREADS, WS_K1_MINWAVES) void k_preprocess(const
         const uint32_t idx = block_base + it * K1_THREADS + tid;
         float camspace[4], pos2d[4];
         vis[it] = (idx < n) && k1_project<COMPRESSED>(p, fr[it].xyz, camspace, pos2d);
+        if (DEPTH) zcam[DEPTH ? it : 0] = camspace[2];  // (read only where vis[it]: k1_project computed it)
         const unsigned long long vmask = __ballot(vis[it]);
         lane_rank[it] = __builtin_amdgcn_mbcnt_hi((uint32_t)(vmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vmask, 0u));
         if (lane == 0) s_cnt[it][wave] = (uint32_t)__popcll(vmask);
@@ -659,6 +667,7 @@ __global__ __launch_bounds__(K1_THREADS, WS_K1_MINWAVES) void k_preprocess(const
             b.keys[slot] = so[it].key;
             b.footprints[slot] = so[it].fp;
             if (b.src_index) b.src_index[slot] = block_base + it * K1_THREADS + tid;
+            if (DEPTH) k1_store_depth(slot, zcam[DEPTH ? it : 0], depths...);
         }
     }
     // ---- the frame's footprint totals at both binning granularities (ws_internal.h bin_shift_decide) -----------------
@@ -714,17 +723,33 @@ K1Kernel k1_kernel(bool compressed, int mode) {
     if (compressed) return mode == FP_RECT_COUNT ? &k_preprocess<true, FP_RECT_COUNT> : &k_preprocess<true, FP_RECT_PACKED>;
     return mode == FP_RECT_COUNT ? &k_preprocess<false, FP_RECT_COUNT> : &k_preprocess<false, FP_RECT_PACKED>;
 }
+typedef void (*K1KernelZ)(const K1Params, const K1Buffers, float*);
+K1KernelZ k1_kernel_depth(bool compressed, int mode) {  // (nullptr: no DEPTH form for this footprint mode)
+    if (mode != FP_RECT_COUNT && mode != FP_RECT_PACKED) return nullptr;
+    if (compressed)
+        return mode == FP_RECT_COUNT ? &k_preprocess<true, FP_RECT_COUNT, true, float*> : &k_preprocess<true, FP_RECT_PACKED, true, float*>;
+    return mode == FP_RECT_COUNT ? &k_preprocess<false, FP_RECT_COUNT, true, float*> : &k_preprocess<false, FP_RECT_PACKED, true, float*>;
+}
 }  // namespace
 
-const void* preprocess_kernel_func(bool compressed, int footprint_mode) {
+const void* preprocess_kernel_func(bool compressed, int footprint_mode, bool depth) {
+    if (depth) return reinterpret_cast<const void*>(k1_kernel_depth(compressed, footprint_mode));
     return reinterpret_cast<const void*>(k1_kernel(compressed, footprint_mode));
 }
 
 uint32_t preprocess_blocks(uint32_t n) { return (n + K1_THREADS * K1_ITEMS - 1) / (K1_THREADS * K1_ITEMS); }
 
-int launch_preprocess(const K1Params& p, const K1Buffers& b, bool compressed, int footprint_mode, hipStream_t stream) {
+int launch_preprocess(const K1Params& p, const K1Buffers& b, bool compressed, int footprint_mode, hipStream_t stream,
+                      float* depths) {
     const uint32_t blocks = preprocess_blocks(p.num_points);
     if (blocks == 0) return WS_OK;
+    if (depths) {
+        const K1KernelZ k = k1_kernel_depth(compressed, footprint_mode);
+        if (!k) return fail(WS_ERR_UNSUPPORTED, "preprocess: no z plane with this footprint mode");
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(K1_THREADS), 0, stream, p, b, depths);
+        WS_HIP(hipGetLastError());
+        return WS_OK;
+    }
     hipLaunchKernelGGL(k1_kernel(compressed, footprint_mode), dim3(blocks), dim3(K1_THREADS), 0, stream, p, b);
     WS_HIP(hipGetLastError());
     return WS_OK;

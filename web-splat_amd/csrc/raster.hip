@@ -354,6 +354,20 @@ __device__ __forceinline__ void store_pixel(const BlendParams& p, uint32_t px, u
         reinterpret_cast<uint32_t*>(row)[px] = q8(r) | (q8(g) << 8) | (q8(b) << 16) | (q8(al) << 24);
     }
 }
+// The auxiliary planes of one pixel (k_blend's AUX forms; the caller has checked that the pixel lies inside the image).  The
+// plane pointers are kernel arguments: each test is uniform.
+template <int AUX>
+__device__ __forceinline__ void store_aux(const BlendAuxPlanes& a, uint32_t px, uint32_t py, float T, float dz, float wsum, float med) {
+    if (AUX == BLEND_AUX_NONE) return;
+    if (a.alpha) reinterpret_cast<float*>(reinterpret_cast<char*>(a.alpha) + (size_t)py * a.alpha_pitch)[px] = 1.0f - T;
+    if (AUX != BLEND_AUX_Z) return;
+    if (a.depth) reinterpret_cast<float*>(reinterpret_cast<char*>(a.depth) + (size_t)py * a.depth_pitch)[px] = wsum > 0.0f ? dz / wsum : 0.0f;
+    if (a.median) reinterpret_cast<float*>(reinterpret_cast<char*>(a.median) + (size_t)py * a.median_pitch)[px] = T <= 0.5f ? med : 0.0f;
+}
+// k_blend's trailing argument pack: empty (the colour image only -- the kernel-argument layout of the forms without planes,
+// hidden arguments included, stays what it is without them) or the planes
+__device__ __forceinline__ BlendAuxPlanes blend_aux_of() { return BlendAuxPlanes{}; }
+__device__ __forceinline__ BlendAuxPlanes blend_aux_of(const BlendAuxPlanes& a) { return a; }
 
 // ---- k_blend_order: the compositing workgroups in longest-list-first order --------------------------------------------------
 // The hardware starts the blend's workgroups in blockIdx order, two per CU, and a frame has ~4x (1080p) more tiles than the
@@ -527,6 +541,18 @@ __device__ __forceinline__ BlendRec blend_load_rec(const float4* s_rec, uint32_t
     r.h = *reinterpret_cast<const float4*>(base + SLOTS * 16);
     return r;
 }
+// AUX == BLEND_AUX_Z: a third plane of 16-B slots holds each staged record's view-space depth in its first word -- at the
+// record's own byte offset plus a constant, one ds_read_b32 with an immediate offset and no address arithmetic.
+template <int SLOTS, int AUX>
+__device__ __forceinline__ float blend_load_z(const float4* s_rec, uint32_t byte_off) {
+    if (AUX != BLEND_AUX_Z) return 0.0f;
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(s_rec) + byte_off + 2 * SLOTS * 16);
+}
+// The depth forms' per-pixel accumulators: sum(w z), sum(w), and the median candidate -- z of the last kept splat that found
+// T above 0.5, i.e. (T only falls) of the splat whose weight took T to 0.5 or below; the store discards it while T > 0.5.
+struct BlendAuxAcc {
+    float dz = 0.0f, wsum = 0.0f, med = 0.0f;
+};
 // EXACT (round 6, verdict r05 item 6; ws_renderer_set_blend_mode(r, WS_BLEND_FAST_EXACT_CUT)): the keep / discard decision of a
 // fragment whose a' lies within the rounding band of the cut-off is taken on the ORACLE's expression -- a = |M^-1 (pixel - centre)|^2
 // from the un-prescaled inverse, source order, a > 2 CUTOFF discards (gaussian.wgsl:60-63; oracle/ws_oracle.c wso_render) -- re-derived
@@ -562,9 +588,10 @@ __device__ __forceinline__ bool blend_exact_keep(const BlendExact& e, uint32_t l
     return a <= CUT_A;
 }
 // One (pixel, splat) pair: gaussian.wgsl:59-66 in the exp2 domain, front-to-back "over".
-template <bool EXACT = false>
+template <bool EXACT = false, int AUX = BLEND_AUX_NONE>
 __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, float ly, float& T, float& cr, float& cg,
-                                                float& cb, const BlendExact& ex = BlendExact{}, uint32_t list_off = 0u) {
+                                                float& cb, const BlendExact& ex = BlendExact{}, uint32_t list_off = 0u,
+                                                BlendAuxAcc* acc = nullptr, float z = 0.0f) {
     const float p0 = fmaf(r.g.x, lx, fmaf(r.g.y, ly, r.g.z));
     const float p1 = fmaf(r.g.w, lx, fmaf(r.h.x, ly, r.h.y));
     const float a = fmaf(p0, p0, p1 * p1);
@@ -586,6 +613,11 @@ __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, flo
         asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "+v"(cr) : "v"(wgt), "v"(r.h.z));
         asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(cg) : "v"(wgt), "v"(r.h.z));
         asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "+v"(cb) : "v"(wgt), "v"(r.h.w));
+        if (AUX == BLEND_AUX_Z) {  // the weight the colour got, the T it met: one FMA, one add, a compare and a select
+            acc->med = T > 0.5f ? z : acc->med;
+            acc->dz = fmaf(wgt, z, acc->dz);
+            acc->wsum += wgt;
+        }
         T -= wgt;
     }
 }
@@ -601,6 +633,13 @@ __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, flo
 #endif
 // entries staged per batch, at most (measured at 4x4: 256 -> blend +8 % on c2, +17 % on c3; 1024 does not leave LDS
 // for two workgroups per CU)
+// minimum waves per SIMD of the depth forms with one tile per workgroup: left to itself the compiler gives the 4x4 form 65
+// VGPRs -- one 1024-thread workgroup per CU instead of two; at 8 it fits 64 with no scratch (Auxiliary planes).
+// (The MULTI forms spill at 8 and keep the default: they run at 4K-class tile counts, where the workgroups are short.  The 4x2
+// form -- the split halves -- is held at six waves by its LDS and fits 64 VGPRs by itself.)
+#ifndef WS_BLEND_AUX_MINWAVES
+#define WS_BLEND_AUX_MINWAVES 8
+#endif
 #ifndef WS_BLEND_STAGE_MAX
 #define WS_BLEND_STAGE_MAX 512
 #endif
@@ -617,11 +656,16 @@ __device__ __forceinline__ uint32_t blend_stamp() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     return (uint32_t)t;
 }
-template <int FORMAT, int QW, int QH, bool MULTI, bool CAPTURE, bool DMA, bool TIMING = false, bool EXACT = false>
-__global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLEND_MINWAVES) void k_blend(const BlendParams p,
-                                                                                                    const uint32_t tpw_log2_arg) {
+template <int FORMAT, int QW, int QH, bool MULTI, bool CAPTURE, bool DMA, bool TIMING = false, bool EXACT = false, int AUX = BLEND_AUX_NONE,
+          typename... Aux>
+__global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX == BLEND_AUX_Z && !MULTI && QW * QH != 8) ? WS_BLEND_AUX_MINWAVES : WS_BLEND_MINWAVES)) void k_blend(const BlendParams p,
+                                                                                                    const uint32_t tpw_log2_arg,
+                                                                                                    const Aux... aux_planes) {
     static_assert(!TIMING || (!MULTI && !DMA && !CAPTURE), "the timing build instruments the production form only");
     static_assert(!EXACT || (!CAPTURE && !DMA && !TIMING), "the exact cut-off decision belongs to the production launch");
+    static_assert(AUX == BLEND_AUX_NONE || (!CAPTURE && !DMA && !TIMING && !EXACT), "the auxiliary planes belong to the FAST production launch");
+    static_assert((AUX == BLEND_AUX_NONE) == (sizeof...(Aux) == 0), "the AUX forms take the planes, the others nothing");
+    const BlendAuxPlanes ax = blend_aux_of(aux_planes...);
     uint32_t tm[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // TIMING: cycles per phase, this wave (SGPRs)
     uint32_t tm_batches = 0u, tm_real0 = 0u;
     const uint32_t tm_start = blend_stamp<TIMING>();
@@ -640,7 +684,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
     // batch is large: -DWS_BLEND_STAGE_MAX=1024 halves the per-batch barriers and still leaves LDS for two workgroups)
     constexpr int LCAP = STAGE < 512 ? STAGE : 512;
 
-    __shared__ float4 s_rec[2 * SLOTS];
+    __shared__ float4 s_rec[(AUX == BLEND_AUX_Z ? 3 : 2) * SLOTS];  // (AUX_Z: + the plane of view-space depths, blend_load_z)
     // quadrant bits of the staged records (0 = slot unused), 16 bits each, TRANSPOSED per sub-round of LCAP slots: the
     // masks of slots lane, lane + 64, lane + 128, ... sit side by side, so a wave's compaction reads all of them with one
     // or two wide LDS loads instead of one dependent load per 64 records
@@ -721,6 +765,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
                      // below, else the first staging barrier of the tile loop -- nothing reads it before)
         s_rec[STAGE] = make_float4(0.0f, 0.0f, 1.0e9f, 0.0f);
         s_rec[SLOTS + STAGE] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (AUX == BLEND_AUX_Z) s_rec[2 * SLOTS + STAGE] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
     if (MULTI) __syncthreads();
     uint32_t tm_last = tm_start;
@@ -734,13 +779,18 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
     uint32_t* my_list = s_list[wave];
 
     RawSplat raw = {{0u, 0u, 0u, 0u}, 0u};
+    float zraw = 0.0f;   // AUX_Z: the view-space depth of the staged entry, gathered with the same index as its record
     uint32_t rbuf = 0u;  // DMA: the raw buffer (slot offset 0 or STAGE) the current tile stages out of
     const uint32_t wslot = (uint32_t)wave * 64u;  // first raw slot of this wave (stager waves only)
     if (stager) {
         const uint2 r0 = MULTI ? s_range[0] : range_one;
         if (r0.y > r0.x) {  // (an empty tile must not touch the entry list)
             if (DMA) blend_gather_lds(p, blend_entry_idx<STAGE>(p, r0, r0.y, tid), s_raw4 + wslot, s_raw1 + wslot);
-            else raw = blend_fetch_raw<STAGE>(p, r0, r0.y, tid);
+            else if (AUX == BLEND_AUX_Z) {
+                const uint32_t idx0 = blend_entry_idx<STAGE>(p, r0, r0.y, tid);
+                raw = blend_gather(p, idx0);
+                zraw = ax.z[idx0];
+            } else raw = blend_fetch_raw<STAGE>(p, r0, r0.y, tid);
         }
     }
     for (uint32_t k = 0; k < tpw; ++k) {
@@ -750,12 +800,17 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
     // tile is composited.  (DMA: issued from the first staging step of this tile, behind its s_waitcnt vmcnt(0): every
     // older LDS-DMA into that buffer -- the unused prefetch of an earlier tile that saturated -- has landed by then.)
     RawSplat raw_next_tile = {{0u, 0u, 0u, 0u}, 0u};
+    float z_next_tile = 0.0f;
     uint2 range_nt = make_uint2(0u, 0u);  // non-empty: the next tile's first batch is still to be requested (DMA)
     if (MULTI && stager && k + 1u < tpw) {
         const uint2 rn = s_range[k + 1u];
         if (rn.y > rn.x) {
             if (DMA) range_nt = rn;
-            else raw_next_tile = blend_fetch_raw<STAGE>(p, rn, rn.y, tid);
+            else if (AUX == BLEND_AUX_Z) {
+                const uint32_t idxn = blend_entry_idx<STAGE>(p, rn, rn.y, tid);
+                raw_next_tile = blend_gather(p, idxn);
+                z_next_tile = ax.z[idxn];
+            } else raw_next_tile = blend_fetch_raw<STAGE>(p, rn, rn.y, tid);
         }
     }
     if (code != 0xFFFFFFFFu) {  // block-uniform
@@ -768,6 +823,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
     // per-pixel "done" flag in the inner loop: a pixel below T_MIN keeps accumulating (its contributions are
     // below T_MIN, the reference has no cut-off at all); T only decides when a wave / the tile may stop.
     float T = inside ? 1.0f : 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    BlendAuxAcc acc;  // (AUX_Z only; dead otherwise)
     const float tile_x0 = (float)(tx * TW), tile_y0 = (float)(ty * TH);
 
     uint32_t hi = range.y;
@@ -815,6 +871,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
                 mask = s.mask;
                 s_rec[tid] = make_float4(s.i00, s.i01, s.c0, s.i10);
                 s_rec[SLOTS + tid] = make_float4(s.i11, s.c1, __uint_as_float(raw.a.w), __uint_as_float(raw.w4));
+                if (AUX == BLEND_AUX_Z) reinterpret_cast<float*>(s_rec + 2 * SLOTS + tid)[0] = zraw;
             }
             s_m[((uint32_t)tid / LCAP) * LCAP + ((uint32_t)tid & 63u) * (LCAP / 64) + (((uint32_t)tid % LCAP) >> 6)] = (uint16_t)mask;
             if (fetch_nt) {
@@ -827,6 +884,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
             // v_mov, i.e. the "prefetch" waited for its own data before the barrier, one exposed round trip per batch
             if (DMA) blend_gather_lds(p, idx_next, s_raw4 + rbuf + wslot, s_raw1 + rbuf + wslot);
             else raw = blend_gather(p, idx_next);
+            if (AUX == BLEND_AUX_Z) zraw = ax.z[idx_next];
             idx_next = blend_entry_idx<STAGE>(p, range, hi_next - range.x > (uint32_t)STAGE ? hi_next - (uint32_t)STAGE : range.x, tid);
         }
         if (TIMING) {
@@ -884,17 +942,22 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
                 uint4 o = lp[0];
                 uint4 on = lp[n4 > 1u ? 1u : 0u];
                 BlendRec cur = blend_load_rec<SLOTS>(s_rec, o.x);
+                float zcur = blend_load_z<SLOTS, AUX>(s_rec, o.x);
                 for (uint32_t g = 0; g < n4; ++g) {
                     const BlendExact exact = {&p, hi, tile_x0 + lx, tile_y0 + ly, W, H};  // (EXACT only; dead code otherwise)
                     const BlendRec r1 = blend_load_rec<SLOTS>(s_rec, o.y);
-                    blend_composite<EXACT>(cur, lx, ly, T, cr, cg, cb, exact, o.x);
+                    const float z1 = blend_load_z<SLOTS, AUX>(s_rec, o.y);
+                    blend_composite<EXACT, AUX>(cur, lx, ly, T, cr, cg, cb, exact, o.x, &acc, zcur);
                     const BlendRec r2 = blend_load_rec<SLOTS>(s_rec, o.z);
-                    blend_composite<EXACT>(r1, lx, ly, T, cr, cg, cb, exact, o.y);
+                    const float z2 = blend_load_z<SLOTS, AUX>(s_rec, o.z);
+                    blend_composite<EXACT, AUX>(r1, lx, ly, T, cr, cg, cb, exact, o.y, &acc, z1);
                     const BlendRec r3 = blend_load_rec<SLOTS>(s_rec, o.w);
-                    blend_composite<EXACT>(r2, lx, ly, T, cr, cg, cb, exact, o.z);
+                    const float z3 = blend_load_z<SLOTS, AUX>(s_rec, o.w);
+                    blend_composite<EXACT, AUX>(r2, lx, ly, T, cr, cg, cb, exact, o.z, &acc, z2);
                     const uint32_t off3 = o.w;
                     cur = blend_load_rec<SLOTS>(s_rec, on.x);  // (re-reads a valid record after the last group)
-                    blend_composite<EXACT>(r3, lx, ly, T, cr, cg, cb, exact, off3);
+                    zcur = blend_load_z<SLOTS, AUX>(s_rec, on.x);
+                    blend_composite<EXACT, AUX>(r3, lx, ly, T, cr, cg, cb, exact, off3, &acc, z3);
                     // the quadrant is saturated: nothing behind can add more than T_MIN (one compare per four pairs;
                     // on dense tiles this stops the walk well inside the staged batch)
                     if ((CAPTURE && p.debug_walked) || TIMING) dbg_walked += 4u;
@@ -964,6 +1027,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
             // begin_render_pass(clear = background) then "over": dst = src + dst * (1 - src.a), all four channels
             store_pixel<FORMAT>(p, sx, sy, cr + p.background[0] * T, cg + p.background[1] * T, cb + p.background[2] * T,
                                 (1.0f - T) + p.background[3] * T);
+            store_aux<AUX>(ax, sx, sy, T, acc.dz, acc.wsum, acc.med);
         }
     }
     if (TIMING && p.debug_timing) {
@@ -1000,6 +1064,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : WS_BLE
         wg_barrier_keep_loads();  // the staging buffers are reused by the next tile
     } else {
         raw = raw_next_tile;
+        if (AUX == BLEND_AUX_Z) zraw = z_next_tile;
         __syncthreads();  // the staging buffers are reused by the next tile
     }
     }  // tiles of this workgroup
@@ -1266,7 +1331,7 @@ int launch_blend_order(const uint2* tile_ranges, const FrameCounters* counters, 
 }
 
 template <int QW, int QH>
-static int launch_blend_shape(const BlendParams& p, hipStream_t stream) {
+static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux, const BlendAuxPlanes& ap) {
     const BlendShape sh = blend_shape(QW, QH);
     uint32_t tpw_log2 = p.tpw_log2 >= 0 ? (uint32_t)p.tpw_log2 : blend_tpw_log2(p.tiles_x, p.tiles_y, sh);
     if (tpw_log2 > sh.tbx_log2 + sh.tby_log2) tpw_log2 = sh.tbx_log2 + sh.tby_log2;
@@ -1275,6 +1340,30 @@ static int launch_blend_shape(const BlendParams& p, hipStream_t stream) {
     const bool capture = p.debug_consumed != nullptr || p.debug_walked != nullptr;  // analysis build of the kernel
     // tuning knob (WS_BLEND_LDS_PAD_KB): unused dynamic LDS that lowers the number of blend workgroups per CU
     const size_t pad = (size_t)p.lds_pad_kb * 1024u;
+    if (aux != BLEND_AUX_NONE) {
+        // the auxiliary planes: the FAST production forms only -- one tile or several per workgroup, split halves (4x2 with
+        // range_row_shift), the longest-first order (p.order) -- all three colour formats
+        if (capture || p.debug_timing || p.dma || p.exact_cut || p.async_staging)
+            return fail(WS_ERR_UNSUPPORTED, "blend: auxiliary planes need the FAST production launch (no capture / timing / DMA / exact cut)");
+        if (aux != BLEND_AUX_ALPHA && aux != BLEND_AUX_Z) return fail(WS_ERR_INVALID, "blend: unknown auxiliary form");
+#define WS_LAUNCH_BLEND_AUX(FMT, AUX_)                                                                                           \
+        if (tpw_log2 > 0u)                                                                                                       \
+            hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, false, AUX_, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap);  \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, false, AUX_, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap)
+#define WS_LAUNCH_BLEND_AUX_FMT(FMT)                                                                                             \
+        if (aux == BLEND_AUX_Z) { WS_LAUNCH_BLEND_AUX(FMT, BLEND_AUX_Z); } else { WS_LAUNCH_BLEND_AUX(FMT, BLEND_AUX_ALPHA); }
+        switch (p.format) {
+            case WS_FORMAT_RGBA32_FLOAT: WS_LAUNCH_BLEND_AUX_FMT(WS_FORMAT_RGBA32_FLOAT); break;
+            case WS_FORMAT_RGBA16_FLOAT: WS_LAUNCH_BLEND_AUX_FMT(WS_FORMAT_RGBA16_FLOAT); break;
+            case WS_FORMAT_RGBA8_UNORM: WS_LAUNCH_BLEND_AUX_FMT(WS_FORMAT_RGBA8_UNORM); break;
+            default: return fail(WS_ERR_INVALID, "blend: unknown colour format");
+        }
+#undef WS_LAUNCH_BLEND_AUX_FMT
+#undef WS_LAUNCH_BLEND_AUX
+        WS_HIP(hipGetLastError());
+        return WS_OK;
+    }
     if (p.debug_timing) {  // analysis: the production form (one tile per workgroup, f32 target, 32x32) with time stamps
         if (QW != 4 || QH != 4 || p.format != WS_FORMAT_RGBA32_FLOAT || capture || tpw_log2 > 0u || p.dma)
             return fail(WS_ERR_UNSUPPORTED, "blend timing: 32x32 tiles, rgba32float target, one tile per workgroup, no capture / DMA");
@@ -1340,9 +1429,14 @@ static int launch_blend_shape(const BlendParams& p, hipStream_t stream) {
     return WS_OK;
 }
 
-int launch_blend(const BlendParams& p, int variant, hipStream_t stream) {
+int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const BlendAuxPlanes* ap) {
     const uint32_t ntiles = p.tiles_x * p.tiles_y;
     if (ntiles == 0) return WS_OK;
+    const int aux = !ap ? BLEND_AUX_NONE : ((ap->depth || ap->median) ? BLEND_AUX_Z : (ap->alpha ? BLEND_AUX_ALPHA : BLEND_AUX_NONE));
+    if (aux == BLEND_AUX_Z && !ap->z) return fail(WS_ERR_STATE, "blend: the depth planes need the frame's z plane");
+    if (aux != BLEND_AUX_NONE && variant != 0) return fail(WS_ERR_UNSUPPORTED, "blend: auxiliary planes need the FAST blend");
+    const BlendAuxPlanes no_planes = {};
+    const BlendAuxPlanes& planes = ap ? *ap : no_planes;
     if (variant == 2) {  // WS_BLEND_TARGET_PRECISION: back to front, destination rounded after every splat
         const uint32_t groups = ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
         switch (p.format) {
@@ -1383,9 +1477,9 @@ int launch_blend(const BlendParams& p, int variant, hipStream_t stream) {
 #else
     if (variant == 1) return fail(WS_ERR_UNSUPPORTED, "blend variant 1 (k_blend_q) is only in the experimental build");
 #endif
-    if (p.qw == 2u && p.qh == 2u) return launch_blend_shape<2, 2>(p, stream);
-    if (p.qw == 4u && p.qh == 2u) return launch_blend_shape<4, 2>(p, stream);
-    if (p.qw == 4u && p.qh == 4u) return launch_blend_shape<4, 4>(p, stream);
+    if (p.qw == 2u && p.qh == 2u) return launch_blend_shape<2, 2>(p, stream, aux, planes);
+    if (p.qw == 4u && p.qh == 2u) return launch_blend_shape<4, 2>(p, stream, aux, planes);
+    if (p.qw == 4u && p.qh == 4u) return launch_blend_shape<4, 4>(p, stream, aux, planes);
     return fail(WS_ERR_INVALID, "blend: unsupported tile shape");
 }
 

@@ -124,6 +124,7 @@ struct ws_renderer {
                                     // here it is per renderer so that renderers never share scratch)
     uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr;
     uint32_t* src_index = nullptr;
+    float* depths = nullptr;         // [N] view-space depth per store slot (ws_renderer_enable_depth; allocated while it is on)
     uint64_t* k1_status = nullptr;   // epoch-tagged look-back words (never re-zeroed)
     uint64_t* bin_status = nullptr;
     uint32_t* bin_offsets = nullptr;
@@ -186,6 +187,9 @@ struct ws_renderer {
 
     int blend_mode = WS_BLEND_FAST;  // ws_renderer_set_blend_mode
     bool capture = false;
+    bool depth = false;                  // ws_renderer_enable_depth: K1 writes the z plane from the next prepare() on
+    float* k1_depths = nullptr;          // the z plane the prepare() in progress writes (nullptr: depth off)
+    bool prepared_depth = false;         // the last prepared frame wrote the z plane
     uint32_t* debug_consumed = nullptr;  // [tiles], capture mode only
     uint32_t* debug_walked = nullptr;    // [tiles][17], capture mode only
     uint4* blend_order = nullptr;        // [blend_order_blocks]: the blend's tiles, longest list first (k_blend_order)
@@ -269,6 +273,9 @@ static void renderer_free_scratch(ws_renderer* r) {
     dfree(r->fat.status);
     r->fat = FatSortScratch();
     dfree(r->src_index);
+    dfree(r->depths);
+    r->k1_depths = nullptr;
+    r->prepared_depth = false;
     dfree(r->k1_status);
     dfree(r->bin_status);
     dfree(r->bin_offsets);
@@ -1084,7 +1091,7 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         if (phase == FRAME_CLEAR) return WS_OK;
         if (km) km->begin(stream, true);
         if (r->timers) WS_HIP(hipEventRecord(r->ev[0], stream));
-        if ((rc = launch_preprocess(kp, kb, pc->compressed, r->footprint_mode, stream))) return rc;
+        if ((rc = launch_preprocess(kp, kb, pc->compressed, r->footprint_mode, stream, r->k1_depths))) return rc;
         km_mark(km, pc->compressed ? "k_preprocess<compressed>" : "k_preprocess");
         if (r->timers) WS_HIP(hipEventRecord(r->ev[1], stream));
         if (km) {  // calibration interval between two kernels: the dispatch latency of a dependent launch
@@ -1284,6 +1291,10 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     r->prepared = false;
     int rc = renderer_ensure_scratch(r, pc->num_points, args->viewport[0], args->viewport[1]);
     if (rc) return rc;
+    // the z plane: 4 B per splat, allocated with the scratch (and freed with it) while depth is on
+    if (r->depth && !r->depths && (rc = dmalloc(&r->depths, (size_t)pc->num_points + 8))) return rc;
+    r->k1_depths = r->depth ? r->depths : nullptr;
+    r->prepared_depth = false;
     // the footprint word K1 leaves per splat (ws_internal.h): the packed rectangle while the viewport has at most 256
     // binning tiles per axis, the rectangle's tile count beyond that; WS_FOOTPRINT=ellipse: the ellipse's own tile count
     const int fp_mode = r->ctx->footprint == FP_ELLIPSE ? FP_ELLIPSE
@@ -1360,7 +1371,11 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     const bool use_graph = r->ctx->use_graph && stream != nullptr && !r->marks.active && !r->timers && !r->capture &&
                            cut_mode == 0;
     r->order_mode_this_frame = decide_blend_order(r, stream);
-    if (!use_graph) return enqueue_frame(r, pc, kp, kb, stream);
+    if (!use_graph) {
+        rc = enqueue_frame(r, pc, kp, kb, stream);
+        if (rc == WS_OK) r->prepared_depth = r->k1_depths != nullptr;
+        return rc;
+    }
     ws_renderer::FrameGraph& g = r->fg;
     if (!(g.valid && g.pc == pc && g.generation == r->scratch_generation && g.order_mode == r->order_mode_this_frame)) {
         renderer_free_graph(r);
@@ -1382,7 +1397,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         WS_HIP(hipGraphGetNodes(graph, nullptr, &nn));
         std::vector<hipGraphNode_t> nodes(nn);
         WS_HIP(hipGraphGetNodes(graph, nodes.data(), &nn));
-        const void* k1_func = preprocess_kernel_func(pc->compressed, r->footprint_mode);
+        const void* k1_func = preprocess_kernel_func(pc->compressed, r->footprint_mode, r->k1_depths != nullptr);
         for (size_t i = 0; i < nn && !g.k1_node; ++i) {
             hipGraphNodeType ty;
             if (hipGraphNodeGetType(nodes[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
@@ -1415,7 +1430,9 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     }
     const int slot = (int)(g.next++ % ws_renderer::GRAPH_RING);
     if (g.used[slot]) WS_HIP(hipEventSynchronize(g.done[slot]));  // an earlier launch of this executable graph must have run
-    void* k1_args[2] = {const_cast<K1Params*>(&kp), const_cast<K1Buffers*>(&kb)};
+    // (the DEPTH form of K1 takes the z plane as a third argument; toggling depth re-captures: ws_renderer_enable_depth)
+    float* k1_depths = r->k1_depths;
+    void* k1_args[3] = {const_cast<K1Params*>(&kp), const_cast<K1Buffers*>(&kb), &k1_depths};
     hipKernelNodeParams np = g.k1_params;
     np.kernelParams = k1_args;
     np.extra = nullptr;
@@ -1431,6 +1448,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     r->sorted_keys_skipped = g.sorted_keys_skipped;
     r->blend_order_valid = g.blend_order_valid;  // what THIS graph's frames write, whatever a launch-by-launch frame left behind
     r->prepared = true;
+    r->prepared_depth = r->k1_depths != nullptr;
     r->prepared_pc = pc;
     r->last_stream = stream;
     return WS_OK;
@@ -1466,7 +1484,7 @@ int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_point
     for (uint32_t i = 0; i < n; ++i) {
         ws_renderer* r = rs[i];
         if (!r || !streams[i] || r->ctx != rs[0]->ctx || r->compressed != pc->compressed || r->timers || r->marks.active ||
-            r->capture || r->ctx->use_graph || r->ctx->debug_cut)
+            r->capture || r->depth || r->ctx->use_graph || r->ctx->debug_cut)
             return WS_ERR_UNSUPPORTED;
         for (uint32_t j = 0; j < i; ++j)
             if (rs[j] == r || streams[j] == streams[i]) return WS_ERR_UNSUPPORTED;
@@ -1510,8 +1528,9 @@ int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_point
 
 extern "C" {
 
-int ws_renderer_render(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
-                       size_t row_pitch_bytes, void* stream_v) {
+// render() and render_aux(): planes == nullptr is the colour image alone (the launch render() has always made)
+static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
+                        size_t row_pitch_bytes, void* stream_v, const BlendAuxPlanes* planes) {
     if (!r || !pc || !d_rgba_out) return fail(WS_ERR_INVALID, "ws_renderer_render: null argument");
     if (!r->prepared || r->prepared_pc != pc)
         return fail(WS_ERR_STATE, "ws_renderer_render: prepare() was not called for this point cloud");
@@ -1583,7 +1602,7 @@ int ws_renderer_render(ws_renderer* r, const ws_pointcloud* pc, const float back
     if (km) km->begin(stream, false);
     if (r->timers) WS_HIP(hipEventRecord(r->ev[4], stream));
     if (r->ctx->debug_cut >= 1 && r->ctx->debug_cut <= 4) return WS_OK;  // analysis only
-    int rc = launch_blend(bp, r->blend_mode == WS_BLEND_TARGET_PRECISION ? 2 : r->ctx->blend_variant, stream);
+    int rc = launch_blend(bp, r->blend_mode == WS_BLEND_TARGET_PRECISION ? 2 : r->ctx->blend_variant, stream, planes);
     if (rc) return rc;
     r->frames_enqueued = bp.frame_seq;
     km_mark(km, r->blend_mode == WS_BLEND_TARGET_PRECISION ? "k_blend_strict" : "k_blend");
@@ -1593,6 +1612,65 @@ int ws_renderer_render(ws_renderer* r, const ws_pointcloud* pc, const float back
     }
     r->last_stream = stream;
     return WS_OK;
+}
+
+int ws_renderer_render(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
+                       size_t row_pitch_bytes, void* stream_v) {
+    return render_frame(r, pc, background, d_rgba_out, row_pitch_bytes, stream_v, nullptr);
+}
+
+int ws_renderer_enable_depth(ws_renderer* r, int enable) {
+    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_enable_depth: null renderer");
+    if (r->depth != (enable != 0)) {
+        r->depth = enable != 0;
+        // K1's other form: a captured frame graph holds the old one (and its argument list) -- the next prepare() captures anew
+        ++r->scratch_generation;
+    }
+    return WS_OK;
+}
+
+int ws_renderer_render_aux(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
+                           size_t row_pitch_bytes, const ws_aux_targets* aux, void* stream) {
+    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_render_aux: null renderer");
+    if (!aux || (!aux->depth && !aux->median_depth && !aux->alpha))
+        return render_frame(r, pc, background, d_rgba_out, row_pitch_bytes, stream, nullptr);
+    for (int i = 0; i < 4; ++i)
+        if (aux->reserved[i]) return fail(WS_ERR_INVALID, "ws_renderer_render_aux: reserved words must be zero");
+    const size_t row = (size_t)4 * r->vw;
+    const struct { const float* p; size_t pitch; } planes[3] = {{aux->depth, aux->depth_pitch}, {aux->median_depth, aux->median_depth_pitch},
+                                                                 {aux->alpha, aux->alpha_pitch}};
+    for (const auto& pl : planes)
+        if (pl.p && (pl.pitch < row || (pl.pitch % 4) != 0 || (reinterpret_cast<uintptr_t>(pl.p) % 4) != 0))
+            return fail(WS_ERR_INVALID, "ws_renderer_render_aux: plane pitch below 4 x width, or pitch / pointer not 4-B aligned");
+    if (r->blend_mode != WS_BLEND_FAST)
+        return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need WS_BLEND_FAST");
+    if (r->capture || r->blend_timing || r->ctx->blend_variant != 0 || r->ctx->blend_dma || r->ctx->debug_cut)
+        return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need the production blend (no capture / timing / variants)");
+    if (r->prepared && r->prepared_pc == pc && (aux->depth || aux->median_depth) && !r->prepared_depth)
+        return fail(WS_ERR_STATE, "ws_renderer_render_aux: depth planes need ws_renderer_enable_depth before prepare()");
+    BlendAuxPlanes bp;
+    bp.depth = aux->depth;
+    bp.depth_pitch = aux->depth_pitch;
+    bp.median = aux->median_depth;
+    bp.median_pitch = aux->median_depth_pitch;
+    bp.alpha = aux->alpha;
+    bp.alpha_pitch = aux->alpha_pitch;
+    bp.z = r->prepared_depth ? r->depths : nullptr;
+    return render_frame(r, pc, background, d_rgba_out, row_pitch_bytes, stream, &bp);
+}
+
+int ws_renderer_download_depths(ws_renderer* r, uint32_t capacity, float* z, uint32_t* num_visible) {
+    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_download_depths: null renderer");
+    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_depths: no prepared frame");
+    if (!r->prepared_depth) return fail(WS_ERR_STATE, "ws_renderer_download_depths: depth was off at prepare()");
+    ws_frame_stats st;
+    int rc = ws_renderer_frame_stats(r, &st);
+    if (rc) return rc;
+    if (num_visible) *num_visible = st.num_visible;
+    const uint32_t v = st.num_visible;
+    if (z && capacity < v) return fail(WS_ERR_INVALID, "ws_renderer_download_depths: capacity smaller than the visible count");
+    if (!z || v == 0) return WS_OK;
+    return copy_d2h(z, r->depths, (size_t)v * sizeof(float), r->last_stream);
 }
 
 int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out) {

@@ -413,7 +413,10 @@ struct K1Buffers {
     unsigned long long* trace;   // nullptr, or {first workgroup start, last workgroup end} of this launch on the 100-MHz device clock
                                  //   (ws_renderer_enable_frame_trace: analysis of frames in flight; rocprofv3 serialises them)
 };
-int launch_preprocess(const K1Params& p, const K1Buffers& b, bool compressed, int footprint_mode, hipStream_t stream);
+// depths: nullptr, or [N] -- K1's DEPTH form also stores the view-space depth of each store slot (ws_renderer_enable_depth).  It
+// travels as a third kernel argument of that form only, so the other forms keep their kernel-argument layout.
+int launch_preprocess(const K1Params& p, const K1Buffers& b, bool compressed, int footprint_mode, hipStream_t stream,
+                      float* depths = nullptr);
 // K1 of up to K1_MAX_VIEWS views of ONE scene in one launch (preprocess.hip k_preprocess_multi): the scene is read once
 constexpr int K1_MAX_VIEWS = 4;
 struct K1MultiArgs {
@@ -423,7 +426,7 @@ struct K1MultiArgs {
 };
 int launch_preprocess_multi(const K1Params* p, const K1Buffers* b, uint32_t nv, bool compressed, int footprint_mode,
                             hipStream_t stream);
-const void* preprocess_kernel_func(bool compressed, int footprint_mode);  // host-side kernel symbol (identifies K1's node in a captured graph)
+const void* preprocess_kernel_func(bool compressed, int footprint_mode, bool depth);  // host-side kernel symbol (identifies K1's node in a captured graph)
 uint32_t preprocess_blocks(uint32_t n);
 
 // ---- binning + blend ----------------------------------------------------------------------------
@@ -490,8 +493,24 @@ struct BlendParams {
     uint32_t* debug_timing;     // nullptr, or [tiles][16 waves][BLEND_TIMING_WORDS]: per-wave phase times (ws_renderer_enable_blend_timing)
     unsigned long long* trace;  // nullptr, or {first workgroup start, last workgroup end} of this launch (ws_renderer_enable_frame_trace)
 };
+// The auxiliary planes of ws_renderer_render_aux: f32, one value per pixel, rows of *_pitch bytes; nullptr = not asked for.
+// A third kernel argument of k_blend's AUX forms only (the other forms keep their kernel-argument layout).
+struct BlendAuxPlanes {
+    float* depth;          // expected view-space depth sum(w z) / sum(w), 0 where nothing is drawn
+    size_t depth_pitch;
+    float* median;         // z of the splat after which T <= 0.5, 0 where T stays above 0.5
+    size_t median_pitch;
+    float* alpha;          // coverage 1 - T
+    size_t alpha_pitch;
+    const float* z;        // [V] view-space depth per store slot (K1's DEPTH form); needed by the first two
+};
+// Forms of the FAST blend (k_blend's AUX parameter): no auxiliary plane (the colour image only), coverage only, and the depth
+// forms -- z staged beside every record, sum(w z), sum(w) and the median's crossing accumulated -- which write any of the three.
+enum BlendAux { BLEND_AUX_NONE = 0, BLEND_AUX_ALPHA = 1, BLEND_AUX_Z = 2 };
 constexpr int BLEND_TIMING_WORDS = 16;
-int launch_blend(const BlendParams& p, int variant, hipStream_t stream);
+// aux: nullptr or no plane = the colour image only; otherwise variant 0 only -- the FAST production launch (capture, timing,
+// LDS-DMA and exact-cut forms refuse it)
+int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const BlendAuxPlanes* aux = nullptr);
 // the blend's workgroups in longest-list-first order (raster.hip k_blend_order): order[blend_order_blocks(..)]
 uint32_t blend_order_blocks(uint32_t tiles_x, uint32_t tiles_y);
 int launch_blend_order(const uint2* tile_ranges, const FrameCounters* counters, uint32_t tiles_x, uint32_t tiles_y, uint4* order,

@@ -146,6 +146,12 @@ class ws_frame_stats(C.Structure):
                 ("tile_entries_capacity", C.c_uint32), ("overflow", C.c_uint32)]
 
 
+class ws_aux_targets(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("depth_pitch", C.c_size_t), ("median_depth", C.c_void_p),
+                ("median_depth_pitch", C.c_size_t), ("alpha", C.c_void_p), ("alpha_pitch", C.c_size_t),
+                ("reserved", C.c_uint32 * 4)]
+
+
 assert C.sizeof(ws_camera_uniform) == 272
 assert C.sizeof(ws_settings_uniform) == 80
 assert C.sizeof(ws_gaussian_quantization) == 64
@@ -256,6 +262,9 @@ SIGNATURES = {
     "ws_renderer_binning_tile": (C.c_int, [_P, _u32p, _u32p]),
     "ws_renderer_set_tile_entry_capacity": (C.c_int, [_P, C.c_uint64]),
     "ws_renderer_download_frame": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _u32p]),
+    "ws_renderer_enable_depth": (C.c_int, [_P, C.c_int]),
+    "ws_renderer_render_aux": (C.c_int, [_P, _P, _f32p, _P, C.c_size_t, C.POINTER(ws_aux_targets), _P]),
+    "ws_renderer_download_depths": (C.c_int, [_P, C.c_uint32, _f32p, _u32p]),
     "ws_sorter_create": (C.c_int, [_P, C.c_uint32, _PP]),
     "ws_sorter_destroy": (None, [_P]),
     "ws_sorter_sort": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),

@@ -608,8 +608,12 @@ class GaussianRenderer:
         self.handle = h
         self._own_target = None
         self._own_target_shape = None
+        self._aux = {}            # plane name -> renderer-owned device buffer (H x W f32) of render_aux
+        self._aux_shape = None
+        self._aux_last = ()       # the planes the last render_aux wrote
 
     def close(self):
+        self._free_aux()
         if self._own_target:
             self.ctx.free(self._own_target)
             self._own_target = None
@@ -746,6 +750,58 @@ class GaussianRenderer:
         bg = (C.c_float * 4)(*[float(x) for x in background])
         check(lib.ws_renderer_render(self.handle, pc.handle, bg, C.c_void_p(target_ptr), pitch, C.c_void_p(stream or 0)))
         return target_ptr
+
+    def enable_depth(self, on=True):
+        """K1 also writes each visible splat's view-space depth (4 B per splat) from the next prepare() on: what the depth and
+        median_depth planes of render_aux() are built from."""
+        check(lib.ws_renderer_enable_depth(self.handle, int(bool(on))))
+
+    def _free_aux(self):
+        for ptr in self._aux.values():
+            self.ctx.free(ptr)
+        self._aux = {}
+        self._aux_shape = None
+
+    def render_aux(self, pc: PointCloud, depth=True, median_depth=False, alpha=False, background=(0.0, 0.0, 0.0, 0.0),
+                   stream=None):
+        """render() into the renderer-owned target plus the asked-for auxiliary planes (websplat.h ws_renderer_render_aux) into
+        renderer-owned H x W float32 buffers; download_aux() reads them back."""
+        w, h = self._viewport
+        if self._own_target_shape != (w, h):
+            if self._own_target:
+                self.ctx.free(self._own_target)
+            self._own_target = self.ctx.malloc(w * h * self.texel_bytes)
+            self._own_target_shape = (w, h)
+        if self._aux_shape != (w, h):
+            self._free_aux()
+            self._aux_shape = (w, h)
+        want = [name for name, on in (("depth", depth), ("median_depth", median_depth), ("alpha", alpha)) if on]
+        t = L.ws_aux_targets()
+        for name in want:
+            if name not in self._aux:
+                self._aux[name] = self.ctx.malloc(w * h * 4)
+            setattr(t, name, C.c_void_p(self._aux[name]))
+            setattr(t, name + "_pitch", w * 4)
+        bg = (C.c_float * 4)(*[float(x) for x in background])
+        check(lib.ws_renderer_render_aux(self.handle, pc.handle, bg, C.c_void_p(self._own_target), w * self.texel_bytes,
+                                         C.byref(t), C.c_void_p(stream or 0)))
+        self._aux_last = tuple(want)
+        return self._own_target
+
+    def download_aux(self) -> dict:
+        """{plane name: H x W float32} of the planes the last render_aux() wrote (syncs)."""
+        w, h = self._aux_shape or (0, 0)
+        self.ctx.sync()
+        return {name: self.ctx.download(self._aux[name], (h, w), np.float32) for name in self._aux_last}
+
+    def download_depths(self) -> np.ndarray:
+        """The prepared frame's view-space depth per visible splat, store order (needs enable_depth before prepare; syncs)."""
+        nv = C.c_uint32()
+        check(lib.ws_renderer_download_depths(self.handle, 0, None, C.byref(nv)))
+        z = np.empty(nv.value, dtype=np.float32)
+        if nv.value:
+            check(lib.ws_renderer_download_depths(self.handle, nv.value, z.ctypes.data_as(C.POINTER(C.c_float)), C.byref(nv)))
+        return z
 
     def download_target_rgba8(self) -> np.ndarray:
         """bin/render.rs:187-246 download_texture of the renderer-owned target: H x W x 4 uint8 (truncating)."""
