@@ -366,6 +366,50 @@ typedef struct ws_aux_targets {
  * WS_BLEND_TARGET_PRECISION or WS_BLEND_FAST_EXACT_CUT (not built yet: a later change), capture mode or blend timing. */
 int ws_renderer_render_aux(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
                            size_t row_pitch_bytes, const ws_aux_targets* aux, void* stream);
+/* ---- Compositing over an existing target, behind an opaque depth buffer ------------------------------------------------
+ * The reference draws into a pass the caller begins (renderer.rs:250-260) with PREMULTIPLIED_ALPHA_BLENDING (renderer.rs:63-67),
+ * so a host may begin it with LoadOp::Load and put the splats over a sky, a grid or a mesh pass.  This is that path, plus the
+ * exact mesh + splat composite: every splat behind the opaque surface is dropped, per pixel, during the blend.
+ * Below, T and the weights w_i are the FAST blend's, early termination included (WS_BLEND_TARGET_PRECISION: that blend's, no
+ * early termination).
+ *   comp == NULL, or load == 0 with no occluder: exactly ws_renderer_render_aux (same launch, same bytes).
+ *   load == 1: out = C + T * dst on all four channels, C = sum(w_i c_i) the splats' premultiplied colour and coverage, dst the
+ *     texel the target held, decoded from its format: f32, f16, or unorm8 as k / 255 (f32 division).  This is what the
+ *     reference's pipeline computes over a loaded pass, with the FAST mode's single rounding at the store; the result is
+ *     rounded once, as by ws_renderer_render.  `background` is ignored.  (WS_BLEND_TARGET_PRECISION starts its destination
+ *     from dst and rounds after every splat, as a wgpu pass with LoadOp::Load does.)
+ *   occluder: splat i takes part at pixel p iff z_i < D(p) in f32, z_i the value of the frame's z plane
+ *     (ws_renderer_download_depths): per splat, at its centre depth -- the granularity of the depth sort.  A pair that fails
+ *     the test is skipped exactly like a pair outside the cut-off: no weight, T unchanged.
+ *       WS_OCCLUDER_VIEW_Z     D = occluder[p].  +inf means "no geometry here"; NaN drops every splat (the comparison is false).
+ *       WS_OCCLUDER_NDC_DEPTH  D = (n * f) / (f - d * (f - n)), d = occluder[p], n and f the prepared frame's znear and zfar
+ *                              (-proj[3][2] / proj[2][2] and -proj[3][2] / (proj[2][2] - 1), what K1 derives from the
+ *                              projection).  Evaluated in f32 in exactly this order -- n * f, f - n, d * (f - n), the
+ *                              difference, then a correctly rounded division -- with no contraction into an FMA.  d >= 1 (a
+ *                              cleared depth buffer) is +inf.
+ *   Auxiliary planes follow the same weights: depth, median_depth and alpha describe the unoccluded splats only; alpha stays
+ *     1 - T whatever the target held.
+ * Every pixel of the target is read and written by exactly one thread of the frame's compositing launch, once: the target
+ * may be the caller's colour attachment itself.  The occluder plane is read only.
+ * Errors: WS_ERR_STATE when an occluder is given but the prepared frame has no z plane (ws_renderer_enable_depth before
+ * prepare()); WS_ERR_INVALID for an occluder pitch below 4 x width, a pitch or pointer not 4-B aligned, load other than 0 / 1,
+ * a non-zero reserved word or an unknown kind (and render_aux's errors for the planes); WS_ERR_UNSUPPORTED with load or an
+ * occluder under WS_BLEND_FAST_EXACT_CUT, in capture mode or with blend timing (as the planes; the planes also need
+ * WS_BLEND_FAST). */
+typedef enum ws_occluder_kind {
+    WS_OCCLUDER_VIEW_Z = 0,     /* f32 view-space depth, positive in front of the camera: the units of the depth planes */
+    WS_OCCLUDER_NDC_DEPTH = 1   /* f32 [0, 1] depth-buffer value under the frame's own projection (camera.rs build_proj, wgpu) */
+} ws_occluder_kind;
+typedef struct ws_composite_desc {
+    uint32_t load;              /* 0: clear to `background` first (= render / render_aux); 1: LoadOp::Load, over the target's texels */
+    uint32_t occluder_kind;     /* ws_occluder_kind */
+    const float* occluder;      /* device plane, one f32 per pixel; NULL = no depth test */
+    size_t occluder_pitch;      /* bytes; >= 4 x width, multiple of 4; 4-B aligned pointer */
+    uint32_t reserved[4];       /* must be zero */
+} ws_composite_desc;
+int ws_renderer_render_composite(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba,
+                                 size_t row_pitch_bytes, const ws_aux_targets* aux, const ws_composite_desc* comp,
+                                 void* stream);
 /* GaussianRenderer::num_visible_points (syncs) */
 int ws_renderer_num_visible(ws_renderer* r, uint32_t* out);
 int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out); /* syncs */

@@ -368,6 +368,34 @@ __device__ __forceinline__ void store_aux(const BlendAuxPlanes& a, uint32_t px, 
 // hidden arguments included, stays what it is without them) or the planes
 __device__ __forceinline__ BlendAuxPlanes blend_aux_of() { return BlendAuxPlanes{}; }
 __device__ __forceinline__ BlendAuxPlanes blend_aux_of(const BlendAuxPlanes& a) { return a; }
+__device__ __forceinline__ BlendAuxPlanes blend_aux_of(const BlendAuxPlanes& a, const BlendComposite&) { return a; }
+// ... and the composite forms' second trailing argument (ws_renderer_render_composite)
+__device__ __forceinline__ BlendComposite blend_comp_of() { return BlendComposite{}; }
+__device__ __forceinline__ BlendComposite blend_comp_of(const BlendAuxPlanes&) { return BlendComposite{}; }
+__device__ __forceinline__ BlendComposite blend_comp_of(const BlendAuxPlanes&, const BlendComposite& c) { return c; }
+// LOAD: the texel the target holds at (px, py), decoded from its format -- f32, f16, or unorm8 as k / 255 (k_display's decode)
+template <int FORMAT>
+__device__ __forceinline__ float4 load_pixel(const BlendParams& p, uint32_t px, uint32_t py) {
+    const char* row = reinterpret_cast<const char*>(p.out) + (size_t)py * p.pitch;
+    if (FORMAT == WS_FORMAT_RGBA32_FLOAT) return reinterpret_cast<const float4*>(row)[px];
+    if (FORMAT == WS_FORMAT_RGBA16_FLOAT) {
+        const uint2 v = reinterpret_cast<const uint2*>(row)[px];
+        return make_float4(h2f(v.x), h2f(v.x >> 16), h2f(v.y), h2f(v.y >> 16));
+    }
+    const uint32_t v = reinterpret_cast<const uint32_t*>(row)[px];
+    return make_float4((float)(v & 255u) / 255.0f, (float)((v >> 8) & 255u) / 255.0f, (float)((v >> 16) & 255u) / 255.0f,
+                       (float)(v >> 24) / 255.0f);
+}
+// OCCLUDE: D(p), the view-space depth of the opaque surface at (px, py).  The NDC kind maps a [0, 1] depth-buffer value d under
+// the frame's projection with the header's expression, in this order and with no contraction: (n * f) / (f - (d * (f - n))),
+// correctly rounded f32 division; d >= 1 (a cleared buffer) is +inf.  (The caller has checked that the pixel is inside.)
+__device__ __forceinline__ float occluder_depth(const BlendComposite& c, uint32_t px, uint32_t py) {
+#pragma clang fp contract(off)
+    const float d = reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.occluder) + (size_t)py * c.occluder_pitch)[px];
+    if (!c.occ_ndc) return d;
+    const float n = c.znear, f = c.zfar;
+    return d >= 1.0f ? __builtin_inff() : (n * f) / (f - d * (f - n));
+}
 
 // ---- k_blend_order: the compositing workgroups in longest-list-first order --------------------------------------------------
 // The hardware starts the blend's workgroups in blockIdx order, two per CU, and a frame has ~4x (1080p) more tiles than the
@@ -541,11 +569,12 @@ __device__ __forceinline__ BlendRec blend_load_rec(const float4* s_rec, uint32_t
     r.h = *reinterpret_cast<const float4*>(base + SLOTS * 16);
     return r;
 }
-// AUX == BLEND_AUX_Z: a third plane of 16-B slots holds each staged record's view-space depth in its first word -- at the
-// record's own byte offset plus a constant, one ds_read_b32 with an immediate offset and no address arithmetic.
-template <int SLOTS, int AUX>
+// STAGE_Z (AUX == BLEND_AUX_Z or the OCCLUDE composite forms): a third plane of 16-B slots holds each staged record's view-space
+// depth in its first word -- at the record's own byte offset plus a constant, one ds_read_b32 with an immediate offset and no
+// address arithmetic.
+template <int SLOTS, bool STAGE_Z>
 __device__ __forceinline__ float blend_load_z(const float4* s_rec, uint32_t byte_off) {
-    if (AUX != BLEND_AUX_Z) return 0.0f;
+    if (!STAGE_Z) return 0.0f;
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(s_rec) + byte_off + 2 * SLOTS * 16);
 }
 // The depth forms' per-pixel accumulators: sum(w z), sum(w), and the median candidate -- z of the last kept splat that found
@@ -588,10 +617,11 @@ __device__ __forceinline__ bool blend_exact_keep(const BlendExact& e, uint32_t l
     return a <= CUT_A;
 }
 // One (pixel, splat) pair: gaussian.wgsl:59-66 in the exp2 domain, front-to-back "over".
-template <bool EXACT = false, int AUX = BLEND_AUX_NONE>
+// OCC: the pair also needs z < D (the pixel's occluder depth); a pair that fails is skipped like one outside the cut-off.
+template <bool EXACT = false, int AUX = BLEND_AUX_NONE, bool OCC = false>
 __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, float ly, float& T, float& cr, float& cg,
                                                 float& cb, const BlendExact& ex = BlendExact{}, uint32_t list_off = 0u,
-                                                BlendAuxAcc* acc = nullptr, float z = 0.0f) {
+                                                BlendAuxAcc* acc = nullptr, float z = 0.0f, float D = 0.0f) {
     const float p0 = fmaf(r.g.x, lx, fmaf(r.g.y, ly, r.g.z));
     const float p1 = fmaf(r.g.w, lx, fmaf(r.h.x, ly, r.h.y));
     const float a = fmaf(p0, p0, p1 * p1);
@@ -599,6 +629,7 @@ __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, flo
     if (EXACT) {
         if (__builtin_expect(keep && a >= CUT_A2 * (1.0f - CUT_BAND), 0)) keep = blend_exact_keep(ex, list_off);
     }
+    if (OCC) keep = keep && z < D;
     if (keep) {
         // b = min(0.99, 2^-a' * alpha), alpha = high half of h.w.  One asm block: gfx950 needs one wait state between
         // a transcendental's result and a VALU instruction reading it, and the compiler does not look inside asm.
@@ -657,15 +688,20 @@ __device__ __forceinline__ uint32_t blend_stamp() {
     return (uint32_t)t;
 }
 template <int FORMAT, int QW, int QH, bool MULTI, bool CAPTURE, bool DMA, bool TIMING = false, bool EXACT = false, int AUX = BLEND_AUX_NONE,
-          typename... Aux>
-__global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX == BLEND_AUX_Z && !MULTI && QW * QH != 8) ? WS_BLEND_AUX_MINWAVES : WS_BLEND_MINWAVES)) void k_blend(const BlendParams p,
+          int COMP = BLEND_COMP_NONE, typename... Aux>
+__global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : (((AUX == BLEND_AUX_Z || (COMP & BLEND_COMP_OCCLUDE)) && !MULTI && QW * QH != 8) ? WS_BLEND_AUX_MINWAVES : WS_BLEND_MINWAVES)) void k_blend(const BlendParams p,
                                                                                                     const uint32_t tpw_log2_arg,
                                                                                                     const Aux... aux_planes) {
     static_assert(!TIMING || (!MULTI && !DMA && !CAPTURE), "the timing build instruments the production form only");
     static_assert(!EXACT || (!CAPTURE && !DMA && !TIMING), "the exact cut-off decision belongs to the production launch");
-    static_assert(AUX == BLEND_AUX_NONE || (!CAPTURE && !DMA && !TIMING && !EXACT), "the auxiliary planes belong to the FAST production launch");
-    static_assert((AUX == BLEND_AUX_NONE) == (sizeof...(Aux) == 0), "the AUX forms take the planes, the others nothing");
+    static_assert((AUX == BLEND_AUX_NONE && COMP == BLEND_COMP_NONE) || (!CAPTURE && !DMA && !TIMING && !EXACT),
+                  "the auxiliary planes and the composite belong to the FAST production launch");
+    static_assert(sizeof...(Aux) == (COMP != BLEND_COMP_NONE ? 2 : (AUX != BLEND_AUX_NONE ? 1 : 0)),
+                  "the AUX forms take the planes, the COMP forms the planes and the composite, the others nothing");
     const BlendAuxPlanes ax = blend_aux_of(aux_planes...);
+    const BlendComposite cp = blend_comp_of(aux_planes...);
+    constexpr bool OCC = (COMP & BLEND_COMP_OCCLUDE) != 0;
+    constexpr bool STAGE_Z = AUX == BLEND_AUX_Z || OCC;  // the third LDS plane: z beside every staged record
     uint32_t tm[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // TIMING: cycles per phase, this wave (SGPRs)
     uint32_t tm_batches = 0u, tm_real0 = 0u;
     const uint32_t tm_start = blend_stamp<TIMING>();
@@ -684,7 +720,8 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
     // batch is large: -DWS_BLEND_STAGE_MAX=1024 halves the per-batch barriers and still leaves LDS for two workgroups)
     constexpr int LCAP = STAGE < 512 ? STAGE : 512;
 
-    __shared__ float4 s_rec[(AUX == BLEND_AUX_Z ? 3 : 2) * SLOTS];  // (AUX_Z: + the plane of view-space depths, blend_load_z)
+    __shared__ float4 s_rec[(STAGE_Z ? 3 : 2) * SLOTS];  // (STAGE_Z: + the plane of view-space depths, blend_load_z)
+    __shared__ float s_dmax[OCC ? NW : 1];  // OCCLUDE: the largest D of each wave's pixels, this tile
     // quadrant bits of the staged records (0 = slot unused), 16 bits each, TRANSPOSED per sub-round of LCAP slots: the
     // masks of slots lane, lane + 64, lane + 128, ... sit side by side, so a wave's compaction reads all of them with one
     // or two wide LDS loads instead of one dependent load per 64 records
@@ -765,7 +802,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
                      // below, else the first staging barrier of the tile loop -- nothing reads it before)
         s_rec[STAGE] = make_float4(0.0f, 0.0f, 1.0e9f, 0.0f);
         s_rec[SLOTS + STAGE] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (AUX == BLEND_AUX_Z) s_rec[2 * SLOTS + STAGE] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (STAGE_Z) s_rec[2 * SLOTS + STAGE] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
     if (MULTI) __syncthreads();
     uint32_t tm_last = tm_start;
@@ -779,14 +816,14 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
     uint32_t* my_list = s_list[wave];
 
     RawSplat raw = {{0u, 0u, 0u, 0u}, 0u};
-    float zraw = 0.0f;   // AUX_Z: the view-space depth of the staged entry, gathered with the same index as its record
+    float zraw = 0.0f;   // STAGE_Z: the view-space depth of the staged entry, gathered with the same index as its record
     uint32_t rbuf = 0u;  // DMA: the raw buffer (slot offset 0 or STAGE) the current tile stages out of
     const uint32_t wslot = (uint32_t)wave * 64u;  // first raw slot of this wave (stager waves only)
     if (stager) {
         const uint2 r0 = MULTI ? s_range[0] : range_one;
         if (r0.y > r0.x) {  // (an empty tile must not touch the entry list)
             if (DMA) blend_gather_lds(p, blend_entry_idx<STAGE>(p, r0, r0.y, tid), s_raw4 + wslot, s_raw1 + wslot);
-            else if (AUX == BLEND_AUX_Z) {
+            else if (STAGE_Z) {
                 const uint32_t idx0 = blend_entry_idx<STAGE>(p, r0, r0.y, tid);
                 raw = blend_gather(p, idx0);
                 zraw = ax.z[idx0];
@@ -806,7 +843,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
         const uint2 rn = s_range[k + 1u];
         if (rn.y > rn.x) {
             if (DMA) range_nt = rn;
-            else if (AUX == BLEND_AUX_Z) {
+            else if (STAGE_Z) {
                 const uint32_t idxn = blend_entry_idx<STAGE>(p, rn, rn.y, tid);
                 raw_next_tile = blend_gather(p, idxn);
                 z_next_tile = ax.z[idxn];
@@ -825,6 +862,22 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
     float T = inside ? 1.0f : 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
     BlendAuxAcc acc;  // (AUX_Z only; dead otherwise)
     const float tile_x0 = (float)(tx * TW), tile_y0 = (float)(ty * TH);
+    // OCCLUDE: the pixel's occluder depth D, loaded and converted once per tile (-inf outside the image, where nothing is
+    // stored), and Dmax, the largest D of the tile (NaN pixels do not count: they keep no splat whatever Dmax is).  A record
+    // with z >= Dmax fails z < D at every pixel of the tile, so the stager drops it before any wave walks it.
+    float D = 0.0f, Dmax = 0.0f;
+    if (OCC) {
+        D = inside ? occluder_depth(cp, px, py) : -__builtin_inff();
+        float m = D;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) m = fmaxf(m, __shfl_xor(m, s));
+        if (lane == 0) s_dmax[wave] = m;
+        __syncthreads();  // (the previous tile's readers are past the barrier that ends it)
+        Dmax = s_dmax[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) Dmax = fmaxf(Dmax, s_dmax[w]);
+        Dmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(Dmax)));  // (workgroup-uniform: an SGPR)
+    }
 
     uint32_t hi = range.y;
     // Two-deep pipeline of the staging loads: while batch b is composited, the Splat records of batch b+1 (their indices
@@ -869,9 +922,10 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
                 const stage::Staged s = stage::decode<QW, QH>(raw.a.x, raw.a.y, raw.a.z, raw.a.w, raw.w4, W, H, tile_x0,
                                                               tile_y0, CUT_A2);
                 mask = s.mask;
+                if (OCC && !(zraw < Dmax)) mask = 0u;  // behind every pixel's occluder: no wave lists it
                 s_rec[tid] = make_float4(s.i00, s.i01, s.c0, s.i10);
                 s_rec[SLOTS + tid] = make_float4(s.i11, s.c1, __uint_as_float(raw.a.w), __uint_as_float(raw.w4));
-                if (AUX == BLEND_AUX_Z) reinterpret_cast<float*>(s_rec + 2 * SLOTS + tid)[0] = zraw;
+                if (STAGE_Z) reinterpret_cast<float*>(s_rec + 2 * SLOTS + tid)[0] = zraw;
             }
             s_m[((uint32_t)tid / LCAP) * LCAP + ((uint32_t)tid & 63u) * (LCAP / 64) + (((uint32_t)tid % LCAP) >> 6)] = (uint16_t)mask;
             if (fetch_nt) {
@@ -884,7 +938,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
             // v_mov, i.e. the "prefetch" waited for its own data before the barrier, one exposed round trip per batch
             if (DMA) blend_gather_lds(p, idx_next, s_raw4 + rbuf + wslot, s_raw1 + rbuf + wslot);
             else raw = blend_gather(p, idx_next);
-            if (AUX == BLEND_AUX_Z) zraw = ax.z[idx_next];
+            if (STAGE_Z) zraw = ax.z[idx_next];
             idx_next = blend_entry_idx<STAGE>(p, range, hi_next - range.x > (uint32_t)STAGE ? hi_next - (uint32_t)STAGE : range.x, tid);
         }
         if (TIMING) {
@@ -942,22 +996,22 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
                 uint4 o = lp[0];
                 uint4 on = lp[n4 > 1u ? 1u : 0u];
                 BlendRec cur = blend_load_rec<SLOTS>(s_rec, o.x);
-                float zcur = blend_load_z<SLOTS, AUX>(s_rec, o.x);
+                float zcur = blend_load_z<SLOTS, STAGE_Z>(s_rec, o.x);
                 for (uint32_t g = 0; g < n4; ++g) {
                     const BlendExact exact = {&p, hi, tile_x0 + lx, tile_y0 + ly, W, H};  // (EXACT only; dead code otherwise)
                     const BlendRec r1 = blend_load_rec<SLOTS>(s_rec, o.y);
-                    const float z1 = blend_load_z<SLOTS, AUX>(s_rec, o.y);
-                    blend_composite<EXACT, AUX>(cur, lx, ly, T, cr, cg, cb, exact, o.x, &acc, zcur);
+                    const float z1 = blend_load_z<SLOTS, STAGE_Z>(s_rec, o.y);
+                    blend_composite<EXACT, AUX, OCC>(cur, lx, ly, T, cr, cg, cb, exact, o.x, &acc, zcur, D);
                     const BlendRec r2 = blend_load_rec<SLOTS>(s_rec, o.z);
-                    const float z2 = blend_load_z<SLOTS, AUX>(s_rec, o.z);
-                    blend_composite<EXACT, AUX>(r1, lx, ly, T, cr, cg, cb, exact, o.y, &acc, z1);
+                    const float z2 = blend_load_z<SLOTS, STAGE_Z>(s_rec, o.z);
+                    blend_composite<EXACT, AUX, OCC>(r1, lx, ly, T, cr, cg, cb, exact, o.y, &acc, z1, D);
                     const BlendRec r3 = blend_load_rec<SLOTS>(s_rec, o.w);
-                    const float z3 = blend_load_z<SLOTS, AUX>(s_rec, o.w);
-                    blend_composite<EXACT, AUX>(r2, lx, ly, T, cr, cg, cb, exact, o.z, &acc, z2);
+                    const float z3 = blend_load_z<SLOTS, STAGE_Z>(s_rec, o.w);
+                    blend_composite<EXACT, AUX, OCC>(r2, lx, ly, T, cr, cg, cb, exact, o.z, &acc, z2, D);
                     const uint32_t off3 = o.w;
                     cur = blend_load_rec<SLOTS>(s_rec, on.x);  // (re-reads a valid record after the last group)
-                    zcur = blend_load_z<SLOTS, AUX>(s_rec, on.x);
-                    blend_composite<EXACT, AUX>(r3, lx, ly, T, cr, cg, cb, exact, off3, &acc, z3);
+                    zcur = blend_load_z<SLOTS, STAGE_Z>(s_rec, on.x);
+                    blend_composite<EXACT, AUX, OCC>(r3, lx, ly, T, cr, cg, cb, exact, off3, &acc, z3, D);
                     // the quadrant is saturated: nothing behind can add more than T_MIN (one compare per four pairs;
                     // on dense tiles this stops the walk well inside the staged batch)
                     if ((CAPTURE && p.debug_walked) || TIMING) dbg_walked += 4u;
@@ -1025,8 +1079,13 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
         const uint32_t sx = tx * TW + (uint32_t)lx, sy = ty * TH + (uint32_t)ly;
         if (sx < p.width && sy < p.height) {
             // begin_render_pass(clear = background) then "over": dst = src + dst * (1 - src.a), all four channels
-            store_pixel<FORMAT>(p, sx, sy, cr + p.background[0] * T, cg + p.background[1] * T, cb + p.background[2] * T,
-                                (1.0f - T) + p.background[3] * T);
+            if (COMP & BLEND_COMP_LOAD) {  // LoadOp::Load: over the texel the target holds (this lane reads and writes it, once)
+                const float4 d = load_pixel<FORMAT>(p, sx, sy);
+                store_pixel<FORMAT>(p, sx, sy, cr + d.x * T, cg + d.y * T, cb + d.z * T, (1.0f - T) + d.w * T);
+            } else {
+                store_pixel<FORMAT>(p, sx, sy, cr + p.background[0] * T, cg + p.background[1] * T, cb + p.background[2] * T,
+                                    (1.0f - T) + p.background[3] * T);
+            }
             store_aux<AUX>(ax, sx, sy, T, acc.dz, acc.wsum, acc.med);
         }
     }
@@ -1064,7 +1123,7 @@ __global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : ((AUX 
         wg_barrier_keep_loads();  // the staging buffers are reused by the next tile
     } else {
         raw = raw_next_tile;
-        if (AUX == BLEND_AUX_Z) zraw = z_next_tile;
+        if (STAGE_Z) zraw = z_next_tile;
         __syncthreads();  // the staging buffers are reused by the next tile
     }
     }  // tiles of this workgroup
@@ -1143,9 +1202,16 @@ __device__ __forceinline__ float quantize_target(float v) {
     return v;
 }
 
-template <int FORMAT>
-__global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p) {
+// The composite form (COMP, ws_renderer_render_composite; trailing arguments: the planes -- for their z -- and the composite):
+// load starts the destination from the target's texel instead of the quantised background, which is what a wgpu pass with
+// LoadOp::Load and this pipeline computes, rounding for rounding; an occluder reads z[idx] of every staged splat and keeps a
+// pair only while z < D(p).  Both are run-time switches here: throughput is not this kernel's point.
+template <int FORMAT, bool COMP = false, typename... A>
+__global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p, const A... comp_args) {
 #pragma clang fp contract(off)  // the oracle's arithmetic: separate multiplies and adds
+    static_assert(sizeof...(A) == (COMP ? 2 : 0), "the composite form takes the planes and the composite, the other nothing");
+    const BlendAuxPlanes ax = blend_aux_of(comp_args...);
+    const BlendComposite cp = blend_comp_of(comp_args...);
     const uint32_t b = blockIdx.x;
     if (b == 0 && threadIdx.x == 0 && p.sticky) {  // as in k_blend
         const uint32_t bits = p.counters->overflow;
@@ -1167,6 +1233,15 @@ __global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p) {
     const float W = (float)p.width, H = (float)p.height;
     float d0 = quantize_target<FORMAT>(p.background[0]), d1 = quantize_target<FORMAT>(p.background[1]),
           d2 = quantize_target<FORMAT>(p.background[2]), d3 = quantize_target<FORMAT>(p.background[3]);
+    const bool occ = COMP && cp.occluder != nullptr;  // (uniform)
+    float D = 0.0f;
+    if (COMP && inside) {
+        if (cp.load) {  // the texel is already of the target's precision: its decode is exact
+            const float4 t = load_pixel<FORMAT>(p, px, py);
+            d0 = t.x; d1 = t.y; d2 = t.z; d3 = t.w;
+        }
+        if (occ) D = occluder_depth(cp, px, py);
+    }
     uint2 range = p.tile_ranges[tile_list_index(p, tx, ty)];
     range.x = range.y ? 0xFFFFFFFFu - range.x : 0u;
     for (uint32_t lo = range.x; lo < range.y; lo += 64u) {  // far -> near: ascending position in the tile's list
@@ -1175,6 +1250,7 @@ __global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p) {
         const uint32_t idx = p.entry_vals[valid ? e : range.y - 1u];
         const uint32_t* sp = reinterpret_cast<const uint32_t*>(p.splats + (size_t)idx * SPLAT_STRIDE);
         const StagedSplat s = decode_splat(sp[0], sp[1], sp[2], sp[3], sp[4], W, H, qx_lo, qy_lo, valid);
+        const float zs = occ ? ax.z[idx] : 0.0f;  // the staged splat's view-space depth (K1's z plane)
         unsigned long long rel = __ballot(s.touch);
         while (rel) {
             const int k = __ffsll((long long)rel) - 1;
@@ -1184,7 +1260,7 @@ __global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p) {
             const float p0 = bcast(s.i00, k) * dx + bcast(s.i01, k) * dy;
             const float p1 = bcast(s.i10, k) * dx + bcast(s.i11, k) * dy;
             const float a = p0 * p0 + p1 * p1;
-            if (a <= CUT_A) {
+            if (a <= CUT_A && (!occ || bcast(zs, k) < D)) {
                 const float bb = fminf(0.99f, expf(-a) * bcast(s.alpha, k));
                 const float om = 1.0f - bb;
                 d0 = quantize_target<FORMAT>(bcast(s.r, k) * bb + d0 * om);
@@ -1331,7 +1407,8 @@ int launch_blend_order(const uint2* tile_ranges, const FrameCounters* counters, 
 }
 
 template <int QW, int QH>
-static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux, const BlendAuxPlanes& ap) {
+static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux, const BlendAuxPlanes& ap, int comp,
+                              const BlendComposite& cp) {
     const BlendShape sh = blend_shape(QW, QH);
     uint32_t tpw_log2 = p.tpw_log2 >= 0 ? (uint32_t)p.tpw_log2 : blend_tpw_log2(p.tiles_x, p.tiles_y, sh);
     if (tpw_log2 > sh.tbx_log2 + sh.tby_log2) tpw_log2 = sh.tbx_log2 + sh.tby_log2;
@@ -1340,6 +1417,37 @@ static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux,
     const bool capture = p.debug_consumed != nullptr || p.debug_walked != nullptr;  // analysis build of the kernel
     // tuning knob (WS_BLEND_LDS_PAD_KB): unused dynamic LDS that lowers the number of blend workgroups per CU
     const size_t pad = (size_t)p.lds_pad_kb * 1024u;
+    if (comp != BLEND_COMP_NONE) {
+        // the composite: the launches of the auxiliary planes below (FAST production forms, all three formats), with LOAD and /
+        // or OCCLUDE; no plane = the coverage form with a null alpha pointer (one uniform branch at the store)
+        if (capture || p.debug_timing || p.dma || p.exact_cut || p.async_staging)
+            return fail(WS_ERR_UNSUPPORTED, "blend: the composite needs the FAST production launch (no capture / timing / DMA / exact cut)");
+        if (comp < BLEND_COMP_LOAD || comp > (BLEND_COMP_LOAD | BLEND_COMP_OCCLUDE)) return fail(WS_ERR_INVALID, "blend: unknown composite form");
+#define WS_LAUNCH_BLEND_COMP(FMT, AUX_, COMP_)                                                                                   \
+        if (tpw_log2 > 0u)                                                                                                       \
+            hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, false, AUX_, COMP_, BlendAuxPlanes, BlendComposite>), \
+                               dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap, cp);                                          \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, false, AUX_, COMP_, BlendAuxPlanes, BlendComposite>), \
+                               dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap, cp)
+#define WS_LAUNCH_BLEND_COMP_AUX(FMT, AUX_)                                                                                      \
+        if (comp == BLEND_COMP_LOAD) { WS_LAUNCH_BLEND_COMP(FMT, AUX_, BLEND_COMP_LOAD); }                                       \
+        else if (comp == BLEND_COMP_OCCLUDE) { WS_LAUNCH_BLEND_COMP(FMT, AUX_, BLEND_COMP_OCCLUDE); }                            \
+        else { WS_LAUNCH_BLEND_COMP(FMT, AUX_, BLEND_COMP_LOAD | BLEND_COMP_OCCLUDE); }
+#define WS_LAUNCH_BLEND_COMP_FMT(FMT)                                                                                            \
+        if (aux == BLEND_AUX_Z) { WS_LAUNCH_BLEND_COMP_AUX(FMT, BLEND_AUX_Z); } else { WS_LAUNCH_BLEND_COMP_AUX(FMT, BLEND_AUX_ALPHA); }
+        switch (p.format) {
+            case WS_FORMAT_RGBA32_FLOAT: WS_LAUNCH_BLEND_COMP_FMT(WS_FORMAT_RGBA32_FLOAT); break;
+            case WS_FORMAT_RGBA16_FLOAT: WS_LAUNCH_BLEND_COMP_FMT(WS_FORMAT_RGBA16_FLOAT); break;
+            case WS_FORMAT_RGBA8_UNORM: WS_LAUNCH_BLEND_COMP_FMT(WS_FORMAT_RGBA8_UNORM); break;
+            default: return fail(WS_ERR_INVALID, "blend: unknown colour format");
+        }
+#undef WS_LAUNCH_BLEND_COMP_FMT
+#undef WS_LAUNCH_BLEND_COMP_AUX
+#undef WS_LAUNCH_BLEND_COMP
+        WS_HIP(hipGetLastError());
+        return WS_OK;
+    }
     if (aux != BLEND_AUX_NONE) {
         // the auxiliary planes: the FAST production forms only -- one tile or several per workgroup, split halves (4x2 with
         // range_row_shift), the longest-first order (p.order) -- all three colour formats
@@ -1348,9 +1456,9 @@ static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux,
         if (aux != BLEND_AUX_ALPHA && aux != BLEND_AUX_Z) return fail(WS_ERR_INVALID, "blend: unknown auxiliary form");
 #define WS_LAUNCH_BLEND_AUX(FMT, AUX_)                                                                                           \
         if (tpw_log2 > 0u)                                                                                                       \
-            hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, false, AUX_, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap);  \
+            hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, false, AUX_, BLEND_COMP_NONE, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap);  \
         else                                                                                                                     \
-            hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, false, AUX_, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap)
+            hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, false, AUX_, BLEND_COMP_NONE, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap)
 #define WS_LAUNCH_BLEND_AUX_FMT(FMT)                                                                                             \
         if (aux == BLEND_AUX_Z) { WS_LAUNCH_BLEND_AUX(FMT, BLEND_AUX_Z); } else { WS_LAUNCH_BLEND_AUX(FMT, BLEND_AUX_ALPHA); }
         switch (p.format) {
@@ -1429,14 +1537,38 @@ static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux,
     return WS_OK;
 }
 
-int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const BlendAuxPlanes* ap) {
+int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const BlendAuxPlanes* ap, const BlendComposite* cpp) {
     const uint32_t ntiles = p.tiles_x * p.tiles_y;
     if (ntiles == 0) return WS_OK;
     const int aux = !ap ? BLEND_AUX_NONE : ((ap->depth || ap->median) ? BLEND_AUX_Z : (ap->alpha ? BLEND_AUX_ALPHA : BLEND_AUX_NONE));
     if (aux == BLEND_AUX_Z && !ap->z) return fail(WS_ERR_STATE, "blend: the depth planes need the frame's z plane");
     if (aux != BLEND_AUX_NONE && variant != 0) return fail(WS_ERR_UNSUPPORTED, "blend: auxiliary planes need the FAST blend");
+    const int comp = !cpp ? BLEND_COMP_NONE : ((cpp->load ? BLEND_COMP_LOAD : 0) | (cpp->occluder ? BLEND_COMP_OCCLUDE : 0));
+    if ((comp & BLEND_COMP_OCCLUDE) && (!ap || !ap->z)) return fail(WS_ERR_STATE, "blend: an occluder needs the frame's z plane");
+    if (comp != BLEND_COMP_NONE && variant != 0 && variant != 2)
+        return fail(WS_ERR_UNSUPPORTED, "blend: the composite needs the FAST blend or WS_BLEND_TARGET_PRECISION");
     const BlendAuxPlanes no_planes = {};
     const BlendAuxPlanes& planes = ap ? *ap : no_planes;
+    const BlendComposite no_comp = {};
+    const BlendComposite& cp = cpp ? *cpp : no_comp;
+    if (variant == 2 && comp != BLEND_COMP_NONE) {  // the composite form of k_blend_strict (load / occluder: run-time switches)
+        const uint32_t groups = ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
+        switch (p.format) {
+            case WS_FORMAT_RGBA32_FLOAT:
+                hipLaunchKernelGGL((k_blend_strict<WS_FORMAT_RGBA32_FLOAT, true, BlendAuxPlanes, BlendComposite>), dim3(groups), dim3(64), 0, stream, p, planes, cp);
+                break;
+            case WS_FORMAT_RGBA16_FLOAT:
+                hipLaunchKernelGGL((k_blend_strict<WS_FORMAT_RGBA16_FLOAT, true, BlendAuxPlanes, BlendComposite>), dim3(groups), dim3(64), 0, stream, p, planes, cp);
+                break;
+            case WS_FORMAT_RGBA8_UNORM:
+                hipLaunchKernelGGL((k_blend_strict<WS_FORMAT_RGBA8_UNORM, true, BlendAuxPlanes, BlendComposite>), dim3(groups), dim3(64), 0, stream, p, planes, cp);
+                break;
+            default:
+                return fail(WS_ERR_INVALID, "blend: unknown colour format");
+        }
+        WS_HIP(hipGetLastError());
+        return WS_OK;
+    }
     if (variant == 2) {  // WS_BLEND_TARGET_PRECISION: back to front, destination rounded after every splat
         const uint32_t groups = ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
         switch (p.format) {
@@ -1477,9 +1609,9 @@ int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const Bl
 #else
     if (variant == 1) return fail(WS_ERR_UNSUPPORTED, "blend variant 1 (k_blend_q) is only in the experimental build");
 #endif
-    if (p.qw == 2u && p.qh == 2u) return launch_blend_shape<2, 2>(p, stream, aux, planes);
-    if (p.qw == 4u && p.qh == 2u) return launch_blend_shape<4, 2>(p, stream, aux, planes);
-    if (p.qw == 4u && p.qh == 4u) return launch_blend_shape<4, 4>(p, stream, aux, planes);
+    if (p.qw == 2u && p.qh == 2u) return launch_blend_shape<2, 2>(p, stream, aux, planes, comp, cp);
+    if (p.qw == 4u && p.qh == 2u) return launch_blend_shape<4, 2>(p, stream, aux, planes, comp, cp);
+    if (p.qw == 4u && p.qh == 4u) return launch_blend_shape<4, 4>(p, stream, aux, planes, comp, cp);
     return fail(WS_ERR_INVALID, "blend: unsupported tile shape");
 }
 

@@ -190,6 +190,7 @@ struct ws_renderer {
     bool depth = false;                  // ws_renderer_enable_depth: K1 writes the z plane from the next prepare() on
     float* k1_depths = nullptr;          // the z plane the prepare() in progress writes (nullptr: depth off)
     bool prepared_depth = false;         // the last prepared frame wrote the z plane
+    float prepared_znear = 0.0f, prepared_zfar = 0.0f;  // K1Params::znear / zfar of the last prepare (the composite's NDC occluder)
     uint32_t* debug_consumed = nullptr;  // [tiles], capture mode only
     uint32_t* debug_walked = nullptr;    // [tiles][17], capture mode only
     uint4* blend_order = nullptr;        // [blend_order_blocks]: the blend's tiles, longest list first (k_blend_order)
@@ -1324,6 +1325,8 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
                          ? (uint32_t)r->ctx->bin_request : (uint32_t)BIN_NEVER;
     kp.znear = -kp.cam.proj[3 * 4 + 2] / kp.cam.proj[2 * 4 + 2];
     kp.zfar = -kp.cam.proj[3 * 4 + 2] / (kp.cam.proj[2 * 4 + 2] - 1.0f);
+    r->prepared_znear = kp.znear;
+    r->prepared_zfar = kp.zfar;
     // fade-in (preprocess.wgsl:196-203): dd = 5 |centre - xyz| / extend <= 10 because the centroid lies inside the
     // bbox and extend >= its radius; beyond walltime 11 s smoothstep(walltime - dd) is exactly 1 for every Gaussian.
     // (the clip box only removes Gaussians, so the bound holds for user boxes too)
@@ -1528,9 +1531,11 @@ int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_point
 
 extern "C" {
 
-// render() and render_aux(): planes == nullptr is the colour image alone (the launch render() has always made)
+// render(), render_aux() and render_composite(): planes == nullptr and comp == nullptr is the colour image alone over the
+// background (the launch render() has always made)
 static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
-                        size_t row_pitch_bytes, void* stream_v, const BlendAuxPlanes* planes) {
+                        size_t row_pitch_bytes, void* stream_v, const BlendAuxPlanes* planes,
+                        const BlendComposite* comp = nullptr) {
     if (!r || !pc || !d_rgba_out) return fail(WS_ERR_INVALID, "ws_renderer_render: null argument");
     if (!r->prepared || r->prepared_pc != pc)
         return fail(WS_ERR_STATE, "ws_renderer_render: prepare() was not called for this point cloud");
@@ -1602,7 +1607,7 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     if (km) km->begin(stream, false);
     if (r->timers) WS_HIP(hipEventRecord(r->ev[4], stream));
     if (r->ctx->debug_cut >= 1 && r->ctx->debug_cut <= 4) return WS_OK;  // analysis only
-    int rc = launch_blend(bp, r->blend_mode == WS_BLEND_TARGET_PRECISION ? 2 : r->ctx->blend_variant, stream, planes);
+    int rc = launch_blend(bp, r->blend_mode == WS_BLEND_TARGET_PRECISION ? 2 : r->ctx->blend_variant, stream, planes, comp);
     if (rc) return rc;
     r->frames_enqueued = bp.frame_seq;
     km_mark(km, r->blend_mode == WS_BLEND_TARGET_PRECISION ? "k_blend_strict" : "k_blend");
@@ -1629,11 +1634,8 @@ int ws_renderer_enable_depth(ws_renderer* r, int enable) {
     return WS_OK;
 }
 
-int ws_renderer_render_aux(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
-                           size_t row_pitch_bytes, const ws_aux_targets* aux, void* stream) {
-    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_render_aux: null renderer");
-    if (!aux || (!aux->depth && !aux->median_depth && !aux->alpha))
-        return render_frame(r, pc, background, d_rgba_out, row_pitch_bytes, stream, nullptr);
+// The checks of render_aux() on a ws_aux_targets with at least one plane; fills *bp (z: the frame's plane, if it has one).
+static int aux_planes_of(ws_renderer* r, const ws_pointcloud* pc, const ws_aux_targets* aux, BlendAuxPlanes* bp) {
     for (int i = 0; i < 4; ++i)
         if (aux->reserved[i]) return fail(WS_ERR_INVALID, "ws_renderer_render_aux: reserved words must be zero");
     const size_t row = (size_t)4 * r->vw;
@@ -1648,15 +1650,64 @@ int ws_renderer_render_aux(ws_renderer* r, const ws_pointcloud* pc, const float 
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need the production blend (no capture / timing / variants)");
     if (r->prepared && r->prepared_pc == pc && (aux->depth || aux->median_depth) && !r->prepared_depth)
         return fail(WS_ERR_STATE, "ws_renderer_render_aux: depth planes need ws_renderer_enable_depth before prepare()");
+    bp->depth = aux->depth;
+    bp->depth_pitch = aux->depth_pitch;
+    bp->median = aux->median_depth;
+    bp->median_pitch = aux->median_depth_pitch;
+    bp->alpha = aux->alpha;
+    bp->alpha_pitch = aux->alpha_pitch;
+    bp->z = r->prepared_depth ? r->depths : nullptr;
+    return WS_OK;
+}
+
+int ws_renderer_render_aux(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba_out,
+                           size_t row_pitch_bytes, const ws_aux_targets* aux, void* stream) {
+    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_render_aux: null renderer");
+    if (!aux || (!aux->depth && !aux->median_depth && !aux->alpha))
+        return render_frame(r, pc, background, d_rgba_out, row_pitch_bytes, stream, nullptr);
     BlendAuxPlanes bp;
-    bp.depth = aux->depth;
-    bp.depth_pitch = aux->depth_pitch;
-    bp.median = aux->median_depth;
-    bp.median_pitch = aux->median_depth_pitch;
-    bp.alpha = aux->alpha;
-    bp.alpha_pitch = aux->alpha_pitch;
-    bp.z = r->prepared_depth ? r->depths : nullptr;
+    const int rc = aux_planes_of(r, pc, aux, &bp);
+    if (rc) return rc;
     return render_frame(r, pc, background, d_rgba_out, row_pitch_bytes, stream, &bp);
+}
+
+int ws_renderer_render_composite(ws_renderer* r, const ws_pointcloud* pc, const float background[4], void* d_rgba,
+                                 size_t row_pitch_bytes, const ws_aux_targets* aux, const ws_composite_desc* comp,
+                                 void* stream) {
+    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_render_composite: null renderer");
+    if (comp) {
+        for (int i = 0; i < 4; ++i)
+            if (comp->reserved[i]) return fail(WS_ERR_INVALID, "ws_renderer_render_composite: reserved words must be zero");
+        if (comp->load > 1u) return fail(WS_ERR_INVALID, "ws_renderer_render_composite: load is 0 or 1");
+        if (comp->occluder_kind != WS_OCCLUDER_VIEW_Z && comp->occluder_kind != WS_OCCLUDER_NDC_DEPTH)
+            return fail(WS_ERR_INVALID, "ws_renderer_render_composite: unknown occluder kind");
+        if (comp->occluder && (comp->occluder_pitch < (size_t)4 * r->vw || (comp->occluder_pitch % 4) != 0 ||
+                               (reinterpret_cast<uintptr_t>(comp->occluder) % 4) != 0))
+            return fail(WS_ERR_INVALID, "ws_renderer_render_composite: occluder pitch below 4 x width, or pitch / pointer not 4-B aligned");
+    }
+    // no composite asked for: render_aux (the same launch, the same bytes)
+    if (!comp || (!comp->load && !comp->occluder))
+        return ws_renderer_render_aux(r, pc, background, d_rgba, row_pitch_bytes, aux, stream);
+    if (r->blend_mode == WS_BLEND_FAST_EXACT_CUT)
+        return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_composite: load / occluder need WS_BLEND_FAST or WS_BLEND_TARGET_PRECISION");
+    if (r->capture || r->blend_timing || r->ctx->blend_variant != 0 || r->ctx->blend_dma || r->ctx->debug_cut)
+        return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_composite: load / occluder need the production blend (no capture / timing / variants)");
+    BlendAuxPlanes bp = {};
+    if (aux && (aux->depth || aux->median_depth || aux->alpha)) {
+        const int rc = aux_planes_of(r, pc, aux, &bp);
+        if (rc) return rc;
+    }
+    if (comp->occluder && r->prepared && r->prepared_pc == pc && !r->prepared_depth)
+        return fail(WS_ERR_STATE, "ws_renderer_render_composite: an occluder needs ws_renderer_enable_depth before prepare()");
+    bp.z = r->prepared_depth ? r->depths : nullptr;
+    BlendComposite c;
+    c.occluder = comp->occluder;
+    c.occluder_pitch = comp->occluder_pitch;
+    c.znear = r->prepared_znear;
+    c.zfar = r->prepared_zfar;
+    c.occ_ndc = comp->occluder_kind == WS_OCCLUDER_NDC_DEPTH ? 1 : 0;
+    c.load = comp->load ? 1 : 0;
+    return render_frame(r, pc, background, d_rgba, row_pitch_bytes, stream, &bp, &c);
 }
 
 int ws_renderer_download_depths(ws_renderer* r, uint32_t capacity, float* z, uint32_t* num_visible) {

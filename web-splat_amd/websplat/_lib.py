@@ -152,6 +152,15 @@ class ws_aux_targets(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+WS_OCCLUDER_VIEW_Z = 0
+WS_OCCLUDER_NDC_DEPTH = 1
+
+
+class ws_composite_desc(C.Structure):
+    _fields_ = [("load", C.c_uint32), ("occluder_kind", C.c_uint32), ("occluder", C.c_void_p), ("occluder_pitch", C.c_size_t),
+                ("reserved", C.c_uint32 * 4)]
+
+
 assert C.sizeof(ws_camera_uniform) == 272
 assert C.sizeof(ws_settings_uniform) == 80
 assert C.sizeof(ws_gaussian_quantization) == 64
@@ -265,6 +274,8 @@ SIGNATURES = {
     "ws_renderer_enable_depth": (C.c_int, [_P, C.c_int]),
     "ws_renderer_render_aux": (C.c_int, [_P, _P, _f32p, _P, C.c_size_t, C.POINTER(ws_aux_targets), _P]),
     "ws_renderer_download_depths": (C.c_int, [_P, C.c_uint32, _f32p, _u32p]),
+    "ws_renderer_render_composite": (C.c_int, [_P, _P, _f32p, _P, C.c_size_t, C.POINTER(ws_aux_targets),
+                                               C.POINTER(ws_composite_desc), _P]),
     "ws_sorter_create": (C.c_int, [_P, C.c_uint32, _PP]),
     "ws_sorter_destroy": (None, [_P]),
     "ws_sorter_sort": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),

@@ -611,9 +611,12 @@ class GaussianRenderer:
         self._aux = {}            # plane name -> renderer-owned device buffer (H x W f32) of render_aux
         self._aux_shape = None
         self._aux_last = ()       # the planes the last render_aux wrote
+        self._occluder = None     # renderer-owned device copy (H x W f32) of render_composite's numpy occluder
+        self._occluder_shape = None
 
     def close(self):
         self._free_aux()
+        self._free_occluder()
         if self._own_target:
             self.ctx.free(self._own_target)
             self._own_target = None
@@ -787,6 +790,86 @@ class GaussianRenderer:
                                          C.byref(t), C.c_void_p(stream or 0)))
         self._aux_last = tuple(want)
         return self._own_target
+
+    def _target_for_viewport(self) -> int:
+        w, h = self._viewport
+        if self._own_target_shape != (w, h):
+            if self._own_target:
+                self.ctx.free(self._own_target)
+            self._own_target = self.ctx.malloc(w * h * self.texel_bytes)
+            self._own_target_shape = (w, h)
+        return self._own_target
+
+    def upload_target(self, image: np.ndarray, stream=None):
+        """Copy a host image into the renderer-owned target (prepared viewport; H x W x 4 of the target's dtype: float32,
+        float16 or uint8), e.g. the sky or mesh pass that render_composite(load=True) puts the splats over.  Ordered on
+        `stream` and waited for."""
+        w, h = self._viewport
+        img = np.ascontiguousarray(image)
+        if img.shape != (h, w, 4) or img.dtype != self.np_dtype:
+            raise ValueError(f"upload_target: want a ({h}, {w}, 4) {np.dtype(self.np_dtype).name} image, got {img.shape} {img.dtype}")
+        ptr = self._target_for_viewport()
+        check(lib.ws_memcpy_h2d(self.ctx.handle, C.c_void_p(ptr), img.ctypes.data_as(C.c_void_p), img.nbytes,
+                                C.c_void_p(stream or 0)))
+        return ptr
+
+    def render_composite(self, pc: PointCloud, target_ptr: int = None, pitch: int = None, load=True, occluder=None,
+                         occluder_kind="view_z", occluder_pitch: int = None, depth=False, median_depth=False, alpha=False,
+                         background=(0.0, 0.0, 0.0, 0.0), stream=None):
+        """ws_renderer_render_composite: the splats over the texels the target holds (load=True: out = C + T * dst, dst decoded
+        from the target's format; load=False: over `background`, as render()) and, with an occluder, behind an opaque depth
+        buffer: splat i takes part at pixel p iff z_i < D(p) (its centre depth, in f32).
+
+        occluder: None, an (H, W) float32 numpy array (uploaded on `stream` into a renderer-owned buffer), or a device pointer
+        with `occluder_pitch` bytes per row (default 4 x W).  occluder_kind "view_z": D = the value (view-space depth, positive
+        in front of the camera; +inf = nothing there, NaN keeps no splat); "ndc": a [0, 1] depth-buffer value d under the
+        frame's own projection, D = (n f) / (f - d (f - n)) in f32 with no FMA, d >= 1 = +inf.  An occluder needs
+        enable_depth() before prepare().  target_ptr None = the renderer-owned target (fill it with upload_target()).
+        depth / median_depth / alpha: the planes of render_aux(), over the unoccluded splats (download_aux())."""
+        w, h = self._viewport
+        if target_ptr is None:
+            target_ptr = self._target_for_viewport()
+        if pitch is None:
+            pitch = w * self.texel_bytes
+        desc = L.ws_composite_desc()
+        desc.load = 1 if load else 0
+        desc.occluder_kind = {"view_z": L.WS_OCCLUDER_VIEW_Z, "ndc": L.WS_OCCLUDER_NDC_DEPTH}[occluder_kind]
+        if occluder is not None:
+            if isinstance(occluder, np.ndarray):
+                occ = np.ascontiguousarray(occluder, dtype=np.float32)
+                if occ.shape != (h, w):
+                    raise ValueError(f"render_composite: want an ({h}, {w}) occluder, got {occ.shape}")
+                if getattr(self, "_occluder_shape", None) != (w, h):
+                    self._free_occluder()
+                    self._occluder = self.ctx.malloc(w * h * 4)
+                    self._occluder_shape = (w, h)
+                # (on the frame's stream: a frame still in flight there reads the previous plane)
+                check(lib.ws_memcpy_h2d(self.ctx.handle, C.c_void_p(self._occluder), occ.ctypes.data_as(C.c_void_p), occ.nbytes,
+                                        C.c_void_p(stream or 0)))
+                desc.occluder, desc.occluder_pitch = self._occluder, w * 4
+            else:
+                desc.occluder, desc.occluder_pitch = int(occluder), int(occluder_pitch if occluder_pitch is not None else w * 4)
+        if self._aux_shape != (w, h):
+            self._free_aux()
+            self._aux_shape = (w, h)
+        want = [name for name, on in (("depth", depth), ("median_depth", median_depth), ("alpha", alpha)) if on]
+        t = L.ws_aux_targets()
+        for name in want:
+            if name not in self._aux:
+                self._aux[name] = self.ctx.malloc(w * h * 4)
+            setattr(t, name, C.c_void_p(self._aux[name]))
+            setattr(t, name + "_pitch", w * 4)
+        bg = (C.c_float * 4)(*[float(x) for x in background])
+        check(lib.ws_renderer_render_composite(self.handle, pc.handle, bg, C.c_void_p(target_ptr), pitch, C.byref(t),
+                                               C.byref(desc), C.c_void_p(stream or 0)))
+        self._aux_last = tuple(want)
+        return target_ptr
+
+    def _free_occluder(self):
+        if getattr(self, "_occluder", None):
+            self.ctx.free(self._occluder)
+        self._occluder = None
+        self._occluder_shape = None
 
     def download_aux(self) -> dict:
         """{plane name: H x W float32} of the planes the last render_aux() wrote (syncs)."""
