@@ -21,6 +21,9 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "blend_stage.h"
 #include "emit_gen.h"
 #include "lookback.h"
@@ -364,15 +367,16 @@ __device__ __forceinline__ void store_aux(const BlendAuxPlanes& a, uint32_t px, 
     if (a.depth) reinterpret_cast<float*>(reinterpret_cast<char*>(a.depth) + (size_t)py * a.depth_pitch)[px] = wsum > 0.0f ? dz / wsum : 0.0f;
     if (a.median) reinterpret_cast<float*>(reinterpret_cast<char*>(a.median) + (size_t)py * a.median_pitch)[px] = T <= 0.5f ? med : 0.0f;
 }
-// k_blend's trailing argument pack: empty (the colour image only -- the kernel-argument layout of the forms without planes,
-// hidden arguments included, stays what it is without them) or the planes
-__device__ __forceinline__ BlendAuxPlanes blend_aux_of() { return BlendAuxPlanes{}; }
-__device__ __forceinline__ BlendAuxPlanes blend_aux_of(const BlendAuxPlanes& a) { return a; }
-__device__ __forceinline__ BlendAuxPlanes blend_aux_of(const BlendAuxPlanes& a, const BlendComposite&) { return a; }
-// ... and the composite forms' second trailing argument (ws_renderer_render_composite)
-__device__ __forceinline__ BlendComposite blend_comp_of() { return BlendComposite{}; }
-__device__ __forceinline__ BlendComposite blend_comp_of(const BlendAuxPlanes&) { return BlendComposite{}; }
-__device__ __forceinline__ BlendComposite blend_comp_of(const BlendAuxPlanes&, const BlendComposite& c) { return c; }
+// k_blend's trailing argument pack (BlendForm::tail_args): empty (the colour image only -- the kernel-argument layout of the forms
+// without planes, hidden arguments included, stays what it is without them), the planes, or the planes and the composite
+// (ws_renderer_render_composite).  The argument of type T, or an empty T where the form has none.
+template <typename T>
+__device__ __forceinline__ T blend_tail() { return T{}; }
+template <typename T, typename A, typename... Rest>
+__device__ __forceinline__ T blend_tail(const A& a, const Rest&... rest) {
+    if constexpr (std::is_same<T, A>::value) return a;
+    else return blend_tail<T>(rest...);
+}
 // LOAD: the texel the target holds at (px, py), decoded from its format -- f32, f16, or unorm8 as k / 255 (k_display's decode)
 template <int FORMAT>
 __device__ __forceinline__ float4 load_pixel(const BlendParams& p, uint32_t px, uint32_t py) {
@@ -530,7 +534,7 @@ __device__ __forceinline__ RawSplat blend_fetch_raw(const BlendParams& p, uint2 
     return blend_gather(p, blend_entry_idx<STAGE>(p, range, hi, tid));
 }
 
-// ---- gfx950 LDS-DMA staging (k_blend<..., DMA = true>) ------------------------------------------------------------------
+// ---- gfx950 LDS-DMA staging (the dma forms of k_blend) ---------------------------------------------------------------------
 // The gather above holds five VGPRs per thread from the load to the decode, a whole batch later; under the 64-VGPR cap
 // (two 1024-thread workgroups per CU) that is what made every deeper prefetch fail.  global_load_lds_dwordx4 /
 // _dword write the record straight into LDS: nothing is held while the load flies.  The destination of lane l is the
@@ -687,21 +691,22 @@ __device__ __forceinline__ uint32_t blend_stamp() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     return (uint32_t)t;
 }
-template <int FORMAT, int QW, int QH, bool MULTI, bool CAPTURE, bool DMA, bool TIMING = false, bool EXACT = false, int AUX = BLEND_AUX_NONE,
-          int COMP = BLEND_COMP_NONE, typename... Aux>
-__global__ __launch_bounds__(64 * QW * QH, (EXACT && QW * QH == 16) ? 8 : (((AUX == BLEND_AUX_Z || (COMP & BLEND_COMP_OCCLUDE)) && !MULTI && QW * QH != 8) ? WS_BLEND_AUX_MINWAVES : WS_BLEND_MINWAVES)) void k_blend(const BlendParams p,
+// The form's minimum waves per SIMD (__launch_bounds__): the exact cut's 4x4 forms 8, the depth forms with one tile per workgroup
+// WS_BLEND_AUX_MINWAVES (above), every other form the default.
+constexpr int blend_min_waves(BlendForm f) {
+    return (f.exact && f.waves() == 16) ? 8 : ((f.stage_z() && !f.multi && f.waves() != 8) ? WS_BLEND_AUX_MINWAVES : WS_BLEND_MINWAVES);
+}
+template <uint32_t FORM, typename... Tail>
+__global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(BlendForm::of(FORM))) void k_blend(const BlendParams p,
                                                                                                     const uint32_t tpw_log2_arg,
-                                                                                                    const Aux... aux_planes) {
-    static_assert(!TIMING || (!MULTI && !DMA && !CAPTURE), "the timing build instruments the production form only");
-    static_assert(!EXACT || (!CAPTURE && !DMA && !TIMING), "the exact cut-off decision belongs to the production launch");
-    static_assert((AUX == BLEND_AUX_NONE && COMP == BLEND_COMP_NONE) || (!CAPTURE && !DMA && !TIMING && !EXACT),
-                  "the auxiliary planes and the composite belong to the FAST production launch");
-    static_assert(sizeof...(Aux) == (COMP != BLEND_COMP_NONE ? 2 : (AUX != BLEND_AUX_NONE ? 1 : 0)),
-                  "the AUX forms take the planes, the COMP forms the planes and the composite, the others nothing");
-    const BlendAuxPlanes ax = blend_aux_of(aux_planes...);
-    const BlendComposite cp = blend_comp_of(aux_planes...);
-    constexpr bool OCC = (COMP & BLEND_COMP_OCCLUDE) != 0;
-    constexpr bool STAGE_Z = AUX == BLEND_AUX_Z || OCC;  // the third LDS plane: z beside every staged record
+                                                                                                    const Tail... tail) {
+    constexpr BlendForm F = BlendForm::of(FORM);
+    static_assert(F.kernel == BLEND_K && blend_form_legal(F) && sizeof...(Tail) == F.tail_args(), "not a form of k_blend (blend_form.h)");
+    constexpr int FORMAT = F.format, QW = F.qw, QH = F.qh, AUX = F.aux, COMP = F.comp;
+    constexpr bool MULTI = F.multi, CAPTURE = F.capture, DMA = F.dma, TIMING = F.timing, EXACT = F.exact;
+    constexpr bool OCC = F.occlude(), STAGE_Z = F.stage_z();
+    const BlendAuxPlanes ax = blend_tail<BlendAuxPlanes>(tail...);
+    const BlendComposite cp = blend_tail<BlendComposite>(tail...);
     uint32_t tm[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // TIMING: cycles per phase, this wave (SGPRs)
     uint32_t tm_batches = 0u, tm_real0 = 0u;
     const uint32_t tm_start = blend_stamp<TIMING>();
@@ -1206,12 +1211,15 @@ __device__ __forceinline__ float quantize_target(float v) {
 // load starts the destination from the target's texel instead of the quantised background, which is what a wgpu pass with
 // LoadOp::Load and this pipeline computes, rounding for rounding; an occluder reads z[idx] of every staged splat and keeps a
 // pair only while z < D(p).  Both are run-time switches here: throughput is not this kernel's point.
-template <int FORMAT, bool COMP = false, typename... A>
-__global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p, const A... comp_args) {
+template <uint32_t FORM, typename... Tail>
+__global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p, const Tail... tail) {
 #pragma clang fp contract(off)  // the oracle's arithmetic: separate multiplies and adds
-    static_assert(sizeof...(A) == (COMP ? 2 : 0), "the composite form takes the planes and the composite, the other nothing");
-    const BlendAuxPlanes ax = blend_aux_of(comp_args...);
-    const BlendComposite cp = blend_comp_of(comp_args...);
+    constexpr BlendForm F = BlendForm::of(FORM);
+    static_assert(F.kernel == BLEND_K_STRICT && blend_form_legal(F) && sizeof...(Tail) == F.tail_args(), "not a form of k_blend_strict");
+    constexpr int FORMAT = F.format;
+    constexpr bool COMP = F.comp != BLEND_COMP_NONE;
+    const BlendAuxPlanes ax = blend_tail<BlendAuxPlanes>(tail...);
+    const BlendComposite cp = blend_tail<BlendComposite>(tail...);
     const uint32_t b = blockIdx.x;
     if (b == 0 && threadIdx.x == 0 && p.sticky) {  // as in k_blend
         const uint32_t bits = p.counters->overflow;
@@ -1406,213 +1414,69 @@ int launch_blend_order(const uint2* tile_ranges, const FrameCounters* counters, 
     return WS_OK;
 }
 
-template <int QW, int QH>
-static int launch_blend_shape(const BlendParams& p, hipStream_t stream, int aux, const BlendAuxPlanes& ap, int comp,
-                              const BlendComposite& cp) {
-    const BlendShape sh = blend_shape(QW, QH);
-    uint32_t tpw_log2 = p.tpw_log2 >= 0 ? (uint32_t)p.tpw_log2 : blend_tpw_log2(p.tiles_x, p.tiles_y, sh);
-    if (tpw_log2 > sh.tbx_log2 + sh.tby_log2) tpw_log2 = sh.tbx_log2 + sh.tby_log2;
-    const uint32_t grid = blend_grid_blocks(p.tiles_x, p.tiles_y, sh, tpw_log2);
-    constexpr int NT = 64 * QW * QH;
-    const bool capture = p.debug_consumed != nullptr || p.debug_walked != nullptr;  // analysis build of the kernel
-    // tuning knob (WS_BLEND_LDS_PAD_KB): unused dynamic LDS that lowers the number of blend workgroups per CU
-    const size_t pad = (size_t)p.lds_pad_kb * 1024u;
-    if (comp != BLEND_COMP_NONE) {
-        // the composite: the launches of the auxiliary planes below (FAST production forms, all three formats), with LOAD and /
-        // or OCCLUDE; no plane = the coverage form with a null alpha pointer (one uniform branch at the store)
-        if (capture || p.debug_timing || p.dma || p.exact_cut || p.async_staging)
-            return fail(WS_ERR_UNSUPPORTED, "blend: the composite needs the FAST production launch (no capture / timing / DMA / exact cut)");
-        if (comp < BLEND_COMP_LOAD || comp > (BLEND_COMP_LOAD | BLEND_COMP_OCCLUDE)) return fail(WS_ERR_INVALID, "blend: unknown composite form");
-#define WS_LAUNCH_BLEND_COMP(FMT, AUX_, COMP_)                                                                                   \
-        if (tpw_log2 > 0u)                                                                                                       \
-            hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, false, AUX_, COMP_, BlendAuxPlanes, BlendComposite>), \
-                               dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap, cp);                                          \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, false, AUX_, COMP_, BlendAuxPlanes, BlendComposite>), \
-                               dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap, cp)
-#define WS_LAUNCH_BLEND_COMP_AUX(FMT, AUX_)                                                                                      \
-        if (comp == BLEND_COMP_LOAD) { WS_LAUNCH_BLEND_COMP(FMT, AUX_, BLEND_COMP_LOAD); }                                       \
-        else if (comp == BLEND_COMP_OCCLUDE) { WS_LAUNCH_BLEND_COMP(FMT, AUX_, BLEND_COMP_OCCLUDE); }                            \
-        else { WS_LAUNCH_BLEND_COMP(FMT, AUX_, BLEND_COMP_LOAD | BLEND_COMP_OCCLUDE); }
-#define WS_LAUNCH_BLEND_COMP_FMT(FMT)                                                                                            \
-        if (aux == BLEND_AUX_Z) { WS_LAUNCH_BLEND_COMP_AUX(FMT, BLEND_AUX_Z); } else { WS_LAUNCH_BLEND_COMP_AUX(FMT, BLEND_AUX_ALPHA); }
-        switch (p.format) {
-            case WS_FORMAT_RGBA32_FLOAT: WS_LAUNCH_BLEND_COMP_FMT(WS_FORMAT_RGBA32_FLOAT); break;
-            case WS_FORMAT_RGBA16_FLOAT: WS_LAUNCH_BLEND_COMP_FMT(WS_FORMAT_RGBA16_FLOAT); break;
-            case WS_FORMAT_RGBA8_UNORM: WS_LAUNCH_BLEND_COMP_FMT(WS_FORMAT_RGBA8_UNORM); break;
-            default: return fail(WS_ERR_INVALID, "blend: unknown colour format");
-        }
-#undef WS_LAUNCH_BLEND_COMP_FMT
-#undef WS_LAUNCH_BLEND_COMP_AUX
-#undef WS_LAUNCH_BLEND_COMP
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
-    if (aux != BLEND_AUX_NONE) {
-        // the auxiliary planes: the FAST production forms only -- one tile or several per workgroup, split halves (4x2 with
-        // range_row_shift), the longest-first order (p.order) -- all three colour formats
-        if (capture || p.debug_timing || p.dma || p.exact_cut || p.async_staging)
-            return fail(WS_ERR_UNSUPPORTED, "blend: auxiliary planes need the FAST production launch (no capture / timing / DMA / exact cut)");
-        if (aux != BLEND_AUX_ALPHA && aux != BLEND_AUX_Z) return fail(WS_ERR_INVALID, "blend: unknown auxiliary form");
-#define WS_LAUNCH_BLEND_AUX(FMT, AUX_)                                                                                           \
-        if (tpw_log2 > 0u)                                                                                                       \
-            hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, false, AUX_, BLEND_COMP_NONE, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap);  \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, false, AUX_, BLEND_COMP_NONE, BlendAuxPlanes>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2, ap)
-#define WS_LAUNCH_BLEND_AUX_FMT(FMT)                                                                                             \
-        if (aux == BLEND_AUX_Z) { WS_LAUNCH_BLEND_AUX(FMT, BLEND_AUX_Z); } else { WS_LAUNCH_BLEND_AUX(FMT, BLEND_AUX_ALPHA); }
-        switch (p.format) {
-            case WS_FORMAT_RGBA32_FLOAT: WS_LAUNCH_BLEND_AUX_FMT(WS_FORMAT_RGBA32_FLOAT); break;
-            case WS_FORMAT_RGBA16_FLOAT: WS_LAUNCH_BLEND_AUX_FMT(WS_FORMAT_RGBA16_FLOAT); break;
-            case WS_FORMAT_RGBA8_UNORM: WS_LAUNCH_BLEND_AUX_FMT(WS_FORMAT_RGBA8_UNORM); break;
-            default: return fail(WS_ERR_INVALID, "blend: unknown colour format");
-        }
-#undef WS_LAUNCH_BLEND_AUX_FMT
-#undef WS_LAUNCH_BLEND_AUX
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
-    if (p.debug_timing) {  // analysis: the production form (one tile per workgroup, f32 target, 32x32) with time stamps
-        if (QW != 4 || QH != 4 || p.format != WS_FORMAT_RGBA32_FLOAT || capture || tpw_log2 > 0u || p.dma)
-            return fail(WS_ERR_UNSUPPORTED, "blend timing: 32x32 tiles, rgba32float target, one tile per workgroup, no capture / DMA");
-        hipLaunchKernelGGL((k_blend<WS_FORMAT_RGBA32_FLOAT, 4, 4, false, false, false, true>), dim3(grid), dim3(1024), pad, stream, p,
-                           tpw_log2);
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
+// The one place a BlendForm becomes an instantiation: the kernel the form names, with the trailing arguments the form has.
+struct BlendLaunch {
+    const BlendParams& p;
+    uint32_t tpw_log2, grid;
+    size_t pad;  // tuning knob (WS_BLEND_LDS_PAD_KB): unused dynamic LDS that lowers the number of blend workgroups per CU
+    hipStream_t stream;
+    const BlendAuxPlanes& ap;
+    const BlendComposite& cp;
+};
+template <uint32_t FORM>
+static void launch_blend_form(const BlendLaunch& l) {
+    constexpr BlendForm F = BlendForm::of(FORM);
+    if constexpr (F.kernel == BLEND_K && F.tail_args() == 2)
+        hipLaunchKernelGGL((k_blend<FORM, BlendAuxPlanes, BlendComposite>), dim3(l.grid), dim3(64 * F.waves()), l.pad, l.stream, l.p, l.tpw_log2, l.ap, l.cp);
+    else if constexpr (F.kernel == BLEND_K && F.tail_args() == 1)
+        hipLaunchKernelGGL((k_blend<FORM, BlendAuxPlanes>), dim3(l.grid), dim3(64 * F.waves()), l.pad, l.stream, l.p, l.tpw_log2, l.ap);
+    else if constexpr (F.kernel == BLEND_K)
+        hipLaunchKernelGGL((k_blend<FORM>), dim3(l.grid), dim3(64 * F.waves()), l.pad, l.stream, l.p, l.tpw_log2);
+    else if constexpr (F.kernel == BLEND_K_STRICT && F.tail_args() == 2)
+        hipLaunchKernelGGL((k_blend_strict<FORM, BlendAuxPlanes, BlendComposite>), dim3(l.grid), dim3(64), 0, l.stream, l.p, l.ap, l.cp);
+    else if constexpr (F.kernel == BLEND_K_STRICT)
+        hipLaunchKernelGGL((k_blend_strict<FORM>), dim3(l.grid), dim3(64), 0, l.stream, l.p);
 #ifdef WS_EXPERIMENTAL
-    // the barrier-free form (k_blend2): one 32x32 tile per workgroup, production launch only
-    if (p.async_staging && QW == 4 && QH == 4 && !capture && tpw_log2 == 0u && !p.dma && p.range_row_shift == 0u) {
-        switch (p.format) {
-            case WS_FORMAT_RGBA32_FLOAT: hipLaunchKernelGGL(k_blend2<WS_FORMAT_RGBA32_FLOAT>, dim3(grid), dim3(1024), pad, stream, p); break;
-            case WS_FORMAT_RGBA16_FLOAT: hipLaunchKernelGGL(k_blend2<WS_FORMAT_RGBA16_FLOAT>, dim3(grid), dim3(1024), pad, stream, p); break;
-            case WS_FORMAT_RGBA8_UNORM: hipLaunchKernelGGL(k_blend2<WS_FORMAT_RGBA8_UNORM>, dim3(grid), dim3(1024), pad, stream, p); break;
-            default: return fail(WS_ERR_INVALID, "blend: unknown colour format");
-        }
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
-#else
-    if (p.async_staging) return fail(WS_ERR_UNSUPPORTED, "barrier-free staging (k_blend2) is only in the experimental build");
-#endif
-#ifdef WS_EXPERIMENTAL  // (LDS-DMA staging, WS_BLEND_DMA=1: measured neutral; instantiated in the experimental build only)
-#define WS_LAUNCH_BLEND_DMA(FMT)                                                                                          \
-    if (!capture && tpw_log2 > 0u && p.dma)                                                                               \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, true>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2);    \
-    else if (!capture && p.dma)                                                                                           \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, true>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2);   \
+    else if constexpr (F.kernel == BLEND_K_Q)
+        hipLaunchKernelGGL(k_blend_q<F.format>, dim3(l.grid), dim3(64), 0, l.stream, l.p);
     else
-#else
-#define WS_LAUNCH_BLEND_DMA(FMT)
-    if (p.dma) return fail(WS_ERR_UNSUPPORTED, "LDS-DMA staging is only in the experimental build");
+        hipLaunchKernelGGL(k_blend2<F.format>, dim3(l.grid), dim3(1024), l.pad, l.stream, l.p);
 #endif
-#define WS_LAUNCH_BLEND(FMT)                                                                                              \
-    WS_LAUNCH_BLEND_DMA(FMT)                                                                                              \
-    if (p.exact_cut && !capture && tpw_log2 > 0u)                                                                         \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false, false, true>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2);  \
-    else if (p.exact_cut && !capture)                                                                                     \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false, false, true>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2); \
-    else if (capture)                                                                                                          \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, true, false>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2);    \
-    else if (tpw_log2 > 0u)                                                                                               \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, true, false, false>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2);   \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((k_blend<FMT, QW, QH, false, false, false>), dim3(grid), dim3(NT), pad, stream, p, tpw_log2)
-    switch (p.format) {
-        case WS_FORMAT_RGBA32_FLOAT:
-            WS_LAUNCH_BLEND(WS_FORMAT_RGBA32_FLOAT);
-            break;
-        case WS_FORMAT_RGBA16_FLOAT:
-            WS_LAUNCH_BLEND(WS_FORMAT_RGBA16_FLOAT);
-            break;
-        case WS_FORMAT_RGBA8_UNORM:
-            WS_LAUNCH_BLEND(WS_FORMAT_RGBA8_UNORM);
-            break;
-        default:
-            return fail(WS_ERR_INVALID, "blend: unknown colour format");
-    }
-#undef WS_LAUNCH_BLEND
-#undef WS_LAUNCH_BLEND_DMA
-    WS_HIP(hipGetLastError());
-    return WS_OK;
+}
+constexpr BlendFormTable BLEND_FORMS = blend_form_table();
+template <size_t... I>
+static bool launch_blend_form(uint32_t form, const BlendLaunch& l, std::index_sequence<I...>) {
+    return ((form == BLEND_FORMS.bits[I] && (launch_blend_form<BLEND_FORMS.bits[I]>(l), true)) || ...);
 }
 
 int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const BlendAuxPlanes* ap, const BlendComposite* cpp) {
     const uint32_t ntiles = p.tiles_x * p.tiles_y;
     if (ntiles == 0) return WS_OK;
-    const int aux = !ap ? BLEND_AUX_NONE : ((ap->depth || ap->median) ? BLEND_AUX_Z : (ap->alpha ? BLEND_AUX_ALPHA : BLEND_AUX_NONE));
-    if (aux == BLEND_AUX_Z && !ap->z) return fail(WS_ERR_STATE, "blend: the depth planes need the frame's z plane");
-    if (aux != BLEND_AUX_NONE && variant != 0) return fail(WS_ERR_UNSUPPORTED, "blend: auxiliary planes need the FAST blend");
-    const int comp = !cpp ? BLEND_COMP_NONE : ((cpp->load ? BLEND_COMP_LOAD : 0) | (cpp->occluder ? BLEND_COMP_OCCLUDE : 0));
-    if ((comp & BLEND_COMP_OCCLUDE) && (!ap || !ap->z)) return fail(WS_ERR_STATE, "blend: an occluder needs the frame's z plane");
-    if (comp != BLEND_COMP_NONE && variant != 0 && variant != 2)
-        return fail(WS_ERR_UNSUPPORTED, "blend: the composite needs the FAST blend or WS_BLEND_TARGET_PRECISION");
+    const BlendShape sh = blend_shape(p.qw, p.qh);
+    uint32_t tpw_log2 = p.tpw_log2 >= 0 ? (uint32_t)p.tpw_log2 : blend_tpw_log2(p.tiles_x, p.tiles_y, sh);
+    if (tpw_log2 > sh.tbx_log2 + sh.tby_log2) tpw_log2 = sh.tbx_log2 + sh.tby_log2;
+    BlendRequest q{};
+    q.format = p.format, q.qw = p.qw, q.qh = p.qh;
+    q.multi = tpw_log2 > 0u;
+    q.split = p.range_row_shift != 0u;
+    q.mode.capture = p.debug_consumed != nullptr || p.debug_walked != nullptr;  // analysis build of the kernel
+    q.mode.timing = p.debug_timing != nullptr;
+    q.mode.dma = p.dma, q.mode.variant = variant, q.mode.exact_cut = p.exact_cut != 0, q.mode.async_staging = p.async_staging != 0;
+    q.aux = !ap ? BLEND_AUX_NONE : ((ap->depth || ap->median) ? BLEND_AUX_Z : (ap->alpha ? BLEND_AUX_ALPHA : BLEND_AUX_NONE));
+    q.comp = !cpp ? BLEND_COMP_NONE : ((cpp->load ? BLEND_COMP_LOAD : 0) | (cpp->occluder ? BLEND_COMP_OCCLUDE : 0));
+    q.has_z = ap && ap->z;
+    const BlendChoice c = blend_form_of(q);
+    if (c.rc) return fail(c.rc, c.why);
     const BlendAuxPlanes no_planes = {};
-    const BlendAuxPlanes& planes = ap ? *ap : no_planes;
     const BlendComposite no_comp = {};
-    const BlendComposite& cp = cpp ? *cpp : no_comp;
-    if (variant == 2 && comp != BLEND_COMP_NONE) {  // the composite form of k_blend_strict (load / occluder: run-time switches)
-        const uint32_t groups = ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
-        switch (p.format) {
-            case WS_FORMAT_RGBA32_FLOAT:
-                hipLaunchKernelGGL((k_blend_strict<WS_FORMAT_RGBA32_FLOAT, true, BlendAuxPlanes, BlendComposite>), dim3(groups), dim3(64), 0, stream, p, planes, cp);
-                break;
-            case WS_FORMAT_RGBA16_FLOAT:
-                hipLaunchKernelGGL((k_blend_strict<WS_FORMAT_RGBA16_FLOAT, true, BlendAuxPlanes, BlendComposite>), dim3(groups), dim3(64), 0, stream, p, planes, cp);
-                break;
-            case WS_FORMAT_RGBA8_UNORM:
-                hipLaunchKernelGGL((k_blend_strict<WS_FORMAT_RGBA8_UNORM, true, BlendAuxPlanes, BlendComposite>), dim3(groups), dim3(64), 0, stream, p, planes, cp);
-                break;
-            default:
-                return fail(WS_ERR_INVALID, "blend: unknown colour format");
-        }
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
-    if (variant == 2) {  // WS_BLEND_TARGET_PRECISION: back to front, destination rounded after every splat
-        const uint32_t groups = ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
-        switch (p.format) {
-            case WS_FORMAT_RGBA32_FLOAT:
-                hipLaunchKernelGGL(k_blend_strict<WS_FORMAT_RGBA32_FLOAT>, dim3(groups), dim3(64), 0, stream, p);
-                break;
-            case WS_FORMAT_RGBA16_FLOAT:
-                hipLaunchKernelGGL(k_blend_strict<WS_FORMAT_RGBA16_FLOAT>, dim3(groups), dim3(64), 0, stream, p);
-                break;
-            case WS_FORMAT_RGBA8_UNORM:
-                hipLaunchKernelGGL(k_blend_strict<WS_FORMAT_RGBA8_UNORM>, dim3(groups), dim3(64), 0, stream, p);
-                break;
-            default:
-                return fail(WS_ERR_INVALID, "blend: unknown colour format");
-        }
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
-#ifdef WS_EXPERIMENTAL
-    if (variant == 1) {  // one wave per 8x8 quadrant, no LDS (cross-check)
-        const uint32_t groups = ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
-        switch (p.format) {
-            case WS_FORMAT_RGBA32_FLOAT:
-                hipLaunchKernelGGL(k_blend_q<WS_FORMAT_RGBA32_FLOAT>, dim3(groups), dim3(64), 0, stream, p);
-                break;
-            case WS_FORMAT_RGBA16_FLOAT:
-                hipLaunchKernelGGL(k_blend_q<WS_FORMAT_RGBA16_FLOAT>, dim3(groups), dim3(64), 0, stream, p);
-                break;
-            case WS_FORMAT_RGBA8_UNORM:
-                hipLaunchKernelGGL(k_blend_q<WS_FORMAT_RGBA8_UNORM>, dim3(groups), dim3(64), 0, stream, p);
-                break;
-            default:
-                return fail(WS_ERR_INVALID, "blend: unknown colour format");
-        }
-        WS_HIP(hipGetLastError());
-        return WS_OK;
-    }
-#else
-    if (variant == 1) return fail(WS_ERR_UNSUPPORTED, "blend variant 1 (k_blend_q) is only in the experimental build");
-#endif
-    if (p.qw == 2u && p.qh == 2u) return launch_blend_shape<2, 2>(p, stream, aux, planes, comp, cp);
-    if (p.qw == 4u && p.qh == 2u) return launch_blend_shape<4, 2>(p, stream, aux, planes, comp, cp);
-    if (p.qw == 4u && p.qh == 4u) return launch_blend_shape<4, 4>(p, stream, aux, planes, comp, cp);
-    return fail(WS_ERR_INVALID, "blend: unsupported tile shape");
+    // k_blend and k_blend2: one workgroup per tile (or per tpw tiles); the others: one wave per quadrant
+    const uint32_t grid = (c.form.kernel == BLEND_K || c.form.kernel == BLEND_K_ASYNC) ? blend_grid_blocks(p.tiles_x, p.tiles_y, sh, tpw_log2)
+                                                                                        : ((ntiles + 7u) / 8u) * 8u * p.qw * p.qh;
+    const BlendLaunch l = {p, tpw_log2, grid, (size_t)p.lds_pad_kb * 1024u, stream, ap ? *ap : no_planes, cpp ? *cpp : no_comp};
+    if (!launch_blend_form(c.form.bits(), l, std::make_index_sequence<BLEND_FORMS.n>{}))
+        return fail(WS_ERR_INVALID, "blend: no such form");  // (unreachable: blend_form_of returns legal forms only)
+    WS_HIP(hipGetLastError());
+    return WS_OK;
 }
 
 // host-side twin of the staging step (CPU unit test of the quadrant mask; not on any render path)

@@ -1544,6 +1544,16 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
         (reinterpret_cast<uintptr_t>(d_rgba_out) % texel) != 0)
         return fail(WS_ERR_INVALID, "ws_renderer_render: row pitch / alignment does not fit the colour format");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    // Split: two 512-thread workgroups (32x16 halves) per 32x32 binning tile, both reading the tile's list.  Automatic: when the
+    // frame has fewer binning tiles than the chip holds 1024-thread blend workgroups (two per CU) -- small viewports --
+    // the halves fill the chip and balance the long tiles (800x600, 0.5 M Gaussians: +24 % frames/s); above that the
+    // doubled staging costs more with frames in flight than the finer synchronisation saves (DESIGN 3.3).
+    BlendFrameRequest fr{};
+    fr.target_precision = r->blend_mode == WS_BLEND_TARGET_PRECISION, fr.exact_mode = r->blend_mode == WS_BLEND_FAST_EXACT_CUT;
+    fr.variant = r->ctx->blend_variant, fr.capture = r->capture, fr.timing = r->blend_timing;
+    fr.split_wanted = r->ctx->blend_split >= 0 ? r->ctx->blend_split != 0 : (r->tiles_x * r->tiles_y < 2u * (uint32_t)r->ctx->num_cus);
+    fr.order_valid = r->blend_order_valid, fr.qw = r->ctx->tile_qw, fr.qh = r->ctx->tile_qh;
+    const BlendFrameChoice form = blend_frame_choice(fr);
     BlendParams bp;
     bp.splats = r->splats;
     bp.entry_vals = r->entries_sorted;
@@ -1561,18 +1571,12 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     bp.tpw_log2 = r->ctx->blend_tpw_log2;
     bp.lds_pad_kb = r->ctx->blend_lds_pad_kb;
     bp.dma = r->ctx->blend_dma;
-    bp.exact_cut = (r->blend_mode == WS_BLEND_FAST_EXACT_CUT && !r->capture && !r->blend_timing) ? 1 : 0;
+    bp.exact_cut = form.exact_cut ? 1 : 0;
     bp.async_staging = r->ctx->blend_async < 0 ? WS_BLEND_ASYNC_DEFAULT : (r->ctx->blend_async ? 1 : 0);
     bp.num_cus = r->ctx->num_cus;
     bp.range_row_shift = 0;
     bp.bin_tiles_x = r->tiles_x;
-    // Two 512-thread workgroups (32x16 halves) per 32x32 binning tile, both reading the tile's list.  Automatic: when the
-    // frame has fewer binning tiles than the chip holds 1024-thread blend workgroups (two per CU) -- small viewports --
-    // the halves fill the chip and balance the long tiles (800x600, 0.5 M Gaussians: +24 % frames/s); above that the
-    // doubled staging costs more with frames in flight than the finer synchronisation saves (DESIGN 3.3).
-    const bool split = r->ctx->blend_split >= 0 ? r->ctx->blend_split != 0
-                                                 : (r->tiles_x * r->tiles_y < 2u * (uint32_t)r->ctx->num_cus);
-    if (split && bp.qw == 4 && bp.qh == 4 && !r->capture && r->ctx->blend_variant == 0 && r->blend_mode != WS_BLEND_TARGET_PRECISION) {
+    if (form.split) {
         bp.qh = 2;
         bp.tiles_y = (r->vh + 15u) / 16u;
         bp.range_row_shift = 1;
@@ -1582,7 +1586,7 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     bp.demand_mailbox = r->demand_mailbox_dev;
     bp.progress_mailbox = r->demand_mailbox_dev ? r->demand_mailbox_dev + 1 : nullptr;
     bp.frame_seq = r->frames_enqueued + 1u;  // (counted below, once the launch is certain)
-    bp.order = (r->blend_order_valid && bp.qw == 4 && bp.qh == 4 && bp.range_row_shift == 0 && !r->capture) ? r->blend_order : nullptr;
+    bp.order = form.ordered ? r->blend_order : nullptr;
     bp.debug_consumed = r->capture ? r->debug_consumed : nullptr;
     bp.debug_walked = r->capture ? r->debug_walked : nullptr;
     bp.debug_timing = nullptr;
@@ -1607,10 +1611,10 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     if (km) km->begin(stream, false);
     if (r->timers) WS_HIP(hipEventRecord(r->ev[4], stream));
     if (r->ctx->debug_cut >= 1 && r->ctx->debug_cut <= 4) return WS_OK;  // analysis only
-    int rc = launch_blend(bp, r->blend_mode == WS_BLEND_TARGET_PRECISION ? 2 : r->ctx->blend_variant, stream, planes, comp);
+    int rc = launch_blend(bp, form.variant, stream, planes, comp);
     if (rc) return rc;
     r->frames_enqueued = bp.frame_seq;
-    km_mark(km, r->blend_mode == WS_BLEND_TARGET_PRECISION ? "k_blend_strict" : "k_blend");
+    km_mark(km, fr.target_precision ? "k_blend_strict" : "k_blend");
     if (r->timers) {
         WS_HIP(hipEventRecord(r->ev[5], stream));
         r->ev_render_valid = true;
@@ -1634,6 +1638,14 @@ int ws_renderer_enable_depth(ws_renderer* r, int enable) {
     return WS_OK;
 }
 
+// What the entry points know of "the FAST production launch" before a frame is enqueued (the blend mode is theirs to check;
+// the launcher adds the launch's own switches)
+static bool production_launch(const ws_renderer* r) {
+    BlendLaunchMode m{};
+    m.capture = r->capture, m.timing = r->blend_timing, m.dma = r->ctx->blend_dma, m.variant = r->ctx->blend_variant, m.debug_cut = r->ctx->debug_cut;
+    return blend_production_launch(m);
+}
+
 // The checks of render_aux() on a ws_aux_targets with at least one plane; fills *bp (z: the frame's plane, if it has one).
 static int aux_planes_of(ws_renderer* r, const ws_pointcloud* pc, const ws_aux_targets* aux, BlendAuxPlanes* bp) {
     for (int i = 0; i < 4; ++i)
@@ -1646,7 +1658,7 @@ static int aux_planes_of(ws_renderer* r, const ws_pointcloud* pc, const ws_aux_t
             return fail(WS_ERR_INVALID, "ws_renderer_render_aux: plane pitch below 4 x width, or pitch / pointer not 4-B aligned");
     if (r->blend_mode != WS_BLEND_FAST)
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need WS_BLEND_FAST");
-    if (r->capture || r->blend_timing || r->ctx->blend_variant != 0 || r->ctx->blend_dma || r->ctx->debug_cut)
+    if (!production_launch(r))
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need the production blend (no capture / timing / variants)");
     if (r->prepared && r->prepared_pc == pc && (aux->depth || aux->median_depth) && !r->prepared_depth)
         return fail(WS_ERR_STATE, "ws_renderer_render_aux: depth planes need ws_renderer_enable_depth before prepare()");
@@ -1690,7 +1702,7 @@ int ws_renderer_render_composite(ws_renderer* r, const ws_pointcloud* pc, const 
         return ws_renderer_render_aux(r, pc, background, d_rgba, row_pitch_bytes, aux, stream);
     if (r->blend_mode == WS_BLEND_FAST_EXACT_CUT)
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_composite: load / occluder need WS_BLEND_FAST or WS_BLEND_TARGET_PRECISION");
-    if (r->capture || r->blend_timing || r->ctx->blend_variant != 0 || r->ctx->blend_dma || r->ctx->debug_cut)
+    if (!production_launch(r))
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_composite: load / occluder need the production blend (no capture / timing / variants)");
     BlendAuxPlanes bp = {};
     if (aux && (aux->depth || aux->median_depth || aux->alpha)) {

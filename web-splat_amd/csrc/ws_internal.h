@@ -8,6 +8,7 @@
 
 #include <string>
 
+#include "blend_form.h"
 #include "websplat.h"
 
 #if defined(_OPENMP) && !defined(__HIP_DEVICE_COMPILE__)
@@ -504,9 +505,6 @@ struct BlendAuxPlanes {
     size_t alpha_pitch;
     const float* z;        // [V] view-space depth per store slot (K1's DEPTH form); needed by the first two
 };
-// Forms of the FAST blend (k_blend's AUX parameter): no auxiliary plane (the colour image only), coverage only, and the depth
-// forms -- z staged beside every record, sum(w z), sum(w) and the median's crossing accumulated -- which write any of the three.
-enum BlendAux { BLEND_AUX_NONE = 0, BLEND_AUX_ALPHA = 1, BLEND_AUX_Z = 2 };
 // The composite of ws_renderer_render_composite: a trailing kernel argument (after BlendAuxPlanes, whose z it uses) of k_blend's
 // COMP forms and k_blend_strict's composite form only, so the other forms keep their kernel-argument layout.
 struct BlendComposite {
@@ -516,13 +514,10 @@ struct BlendComposite {
     int occ_ndc;             // 0: the plane holds view-space z; 1: [0, 1] depth-buffer values under the frame's projection
     int load;                // 1: over the texels the target holds (LoadOp::Load) instead of the uniform background
 };
-// k_blend's COMP parameter: two independent bits.  LOAD changes the epilogue only (one texel read in place of p.background);
-// OCCLUDE stages z like BLEND_AUX_Z, folds z < D(p) into every pair and drops records behind the tile's largest D at staging.
-enum BlendComp { BLEND_COMP_NONE = 0, BLEND_COMP_LOAD = 1, BLEND_COMP_OCCLUDE = 2 };
 constexpr int BLEND_TIMING_WORDS = 16;
-// aux: nullptr or no plane = the colour image only; otherwise variant 0 only -- the FAST production launch (capture, timing,
-// LDS-DMA and exact-cut forms refuse it).  comp: nullptr = over p.background, no depth test; otherwise variant 0 (the FAST
-// production launch, with or without aux) or variant 2 (k_blend_strict, no aux); an occluder needs aux->z (the frame's z plane).
+// One blend launch: the request (p, variant, the planes, the composite) becomes a BlendForm by blend_form_of (blend_form.h), which
+// also says what is refused and with which code.  aux: nullptr or no plane = the colour image only; comp: nullptr = over
+// p.background, no depth test; an occluder needs aux->z (the frame's z plane).
 int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const BlendAuxPlanes* aux = nullptr,
                  const BlendComposite* comp = nullptr);
 // the blend's workgroups in longest-list-first order (raster.hip k_blend_order): order[blend_order_blocks(..)]
