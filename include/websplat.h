@@ -453,7 +453,8 @@ int ws_renderer_set_tile_entry_capacity(ws_renderer* r, uint64_t entries);
 /* parity read-back of the prepared frame (the reference's test tooling reads buffers back the same way,
  * gpu_rs.rs:900-941 download_buffer): splats = V x 20 B in store order, keys/src_index = V u32 in store
  * order (src_index = original Gaussian index of each slot), sorted = V u32 store indices in draw order
- * (far -> near).  Any pointer may be NULL.  capacity = number of elements each array can hold. Syncs. */
+ * (far -> near).  Any pointer may be NULL.  capacity = number of elements each array can hold. Syncs.
+ * src_index needs a frame whose K1 kept it: capture mode, or ws_renderer_enable_contrib before prepare(). */
 int ws_renderer_download_frame(ws_renderer* r, uint32_t capacity, void* splats, uint32_t* keys,
                                uint32_t* src_index, uint32_t* sorted, uint32_t* num_visible);
 /* The prepared frame's z plane: V view-space depths in store order (the order of ws_renderer_download_frame's splats; z may be
@@ -595,6 +596,48 @@ int ws_render_views(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* sc
  * reference) gives every in-flight frame its own renderer scratch, target and HIP stream. */
 int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, uint32_t num_samples,
                uint32_t frames_in_flight, float* fps);
+/* ---- Per-Gaussian contributions over frames, and pruned point clouds (no counterpart in the reference) ----------------------
+ * What each Gaussian of the resident scene did to the frames added to an accumulator.  For a prepared frame and a pixel p of
+ * the viewport, p's tile list is walked near to far.  A pair (splat i, p) is kept iff a' <= the cut-off on the tile-local
+ * affine form -- the FAST blend's rule, whatever the renderer's blend mode, background, target, occluder or planes.  Its
+ * weight is w = b * T, b = min(0.99, 2^-a' * alpha_i) in f32, T the running f32 transmittance (1 at the start, T <- T - w).
+ * As in the FAST blend an 8x8-px quadrant may stop once all of its pixels have T < 2^-14: every pair left out weighs less
+ * than 2^-14, and together they weigh at most the pixel's remaining T.  Per source Gaussian j (its index in the point cloud):
+ *   sum_q32[j]    (u64) sum over kept pairs of (uint64_t)(w * 2^32); sum_q32 / WS_CONTRIB_SUM_SCALE = sum of weights
+ *   max_weight[j] (f32) the largest w of any pair
+ * over every frame added since creation / the last reset.  Both are integer reductions (the max on the bits of a non-negative
+ * float): bitwise reproducible for the same frames and context configuration, and accumulators of disjoint camera subsets
+ * (ranks) add exactly (ws_contrib_add).  The tile-local arithmetic depends on the tile origin: contexts of different tile
+ * shapes need not agree to the bit.
+ * ws_renderer_enable_contrib(r, 1) before prepare(): K1 keeps the source index of every visible splat (4 B each); nothing else
+ * of the frame changes -- every image and plane is bit-identical -- but, like capture mode, such a renderer does not replay a
+ * captured frame graph.  ws_renderer_accumulate_contrib enqueues on `stream` behind the prepared frame (render() is not
+ * needed) and makes no blend launch.
+ * Errors: WS_ERR_INVALID for null handles, an accumulator and a point cloud of different sizes, capacity or n below
+ * num_points, indices not strictly ascending or not below num_points, n == 0; WS_ERR_STATE when the frame is not prepared for
+ * `pc` or was prepared with contributions off; WS_ERR_UNSUPPORTED in a context with debug_cut. */
+typedef struct ws_contrib ws_contrib;   /* per-Gaussian accumulators for clouds of num_points Gaussians (device memory, zeroed) */
+#define WS_CONTRIB_SUM_SCALE 4294967296.0 /* sum_q32 / scale = sum of weights */
+int  ws_contrib_create(ws_context* ctx, uint32_t num_points, ws_contrib** out);
+void ws_contrib_destroy(ws_contrib* c);
+int  ws_contrib_reset(ws_contrib* c, void* stream);
+uint32_t ws_contrib_num_points(const ws_contrib* c);
+uint32_t ws_contrib_frames(const ws_contrib* c);              /* frames added since creation / reset (host counter) */
+int  ws_renderer_enable_contrib(ws_renderer* r, int enable);  /* before prepare(): K1 keeps source indices (4 B per visible splat) */
+int  ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, void* stream); /* enqueues; after prepare(), render() not needed */
+int  ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, float* max_weight);          /* either may be NULL; syncs */
+int  ws_contrib_add(ws_contrib* c, const uint64_t* sum_q32, const float* max_weight, uint32_t n);          /* host arrays of another accumulator / rank: exact merge */
+/* The Gaussians indices[0..n) of `src` (strictly ascending) as a point cloud of its own, gathered on the device: the 16-B
+ * chunks of every plane, or the 24-B compressed records with the SH / covariance codebooks and the quantisation block copied
+ * whole.  The relative order is kept (K1's store order and the stable sort's ties are the parent's); bbox, centre, up, the
+ * mip / kernel-size / background metadata and sh_deg are inherited verbatim, so fit_near_far, the settings uniform and the
+ * depth keys of the surviving splats stay bit-identical.  The subset owns its memory: `src` may be destroyed first. */
+int  ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, const uint32_t* indices, uint32_t n, ws_pointcloud** out);
+/* Every camera of `split` (sorted by id) added to `c`, set up exactly as ws_render_views does (1600-px cap, fit_near_far,
+ * walltime 100 s, max_sh_deg = pc.sh_deg): one renderer, one stream, one sync at the end, no target and no blend launch.
+ * *frames = cameras added.  WS_ERR_OVERFLOW when a frame overflowed its tile-entry list (read once, after the sync): the
+ * accumulator is then incomplete. */
+int  ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c, uint32_t* frames);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

@@ -1,0 +1,36 @@
+// contrib.h -- per-Gaussian contribution sums of a prepared frame (contrib.hip k_contrib) and the device gather behind
+// ws_pointcloud_create_subset (k_pc_gather).  Internal: the ABI is include/websplat.h, "Per-Gaussian contributions".
+#pragma once
+
+#include "ws_internal.h"
+
+namespace ws {
+
+// One attribution launch over a prepared frame's binned, depth-ordered tile lists.  A sibling of the blend, not a form of it:
+// it writes no pixel.  One workgroup per blend tile (qw x qh quadrants, one wave each), whatever the blend's own scheduling
+// (split halves, longest-first order, tiles per workgroup) would be.
+struct ContribParams {
+    const uint8_t* splats;        // [V] x SPLAT_STRIDE
+    const uint32_t* entry_vals;   // sorted by tile, far -> near inside a tile (store indices)
+    const uint2* tile_ranges;     // (0xFFFFFFFF - begin, end) per binning tile, (0, 0) = empty
+    const uint32_t* src_index;    // [V] store slot -> index into the point cloud (K1, contributions enabled)
+    uint32_t width, height, tiles_x, tiles_y;
+    uint32_t qw, qh;
+    const FrameCounters* counters;  // bin_shift of the frame; its error bits are folded into *sticky (no blend may follow)
+    uint32_t* sticky;
+    uint32_t* demand_mailbox;
+    unsigned long long* sum_q32;  // [num_points]
+    uint32_t* max_bits;           // [num_points] bits of the largest weight
+};
+int launch_contrib(const ContribParams& p, hipStream_t stream);
+
+// dst[i] += src[i] (u64), dst_max[i] = max(dst_max[i], src_max[i]) on the bits: ws_contrib_add
+int launch_contrib_merge(unsigned long long* sum, uint32_t* max_bits, const unsigned long long* add_sum, const uint32_t* add_max,
+                         uint32_t n, hipStream_t stream);
+
+// Gaussians indices[0..n) of a resident scene: `planes` planes of `n_src` records of `words` 32-bit words each
+// (uncompressed: PC_PLANES planes of 4 words; compressed: one plane of 6 words) -> the same layout over n records
+int launch_pc_gather(const uint32_t* src, uint32_t* dst, const uint32_t* indices, uint32_t n_src, uint32_t n, uint32_t planes,
+                     uint32_t words, hipStream_t stream);
+
+}  // namespace ws

@@ -171,6 +171,53 @@ int ws_render_views(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* sc
     return rc;
 }
 
+// Every camera of `split` into a contribution accumulator, set up exactly as ws_render_views sets its frames up.  No target and
+// no blend: prepare() + the attribution launch per camera on one stream, one sync at the end, then one look at the error bits.
+int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c,
+                                uint32_t* frames) {
+    if (!ctx || !pc || !scene || !c) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: null argument");
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: split must be train or test");
+    if (frames) *frames = 0;
+    if (ws_contrib_num_points(c) != ws_pointcloud_num_points(pc))
+        return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: the accumulator was created for another number of points");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_contrib: the context stops its frames early (debug_cut)");
+    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
+    std::vector<ws_scene_camera> cams(n);
+    ws_scene_cameras(scene, split, n, cams.data());
+    ws_renderer* r = nullptr;
+    int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), &r);
+    if (rc) return rc;
+    rc = ws_renderer_enable_contrib(r, 1);
+    uint32_t done = 0;
+    for (uint32_t i = 0; i < n && rc == WS_OK; ++i) {
+        uint32_t w = cams[i].width, h = cams[i].height;
+        if (w > 1600) {  // bin/render.rs:58-62
+            const float s = (float)w / 1600.0f;
+            w = 1600;
+            h = (uint32_t)((float)h / s);
+        }
+        if (w == 0 || h == 0) {
+            rc = fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: camera with an empty image");
+            break;
+        }
+        ws_splatting_args a;
+        offline_args(cams[i], pc, w, h, &a);
+        if ((rc = ws_renderer_prepare(r, pc, &a, nullptr))) break;
+        if ((rc = ws_renderer_accumulate_contrib(r, pc, c, nullptr))) break;
+        ++done;
+    }
+    if (rc == WS_OK) {
+        uint32_t bits = 0;
+        rc = ws_renderer_errors(r, &bits, nullptr, 1);  // (the one sync)
+        if (rc == WS_OK && bits)
+            rc = fail(WS_ERR_OVERFLOW, "ws_scene_accumulate_contrib: a frame reported device-side errors (tile-entry overflow or a look-back "
+                                       "time-out): the accumulator is incomplete");
+    }
+    if (frames) *frames = done;
+    ws_renderer_destroy(r);
+    return rc;
+}
+
 int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, uint32_t num_samples,
                uint32_t frames_in_flight, float* fps) {
     if (!ctx || !pc || !scene || !fps) return fail(WS_ERR_INVALID, "ws_measure: null argument");

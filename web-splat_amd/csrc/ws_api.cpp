@@ -11,6 +11,7 @@
 #include <new>
 #include <vector>
 
+#include "contrib.h"
 #include "ws_internal.h"
 
 namespace ws {
@@ -187,6 +188,8 @@ struct ws_renderer {
 
     int blend_mode = WS_BLEND_FAST;  // ws_renderer_set_blend_mode
     bool capture = false;
+    bool contrib = false;                // ws_renderer_enable_contrib: K1 keeps the source indices from the next prepare() on
+    bool prepared_contrib = false;       // the last prepared frame has them
     bool depth = false;                  // ws_renderer_enable_depth: K1 writes the z plane from the next prepare() on
     float* k1_depths = nullptr;          // the z plane the prepare() in progress writes (nullptr: depth off)
     bool prepared_depth = false;         // the last prepared frame wrote the z plane
@@ -758,6 +761,8 @@ int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* d, ws_pointc
         if (e == hipSuccess) e = hipMemcpy(pc->covars, d->covars, d->covars_bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = hip_fail(e, "ws_pointcloud_create: upload (compressed)");
         pc->device_bytes = d->gaussians_bytes + d->sh_coefs_bytes + d->covars_bytes;
+        pc->sh_bytes_size = d->sh_coefs_bytes;
+        pc->covars_size = d->covars_bytes;
     }
     if (rc != WS_OK) {
         ws_pointcloud_destroy(pc);
@@ -1341,7 +1346,8 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     kb.splats = r->splats;
     kb.keys = r->keys_a;
     kb.footprints = r->fpw_a;
-    kb.src_index = r->capture ? r->src_index : nullptr;
+    kb.src_index = (r->capture || r->contrib) ? r->src_index : nullptr;
+    r->prepared_contrib = r->contrib;
     kb.block_status = r->k1_status;
     kb.counters = r->counters;
     // (the next `trace_cap` frames of a traced renderer: one slot of four stamps per frame, each used once)
@@ -1372,7 +1378,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     // A captured frame graph (one hipGraphLaunch + one kernel-argument update instead of 22 launches + a memset on the host)
     // when the caller gave a real stream and no per-launch instrumentation is on.  The legacy NULL stream cannot be captured.
     const bool use_graph = r->ctx->use_graph && stream != nullptr && !r->marks.active && !r->timers && !r->capture &&
-                           cut_mode == 0;
+                           !r->contrib && cut_mode == 0;
     r->order_mode_this_frame = decide_blend_order(r, stream);
     if (!use_graph) {
         rc = enqueue_frame(r, pc, kp, kb, stream);
@@ -1487,7 +1493,7 @@ int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_point
     for (uint32_t i = 0; i < n; ++i) {
         ws_renderer* r = rs[i];
         if (!r || !streams[i] || r->ctx != rs[0]->ctx || r->compressed != pc->compressed || r->timers || r->marks.active ||
-            r->capture || r->depth || r->ctx->use_graph || r->ctx->debug_cut)
+            r->capture || r->contrib || r->depth || r->ctx->use_graph || r->ctx->debug_cut)
             return WS_ERR_UNSUPPORTED;
         for (uint32_t j = 0; j < i; ++j)
             if (rs[j] == r || streams[j] == streams[i]) return WS_ERR_UNSUPPORTED;
@@ -1920,7 +1926,7 @@ int ws_renderer_download_frame(ws_renderer* r, uint32_t capacity, void* splats, 
     const uint32_t v = st.num_visible;
     if ((splats || keys || src_index || sorted) && capacity < v)
         return fail(WS_ERR_INVALID, "ws_renderer_download_frame: capacity smaller than the visible count");
-    if (src_index && !r->capture)
+    if (src_index && !r->capture && !r->prepared_contrib)
         return fail(WS_ERR_STATE, "ws_renderer_download_frame: src_index needs ws_renderer_enable_capture before prepare");
     if (v == 0) return WS_OK;
     // where the frame's depth sort left its result: behind its last pass, or -- decided on the device -- behind pass 2
@@ -2116,6 +2122,194 @@ int ws_sort_selftest(ws_context* ctx, int* passed) {
     dfree(dv);
     ws_sorter_destroy(s);
     return rc;
+}
+
+}  // extern "C"
+
+// ---- per-Gaussian contributions (include/websplat.h; contrib.hip) ----------------------------------------
+struct ws_contrib {
+    ws_context* ctx = nullptr;
+    uint32_t num_points = 0;
+    unsigned long long* sum_q32 = nullptr;  // [num_points]
+    uint32_t* max_bits = nullptr;           // [num_points] bits of the largest weight (non-negative floats order as their bits)
+    uint32_t frames = 0;
+    hipStream_t last_stream = nullptr;
+};
+
+extern "C" {
+
+int ws_contrib_create(ws_context* ctx, uint32_t num_points, ws_contrib** out) {
+    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_contrib_create: null argument");
+    *out = nullptr;
+    if (num_points == 0) return fail(WS_ERR_INVALID, "ws_contrib_create: no points");
+    ws_contrib* c = new (std::nothrow) ws_contrib();
+    if (!c) return fail(WS_ERR_OOM, "ws_contrib_create: host allocation failed");
+    c->ctx = ctx;
+    c->num_points = num_points;
+    int rc = dmalloc(&c->sum_q32, num_points);
+    if (rc == WS_OK) rc = dmalloc(&c->max_bits, num_points);
+    if (rc == WS_OK) rc = ws_contrib_reset(c, nullptr);
+    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_contrib_create: device sync failed");
+    if (rc != WS_OK) {
+        ws_contrib_destroy(c);
+        return rc;
+    }
+    *out = c;
+    return WS_OK;
+}
+
+void ws_contrib_destroy(ws_contrib* c) {
+    if (!c) return;
+    (void)hipDeviceSynchronize();
+    dfree(c->sum_q32);
+    dfree(c->max_bits);
+    delete c;
+}
+
+int ws_contrib_reset(ws_contrib* c, void* stream_v) {
+    if (!c) return fail(WS_ERR_INVALID, "ws_contrib_reset: null accumulator");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    WS_HIP(hipMemsetAsync(c->sum_q32, 0, (size_t)c->num_points * sizeof(unsigned long long), stream));
+    WS_HIP(hipMemsetAsync(c->max_bits, 0, (size_t)c->num_points * sizeof(uint32_t), stream));
+    c->frames = 0;
+    c->last_stream = stream;
+    return WS_OK;
+}
+
+uint32_t ws_contrib_num_points(const ws_contrib* c) { return c ? c->num_points : 0u; }
+uint32_t ws_contrib_frames(const ws_contrib* c) { return c ? c->frames : 0u; }
+
+int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
+    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_enable_contrib: null renderer");
+    // Only K1's src_index pointer changes (a kernel argument the frame graph's update rewrites anyway); the binning tile and
+    // the blend's form stay what they are, unlike capture.  Off: the frame at hand no longer answers accumulate_contrib.
+    r->contrib = enable != 0;
+    if (!r->contrib) r->prepared_contrib = false;
+    return WS_OK;
+}
+
+int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, void* stream_v) {
+    if (!r || !pc || !c) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_contrib: null argument");
+    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_renderer_accumulate_contrib: the context stops its frames early (debug_cut)");
+    if (c->num_points != pc->num_points)
+        return fail(WS_ERR_INVALID, "ws_renderer_accumulate_contrib: the accumulator was created for another number of points");
+    if (!r->prepared || r->prepared_pc != pc)
+        return fail(WS_ERR_STATE, "ws_renderer_accumulate_contrib: prepare() was not called for this point cloud");
+    if (!r->prepared_contrib)
+        return fail(WS_ERR_STATE, "ws_renderer_accumulate_contrib: needs ws_renderer_enable_contrib before prepare()");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    ContribParams cp;
+    cp.splats = r->splats;
+    cp.entry_vals = r->entries_sorted;
+    cp.tile_ranges = r->tile_ranges;
+    cp.src_index = r->src_index;
+    cp.width = r->vw;
+    cp.height = r->vh;
+    cp.tiles_x = r->tiles_x;
+    cp.tiles_y = r->tiles_y;
+    cp.qw = r->ctx->tile_qw;
+    cp.qh = r->ctx->tile_qh;
+    cp.counters = r->counters;
+    cp.sticky = r->sticky;
+    cp.demand_mailbox = r->demand_mailbox_dev;
+    cp.sum_q32 = c->sum_q32;
+    cp.max_bits = c->max_bits;
+    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
+    if (km) km->begin(stream, false);
+    const int rc = launch_contrib(cp, stream);
+    if (rc) return rc;
+    km_mark(km, "k_contrib");
+    ++c->frames;
+    c->last_stream = stream;
+    r->last_stream = stream;
+    return WS_OK;
+}
+
+int ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, float* max_weight) {
+    if (!c) return fail(WS_ERR_INVALID, "ws_contrib_download: null accumulator");
+    if ((sum_q32 || max_weight) && capacity < c->num_points)
+        return fail(WS_ERR_INVALID, "ws_contrib_download: capacity smaller than the number of points");
+    WS_HIP(hipStreamSynchronize(c->last_stream));
+    int rc = WS_OK;
+    if (sum_q32) rc = copy_d2h(sum_q32, c->sum_q32, (size_t)c->num_points * sizeof(uint64_t), c->last_stream);
+    if (rc == WS_OK && max_weight) rc = copy_d2h(max_weight, c->max_bits, (size_t)c->num_points * sizeof(float), c->last_stream);
+    return rc;
+}
+
+int ws_contrib_add(ws_contrib* c, const uint64_t* sum_q32, const float* max_weight, uint32_t n) {
+    if (!c) return fail(WS_ERR_INVALID, "ws_contrib_add: null accumulator");
+    if (n < c->num_points) return fail(WS_ERR_INVALID, "ws_contrib_add: fewer values than the accumulator has points");
+    if (!sum_q32 && !max_weight) return WS_OK;
+    const size_t np = c->num_points;
+    unsigned long long* d_sum = nullptr;
+    uint32_t* d_max = nullptr;
+    hipStream_t stream = c->last_stream;
+    int rc = WS_OK;
+    if (sum_q32) rc = dmalloc(&d_sum, np);
+    if (rc == WS_OK && max_weight) rc = dmalloc(&d_max, np);
+    hipError_t e = hipSuccess;
+    if (rc == WS_OK && sum_q32) e = hipMemcpyAsync(d_sum, sum_q32, np * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
+    if (rc == WS_OK && e == hipSuccess && max_weight) e = hipMemcpyAsync(d_max, max_weight, np * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) rc = hip_fail(e, "ws_contrib_add: upload");
+    if (rc == WS_OK) rc = launch_contrib_merge(c->sum_q32, c->max_bits, d_sum, d_max, c->num_points, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_contrib_add: stream sync failed");
+    dfree(d_sum);
+    dfree(d_max);
+    return rc;
+}
+
+int ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, const uint32_t* indices, uint32_t n, ws_pointcloud** out) {
+    if (!ctx || !src || !indices || !out) return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: null argument");
+    *out = nullptr;
+    if (n == 0) return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: empty subset");
+    for (uint32_t i = 0; i < n; ++i)
+        if (indices[i] >= src->num_points || (i && indices[i] <= indices[i - 1]))
+            return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: indices must be strictly ascending and below the number of points");
+    ws_pointcloud* pc = new (std::nothrow) ws_pointcloud(*src);  // bbox, centre, up, metadata, sh_deg, quantisation: verbatim
+    if (!pc) return fail(WS_ERR_OOM, "ws_pointcloud_create_subset: host allocation failed");
+    pc->ctx = ctx;
+    pc->num_points = n;
+    pc->planes = nullptr;
+    pc->gaussians_c = pc->sh_bytes = pc->covars = nullptr;
+    // upload, gather and the codebook copies run on a private stream and are waited for (as ws_pointcloud_create_from_ply_rows)
+    uint32_t* d_idx = nullptr;
+    hipStream_t ls = nullptr;
+    int rc = dmalloc(&d_idx, n);
+    hipError_t e = hipSuccess;
+    if (rc == WS_OK) e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
+    if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(d_idx, indices, (size_t)n * 4, hipMemcpyHostToDevice, ls);
+    if (rc == WS_OK && e == hipSuccess) {
+        if (!src->compressed) {
+            pc->device_bytes = (size_t)n * PC_PLANES * 16;
+            e = hipMalloc(reinterpret_cast<void**>(&pc->planes), pc->device_bytes);
+            if (e == hipSuccess)
+                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->planes), reinterpret_cast<uint32_t*>(pc->planes), d_idx,
+                                      src->num_points, n, PC_PLANES, 4, ls);
+        } else {
+            pc->device_bytes = (size_t)n * 24 + src->sh_bytes_size + src->covars_size;
+            e = hipMalloc(reinterpret_cast<void**>(&pc->gaussians_c), (size_t)n * 24);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->sh_bytes), src->sh_bytes_size + 16);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->covars), src->covars_size ? src->covars_size : 1);
+            if (e == hipSuccess) e = hipMemcpyAsync(pc->sh_bytes, src->sh_bytes, src->sh_bytes_size + 16, hipMemcpyDeviceToDevice, ls);
+            if (e == hipSuccess && src->covars_size) e = hipMemcpyAsync(pc->covars, src->covars, src->covars_size, hipMemcpyDeviceToDevice, ls);
+            if (e == hipSuccess)
+                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->gaussians_c), reinterpret_cast<uint32_t*>(pc->gaussians_c), d_idx,
+                                      src->num_points, n, 1, 6, ls);
+        }
+    }
+    if (e != hipSuccess && rc == WS_OK) rc = hip_fail(e, "ws_pointcloud_create_subset: allocation / copy");
+    if (ls) {
+        const hipError_t se = hipStreamSynchronize(ls);
+        if (se != hipSuccess && rc == WS_OK) rc = hip_fail(se, "ws_pointcloud_create_subset: gather");
+        (void)hipStreamDestroy(ls);
+    }
+    dfree(d_idx);
+    if (rc != WS_OK) {
+        ws_pointcloud_destroy(pc);
+        return rc;
+    }
+    *out = pc;
+    return WS_OK;
 }
 
 }  // extern "C"

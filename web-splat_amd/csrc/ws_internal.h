@@ -630,5 +630,6 @@ struct ws_pointcloud {
     uint8_t* gaussians_c = nullptr;  // compressed
     uint8_t* sh_bytes = nullptr;
     uint8_t* covars = nullptr;
+    size_t sh_bytes_size = 0, covars_size = 0;  // compressed: bytes of the two codebooks (ws_pointcloud_create_subset copies them whole)
     size_t device_bytes = 0;
 };

@@ -25,6 +25,7 @@ WS_ERR_UNSUPPORTED = -4
 WS_ERR_STATE = -5
 WS_ERR_IO = -6
 WS_ERR_OVERFLOW = -7
+WS_CONTRIB_SUM_SCALE = 4294967296.0  # sum_q32 / scale = sum of weights
 
 WS_FORMAT_RGBA8_UNORM = 0
 WS_FORMAT_RGBA16_FLOAT = 1
@@ -282,6 +283,17 @@ SIGNATURES = {
     "ws_sorter_sort_depth": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P]),
     "ws_sorter_depth_range": (C.c_int, [_P, _u32p, _u32p, _u32p]),
     "ws_sort_selftest": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ws_contrib_create": (C.c_int, [_P, C.c_uint32, _PP]),
+    "ws_contrib_destroy": (None, [_P]),
+    "ws_contrib_reset": (C.c_int, [_P, _P]),
+    "ws_contrib_num_points": (C.c_uint32, [_P]),
+    "ws_contrib_frames": (C.c_uint32, [_P]),
+    "ws_renderer_enable_contrib": (C.c_int, [_P, C.c_int]),
+    "ws_renderer_accumulate_contrib": (C.c_int, [_P, _P, _P, _P]),
+    "ws_contrib_download": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64), _f32p]),
+    "ws_contrib_add": (C.c_int, [_P, C.POINTER(C.c_uint64), _f32p, C.c_uint32]),
+    "ws_pointcloud_create_subset": (C.c_int, [_P, _P, _u32p, C.c_uint32, _PP]),
+    "ws_scene_accumulate_contrib": (C.c_int, [_P, _P, _P, C.c_int, _P, _u32p]),
 }
 
 

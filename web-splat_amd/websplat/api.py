@@ -594,6 +594,65 @@ class PointCloud:
         check(lib.ws_build_settings_uniform(C.byref(a), self.handle, C.byref(u)))
         return u
 
+    def subset(self, indices) -> "PointCloud":
+        """The Gaussians `indices` (strictly ascending) as a point cloud of its own, gathered on the device; bbox, centre, up
+        and the metadata are the parent's, which may be closed first (ws_pointcloud_create_subset)."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32)
+        h = C.c_void_p()
+        check(lib.ws_pointcloud_create_subset(self.ctx.handle, self.handle, idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size,
+                                              C.byref(h)))
+        return PointCloud(self.ctx, _handle=h)
+
+
+class Contrib:
+    """Per-Gaussian contribution accumulators over frames (websplat.h "Per-Gaussian contributions"): for every Gaussian of a
+    cloud of num_points, the q32 sum of its blend weights over all pixels of all frames added, and its largest weight."""
+
+    def __init__(self, ctx: Context, num_points: int):
+        self.ctx = ctx
+        h = C.c_void_p()
+        check(lib.ws_contrib_create(ctx.handle, int(num_points), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            lib.ws_contrib_destroy(self.handle)
+            self.handle = None
+
+    def reset(self, stream=None):
+        check(lib.ws_contrib_reset(self.handle, C.c_void_p(stream or 0)))
+
+    def num_points(self) -> int:
+        return lib.ws_contrib_num_points(self.handle)
+
+    @property
+    def frames(self) -> int:
+        """frames added since creation / the last reset"""
+        return lib.ws_contrib_frames(self.handle)
+
+    def download(self):
+        """(sum float64 = sum_q32 / 2^32, sum_q32 uint64, max_weight float32), one value per Gaussian (syncs)."""
+        n = self.num_points()
+        q = np.empty(n, dtype=np.uint64)
+        m = np.empty(n, dtype=np.float32)
+        check(lib.ws_contrib_download(self.handle, n, q.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.POINTER(C.c_float))))
+        return q.astype(np.float64) / L.WS_CONTRIB_SUM_SCALE, q, m
+
+    def add(self, sum_q32, max_weight):
+        """Exact merge of another accumulator's (or rank's) downloaded arrays; either may be None."""
+        q = None if sum_q32 is None else np.ascontiguousarray(sum_q32, dtype=np.uint64)
+        m = None if max_weight is None else np.ascontiguousarray(max_weight, dtype=np.float32)
+        n = min(a.size for a in (q, m) if a is not None) if (q is not None or m is not None) else self.num_points()
+        check(lib.ws_contrib_add(self.handle, q.ctypes.data_as(C.POINTER(C.c_uint64)) if q is not None else None,
+                                 m.ctypes.data_as(C.POINTER(C.c_float)) if m is not None else None, n))
+
+
+def accumulate_contrib_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, contrib: "Contrib") -> int:
+    """Every camera of `split`, set up as render_views sets its frames up, added to `contrib`; returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_accumulate_contrib(ctx.handle, pc.handle, scene.handle, _SPLITS[split], contrib.handle, C.byref(n)))
+    return n.value
+
 
 class GaussianRenderer:
     """renderer.rs:33-283.  `prepare` + `render` enqueue on a HIP stream; nothing syncs except the
@@ -758,6 +817,15 @@ class GaussianRenderer:
         """K1 also writes each visible splat's view-space depth (4 B per splat) from the next prepare() on: what the depth and
         median_depth planes of render_aux() are built from."""
         check(lib.ws_renderer_enable_depth(self.handle, int(bool(on))))
+
+    def enable_contrib(self, on=True):
+        """K1 also keeps each visible splat's index into the point cloud (4 B per splat) from the next prepare() on: what
+        accumulate_contrib() attributes the frame's weights through.  Changes no pixel."""
+        check(lib.ws_renderer_enable_contrib(self.handle, int(bool(on))))
+
+    def accumulate_contrib(self, pc: PointCloud, contrib: "Contrib", stream=None):
+        """Add the prepared frame's per-Gaussian weights to `contrib` (enqueues; render() is not needed)."""
+        check(lib.ws_renderer_accumulate_contrib(self.handle, pc.handle, contrib.handle, C.c_void_p(stream or 0)))
 
     def _free_aux(self):
         for ptr in self._aux.values():

@@ -32,3 +32,26 @@ def gather_view_assignment(my_views: List[int], dist=None) -> Optional[List[List
     out = [None] * dist.get_world_size()
     dist.all_gather_object(out, my_views)
     return out
+
+
+def reduce_contrib(sum_q32, max_weight, dist=None, device: str = "cpu"):
+    """All-reduce the per-Gaussian contribution arrays of ranks that scored disjoint camera subsets (Contrib.download()):
+    (sum_q32 uint64, max_weight float32) over the default process group -- integer SUM and float MAX, both exact, so every
+    rank ends with the accumulator one rank would have built from all cameras.  The sums travel as int64: a q32 sum must stay
+    below 2^63, i.e. a Gaussian's total weight below 2^31 (one that covers every pixel of a 1080p frame at weight 1 reaches
+    that after a thousand frames); a value at or above 2^63, before or after the reduction, raises OverflowError."""
+    import numpy as np
+    q = np.ascontiguousarray(sum_q32, dtype=np.uint64)
+    m = np.ascontiguousarray(max_weight, dtype=np.float32)
+    if q.size and int(q.max()) >= 1 << 63:
+        raise OverflowError("reduce_contrib: a q32 sum of 2^63 or more does not travel as int64")
+    if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+        return q.copy(), m.copy()
+    import torch
+    tq = torch.from_numpy(q.view(np.int64).copy()).to(device)
+    tm = torch.from_numpy(m.copy()).to(device)
+    dist.all_reduce(tq, op=dist.ReduceOp.SUM)
+    dist.all_reduce(tm, op=dist.ReduceOp.MAX)
+    if tq.numel() and int(tq.min().item()) < 0:
+        raise OverflowError("reduce_contrib: the reduced q32 sums left the int64 range")
+    return tq.cpu().numpy().view(np.uint64), tm.cpu().numpy()
