@@ -638,6 +638,79 @@ int  ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, cons
  * *frames = cameras added.  WS_ERR_OVERFLOW when a frame overflowed its tile-entry list (read once, after the sync): the
  * accumulator is then incomplete. */
 int  ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c, uint32_t* frames);
+/* ---- Image metrics: PSNR and SSIM between two resident images (no counterpart in the reference) ------------------------------
+ * The two figures every 3DGS evaluation reports, as the INRIA / c3dgs metrics.py defines them, computed on the device between
+ * two images of one size, per image pair.  The definition is bit-level up to the sums:
+ * PIXEL VALUE of an image view (pointer, ws_color_format, row pitch) at (x, y), per colour channel ch:
+ *   (r, g, b, a) decoded as ws_display_composite decodes: f32 as stored, f16 -> f32, unorm8 as (float)k / 255.0f;
+ *   over_background != 0:  k = 1 - a;  t = background[ch] * k;  v = c_ch + t   -- three separately rounded f32 operations,
+ *                          no fused multiply-add (the premultiplied texel over an opaque background);
+ *   over_background == 0:  v = c_ch, alpha is ignored;
+ *   v = min(max(v, 0), 1), NaN -> 0;
+ *   WS_METRICS_QUANTIZE_U8:  q = (uint8_t)(v * 255.0f) (truncation, ws_download_texture_rgba8's rule), v = (float)q / 255.0f:
+ *                          the metric of the PNG ws_render_views would have written.
+ * MSE / PSNR: d = x - y and e = d * d in f32; mse = sum(e) / (3 W H) over the three colour channels, the sum taken in f64;
+ *   psnr = -10 log10(mse) in double on the host, +inf when mse == 0.  With WS_METRICS_QUANTIZE_U8 the record also carries
+ *   sse_u8 = sum (qx - qy)^2, an exact integer (at most 65025 * 3 W H), and mse = sse_u8 / (255^2 * 3 W H) in double.
+ * SSIM (the 3DGS `ssim`): per colour channel, an 11-tap window g[k] ~ exp(-(k - 5)^2 / (2 * 1.5^2)), normalised to sum 1 in
+ *   double and rounded to f32 -- g[0..5] = 0x1.0d956cp-10, 0x1.f1fe02p-8, 0x1.26eb18p-5, 0x1.bff0fep-4, 0x1.b43c4p-3,
+ *   0x1.10656p-2, g[10 - k] = g[k] -- the 2-D window their outer product; ZERO padding of 5 pixels (a tap outside the image
+ *   adds 0 to every moment); moments mu_x, mu_y, E[x^2], E[y^2], E[xy]; s_x = E[x^2] - mu_x^2, s_y likewise, s_xy = E[xy] -
+ *   mu_x mu_y; C1 = 0.01^2, C2 = 0.03^2;
+ *     ssim_map = ((2 mu_x mu_y + C1) (2 s_xy + C2)) / ((mu_x^2 + mu_y^2 + C1) (s_x + s_y + C2)),
+ *   ssim = its mean over 3 W H.  The moments and the map are evaluated in f64 on the f32 pixel values.  d_ssim_map (optional):
+ *   an f32 W x H plane of (map_r + map_g + map_b) / 3, rounded once -- the error heat map.
+ * Reduction: fixed-order sums per workgroup, one partial record each, summed in index order by a second kernel; no float
+ * atomics: the same pair gives the same bits, whatever else the accumulator holds.
+ * An accumulator holds the records of up to max_images comparisons, in ws_metrics_add order.  ws_metrics_add only ENQUEUES on
+ * `stream` (the images must stay valid and unchanged until that work is done); ws_metrics_download syncs and finalises mse,
+ * psnr and ssim on the host.  ONE ACCUMULATOR IS USED FROM ONE STREAM AT A TIME (its partial-record slab is shared by its adds
+ * and grown at add): sync before moving it to another stream.
+ * Image pointers and pitches must be multiples of the texel size (4 / 8 / 16 B); the map's of 4.  Rows may be padded with
+ * anything: nothing past a row's last texel is read.
+ * Errors: WS_ERR_INVALID for null handles (refused before anything touches a device), zero sizes, a pitch below the row or
+ * misaligned, an unknown format or flag bit, capacity < count; WS_ERR_OVERFLOW when the accumulator is full (its records stay). */
+typedef struct ws_image_view {
+    const void* d_pixels;       /* device memory */
+    ws_color_format format;
+    size_t row_pitch_bytes;
+    int32_t over_background;    /* 0: the colour channels as stored; 1: premultiplied over background[] */
+    float background[3];
+} ws_image_view;
+typedef struct ws_image_metrics {
+    double mse, psnr, ssim;
+    uint64_t sse_u8;            /* WS_METRICS_QUANTIZE_U8 only, else 0 */
+    uint32_t width, height, flags, reserved;
+} ws_image_metrics;
+typedef struct ws_metrics ws_metrics;   /* per-image records of up to max_images comparisons (device memory) */
+#define WS_METRICS_QUANTIZE_U8 1u
+int  ws_metrics_create(ws_context* ctx, uint32_t max_images, ws_metrics** out);
+void ws_metrics_destroy(ws_metrics* m);
+int  ws_metrics_reset(ws_metrics* m, void* stream);
+uint32_t ws_metrics_count(const ws_metrics* m);               /* images added since creation / reset (host counter) */
+int  ws_metrics_add(ws_metrics* m, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, uint32_t flags,
+                    float* d_ssim_map /* may be NULL */, size_t map_pitch_bytes, void* stream);                  /* enqueues only */
+int  ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out, uint32_t* count);            /* syncs */
+/* An 8-bit PNG decoded to RGBA8 on the host: greyscale, grey + alpha, RGB or RGBA, non-interlaced, all five filter types; grey
+ * is replicated, a missing alpha is 255.  *rgba is width * height * 4 bytes, released with ws_host_free.  Chunk CRCs and sizes
+ * are checked: a damaged file is WS_ERR_IO; 16-bit, palette and interlaced files are WS_ERR_UNSUPPORTED. */
+int  ws_png_read_rgba8(const char* path, uint32_t* width, uint32_t* height, uint8_t** rgba);
+void ws_host_free(void* p);
+/* Every camera of `split` (WS_SPLIT_TRAIN, WS_SPLIT_TEST or WS_SPLIT_ALL; sorted by id) adds one record to `m`; *frames =
+ * cameras added.  Exactly one of ref_pc / gt_dir:
+ *   ref_pc (the prune check): each camera set up exactly as ws_render_views sets it up (1600-px cap, fit_near_far, walltime
+ *     100 s, Rgba16Float targets cleared to transparent, the context's render-views blend mode), rendered once from `pc`
+ *     (image a) and once from `ref_pc` (image b); both are compared over the background colour of `pc`, or black when it has
+ *     none.  One stream, one sync at the end, no image read-back; if a frame overflowed its tile-entry list the entry lists
+ *     are grown and the whole split runs again (at most twice), else WS_ERR_OVERFLOW.
+ *   gt_dir (ground truth): image b is <gt_dir>/<img_name>, ".png" appended unless the name ends in it (any case), read with
+ *     ws_png_read_rgba8 and taken as opaque unorm8.  There is no resampler: the frame is rendered at the PNG's own size, with
+ *     the field of view of the camera's own fx, fy, width, height.  |png_w * cam_h - png_h * cam_w| > max(cam_w, cam_h) is an
+ *     aspect mismatch: WS_ERR_INVALID, naming the file; a file that cannot be opened is WS_ERR_IO, naming it.  JPEG is out of
+ *     scope.
+ * flags: WS_METRICS_QUANTIZE_U8 or 0.  On an error `m` keeps the records it had before the call. */
+int  ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                       const char* gt_dir, uint32_t flags, ws_metrics* m, uint32_t* frames);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

@@ -218,6 +218,196 @@ int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const 
     return rc;
 }
 
+// Every camera of `split` compared on the device (websplat.h "Image metrics"): `pc` against another cloud, or against
+// ground-truth PNGs.  Like everything here it only calls public entry points.
+namespace {
+
+// bin/render.rs:58-62: the frame size of ws_render_views
+bool capped_size(const ws_scene_camera& c, uint32_t* w, uint32_t* h) {
+    *w = c.width;
+    *h = c.height;
+    if (*w > 1600) {
+        const float s = (float)*w / 1600.0f;
+        *w = 1600;
+        *h = (uint32_t)((float)*h / s);
+    }
+    return *w != 0 && *h != 0;
+}
+
+ws_image_view view_of(const void* p, ws_color_format f, size_t pitch, const float* bg) {
+    ws_image_view v;
+    std::memset(&v, 0, sizeof v);
+    v.d_pixels = p;
+    v.format = f;
+    v.row_pitch_bytes = pitch;
+    v.over_background = bg ? 1 : 0;
+    for (int i = 0; i < 3 && bg; ++i) v.background[i] = bg[i];
+    return v;
+}
+
+// prepare + render one frame, then look at its error bits (syncs): a plain overflow grows the entry list and draws again
+int eval_render_checked(ws_renderer* r, const ws_pointcloud* pc, const ws_splatting_args* a, void* target, size_t pitch) {
+    const float clear[4] = {0, 0, 0, 0};
+    int rc = WS_OK;
+    for (int attempt = 0; attempt < 3; ++attempt) {  // (ws_render_views' overflow retry)
+        if ((rc = ws_renderer_prepare(r, pc, a, nullptr))) return rc;
+        if ((rc = ws_renderer_render(r, pc, clear, target, pitch, nullptr))) return rc;
+        uint32_t bits = 0, needed = 0;
+        if ((rc = ws_renderer_errors(r, &bits, &needed, 1))) return rc;
+        if (bits == 0) return WS_OK;
+        if ((bits & ~1u) != 0 || attempt == 2)
+            return fail(WS_ERR_OVERFLOW, "ws_scene_evaluate: the frame reported device-side errors (tile-entry overflow or a look-back time-out)");
+        ws_renderer_set_tile_entry_capacity(r, (uint64_t)needed + needed / 4 + 4096);
+    }
+    return rc;
+}
+
+int evaluate_against_cloud(ws_context* ctx, const ws_pointcloud* pc, const ws_pointcloud* ref_pc, const std::vector<ws_scene_camera>& cams,
+                           const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
+    size_t bytes = 0;
+    for (const ws_scene_camera& c : cams) {
+        uint32_t w, h;
+        if (!capped_size(c, &w, &h)) return fail(WS_ERR_INVALID, "ws_scene_evaluate: camera with an empty image");
+        bytes = std::max(bytes, (size_t)w * h * 8);
+    }
+    const uint32_t base = ws_metrics_count(m);
+    ws_renderer* rs[2] = {nullptr, nullptr};
+    void* targets[2] = {nullptr, nullptr};
+    const ws_pointcloud* clouds[2] = {pc, ref_pc};
+    int rc = WS_OK;
+    for (int k = 0; k < 2 && rc == WS_OK; ++k) {
+        rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(clouds[k]), ws_pointcloud_compressed(clouds[k]), &rs[k]);
+        if (rc == WS_OK && !ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(rs[k], WS_BLEND_TARGET_PRECISION);
+        if (rc == WS_OK) rc = ws_device_malloc(ctx, bytes, &targets[k]);
+    }
+    const float clear[4] = {0, 0, 0, 0};
+    // One stream, nothing read back per frame: the error bits are looked at once, after the sync.  A pass whose frames
+    // overflowed the tile-entry list is not a measurement: grow the lists and run the whole split again (as ws_measure does).
+    for (int attempt = 0; rc == WS_OK; ++attempt) {
+        *done = 0;
+        for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
+            uint32_t w, h;
+            capped_size(cams[i], &w, &h);
+            for (int k = 0; k < 2 && rc == WS_OK; ++k) {
+                ws_splatting_args a;
+                offline_args(cams[i], clouds[k], w, h, &a);
+                rc = ws_renderer_prepare(rs[k], clouds[k], &a, nullptr);
+                if (rc == WS_OK) rc = ws_renderer_render(rs[k], clouds[k], clear, targets[k], (size_t)w * 8, nullptr);
+            }
+            if (rc != WS_OK) break;
+            const ws_image_view va = view_of(targets[0], WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
+            const ws_image_view vb = view_of(targets[1], WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
+            // (the next frame's renders are ordered behind this comparison on the stream: the two targets are reused)
+            rc = ws_metrics_add(m, &va, &vb, w, h, flags, nullptr, 0, nullptr);
+            if (rc == WS_OK) ++*done;
+        }
+        uint32_t all_bits = 0;
+        for (int k = 0; k < 2 && rc == WS_OK; ++k) {  // (the one sync)
+            uint32_t bits = 0, needed = 0;
+            rc = ws_renderer_errors(rs[k], &bits, &needed, 1);
+            all_bits |= bits;
+            if (rc == WS_OK && (bits & 1u)) ws_renderer_set_tile_entry_capacity(rs[k], (uint64_t)needed + needed / 4 + 4096);
+        }
+        if (rc != WS_OK || all_bits == 0) break;
+        ws_internal_metrics_truncate(m, base);
+        *done = 0;
+        if ((all_bits & ~1u) != 0 || attempt == 2)
+            rc = fail(WS_ERR_OVERFLOW, "ws_scene_evaluate: frames reported device-side errors (tile-entry overflow or a look-back time-out)");
+    }
+    if (rc != WS_OK) {
+        (void)ws_sync(ctx, nullptr);
+        ws_internal_metrics_truncate(m, base);
+        *done = 0;
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (rs[k]) ws_renderer_destroy(rs[k]);
+        if (targets[k]) ws_device_free(ctx, targets[k]);
+    }
+    return rc;
+}
+
+int evaluate_against_files(ws_context* ctx, const ws_pointcloud* pc, const char* gt_dir, const std::vector<ws_scene_camera>& cams,
+                           const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
+    const uint32_t base = ws_metrics_count(m);
+    ws_renderer* r = nullptr;
+    int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), &r);
+    if (rc) return rc;
+    if (!ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(r, WS_BLEND_TARGET_PRECISION);
+    void *target = nullptr, *truth = nullptr;
+    size_t capacity = 0;  // pixels both buffers hold
+    for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
+        const ws_scene_camera& c = cams[i];
+        std::string name(c.img_name, strnlen(c.img_name, sizeof c.img_name));
+        const size_t L = name.size();
+        const bool has_ext = L >= 4 && name[L - 4] == '.' && (name[L - 3] | 0x20) == 'p' && (name[L - 2] | 0x20) == 'n' && (name[L - 1] | 0x20) == 'g';
+        const std::string path = std::string(gt_dir) + "/" + name + (has_ext ? "" : ".png");
+        uint32_t w = 0, h = 0;
+        uint8_t* rgba = nullptr;
+        if ((rc = ws_png_read_rgba8(path.c_str(), &w, &h, &rgba))) break;  // (the message names the file)
+        const uint64_t skew = (uint64_t)w * c.height > (uint64_t)h * c.width ? (uint64_t)w * c.height - (uint64_t)h * c.width
+                                                                              : (uint64_t)h * c.width - (uint64_t)w * c.height;
+        if (c.width == 0 || c.height == 0 || skew > std::max(c.width, c.height))
+            rc = fail(WS_ERR_INVALID, "ws_scene_evaluate: " + path + " (" + std::to_string(w) + " x " + std::to_string(h) + ") does not have the aspect of its camera (" +
+                                          std::to_string(c.width) + " x " + std::to_string(c.height) + ")");
+        const size_t px = (size_t)w * h;
+        if (rc == WS_OK && px > capacity) {  // (every earlier frame has been waited for)
+            if (target) ws_device_free(ctx, target);
+            if (truth) ws_device_free(ctx, truth);
+            target = truth = nullptr;
+            capacity = 0;
+            rc = ws_device_malloc(ctx, px * 8, &target);
+            if (rc == WS_OK) rc = ws_device_malloc(ctx, px * 4, &truth);
+            if (rc == WS_OK) capacity = px;
+        }
+        // no resampler: the camera's own field of view on the PNG's viewport (the renderer derives the focal length from both)
+        ws_splatting_args a;
+        if (rc == WS_OK) offline_args(c, pc, w, h, &a);
+        if (rc == WS_OK) rc = ws_sync(ctx, nullptr);  // the previous comparison still reads `truth`
+        if (rc == WS_OK) rc = ws_memcpy_h2d(ctx, truth, rgba, px * 4, nullptr);
+        ws_host_free(rgba);
+        if (rc == WS_OK) rc = eval_render_checked(r, pc, &a, target, (size_t)w * 8);
+        if (rc != WS_OK) break;
+        const ws_image_view va = view_of(target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
+        const ws_image_view vb = view_of(truth, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr);  // opaque: alpha ignored
+        rc = ws_metrics_add(m, &va, &vb, w, h, flags, nullptr, 0, nullptr);
+        if (rc == WS_OK) ++*done;
+    }
+    const int src = ws_sync(ctx, nullptr);
+    if (rc == WS_OK) rc = src;
+    if (rc != WS_OK) {
+        ws_internal_metrics_truncate(m, base);
+        *done = 0;
+    }
+    if (target) ws_device_free(ctx, target);
+    if (truth) ws_device_free(ctx, truth);
+    ws_renderer_destroy(r);
+    return rc;
+}
+
+}  // namespace
+
+int ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                      const char* gt_dir, uint32_t flags, ws_metrics* m, uint32_t* frames) {
+    if (!ctx || !pc || !scene || !m) return fail(WS_ERR_INVALID, "ws_scene_evaluate: null argument");
+    if (frames) *frames = 0;
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL)
+        return fail(WS_ERR_INVALID, "ws_scene_evaluate: split must be train, test or all");
+    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, "ws_scene_evaluate: exactly one of ref_pc and gt_dir");
+    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_scene_evaluate: unknown flag bits");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_evaluate: the context stops its frames early (debug_cut)");
+    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
+    std::vector<ws_scene_camera> cams(n);
+    ws_scene_cameras(scene, split, n, cams.data());
+    float bg[3] = {0, 0, 0};  // the cloud's own background colour, or black
+    float pc_bg[3];
+    if (ws_pointcloud_background_color(pc, pc_bg) == 1) std::memcpy(bg, pc_bg, sizeof bg);
+    uint32_t done = 0;
+    const int rc = ref_pc ? evaluate_against_cloud(ctx, pc, ref_pc, cams, bg, flags, m, &done)
+                          : evaluate_against_files(ctx, pc, gt_dir, cams, bg, flags, m, &done);
+    if (frames) *frames = done;
+    return rc;
+}
+
 int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, uint32_t num_samples,
                uint32_t frames_in_flight, float* fps) {
     if (!ctx || !pc || !scene || !fps) return fail(WS_ERR_INVALID, "ws_measure: null argument");

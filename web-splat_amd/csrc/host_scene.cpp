@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <new>
@@ -378,5 +379,138 @@ int ws_png_write_rgba8(const char* path, uint32_t width, uint32_t height, const 
     ok = (std::fclose(f) == 0) && ok;
     return ok ? WS_OK : fail(WS_ERR_IO, "ws_png_write_rgba8: write failed");
 }
+
+// The reader of what the writer above and dataset tools write: 8-bit greyscale / grey + alpha / RGB / RGBA, no interlace, the
+// five filter types of ISO/IEC 15948 section 9.  Every length is checked against what is left of the file before it is used,
+// every chunk's CRC-32 is verified, and the decoded size is bounded before anything is allocated.
+static int png_read_impl(const char* path, uint32_t* width, uint32_t* height, uint8_t** rgba) {
+    const std::string who = std::string("ws_png_read_rgba8: ") + path;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return fail(WS_ERR_IO, who + ": cannot open");
+    std::vector<uint8_t> file;
+    {
+        uint8_t buf[65536];
+        size_t got;
+        while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + got);
+        std::fclose(f);
+    }
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    if (file.size() < 8 || std::memcmp(file.data(), sig, 8) != 0) return fail(WS_ERR_IO, who + ": not a PNG file");
+    auto rd32 = [](const uint8_t* q) { return ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3]; };
+    size_t pos = 8;
+    bool have_ihdr = false, have_iend = false;
+    uint32_t w = 0, h = 0, channels = 0;
+    std::vector<uint8_t> idat;
+    while (!have_iend) {
+        if (file.size() - pos < 12) return fail(WS_ERR_IO, who + ": truncated (chunk header)");
+        const uint32_t len = rd32(file.data() + pos);
+        if ((size_t)len > file.size() - pos - 12) return fail(WS_ERR_IO, who + ": truncated (chunk data)");
+        const uint8_t* type = file.data() + pos + 4;
+        const uint8_t* data = type + 4;
+        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), type, 4 + len) != rd32(data + len)) return fail(WS_ERR_IO, who + ": chunk CRC mismatch");
+        if (!have_ihdr) {
+            if (std::memcmp(type, "IHDR", 4) != 0 || len != 13) return fail(WS_ERR_IO, who + ": IHDR is not the first chunk");
+            have_ihdr = true;
+            w = rd32(data);
+            h = rd32(data + 4);
+            if (w == 0 || h == 0 || w > 0x7FFFFFFFu || h > 0x7FFFFFFFu) return fail(WS_ERR_IO, who + ": invalid image size");
+            if (data[10] != 0 || data[11] != 0 || data[12] > 1) return fail(WS_ERR_IO, who + ": invalid IHDR");
+            if (data[12] != 0) return fail(WS_ERR_UNSUPPORTED, who + ": interlaced PNG");
+            const uint8_t depth = data[8], ctype = data[9];
+            if (ctype == 3) return fail(WS_ERR_UNSUPPORTED, who + ": palette PNG");
+            if (ctype != 0 && ctype != 2 && ctype != 4 && ctype != 6) return fail(WS_ERR_IO, who + ": invalid colour type");
+            if (depth != 8) {
+                const bool legal = depth == 16 || (ctype == 0 && (depth == 1 || depth == 2 || depth == 4));
+                return legal ? fail(WS_ERR_UNSUPPORTED, who + ": only 8-bit samples are read") : fail(WS_ERR_IO, who + ": invalid bit depth");
+            }
+            channels = ctype == 0 ? 1u : (ctype == 4 ? 2u : (ctype == 2 ? 3u : 4u));
+            // the decoded image: at most 2^30 bytes of RGBA8 (a 16 k x 16 k image), checked in 64 bits
+            if ((uint64_t)w * (uint64_t)h > (1ull << 28)) return fail(WS_ERR_IO, who + ": image larger than 2^28 pixels");
+        } else if (std::memcmp(type, "IDAT", 4) == 0) {
+            idat.insert(idat.end(), data, data + len);
+        } else if (std::memcmp(type, "IEND", 4) == 0) {
+            have_iend = true;
+        } else if (!(type[0] & 0x20)) {  // a critical chunk this reader does not know (PLTE needs colour type 3)
+            if (std::memcmp(type, "PLTE", 4) != 0) return fail(WS_ERR_UNSUPPORTED, who + ": unknown critical chunk");
+        }
+        pos += 12 + (size_t)len;
+    }
+    const size_t row_bytes = (size_t)w * channels, raw_bytes = (row_bytes + 1) * (size_t)h;
+    // DEFLATE expands at most 1032 : 1: a header that promises more than the data can hold is refused before the allocation
+    if (idat.size() > 0xFFFFFFFFull) return fail(WS_ERR_UNSUPPORTED, who + ": more than 4 GiB of image data");
+    if (idat.empty() || (uint64_t)raw_bytes > (uint64_t)idat.size() * 1032ull + 64ull) return fail(WS_ERR_IO, who + ": image data shorter than the header promises");
+    std::vector<uint8_t> raw(raw_bytes);
+    {
+        z_stream zs;
+        std::memset(&zs, 0, sizeof zs);
+        if (inflateInit(&zs) != Z_OK) return fail(WS_ERR_IO, who + ": inflate init failed");
+        // (both sizes fit zlib's 32-bit counters: the file was bounded above, the image to 5 x 2^28 bytes)
+        zs.next_in = idat.data();
+        zs.avail_in = (uInt)idat.size();
+        zs.next_out = raw.data();
+        zs.avail_out = (uInt)raw_bytes;
+        const int zr = inflate(&zs, Z_FINISH);  // Z_STREAM_END only if the whole stream fits the promised size
+        const bool ok = zr == Z_STREAM_END && (size_t)zs.total_out == raw_bytes;
+        inflateEnd(&zs);
+        if (!ok) return fail(WS_ERR_IO, who + ": damaged image data");
+    }
+    // unfilter in place (section 9.2): bpp = bytes per complete pixel
+    const size_t bpp = channels;
+    for (uint32_t y = 0; y < h; ++y) {
+        uint8_t* line = raw.data() + (size_t)y * (row_bytes + 1);
+        const uint8_t ft = line[0];
+        uint8_t* cur = line + 1;
+        const uint8_t* prev = y ? cur - (row_bytes + 1) : nullptr;
+        if (ft > 4) return fail(WS_ERR_IO, who + ": invalid filter type");
+        for (size_t i = 0; i < row_bytes && ft != 0; ++i) {
+            const int a = i >= bpp ? cur[i - bpp] : 0, b = prev ? prev[i] : 0, c = (prev && i >= bpp) ? prev[i - bpp] : 0;
+            int pr;
+            if (ft == 1) pr = a;
+            else if (ft == 2) pr = b;
+            else if (ft == 3) pr = (a + b) >> 1;
+            else {
+                const int pa = std::abs(b - c), pb = std::abs(a - c), pc = std::abs(a + b - 2 * c);
+                pr = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+            }
+            cur[i] = (uint8_t)(cur[i] + pr);
+        }
+    }
+    uint8_t* out = static_cast<uint8_t*>(std::malloc((size_t)w * h * 4));
+    if (!out) return fail(WS_ERR_OOM, who + ": host allocation failed");
+    for (uint32_t y = 0; y < h; ++y) {
+        const uint8_t* src = raw.data() + (size_t)y * (row_bytes + 1) + 1;
+        uint8_t* dst = out + (size_t)y * w * 4;
+        for (uint32_t x = 0; x < w; ++x, src += channels, dst += 4) {
+            if (channels <= 2) {
+                dst[0] = dst[1] = dst[2] = src[0];
+                dst[3] = channels == 2 ? src[1] : 255;
+            } else {
+                dst[0] = src[0];
+                dst[1] = src[1];
+                dst[2] = src[2];
+                dst[3] = channels == 4 ? src[3] : 255;
+            }
+        }
+    }
+    *width = w;
+    *height = h;
+    *rgba = out;
+    return WS_OK;
+}
+
+int ws_png_read_rgba8(const char* path, uint32_t* width, uint32_t* height, uint8_t** rgba) {
+    if (!path || !width || !height || !rgba) return fail(WS_ERR_INVALID, "ws_png_read_rgba8: null argument");
+    *width = *height = 0;
+    *rgba = nullptr;
+    try {
+        return png_read_impl(path, width, height, rgba);
+    } catch (const std::bad_alloc&) {
+        return fail(WS_ERR_OOM, "ws_png_read_rgba8: host allocation failed");
+    } catch (...) {
+        return fail(WS_ERR_IO, "ws_png_read_rgba8: malformed input");
+    }
+}
+
+void ws_host_free(void* p) { std::free(p); }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "contrib.h"
+#include "metrics.h"
 #include "ws_internal.h"
 
 namespace ws {
@@ -2309,6 +2310,149 @@ int ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, const
         return rc;
     }
     *out = pc;
+    return WS_OK;
+}
+
+}  // extern "C"
+
+// ---- image metrics (include/websplat.h "Image metrics"; metrics.hip) ----------------------------------------
+struct ws_metrics {
+    ws_context* ctx = nullptr;
+    uint32_t max_images = 0;
+    uint32_t count = 0;                  // records added (host counter)
+    MetricsRecord* records = nullptr;    // [max_images]
+    MetricsPartial* slab = nullptr;      // one partial record per workgroup of the add in flight; shared by the adds of one stream
+    uint32_t slab_tiles = 0;
+    hipStream_t last_stream = nullptr;
+};
+
+void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count) {
+    if (m && count < m->count) m->count = count;
+}
+
+namespace {
+int metrics_view(const ws_image_view* v, uint32_t width, const char* which, MetricsView* out) {
+    const std::string who = std::string("ws_metrics_add: image ") + which;
+    if (!v->d_pixels) return fail(WS_ERR_INVALID, who + ": null pixels");
+    size_t texel;
+    switch (v->format) {
+        case WS_FORMAT_RGBA8_UNORM: texel = 4; break;
+        case WS_FORMAT_RGBA16_FLOAT: texel = 8; break;
+        case WS_FORMAT_RGBA32_FLOAT: texel = 16; break;
+        default: return fail(WS_ERR_INVALID, who + ": unknown colour format");
+    }
+    if (v->row_pitch_bytes < texel * width) return fail(WS_ERR_INVALID, who + ": row pitch below the row");
+    if (v->row_pitch_bytes % texel != 0 || reinterpret_cast<uintptr_t>(v->d_pixels) % texel != 0)
+        return fail(WS_ERR_INVALID, who + ": pointer and row pitch must be multiples of the texel size");
+    out->pixels = v->d_pixels;
+    out->pitch = v->row_pitch_bytes;
+    out->format = (int)v->format;
+    out->over_bg = v->over_background != 0;
+    for (int i = 0; i < 3; ++i) out->bg[i] = v->background[i];
+    return WS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ws_metrics_create(ws_context* ctx, uint32_t max_images, ws_metrics** out) {
+    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_metrics_create: null argument");
+    *out = nullptr;
+    if (max_images == 0) return fail(WS_ERR_INVALID, "ws_metrics_create: no images");
+    ws_metrics* m = new (std::nothrow) ws_metrics();
+    if (!m) return fail(WS_ERR_OOM, "ws_metrics_create: host allocation failed");
+    m->ctx = ctx;
+    m->max_images = max_images;
+    const int rc = dmalloc(&m->records, max_images);
+    if (rc != WS_OK) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return WS_OK;
+}
+
+void ws_metrics_destroy(ws_metrics* m) {
+    if (!m) return;
+    (void)hipDeviceSynchronize();
+    dfree(m->records);
+    dfree(m->slab);
+    delete m;
+}
+
+int ws_metrics_reset(ws_metrics* m, void* stream_v) {
+    if (!m) return fail(WS_ERR_INVALID, "ws_metrics_reset: null accumulator");
+    // records are written whole by the add that owns them: emptying is the host counter
+    m->count = 0;
+    m->last_stream = static_cast<hipStream_t>(stream_v);
+    return WS_OK;
+}
+
+uint32_t ws_metrics_count(const ws_metrics* m) { return m ? m->count : 0u; }
+
+int ws_metrics_add(ws_metrics* m, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, uint32_t flags,
+                   float* d_ssim_map, size_t map_pitch_bytes, void* stream_v) {
+    if (!m || !a || !b) return fail(WS_ERR_INVALID, "ws_metrics_add: null argument");
+    if (width == 0 || height == 0) return fail(WS_ERR_INVALID, "ws_metrics_add: empty image");
+    if (width > 65536u || height > 65536u) return fail(WS_ERR_INVALID, "ws_metrics_add: image larger than 65536 pixels on a side");
+    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_metrics_add: unknown flag bits");
+    MetricsParams p;
+    int rc = metrics_view(a, width, "a", &p.a);
+    if (rc == WS_OK) rc = metrics_view(b, width, "b", &p.b);
+    if (rc) return rc;
+    if (d_ssim_map && (map_pitch_bytes < (size_t)width * 4 || map_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(d_ssim_map) % 4 != 0))
+        return fail(WS_ERR_INVALID, "ws_metrics_add: map pitch below 4 x width, or map pointer / pitch not 4-B aligned");
+    if (m->count >= m->max_images) return fail(WS_ERR_OVERFLOW, "ws_metrics_add: the accumulator is full");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const uint32_t tiles = metrics_num_tiles(width, height);
+    if (tiles > m->slab_tiles) {  // (hipFree waits for the adds that still use the old slab)
+        dfree(m->slab);
+        m->slab_tiles = 0;
+        if ((rc = dmalloc(&m->slab, tiles))) return rc;
+        m->slab_tiles = tiles;
+    }
+    p.width = width;
+    p.height = height;
+    p.flags = flags;
+    p.map = d_ssim_map;
+    p.map_pitch = map_pitch_bytes;
+    p.slab = m->slab;
+    if ((rc = launch_image_metrics(p, m->records + m->count, stream))) return rc;
+    ++m->count;
+    m->last_stream = stream;
+    return WS_OK;
+}
+
+int ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out, uint32_t* count) {
+    if (!m) return fail(WS_ERR_INVALID, "ws_metrics_download: null accumulator");
+    if (count) *count = m->count;
+    if (!out) {  // (the count alone)
+        WS_HIP(hipStreamSynchronize(m->last_stream));
+        return WS_OK;
+    }
+    if (capacity < m->count) return fail(WS_ERR_INVALID, "ws_metrics_download: capacity smaller than the number of records");
+    std::vector<MetricsRecord> recs;
+    try {
+        recs.resize(m->count);
+    } catch (...) {
+        return fail(WS_ERR_OOM, "ws_metrics_download: host allocation failed");
+    }
+    WS_HIP(hipStreamSynchronize(m->last_stream));
+    const int rc = copy_d2h(recs.data(), m->records, (size_t)m->count * sizeof(MetricsRecord), m->last_stream);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < m->count; ++i) {
+        const MetricsRecord& r = recs[i];
+        ws_image_metrics& o = out[i];
+        const double n = 3.0 * (double)r.width * (double)r.height;
+        o.mse = (r.flags & WS_METRICS_QUANTIZE_U8) ? (double)r.sse_u8 / (255.0 * 255.0 * n) : r.sse / n;
+        o.psnr = o.mse == 0.0 ? (double)INFINITY : -10.0 * std::log10(o.mse);
+        o.ssim = r.ssim_sum / n;
+        o.sse_u8 = r.sse_u8;
+        o.width = r.width;
+        o.height = r.height;
+        o.flags = r.flags;
+        o.reserved = 0;
+    }
     return WS_OK;
 }
 

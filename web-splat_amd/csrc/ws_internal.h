@@ -561,6 +561,9 @@ uint32_t ws_internal_renderer_frames_enqueued(const ws_renderer* r);
 bool ws_internal_renderer_progress(const ws_renderer* r, uint32_t* started_seq);
 // a renderer that runs beside others (a slot of a view batch with several frames in flight): see ws_api.cpp `throughput_mode`
 void ws_internal_renderer_set_throughput_mode(ws_renderer* r, bool on);
+// ws_scene_evaluate gives back the records of a pass it has to repeat (ws_api.cpp): the host counter only
+struct ws_metrics;
+void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count);
 
 // opaque handle definitions -------------------------------------------------------------------------
 // The depth sort of a frame (V keys + store index + footprint word):

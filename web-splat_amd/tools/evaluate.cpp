@@ -1,0 +1,73 @@
+// websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
+//   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
+// prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
+// another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "websplat.h"
+#include "websplat_env.h"  // the harness-side translation of WS_* switches (the library reads no environment)
+
+int main(int argc, char** argv) {
+    const char *ref = nullptr, *gt = nullptr;
+    int split = WS_SPLIT_TEST;
+    uint32_t flags = 0;
+    bool bad = argc < 3;
+    for (int i = 3; i < argc && !bad; ++i) {
+        if (!std::strcmp(argv[i], "--ref") && i + 1 < argc) ref = argv[++i];
+        else if (!std::strcmp(argv[i], "--gt") && i + 1 < argc) gt = argv[++i];
+        else if (!std::strcmp(argv[i], "--split") && i + 1 < argc) {
+            ++i;
+            if (!std::strcmp(argv[i], "train")) split = WS_SPLIT_TRAIN;
+            else if (!std::strcmp(argv[i], "test")) split = WS_SPLIT_TEST;
+            else bad = true;
+        } else if (!std::strcmp(argv[i], "--quantize")) flags |= WS_METRICS_QUANTIZE_U8;
+        else bad = true;
+    }
+    if (bad || (ref != nullptr) == (gt != nullptr)) {
+        std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]\n", argv[0]);
+        return 2;
+    }
+    ws_context* ctx = nullptr;
+    ws_pointcloud *pc = nullptr, *ref_pc = nullptr;
+    ws_scene* scene = nullptr;
+    ws_metrics* m = nullptr;
+    ws_context_config cfg;
+    ws_context_config_from_env(&cfg);
+    int rc = ws_context_create_with_config(0, &cfg, &ctx);
+    if (rc == WS_OK) rc = ws_scene_load_json(argv[2], &scene);
+    if (rc == WS_OK) rc = ws_pointcloud_load(ctx, argv[1], &pc);
+    if (rc == WS_OK && ref) rc = ws_pointcloud_load(ctx, ref, &ref_pc);
+    const uint32_t n = rc == WS_OK ? ws_scene_cameras(scene, split, 0, nullptr) : 0;
+    std::vector<ws_scene_camera> cams(n);
+    std::vector<ws_image_metrics> recs(n);
+    uint32_t frames = 0, count = 0;
+    if (rc == WS_OK && n == 0) {
+        std::fprintf(stderr, "the split has no cameras\n");
+        rc = WS_ERR_INVALID;
+    }
+    if (rc == WS_OK) ws_scene_cameras(scene, split, n, cams.data());
+    if (rc == WS_OK) rc = ws_metrics_create(ctx, n, &m);
+    if (rc == WS_OK) rc = ws_scene_evaluate(ctx, pc, scene, split, ref_pc, gt, flags, m, &frames);
+    if (rc == WS_OK) rc = ws_metrics_download(m, n, recs.data(), &count);
+    if (rc == WS_OK) {
+        double psnr = 0.0, ssim = 0.0;
+        for (uint32_t i = 0; i < count; ++i) {
+            std::printf("%5u %-32s %4ux%-4u PSNR %8.4f  SSIM %.6f\n", cams[i].id, cams[i].img_name, recs[i].width, recs[i].height, recs[i].psnr,
+                        recs[i].ssim);
+            psnr += recs[i].psnr;
+            ssim += recs[i].ssim;
+        }
+        std::printf("mean over %u images: PSNR %.4f  SSIM %.6f\n", count, psnr / count, ssim / count);
+    } else {
+        std::fprintf(stderr, "error %d: %s\n", rc, ws_last_error());
+    }
+    if (m) ws_metrics_destroy(m);
+    if (ref_pc) ws_pointcloud_destroy(ref_pc);
+    if (pc) ws_pointcloud_destroy(pc);
+    if (scene) ws_scene_destroy(scene);
+    if (ctx) ws_context_destroy(ctx);
+    return rc == WS_OK ? 0 : 1;
+}

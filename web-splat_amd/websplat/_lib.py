@@ -26,6 +26,7 @@ WS_ERR_STATE = -5
 WS_ERR_IO = -6
 WS_ERR_OVERFLOW = -7
 WS_CONTRIB_SUM_SCALE = 4294967296.0  # sum_q32 / scale = sum of weights
+WS_METRICS_QUANTIZE_U8 = 1           # ws_metrics_add / ws_scene_evaluate flag: compare the 8-bit images a PNG would hold
 
 WS_FORMAT_RGBA8_UNORM = 0
 WS_FORMAT_RGBA16_FLOAT = 1
@@ -162,6 +163,18 @@ class ws_composite_desc(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class ws_image_view(C.Structure):
+    _fields_ = [("d_pixels", C.c_void_p), ("format", C.c_int), ("row_pitch_bytes", C.c_size_t), ("over_background", C.c_int32),
+                ("background", C.c_float * 3)]
+
+
+class ws_image_metrics(C.Structure):
+    _fields_ = [("mse", C.c_double), ("psnr", C.c_double), ("ssim", C.c_double), ("sse_u8", C.c_uint64),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(ws_image_view) == 40
+assert C.sizeof(ws_image_metrics) == 48
 assert C.sizeof(ws_camera_uniform) == 272
 assert C.sizeof(ws_settings_uniform) == 80
 assert C.sizeof(ws_gaussian_quantization) == 64
@@ -294,6 +307,16 @@ SIGNATURES = {
     "ws_contrib_add": (C.c_int, [_P, C.POINTER(C.c_uint64), _f32p, C.c_uint32]),
     "ws_pointcloud_create_subset": (C.c_int, [_P, _P, _u32p, C.c_uint32, _PP]),
     "ws_scene_accumulate_contrib": (C.c_int, [_P, _P, _P, C.c_int, _P, _u32p]),
+    "ws_metrics_create": (C.c_int, [_P, C.c_uint32, _PP]),
+    "ws_metrics_destroy": (None, [_P]),
+    "ws_metrics_reset": (C.c_int, [_P, _P]),
+    "ws_metrics_count": (C.c_uint32, [_P]),
+    "ws_metrics_add": (C.c_int, [_P, C.POINTER(ws_image_view), C.POINTER(ws_image_view), C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                 C.c_size_t, _P]),
+    "ws_metrics_download": (C.c_int, [_P, C.c_uint32, C.POINTER(ws_image_metrics), _u32p]),
+    "ws_png_read_rgba8": (C.c_int, [C.c_char_p, _u32p, _u32p, C.POINTER(C.POINTER(C.c_uint8))]),
+    "ws_host_free": (None, [_P]),
+    "ws_scene_evaluate": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_uint32, _P, _u32p]),
 }
 
 

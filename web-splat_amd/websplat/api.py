@@ -654,6 +654,145 @@ def accumulate_contrib_scene(ctx: "Context", pc: "PointCloud", scene: Scene, spl
     return n.value
 
 
+@dataclass
+class ImageView:
+    """One image as the metrics see it (ws_image_view): device pointer, format name ("rgba8unorm" / "rgba16float" / "rgba32float"),
+    row pitch in bytes, and the background colour the premultiplied texels go over (None: the colour channels as stored)."""
+    ptr: int
+    format: str
+    pitch: int
+    background: Optional[Sequence[float]] = None
+
+    def to_c(self):
+        v = L.ws_image_view()
+        v.d_pixels = self.ptr
+        v.format = FORMATS[self.format][0]
+        v.row_pitch_bytes = int(self.pitch)
+        v.over_background = 0 if self.background is None else 1
+        if self.background is not None:
+            v.background[:] = [float(x) for x in self.background[:3]]
+        return v
+
+
+def _as_view(v) -> ImageView:
+    return v if isinstance(v, ImageView) else ImageView(*v)
+
+
+class Metrics:
+    """PSNR / SSIM records of up to max_images image pairs, computed on the device (websplat.h "Image metrics").  One
+    accumulator is used from one stream at a time."""
+
+    def __init__(self, ctx: Context, max_images: int):
+        self.ctx = ctx
+        h = C.c_void_p()
+        check(lib.ws_metrics_create(ctx.handle, int(max_images), C.byref(h)))
+        self.handle = h
+        self.max_images = int(max_images)
+        self._maps = []  # (device plane, width, height) of the adds that asked for the SSIM map, in add order
+
+    def _free_maps(self):
+        for ptr, _, _ in self._maps:
+            self.ctx.free(ptr)
+        self._maps = []
+
+    def close(self):
+        if self.handle:
+            lib.ws_metrics_destroy(self.handle)  # (waits for the device)
+            self.handle = None
+            self._free_maps()
+
+    def reset(self, stream=None):
+        check(lib.ws_metrics_reset(self.handle, C.c_void_p(stream or 0)))
+        self.ctx.sync(stream)
+        self._free_maps()
+
+    @property
+    def count(self) -> int:
+        """image pairs added since creation / the last reset"""
+        return lib.ws_metrics_count(self.handle)
+
+    def add(self, a, b, width: int, height: int, quantize_u8=False, ssim_map=False, stream=None):
+        """Enqueue the comparison of views a and b (ImageView, or (ptr, format, pitch, background-or-None) tuples).  ssim_map:
+        also keep the W x H map, returned by maps()."""
+        va, vb = _as_view(a).to_c(), _as_view(b).to_c()
+        d_map, pitch = None, 0
+        if ssim_map:
+            d_map, pitch = self.ctx.malloc(int(width) * int(height) * 4), int(width) * 4
+        try:
+            check(lib.ws_metrics_add(self.handle, C.byref(va), C.byref(vb), int(width), int(height),
+                                     L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, C.c_void_p(d_map or 0), pitch,
+                                     C.c_void_p(stream or 0)))
+        except Exception:
+            if d_map:
+                self.ctx.free(d_map)
+            raise
+        if d_map:
+            self._maps.append((d_map, int(width), int(height)))
+
+    def download(self):
+        """One dict per image pair, in add order: mse, psnr, ssim, sse_u8, width, height, flags (syncs)."""
+        n = self.count
+        buf = (L.ws_image_metrics * max(n, 1))()
+        got = C.c_uint32()
+        check(lib.ws_metrics_download(self.handle, n, buf, C.byref(got)))
+        return [{k: getattr(buf[i], k) for k in ("mse", "psnr", "ssim", "sse_u8", "width", "height", "flags")} for i in range(got.value)]
+
+    def maps(self):
+        """The SSIM maps (H x W float32) of the adds that asked for one, in add order (call after download(), which syncs)."""
+        return [self.ctx.download(ptr, (h, w), np.float32) for ptr, w, h in self._maps]
+
+
+_NP_FORMATS = {np.dtype(np.uint8): "rgba8unorm", np.dtype(np.float16): "rgba16float", np.dtype(np.float32): "rgba32float"}
+
+
+def image_metrics(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, background_a=None, background_b=None, quantize_u8=False,
+                  ssim_map=False):
+    """PSNR / SSIM of two H x W x 4 numpy images (uint8, float16 or float32, each its own format): upload, add, download.
+    Returns the record's dict, or (dict, H x W float32 map) with ssim_map."""
+    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
+    for im in imgs:
+        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
+            raise ValueError("image_metrics: two H x W x 4 arrays of one size, uint8 / float16 / float32")
+    h, w = imgs[0].shape[:2]
+    ptrs = []
+    m = Metrics(ctx, 1)
+    try:
+        views = []
+        for im, bg in zip(imgs, (background_a, background_b)):
+            ptrs.append(ctx.malloc(im.nbytes))
+            ctx.upload(ptrs[-1], im)
+            views.append(ImageView(ptrs[-1], _NP_FORMATS[im.dtype], w * im.itemsize * 4, bg))
+        m.add(views[0], views[1], w, h, quantize_u8=quantize_u8, ssim_map=ssim_map)
+        rec = m.download()[0]
+        return (rec, m.maps()[0]) if ssim_map else rec
+    finally:
+        m.close()
+        for p in ptrs:
+            ctx.free(p)
+
+
+def read_png(path: str) -> np.ndarray:
+    """An 8-bit grey / grey + alpha / RGB / RGBA PNG as H x W x 4 uint8 (ws_png_read_rgba8)."""
+    w, h = C.c_uint32(), C.c_uint32()
+    p = C.POINTER(C.c_uint8)()
+    check(lib.ws_png_read_rgba8(str(path).encode(), C.byref(w), C.byref(h), C.byref(p)))
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()
+    finally:
+        lib.ws_host_free(p)
+
+
+def evaluate_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, metrics: "Metrics", ref: "PointCloud" = None,
+                   gt_dir: str = None, quantize_u8=False) -> int:
+    """Every camera of `split` adds one record to `metrics`: `pc` against the cloud `ref` (set up as render_views sets its
+    frames up) or against the PNGs <gt_dir>/<img_name>[.png], rendered at each PNG's size.  Returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_evaluate(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+                                None if gt_dir is None else str(gt_dir).encode(), L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0,
+                                metrics.handle, C.byref(n)))
+    return n.value
+
+
 class GaussianRenderer:
     """renderer.rs:33-283.  `prepare` + `render` enqueue on a HIP stream; nothing syncs except the
     read-back helpers (num_visible_points, frame_stats, stage_times, download_*)."""
