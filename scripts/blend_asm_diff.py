@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Is the device code of raster.hip the same, kernel for kernel, in two trees?  (The check of a blend refactor: no GPU needed.)
+"""Is the device code of a translation unit (raster.hip, contrib.hip, ...) the same, kernel for kernel, in two trees?  (The check of
+a kernel refactor: no GPU needed.)
 
   hipcc <the Makefile's COMMON flags> [-DWS_EXPERIMENTAL] --cuda-device-only -S csrc/raster.hip -o {old,new}.s
-  python scripts/blend_asm_diff.py old.s new.s > profiles/.../blend_asm_diff_<build>.txt
+  python scripts/blend_asm_diff.py [--may-differ REGEX] old.s new.s > profiles/.../blend_asm_diff_<build>.txt
 
 Per .amdhsa_kernel: the function body and its .amdhsa_* descriptor block, the kernel's own mangled name replaced by a
 placeholder, the function index stripped from .LBB<n>_ / .Lfunc_end<n> labels, comment lines and trailing comments dropped.
 Verdict SAME iff (1) the multisets of normalised kernels are equal, (2) the kernels that are not k_blend / k_blend_strict are equal
 WITH their names, (3) the paired k_blend / k_blend_strict kernels agree in the metadata note: kernarg segment size, argument
-offsets and sizes, VGPRs, SGPRs, LDS, scratch.  Prints the per-kernel resource table of the new file; exit status 1 unless SAME."""
+offsets and sizes, VGPRs, SGPRs, LDS, scratch.  Prints the per-kernel resource table of the new file; exit status 1 unless SAME.
+Kernels whose demangled name matches --may-differ are left out of the verdict and listed with their resources before and after."""
 import collections
 import hashlib
 import re
@@ -63,11 +65,25 @@ def is_blend(demangled):
     return re.search(r"\bk_blend(_strict)?<", demangled) is not None
 
 
-def main(old_path, new_path):
+def main(old_path, new_path, may_differ=None):
     old, new = kernels(old_path), kernels(new_path)
     old_meta, new_meta = metadata(old_path), metadata(new_path)
     names = demangle(sorted(set(old) | set(new)))
     problems = []
+    if may_differ:  # before / after rows of the kernels the verdict leaves out; both sides must still have them
+        print(f"left out of the verdict (--may-differ {may_differ!r}):")
+        print(f"{'':6s} {'kernarg':>7s} {'vgpr':>4s} {'sgpr':>4s} {'lds':>6s} {'scratch':>7s} {'lines':>6s}  kernel")
+        for n in sorted((n for n in set(old) | set(new) if re.search(may_differ, names[n])), key=lambda n: names[n]):
+            for side, ks, meta in (("old", old, old_meta), ("new", new, new_meta)):
+                if n in ks:
+                    m = meta[n]
+                    print(f"{side:6s} {m[0]:7d} {m[1]:4d} {m[2]:4d} {m[3]:6d} {m[4]:7d} {len(ks[n].splitlines()):6d}  {names[n]}"
+                          f"{'  (body unchanged)' if side == 'new' and old.get(n) == ks[n] else ''}")
+                else:
+                    problems.append(f"missing in {side}: {names[n]}")
+            old.pop(n, None)
+            new.pop(n, None)
+        print()
     digest = lambda t: hashlib.sha256(t.encode()).hexdigest()[:16]
     by_text_old = collections.defaultdict(list)
     for n, t in old.items():
@@ -112,6 +128,8 @@ def main(old_path, new_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    pattern = args[1] if len(args) == 4 and args[0] == "--may-differ" else None
+    if len(args) != (4 if pattern else 2):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[-2], args[-1], pattern))

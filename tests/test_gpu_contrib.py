@@ -1,7 +1,8 @@
 """Per-Gaussian contribution sums over frames (include/websplat.h "Per-Gaussian contributions", contrib.hip k_contrib).
 
   1. against a float64 front-to-back walk of the device's own frame (tests/contrib_ref.py), every Gaussian compared, over the
-     tile shapes, binning shifts and split setting, and on a compressed cloud
+     tile shapes, binning shifts and split setting, and on a compressed cloud; tile lists of exactly the lengths at which
+     the staging changes batch or sub-round
   2. oracle-free: the sums add up to the coverage plane; bitwise reproducible, additive over frames and accumulators; the
      sum / max invariants; culled Gaussians are exactly 0
   3. enable_contrib changes no pixel; the error cases of the C ABI
@@ -52,7 +53,7 @@ def _accumulate(ws, c, pc, args, compressed=False, sh_deg=3, with_frame=False, w
         r.close()
 
 
-def _compare(got, ref):
+def _compare(got, ref, min_drawn=1000):
     tol_sum, tol_max = contrib_ref.bounds(ref)
     d_sum = np.abs(got["sum"] - ref["sum"])
     d_max = np.abs(got["max"].astype(np.float64) - ref["max"])
@@ -63,7 +64,7 @@ def _compare(got, ref):
           f"(ref {ref['sum'][worst_s]:.6e}, tol {tol_sum[worst_s]:.3e}); max rel err without P/U "
           f"{np.max(np.where((ref['P'] == 0) & (ref['U'] == 0) & (ref['sum'] > 0), d_sum / np.maximum(ref['sum'], 1e-300), 0)):.3e}; "
           f"max: max |d| {d_max.max():.3e}, worst excess {(d_max - tol_max)[worst_m]:.3e} at {worst_m}")
-    assert drawn > 1000
+    assert drawn > min_drawn
     assert np.all(d_sum <= tol_sum), f"{int((d_sum > tol_sum).sum())} sums out of bound"
     assert np.all(d_max <= tol_max), f"{int((d_max > tol_max).sum())} maxima out of bound"
 
@@ -94,6 +95,56 @@ def test_against_f64_c1(ws, oracle, seed, cfg):
             _compare(got, _reference(("c1", seed), got["frame"], 320, 240, pc.num_points()))
         finally:
             pc.close()
+    finally:
+        c.close()
+
+
+def _stack(k, opacity):
+    """k isotropic Gaussians on the optical axis at distinct depths, each covering the whole 32 x 32 viewport (sigma ~ 12 px:
+    the cut-off ellipse reaches 26 px from the centre, the corners are 22.6 px away), so every tile lists all k and every
+    quadrant's wave walks all of them -- until it saturates."""
+    z = np.linspace(-0.25, 0.25, k, dtype=np.float32) if k > 1 else np.zeros(1, dtype=np.float32)
+    xyz = np.stack([np.zeros(k, np.float32), np.zeros(k, np.float32), z], axis=1)
+    rng = np.random.default_rng(k)
+    f_dc = rng.uniform(-1.0, 1.0, size=(k, 3)).astype(np.float32)
+    rot = np.tile(np.array([1.0, 0.0, 0.0, 0.0], np.float32), (k, 1))
+    log_scale = np.full((k, 3), np.log(12.0 * 3.0 / 320.0), np.float32)
+    logit = np.full(k, np.log(opacity / (1.0 - opacity)), np.float32)
+    return synth._rows(xyz, f_dc, np.zeros((k, 45), np.float32), logit, log_scale, rot)
+
+
+# list lengths around the batch size (STAGE = 512 at the 4x4 tile, 256 at 2x2) and the sub-round size (LCAP), one and two batches
+BOUNDARY_CASES = [({}, k) for k in (1, 511, 512, 513, 1024, 1025)] + [({"tile_qw": 2, "tile_qh": 2}, k) for k in (255, 256, 257, 513)]
+
+
+@pytest.mark.parametrize("opacity", [0.002, 0.9], ids=["faint", "opaque"])
+@pytest.mark.parametrize("cfg,k", BOUNDARY_CASES, ids=[f"{'2x2' if c else '4x4'}-{k}" for c, k in BOUNDARY_CASES])
+def test_list_lengths_at_staging_boundaries(ws, cfg, k, opacity):
+    """Tile lists of exactly k entries.  Faint: T stays above T_MIN (0.998^1025 = 0.13), every batch is walked to its end and
+    every Gaussian draws.  Opaque: every pixel is below T_MIN after ~60 layers (b >= 0.15 at the corners), the tile saturates
+    inside its first batch, the walk and the batch loop take their early exits and the Gaussians behind get exactly 0 (a single
+    Gaussian, k = 1, saturates nothing: it has to draw)."""
+    c = _ctx(ws, bin_request=0, **cfg)
+    try:
+        gpc = ws.GenericGaussianPointCloud.from_ply_rows(_stack(k, opacity), 3)
+        cj = synth.look_at_camera(0, [0.0, 0.0, -3.0], [0.0, 0.0, 0.0], 32, 32, 320.0, 320.0)
+        cam = ws.PerspectiveCamera.from_scene_camera(cj.position, cj.rotation, cj.fx, cj.fy, 32, 32)
+        # (the cloud's own box is a segment of the optical axis, for k = 1 a point: near / far fitted to it touch the Gaussians)
+        cam.fit_near_far(ws.Aabb([-1, -1, -1], [1, 1, 1]))
+        args = ws.SplattingArgs(camera=cam, viewport=(32, 32), max_sh_deg=3)
+        pc = ws.PointCloud(c, gpc)
+        try:
+            got = _accumulate(ws, c, pc, args, with_frame=True, with_alpha=True)  # (asserts overflow == 0)
+        finally:
+            pc.close()
+        q = got["q"]
+        print(f"k {k} opacity {opacity} longest list {got['longest']} drawn {int((q > 0).sum())} zero {int((q == 0).sum())}")
+        assert got["longest"] == k
+        if opacity < 0.5 or k == 1:
+            assert np.all(q > 0)
+        else:
+            assert (q == 0).any() and (q > 0).any()
+        _compare(got, contrib_ref.contrib_f64(got["frame"], 32, 32, k), min_drawn=0)
     finally:
         c.close()
 

@@ -93,7 +93,9 @@ WS_HD uint32_t quadrant_mask(float A, float B2, float C, float D, float cxl, flo
     const float dA2 = D * invA * invA;
     const float rpad = 8e-6f * cA;
     uint32_t mask = 0u;
+#if defined(__HIPCC__)
 #pragma unroll
+#endif
     for (int r = 0; r < QH; ++r) {
         const float y0 = (float)(8 * r) + 0.5f - cyl, y1 = y0 + 7.0f;
         const float lo = fmaxf(y0, -ymax), hi = fminf(y1, ymax);

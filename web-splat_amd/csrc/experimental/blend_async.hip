@@ -14,8 +14,9 @@
 // A stager wave stages batch b + 1 EARLY (before it walks batch b) if batch b - 1's buffer is already free -- true for the
 // slowest wave, which is what keeps everybody supplied -- else LATE (behind its walk of batch b): a fast wave runs up to one
 // batch ahead of the slowest instead of waiting for it twice per batch.  A tile with ONE batch (the median hd1m tile) never waits
-// at all behind its staging: every wave stores its pixels when its own walk ends.  Per wave the compaction, the walk and the
-// saturation test are k_blend's, statement for statement: the image is bit-identical (test_async_blend_is_bit_identical).
+// at all behind its staging: every wave stores its pixels when its own walk ends.  Staging and compaction are the calls k_blend
+// makes (blend_tile.h), one sub-round per batch; the walk and the saturation test repeat k_blend's FAST walk (its padded groups of
+// four, blend_composite): the image is bit-identical (test_async_blend_is_bit_identical).
 // One tile per workgroup at the 32x32 tile (4 x 4 quadrants); every other shape / MULTI / capture / timing stays with k_blend.
 // LDS: 2 x 16.4 KB records + 2 x 1 KB masks + 33.8 KB lists = 68.7 KB: two workgroups per CU, as k_blend.
 __device__ __forceinline__ uint32_t lds_peek(const uint32_t* w) {  // wave-uniform read of an LDS counter other waves bump
@@ -36,28 +37,25 @@ __device__ __forceinline__ void lds_bump(uint32_t* w) {  // this wave's earlier 
 #endif
 template <int FORMAT>
 __global__ __launch_bounds__(1024, 8) void k_blend2(const BlendParams p) {
-    constexpr int QW = 4, QH = 4, NW = 16, STAGE = 512, SLOTS = STAGE + 1, LCAP = 512, TW = 32, TH = 32;
+    constexpr int QW = 4, QH = 4;
+    using G = tile::Geometry<QW, QH, 512>;  // (the double-buffered LDS below is sized for batches of 512, whatever k_blend stages)
+    constexpr int NW = G::NW, STAGE = G::STAGE, SLOTS = G::SLOTS, LCAP = G::LCAP, TW = G::TW, TH = G::TH;
+    static_assert(STAGE == LCAP, "one sub-round per batch");
     constexpr uint32_t NSTAGERS = STAGE / 64;
     __shared__ float4 s_rec[2][2 * SLOTS];
     __shared__ __attribute__((aligned(16))) uint16_t s_m[2][STAGE];
     __shared__ __attribute__((aligned(16))) uint32_t s_list[NW][LCAP + 16];
     __shared__ uint32_t s_ctr[8];  // [0..1] staged per parity, [2..3] walked per parity, [4] dead waves
 
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.sticky) {
-        const uint32_t bits = p.counters->overflow;
-        if (bits) fold_frame_errors(p, bits);
-        post_frame_progress(p);
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.sticky) blend_frame_begin(p);
     const BlendShape shape = blend_shape(QW, QH);
     const BlendBlock blk = blend_block_of(blockIdx.x, p.tiles_x, p.tiles_y, shape, 0u);
     const bool ordered = p.order != nullptr;
     if (!ordered && !blk.valid) return;  // block-uniform
     const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int qx = wave % QW, qy = wave / QW;
-    const float lx = (float)(qx * 8 + (lane & 7)) + 0.5f;
-    const float ly = (float)(qy * 8 + (lane >> 3)) + 0.5f;
-    const uint32_t qbit = 1u << wave;
+    const tile::Quadrant me = tile::quadrant<QW>(tid);
+    const int wave = me.wave, lane = me.lane;
+    const float lx = me.lx, ly = me.ly;
     const bool stager = wave < (int)NSTAGERS;  // waves 0..7 (decided on the SGPR copy of the wave index: every `if (stager)` is a scalar branch)
     uint2 range = make_uint2(0u, 0u);
     uint32_t code = 0xFFFFFFFFu;
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(1024, 8) void k_blend2(const BlendParams p) {
         if (tx < p.tiles_x && ty < p.tiles_y) {
             code = tx | (ty << 16);
             range = p.tile_ranges[tile_list_index(p, tx, ty)];
-            range.x = range.y ? 0xFFFFFFFFu - range.x : 0u;
+            range.x = tile::range_begin(range.x, range.y);
         }
     }
     if (code == 0xFFFFFFFFu) return;  // block-uniform
@@ -87,16 +85,15 @@ __global__ __launch_bounds__(1024, 8) void k_blend2(const BlendParams p) {
     RawSplat raw = {{0u, 0u, 0u, 0u}, 0u};
     uint32_t idx_next = 0u;
     if (stager && nbatch) {
-        raw = blend_fetch_raw<STAGE>(p, range, range.y, tid);
-        idx_next = blend_entry_idx<STAGE>(p, range, nbatch > 1u ? hi_of(1u) : range.x, tid);
+        raw = tile::gather(p.splats, tile::entry_idx<STAGE>(p.entry_vals, range, range.y, tid));
+        idx_next = tile::entry_idx<STAGE>(p.entry_vals, range, nbatch > 1u ? hi_of(1u) : range.x, tid);
     }
     if (tid < 8) s_ctr[tid] = 0u;
     if (tid < 2) {  // the null record of both buffers (a' = 1e18: never inside the cut-off), pads the lists to multiples of four
         s_rec[tid][STAGE] = make_float4(0.0f, 0.0f, 1.0e9f, 0.0f);
         s_rec[tid][SLOTS + STAGE] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    const uint32_t px = tx * TW + qx * 8 + (lane & 7);
-    const uint32_t py = ty * TH + qy * 8 + (lane >> 3);
+    const uint32_t px = me.px(tx * TW), py = me.py(ty * TH);
     const bool inside = px < p.width && py < p.height;
     float T = inside ? 1.0f : 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
     const float W = (float)p.width, H = (float)p.height;
@@ -112,20 +109,15 @@ __global__ __launch_bounds__(1024, 8) void k_blend2(const BlendParams p) {
         // stage batch sb into buffer sb & 1 (this thread's slot) and send the loads of the batches behind it on their way
         auto stage_batch = [&]() {
             const uint32_t hi = hi_of(sb);
-            const uint32_t nb = (hi - range.x) < (uint32_t)STAGE ? (hi - range.x) : (uint32_t)STAGE;
+            const uint32_t nb = tile::batch_len<STAGE>(range.x, hi);
             float4* rec = s_rec[sb & 1u];
             uint32_t mask = 0u;
-            if ((uint32_t)tid < nb) {
-                const stage::Staged st = stage::decode<QW, QH>(raw.a.x, raw.a.y, raw.a.z, raw.a.w, raw.w4, W, H, tile_x0, tile_y0, CUT_A2);
-                mask = st.mask;
-                rec[tid] = make_float4(st.i00, st.i01, st.c0, st.i10);
-                rec[SLOTS + tid] = make_float4(st.i11, st.c1, __uint_as_float(raw.a.w), __uint_as_float(raw.w4));
-            }
-            s_m[sb & 1u][((uint32_t)tid & 63u) * (LCAP / 64) + ((uint32_t)tid >> 6)] = (uint16_t)mask;
+            if ((uint32_t)tid < nb) mask = tile::stage_store<QW, QH, SLOTS>(rec, tid, raw, W, H, tile_x0, tile_y0);
+            s_m[sb & 1u][tile::mask_slot<LCAP>((uint32_t)tid, (uint32_t)lane)] = (uint16_t)mask;
             // (unconditional, addresses clamped into the tile's range -- see k_blend: a conditional prefetch waits for its own data)
-            raw = blend_gather(p, idx_next);
+            raw = tile::gather(p.splats, idx_next);
             const uint32_t h2 = sb + 2u < nbatch ? hi_of(sb + 2u) : range.x;
-            idx_next = blend_entry_idx<STAGE>(p, range, h2, tid);
+            idx_next = tile::entry_idx<STAGE>(p.entry_vals, range, h2, tid);
             lds_bump(&s_ctr[sb & 1u]);
             ++sb;
             walked_since_stage = false;
@@ -168,25 +160,10 @@ __global__ __launch_bounds__(1024, 8) void k_blend2(const BlendParams p) {
                 // (the buffer's byte offset is folded into the list entries: the walk's LDS addresses stay list entry + constant)
                 const uint32_t bufoff = (b & 1u) * (uint32_t)(2 * SLOTS * 16);
                 const float4* rec = s_rec[0];
-                // wave-private compaction: records whose kept ellipse reaches this quadrant, near -> far (k_blend's, one sub-round)
-                const uint2* mp = reinterpret_cast<const uint2*>(s_m[b & 1u] + (uint32_t)lane * (LCAP / 64));
-                uint32_t n = 0;
-                uint32_t slot16 = (uint32_t)lane * 16u + bufoff;
+                // wave-private compaction: records whose kept ellipse reaches this quadrant, near -> far (slots past the batch's end hold mask 0)
+                uint32_t slot16 = tile::list_value((uint32_t)lane) + bufoff;
                 asm volatile("" : "+v"(slot16));
-#pragma unroll
-                for (int h = 0; h < LCAP / 256; ++h) {
-                    const uint2 mm = mp[h];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int r = h * 4 + q;
-                        const uint32_t word = (q & 2) ? mm.y : mm.x;
-                        const bool t = (word & (qbit << ((q & 1) * 16))) != 0u;  // (slots past the batch's end hold mask 0)
-                        const unsigned long long bal = __ballot(t);
-                        const uint32_t pos = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                        if (t) my_list[pos] = slot16 + (uint32_t)r * 1024u;
-                        n += (uint32_t)__popcll(bal);
-                    }
-                }
+                const uint32_t n = tile::compact<LCAP, false>(s_m[b & 1u], my_list, 0u, 0u, lane, me.bit, slot16);
                 if (n > 0u) {
                     if (lane < 4 && ((n + (uint32_t)lane) >> 2) == (n >> 2) && (n & 3u)) my_list[n + lane] = (uint32_t)STAGE * 16u + bufoff;  // pad to x4
                     const uint32_t n4 = (n + 3u) >> 2;

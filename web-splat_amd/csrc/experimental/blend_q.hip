@@ -5,11 +5,7 @@ template <int FORMAT>
 __global__ __launch_bounds__(64) void k_blend_q(const BlendParams p) {
     // blockIdx -> (tile, quadrant): workgroup b runs on XCD b % 8 (observed; used for locality only)
     const uint32_t b = blockIdx.x;
-    if (b == 0 && threadIdx.x == 0 && p.sticky) {  // as in k_blend
-        const uint32_t bits = p.counters->overflow;
-        if (bits) fold_frame_errors(p, bits);
-        post_frame_progress(p);
-    }
+    if (b == 0 && threadIdx.x == 0 && p.sticky) blend_frame_begin(p);  // as in k_blend
     const uint32_t xcd = b & 7u, j = b >> 3;
     const uint32_t nq = p.qw * p.qh;
     const uint32_t q = j % nq;
@@ -28,7 +24,7 @@ __global__ __launch_bounds__(64) void k_blend_q(const BlendParams p) {
     const float W = (float)p.width, H = (float)p.height;
 
     uint2 range = p.tile_ranges[tile_list_index(p, tx, ty)];
-    range.x = range.y ? 0xFFFFFFFFu - range.x : 0u;
+    range.x = tile::range_begin(range.x, range.y);
     float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
     bool done = !inside;
 
@@ -39,15 +35,8 @@ __global__ __launch_bounds__(64) void k_blend_q(const BlendParams p) {
     if (range.y > range.x) {
     // entry index of this lane in the chunk that ends at hi_ (lane 0 = nearest); hi_ is clamped so the address
     // is always inside [range.x, range.y)
-    auto entry_at = [&](uint32_t hi_) -> uint32_t {
-        const uint32_t h = hi_ > range.x ? hi_ : range.x + 1u;
-        const uint32_t nbb = (h - range.x) < 64u ? (h - range.x) : 64u;
-        const uint32_t off = (uint32_t)lane < nbb ? (uint32_t)lane : nbb - 1u;
-        return p.entry_vals[h - 1u - off];
-    };
-    auto chunk_len = [&](uint32_t hi_) -> uint32_t {
-        return hi_ > range.x ? ((hi_ - range.x) < 64u ? (hi_ - range.x) : 64u) : 0u;
-    };
+    auto entry_at = [&](uint32_t hi_) -> uint32_t { return tile::entry_idx<64>(p.entry_vals, range, hi_, lane); };
+    auto chunk_len = [&](uint32_t hi_) -> uint32_t { return hi_ > range.x ? tile::batch_len<64>(range.x, hi_) : 0u; };
     uint32_t hi = range.y;                        // chunk being composited ends here
     uint32_t hi1 = hi - chunk_len(hi);            // next chunk
     uint32_t idx_cur = entry_at(hi);

@@ -24,7 +24,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "blend_stage.h"
+#include "blend_tile.h"
 #include "emit_gen.h"
 #include "lookback.h"
 #include "ws_internal.h"
@@ -276,8 +276,8 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(const emit::Source src
 // band-by-band x-range, blend_stage.h -- not the bounding box), every wave compacts the staged records to those
 // that reach its quadrant -- one LDS read + one ballot per 64 records -- and then walks only those, with the next
 // record's LDS reads in flight while the current one is composited.
-constexpr float LOG2E = stage::LOG2E_F;
-constexpr float CUT_A2 = CUT_A * LOG2E;  // gaussian.wgsl:61 cut-off, in the exp2 domain
+using tile::CUT_A2;
+using tile::RawSplat;
 
 // blockIdx -> tiles.  64x64-pixel blocks (16 / 8 / 4 tiles) are dealt round-robin to the 8 XCDs (workgroup b runs
 // on XCD b % 8 -- observed, used for locality only): a splat's tiles mostly share a block, so its 20-B record and
@@ -331,12 +331,9 @@ inline uint32_t blend_tpw_log2(uint32_t tiles_x, uint32_t tiles_y, BlendShape sh
     return want < most ? want : most;
 }
 
-// Index of the binned list blend tile (tx, ty) composites: its own, the binning tile's it is a half of (split mode), or
-// -- when the frame binned at twice the blend's tile size (FrameCounters::bin_shift) -- the 2 x 2 block's it belongs to.
+// Index of the binned list blend tile (tx, ty) composites (blend_tile.h list_index)
 __device__ __forceinline__ uint32_t tile_list_index(const BlendParams& p, uint32_t tx, uint32_t ty) {
-    const uint32_t s = p.counters->bin_shift;
-    const uint32_t btx = s ? (p.bin_tiles_x + 1u) >> 1 : p.bin_tiles_x;
-    return ((ty >> p.range_row_shift) >> s) * btx + (tx >> s);
+    return tile::list_index(tx, ty, p.counters->bin_shift, p.bin_tiles_x, p.range_row_shift);
 }
 
 template <int FORMAT>
@@ -423,7 +420,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_blend_order(const uint2* __re
     for (uint32_t c = tid; c < (uint32_t)ORDER_CLASSES; c += ORDER_THREADS) s_cnt[c] = 0u;
     __syncthreads();
     const uint32_t s = counters->bin_shift;
-    const uint32_t btx = s ? (bin_tiles_x + 1u) >> 1 : bin_tiles_x;
+    const uint32_t btx = s ? (bin_tiles_x + 1u) >> 1 : bin_tiles_x;  // (tile::list_index without a split, its row length hoisted)
     const uint32_t ntiles = tiles_x * tiles_y;
     // Agent-scope loads and stores throughout (they go past the per-XCD L2s, which are not coherent with one another): this
     // ONE workgroup reads ranges that the whole chip wrote with memory-side atomics over lines the frame's memset left in the
@@ -434,7 +431,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_blend_order(const uint2* __re
         const unsigned long long w = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(tile_ranges + (ty >> s) * btx + (tx >> s)),
                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint2 r = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-        r.x = r.y ? 0xFFFFFFFFu - r.x : 0u;
+        r.x = tile::range_begin(r.x, r.y);
         return r;
     };
     auto put = [&](uint32_t pos, uint32_t code, uint2 r) {
@@ -481,12 +478,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_blend_order(const uint2* __re
     for (uint32_t b = ntiles + tid; b < nblocks; b += ORDER_THREADS) put(b, 0xFFFFFFFFu, make_uint2(0u, 0u));
 }
 
-// The last kernel of a frame folds the frame's error bits (per-frame zero arena) into the renderer's sticky words, which no
-// per-frame memset clears: [0] the bits, [1] the largest entry demand of an overflowed frame.  The demand is ALSO posted --
-// a plain system-scope store by this one thread -- to a host-visible mailbox word (pinned, mapped memory) that the next
-// prepare() reads without any device synchronisation: a renderer whose frames overflow its entry list grows the list by
-// itself, whether or not its caller ever polls ws_renderer_errors.
-// (the same thread, when the blend starts: "frame frame_seq of this renderer has reached its compositing pass")
+// "frame frame_seq of this renderer has reached its compositing pass"
 __device__ __forceinline__ void post_frame_progress(const BlendParams& p) {
     if (p.progress_mailbox) {
         __hip_atomic_store(p.progress_mailbox, p.frame_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -494,44 +486,10 @@ __device__ __forceinline__ void post_frame_progress(const BlendParams& p) {
         if (cls) __hip_atomic_store(p.progress_mailbox + 1, cls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-__device__ __forceinline__ void fold_frame_errors(const BlendParams& p, uint32_t bits) {
-    atomicOr(p.sticky, bits);
-    if (bits & 1u) {
-        const uint32_t need = p.counters->entries_needed;
-        const uint32_t before = atomicMax(p.sticky + 1, need);  // what a retry (or the next prepare) allocates
-        if (p.demand_mailbox) __hip_atomic_store(p.demand_mailbox, need > before ? need : before, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// raw words of one staged entry: the 20-B Splat record (pointcloud.rs:352-358)
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-struct RawSplat {
-    u32x4_t a;    // words 0..3: kept as ONE 128-bit value from the load to the decode (see blend_fetch_raw)
-    uint32_t w4;
-};
-// This thread's entry of the batch that ends at `hi` (slot 0 = nearest): its Splat index.  The address is clamped into
-// the tile's (non-empty) range, so the load never depends on a branch and can be issued batches ahead.
-template <int STAGE>
-__device__ __forceinline__ uint32_t blend_entry_idx(const BlendParams& p, uint2 range, uint32_t hi, int tid) {
-    const uint32_t h = hi > range.x ? hi : range.x + 1u;
-    const uint32_t nb = (h - range.x) < (uint32_t)STAGE ? (h - range.x) : (uint32_t)STAGE;
-    const uint32_t off = (uint32_t)tid < nb ? (uint32_t)tid : nb - 1u;
-    return p.entry_vals[h - 1u - off];
-}
-// The 20-B Splat record.  One dwordx4 + one dword, and the four words stay a single 128-bit value until the decode: as
-// five scalars the compiler parked three of them in other registers right behind the load (s_waitcnt vmcnt + v_mov: the
-// gather of the next batch never overlapped the walk of the current one); five separate dword loads fix that too but cost
-// 2.5x the address lookups of a random gather (measured: blend +35 % on hd1m, +29 % on c3).
-__device__ __forceinline__ RawSplat blend_gather(const BlendParams& p, uint32_t idx) {
-    const char* sp = reinterpret_cast<const char*>(p.splats) + (size_t)idx * SPLAT_STRIDE;
-    RawSplat r;
-    __builtin_memcpy(&r.a, sp, 16);
-    __builtin_memcpy(&r.w4, sp + 16, 4);
-    return r;
-}
-template <int STAGE>
-__device__ __forceinline__ RawSplat blend_fetch_raw(const BlendParams& p, uint2 range, uint32_t hi, int tid) {
-    return blend_gather(p, blend_entry_idx<STAGE>(p, range, hi, tid));
+// The first thread of the frame's last kernel: the frame's error bits into the sticky words (blend_tile.h), progress to the host
+__device__ __forceinline__ void blend_frame_begin(const BlendParams& p) {
+    tile::fold_frame_errors(p.counters, p.sticky, p.demand_mailbox);
+    post_frame_progress(p);
 }
 
 // ---- gfx950 LDS-DMA staging (the dma forms of k_blend) ---------------------------------------------------------------------
@@ -635,15 +593,7 @@ __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, flo
     }
     if (OCC) keep = keep && z < D;
     if (keep) {
-        // b = min(0.99, 2^-a' * alpha), alpha = high half of h.w.  One asm block: gfx950 needs one wait state between
-        // a transcendental's result and a VALU instruction reading it, and the compiler does not look inside asm.
-        float b;
-        asm("v_exp_f32_e64 %0, -%1\n\ts_nop 0\n\t"
-            "v_fma_mix_f32 %0, %0, %2, 0 op_sel:[0,1,0] op_sel_hi:[0,1,0]\n\t"
-            "v_min_f32_e32 %0, 0x3f7d70a4, %0"
-            : "=&v"(b)
-            : "v"(a), "v"(r.h.w));
-        const float wgt = b * T;
+        const float wgt = tile::opacity_at(a, r.h.w) * T;  // b T, b = min(0.99, 2^-a' * alpha)
         // plain (mixed-precision) FMAs: the compiler's v_pk_fma_f32 pairing costs a v_pk_mov and issues at half rate
         asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "+v"(cr) : "v"(wgt), "v"(r.h.z));
         asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(cg) : "v"(wgt), "v"(r.h.z));
@@ -666,17 +616,12 @@ __device__ __forceinline__ void blend_composite(const BlendRec& r, float lx, flo
 #ifndef WS_BLEND_MINWAVES
 #define WS_BLEND_MINWAVES 1
 #endif
-// entries staged per batch, at most (measured at 4x4: 256 -> blend +8 % on c2, +17 % on c3; 1024 does not leave LDS
-// for two workgroups per CU)
 // minimum waves per SIMD of the depth forms with one tile per workgroup: left to itself the compiler gives the 4x4 form 65
 // VGPRs -- one 1024-thread workgroup per CU instead of two; at 8 it fits 64 with no scratch (Auxiliary planes).
 // (The MULTI forms spill at 8 and keep the default: they run at 4K-class tile counts, where the workgroups are short.  The 4x2
 // form -- the split halves -- is held at six waves by its LDS and fits 64 VGPRs by itself.)
 #ifndef WS_BLEND_AUX_MINWAVES
 #define WS_BLEND_AUX_MINWAVES 8
-#endif
-#ifndef WS_BLEND_STAGE_MAX
-#define WS_BLEND_STAGE_MAX 512
 #endif
 // ---- TIMING build of k_blend (ws_renderer_enable_blend_timing; analysis only, never on a production launch) -------------
 // Wave-uniform time stamps (s_memtime: the shader clock) bracket the phases of a tile -- range load, the first batch's
@@ -716,22 +661,13 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
         tm_real0 = (uint32_t)rt;
     }
     const uint32_t tpw_log2 = MULTI ? tpw_log2_arg : 0u;  // MULTI = several tiles per workgroup (4K-class tile counts)
-    constexpr int NW = QW * QH;                  // waves = quadrants
-    constexpr int NT = 64 * NW;
-    constexpr int STAGE = NT < WS_BLEND_STAGE_MAX ? NT : WS_BLEND_STAGE_MAX;   // entries staged per batch
-    constexpr int SLOTS = STAGE + 1;
-    constexpr int TW = 8 * QW, TH = 8 * QH;
-    // (a wave compacts and walks a staged batch in sub-rounds of at most LCAP records, so the lists stay small when the
-    // batch is large: -DWS_BLEND_STAGE_MAX=1024 halves the per-batch barriers and still leaves LDS for two workgroups)
-    constexpr int LCAP = STAGE < 512 ? STAGE : 512;
+    using G = tile::Geometry<QW, QH>;  // the staged-batch layout: blend_tile.h
+    constexpr int NW = G::NW, NT = G::NT, STAGE = G::STAGE, SLOTS = G::SLOTS, LCAP = G::LCAP, TW = G::TW, TH = G::TH;
 
     __shared__ float4 s_rec[(STAGE_Z ? 3 : 2) * SLOTS];  // (STAGE_Z: + the plane of view-space depths, blend_load_z)
     __shared__ float s_dmax[OCC ? NW : 1];  // OCCLUDE: the largest D of each wave's pixels, this tile
-    // quadrant bits of the staged records (0 = slot unused), 16 bits each, TRANSPOSED per sub-round of LCAP slots: the
-    // masks of slots lane, lane + 64, lane + 128, ... sit side by side, so a wave's compaction reads all of them with one
-    // or two wide LDS loads instead of one dependent load per 64 records
+    // quadrant bits of the staged records (0 = slot unused), 16 bits each, transposed per sub-round (tile::mask_slot)
     __shared__ __attribute__((aligned(16))) uint16_t s_m[STAGE];
-    static_assert(LCAP % 256 == 0, "sub-round layout of the quadrant masks: four 16-bit masks per 64-bit piece");
     // per wave: byte offsets of the staged records that reach its quadrant, near -> far, padded with the null record
     __shared__ __attribute__((aligned(16))) uint32_t s_list[NW][LCAP + 16];
     __shared__ uint2 s_range[16];   // [begin, end) of this workgroup's tiles in the sorted entry list
@@ -739,18 +675,14 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
     __shared__ uint32_t s_dbg_max;  // capture mode: most records any wave walked in the current batch
     // DMA: raw Splat records as the LDS-DMA leaves them, plane of the 16-B parts and plane of the 4-B parts; two buffers:
     // the tile being composited stages out of one, the first batch of the workgroup's NEXT tile lands in the other
-    __shared__ __attribute__((aligned(16))) u32x4_t s_raw4[DMA ? (MULTI ? 2 : 1) * STAGE : 1];
+    __shared__ __attribute__((aligned(16))) tile::u32x4_t s_raw4[DMA ? (MULTI ? 2 : 1) * STAGE : 1];
     __shared__ uint32_t s_raw1[DMA ? (MULTI ? 2 : 1) * STAGE : 1];
     __shared__ uint32_t s_alive[2];  // DMA: "some pixel of the tile is not saturated yet", per batch parity
 
     // The frame's error bits (entry overflow, look-back spin time-outs) live in the per-frame zero arena; the last
     // kernel of the frame folds them into a word that survives the next frame's memset, so a batch of frames enqueued
     // back to back can be checked once at the end (ws_renderer_errors / ws_view_batch_errors).
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.sticky) {
-        const uint32_t bits = p.counters->overflow;
-        if (bits) fold_frame_errors(p, bits);
-        post_frame_progress(p);
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.sticky) blend_frame_begin(p);
     ws_trace_begin(p.trace);
     const BlendShape shape = blend_shape(QW, QH);
     const BlendBlock blk = blend_block_of(blockIdx.x, p.tiles_x, p.tiles_y, shape, tpw_log2);
@@ -761,6 +693,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
     if (!ordered && !blk.valid) return;  // block-uniform
     const uint32_t tpw = 1u << tpw_log2, wpb = shape.tpb() >> tpw_log2;
     const int tid = threadIdx.x;
+    // (tile::quadrant's set-up, written out: through the struct the compiler pairs these sums differently in most forms)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;  // (wave-uniform: lives in an SGPR)
     const int qx = wave % QW, qy = wave / QW;
     const float lx = (float)(qx * 8 + (lane & 7)) + 0.5f;  // tile-local pixel centre
@@ -787,7 +720,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
         if (tx < p.tiles_x && ty < p.tiles_y) {
             code_one = tx | (ty << 16);
             range_one = p.tile_ranges[tile_list_index(p, tx, ty)];
-            range_one.x = range_one.y ? 0xFFFFFFFFu - range_one.x : 0u;
+            range_one.x = tile::range_begin(range_one.x, range_one.y);
         }
     } else if ((uint32_t)tid < tpw) {
         const uint32_t slot = blk.w + (uint32_t)tid * wpb;
@@ -798,7 +731,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
         if (tx < p.tiles_x && ty < p.tiles_y) {
             code = tx | (ty << 16);
             range = p.tile_ranges[tile_list_index(p, tx, ty)];
-            range.x = range.y ? 0xFFFFFFFFu - range.x : 0u;
+            range.x = tile::range_begin(range.x, range.y);
         }
         s_range[tid] = range;
         s_txy[tid] = code;
@@ -827,12 +760,12 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
     if (stager) {
         const uint2 r0 = MULTI ? s_range[0] : range_one;
         if (r0.y > r0.x) {  // (an empty tile must not touch the entry list)
-            if (DMA) blend_gather_lds(p, blend_entry_idx<STAGE>(p, r0, r0.y, tid), s_raw4 + wslot, s_raw1 + wslot);
+            if (DMA) blend_gather_lds(p, tile::entry_idx<STAGE>(p.entry_vals, r0, r0.y, tid), s_raw4 + wslot, s_raw1 + wslot);
             else if (STAGE_Z) {
-                const uint32_t idx0 = blend_entry_idx<STAGE>(p, r0, r0.y, tid);
-                raw = blend_gather(p, idx0);
+                const uint32_t idx0 = tile::entry_idx<STAGE>(p.entry_vals, r0, r0.y, tid);
+                raw = tile::gather(p.splats, idx0);
                 zraw = ax.z[idx0];
-            } else raw = blend_fetch_raw<STAGE>(p, r0, r0.y, tid);
+            } else raw = tile::gather(p.splats, tile::entry_idx<STAGE>(p.entry_vals, r0, r0.y, tid));
         }
     }
     for (uint32_t k = 0; k < tpw; ++k) {
@@ -849,10 +782,10 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
         if (rn.y > rn.x) {
             if (DMA) range_nt = rn;
             else if (STAGE_Z) {
-                const uint32_t idxn = blend_entry_idx<STAGE>(p, rn, rn.y, tid);
-                raw_next_tile = blend_gather(p, idxn);
+                const uint32_t idxn = tile::entry_idx<STAGE>(p.entry_vals, rn, rn.y, tid);
+                raw_next_tile = tile::gather(p.splats, idxn);
                 z_next_tile = ax.z[idxn];
-            } else raw_next_tile = blend_fetch_raw<STAGE>(p, rn, rn.y, tid);
+            } else raw_next_tile = tile::gather(p.splats, tile::entry_idx<STAGE>(p.entry_vals, rn, rn.y, tid));
         }
     }
     if (code != 0xFFFFFFFFu) {  // block-uniform
@@ -889,7 +822,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
     // arrived during batch b-1) and the entry indices of batch b+2 are in flight.
     uint32_t idx_next = 0u;
     if (stager && range.y > range.x)
-        idx_next = blend_entry_idx<STAGE>(p, range, range.y - range.x > (uint32_t)STAGE ? range.y - (uint32_t)STAGE : range.x, tid);
+        idx_next = tile::entry_idx<STAGE>(p.entry_vals, range, range.y - range.x > (uint32_t)STAGE ? range.y - (uint32_t)STAGE : range.x, tid);
     // capture build only (p.debug_walked): records this wave walked, and the sum over batches of the most any wave
     // walked in the batch (the lock-step cost of the per-batch barriers)
     uint32_t dbg_walked = 0u, dbg_lockstep = 0u, dbg_deepest = 0u;
@@ -899,7 +832,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
     }
     uint32_t bpar = 0u;  // DMA: parity of the batch (which s_alive word it uses)
     while (hi > range.x) {
-        const uint32_t nb = (hi - range.x) < (uint32_t)STAGE ? (hi - range.x) : (uint32_t)STAGE;
+        const uint32_t nb = tile::batch_len<STAGE>(range.x, hi);
         const uint32_t hi_next = hi - nb;
         if (TIMING) {
             // the batch's Splat records (and the index load behind them) have landed: first batch = the tile's dependent
@@ -918,12 +851,13 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
             if (DMA) {
                 // this wave's LDS-DMA of the batch (issued one batch, or one tile, ago) and its index loads have landed
                 wait_vector_loads();
-                if (fetch_nt) idx_nt = blend_entry_idx<STAGE>(p, range_nt, range_nt.y, tid);  // consumed behind the decode
+                if (fetch_nt) idx_nt = tile::entry_idx<STAGE>(p.entry_vals, range_nt, range_nt.y, tid);  // consumed behind the decode
                 if (tid == 0) s_alive[bpar] = 0u;  // (its readers of two batches ago are long past; its writers come after the barrier)
                 raw.a = s_raw4[rbuf + (uint32_t)tid];
                 raw.w4 = s_raw1[rbuf + (uint32_t)tid];
             }
             if ((uint32_t)tid < nb) {
+                // (tile::stage_store, written out: the call changes the code of most forms)
                 const stage::Staged s = stage::decode<QW, QH>(raw.a.x, raw.a.y, raw.a.z, raw.a.w, raw.w4, W, H, tile_x0,
                                                               tile_y0, CUT_A2);
                 mask = s.mask;
@@ -932,7 +866,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
                 s_rec[SLOTS + tid] = make_float4(s.i11, s.c1, __uint_as_float(raw.a.w), __uint_as_float(raw.w4));
                 if (STAGE_Z) reinterpret_cast<float*>(s_rec + 2 * SLOTS + tid)[0] = zraw;
             }
-            s_m[((uint32_t)tid / LCAP) * LCAP + ((uint32_t)tid & 63u) * (LCAP / 64) + (((uint32_t)tid % LCAP) >> 6)] = (uint16_t)mask;
+            s_m[tile::mask_slot<LCAP>((uint32_t)tid, (uint32_t)lane)] = (uint16_t)mask;
             if (fetch_nt) {
                 blend_gather_lds(p, idx_nt, s_raw4 + (rbuf ^ (uint32_t)STAGE) + wslot, s_raw1 + (rbuf ^ (uint32_t)STAGE) + wslot);
                 range_nt = make_uint2(0u, 0u);
@@ -942,9 +876,9 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
             // merged the loaded words with the old ones at the join -- s_waitcnt vmcnt directly behind the loads and three
             // v_mov, i.e. the "prefetch" waited for its own data before the barrier, one exposed round trip per batch
             if (DMA) blend_gather_lds(p, idx_next, s_raw4 + rbuf + wslot, s_raw1 + rbuf + wslot);
-            else raw = blend_gather(p, idx_next);
+            else raw = tile::gather(p.splats, idx_next);
             if (STAGE_Z) zraw = ax.z[idx_next];
-            idx_next = blend_entry_idx<STAGE>(p, range, hi_next - range.x > (uint32_t)STAGE ? hi_next - (uint32_t)STAGE : range.x, tid);
+            idx_next = tile::entry_idx<STAGE>(p.entry_vals, range, hi_next - range.x > (uint32_t)STAGE ? hi_next - (uint32_t)STAGE : range.x, tid);
         }
         if (TIMING) {
             const uint32_t t = blend_stamp<TIMING>();
@@ -962,28 +896,25 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
         // a wave whose 64 pixels are saturated only keeps staging
         for (uint32_t sub = 0; sub < nb && __ballot(T >= T_MIN) != 0ull; sub += (uint32_t)LCAP) {
             // wave-private compaction: records whose kept ellipse reaches this quadrant, in near -> far order
-            // (the masks of the sub-round's slots lane, lane + 64, ... in 64-bit pieces -- slots past nb hold 0)
-            const uint2* mp = reinterpret_cast<const uint2*>(s_m + sub + (uint32_t)lane * (LCAP / 64));
+            // (tile::compact's loop on the layout functions of blend_tile.h, written out: the call reorders the code of every form)
+            const uint2* mp = reinterpret_cast<const uint2*>(s_m + tile::mask_read_base<LCAP>(sub, (uint32_t)lane));
             uint32_t n = 0;
-            uint32_t slot16 = (sub + (uint32_t)lane) * 16u;  // byte offset of the record of round 0
+            uint32_t slot16 = tile::list_value(tile::compact_slot(sub, (uint32_t)lane, 0, 0));  // byte offset of the record of round 0
             asm volatile("" : "+v"(slot16));  // (recomputed here: hoisted out of the tile loop, the eight offsets of the
                                               // unrolled rounds would hold eight registers for the whole kernel)
 #pragma unroll
             for (int h = 0; h < LCAP / 256; ++h) {
 #if WS_BLEND_COMPACT_SKIP
-                // (a batch of at most 256 entries -- the median hd1m tile stages 197 -- has nothing in its upper slots: a scalar branch
-                //  saves their mask load and four ballots)
-                if (h > 0 && nb - sub <= (uint32_t)(h * 256)) break;
+                if (tile::piece_empty(nb, sub, h)) break;
 #endif
                 const uint2 mm = mp[h];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int r = h * 4 + q;
                     const uint32_t word = (q & 2) ? mm.y : mm.x;
                     const bool t = (word & (qbit << ((q & 1) * 16))) != 0u;
                     const unsigned long long bal = __ballot(t);
                     const uint32_t pos = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                    if (t) my_list[pos] = slot16 + (uint32_t)r * 1024u;
+                    if (t) my_list[pos] = slot16 + tile::list_value(tile::compact_slot(0u, 0u, h, q));
                     n += (uint32_t)__popcll(bal);
                 }
             }
@@ -1121,7 +1052,7 @@ __global__ __launch_bounds__(64 * BlendForm::of(FORM).waves(), blend_min_waves(B
     if (DMA) {
         if (stager && range_nt.y > range_nt.x) {  // this tile had no batch to issue the next tile's first batch from
             wait_vector_loads();
-            blend_gather_lds(p, blend_entry_idx<STAGE>(p, range_nt, range_nt.y, tid), s_raw4 + (rbuf ^ (uint32_t)STAGE) + wslot,
+            blend_gather_lds(p, tile::entry_idx<STAGE>(p.entry_vals, range_nt, range_nt.y, tid), s_raw4 + (rbuf ^ (uint32_t)STAGE) + wslot,
                              s_raw1 + (rbuf ^ (uint32_t)STAGE) + wslot);
         }
         rbuf ^= (uint32_t)STAGE;
@@ -1221,11 +1152,7 @@ __global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p, const 
     const BlendAuxPlanes ax = blend_tail<BlendAuxPlanes>(tail...);
     const BlendComposite cp = blend_tail<BlendComposite>(tail...);
     const uint32_t b = blockIdx.x;
-    if (b == 0 && threadIdx.x == 0 && p.sticky) {  // as in k_blend
-        const uint32_t bits = p.counters->overflow;
-        if (bits) fold_frame_errors(p, bits);
-        post_frame_progress(p);
-    }
+    if (b == 0 && threadIdx.x == 0 && p.sticky) blend_frame_begin(p);  // as in k_blend
     const uint32_t xcd = b & 7u, j = b >> 3;
     const uint32_t nq = p.qw * p.qh;
     const uint32_t q = j % nq;
@@ -1251,7 +1178,7 @@ __global__ __launch_bounds__(64) void k_blend_strict(const BlendParams p, const 
         if (occ) D = occluder_depth(cp, px, py);
     }
     uint2 range = p.tile_ranges[tile_list_index(p, tx, ty)];
-    range.x = range.y ? 0xFFFFFFFFu - range.x : 0u;
+    range.x = tile::range_begin(range.x, range.y);
     for (uint32_t lo = range.x; lo < range.y; lo += 64u) {  // far -> near: ascending position in the tile's list
         const uint32_t e = lo + (uint32_t)lane;
         const bool valid = e < range.y;
@@ -1483,9 +1410,9 @@ int launch_blend(const BlendParams& p, int variant, hipStream_t stream, const Bl
 int debug_stage_splat(const uint32_t w[5], float W, float H, float tile_x0, float tile_y0, uint32_t qw, uint32_t qh,
                       float rec[10], uint32_t* mask) {
     stage::Staged s;
-    if (qw == 2u && qh == 2u) s = stage::decode<2, 2>(w[0], w[1], w[2], w[3], w[4], W, H, tile_x0, tile_y0, CUT_A * stage::LOG2E_F);
-    else if (qw == 4u && qh == 2u) s = stage::decode<4, 2>(w[0], w[1], w[2], w[3], w[4], W, H, tile_x0, tile_y0, CUT_A * stage::LOG2E_F);
-    else if (qw == 4u && qh == 4u) s = stage::decode<4, 4>(w[0], w[1], w[2], w[3], w[4], W, H, tile_x0, tile_y0, CUT_A * stage::LOG2E_F);
+    if (qw == 2u && qh == 2u) s = stage::decode<2, 2>(w[0], w[1], w[2], w[3], w[4], W, H, tile_x0, tile_y0, tile::CUT_A2);
+    else if (qw == 4u && qh == 2u) s = stage::decode<4, 2>(w[0], w[1], w[2], w[3], w[4], W, H, tile_x0, tile_y0, tile::CUT_A2);
+    else if (qw == 4u && qh == 4u) s = stage::decode<4, 4>(w[0], w[1], w[2], w[3], w[4], W, H, tile_x0, tile_y0, tile::CUT_A2);
     else return fail(WS_ERR_INVALID, "unsupported tile shape");
     const float v[10] = {s.i00, s.i01, s.c0, s.i10, s.i11, s.c1, s.alpha, s.r, s.g, s.b};
     for (int i = 0; i < 10; ++i) rec[i] = v[i];
