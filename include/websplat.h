@@ -638,6 +638,43 @@ int  ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, cons
  * *frames = cameras added.  WS_ERR_OVERFLOW when a frame overflowed its tile-entry list (read once, after the sync): the
  * accumulator is then incomplete. */
 int  ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c, uint32_t* frames);
+/* ---- Attributing a pixel plane to Gaussians: weighted contribution sums (no counterpart in the reference) ---------------------
+ * (Declared behind "Image metrics" below, whose types they use; this is the normative text.)
+ * ws_renderer_accumulate_weighted is ws_renderer_accumulate_contrib with every weight multiplied by a per-pixel value E(p) of a
+ * caller-supplied f32 plane over the prepared frame's viewport: for every Gaussian j, the sum over its kept (pixel, splat)
+ * pairs of w * E(p).  E == 1 gives the contribution sum; E an error map gives blame (sum / plain sum = the mean error under the
+ * Gaussian); E a 0/1 mask gives a visibility-weighted selection.  To the bit:
+ *   the kept pairs, b, w = b * T, T <- T - w, the quadrant's stop at T < 2^-14 and everything else that decides which pairs are
+ *     walked are EXACTLY those of ws_renderer_accumulate_contrib: the plane never influences them;
+ *   E(p) = min(max(fma(scale, plane[p], bias), 0), 1) in f32 (one fused multiply-add), NaN -> 0; read once per pixel; nothing
+ *     past a row's width-th value is read (rows may be padded with anything);
+ *   v = w * E, one rounded f32 multiply;
+ *   sum_q32[j] += (uint64_t)(v * 2^32) (truncation);  max_weight[j] = max(max_weight[j], v) over pairs whose q32 is not 0.
+ * The results land in an ordinary ws_contrib -- integer reductions, bitwise reproducible, mergeable with ws_contrib_add -- and
+ * the call counts as a frame of it.  For two planes with E_A + E_B == 1 at every pixel where each is 0 or 1 (a mask and its
+ * complement) the two sums add up to the plain sum exactly.  An 8x8-px quadrant whose 64 values of E are all 0 is not walked
+ * (it can add nothing), which is what makes a small mask cheap; no result depends on it.
+ * scale / bias exist so that a plane can be used as it is produced: ws_metrics_add's SSIM map through scale -0.5, bias 0.5 is
+ * DSSIM = (1 - ssim) / 2 in [0, 1].
+ * Errors: state and size errors as ws_renderer_accumulate_contrib; WS_ERR_INVALID for a null view or d_values, a row pitch
+ * below 4 * width or not a multiple of 4, a pointer not 4-B aligned, a non-finite scale or bias.
+ * ws_image_error_plane: a per-pixel error plane of two resident images of one size, one thread per pixel (enqueues only).
+ * Both images give their PIXEL VALUE exactly as "Image metrics" defines it (decode, over_background, clamp, and
+ * WS_METRICS_QUANTIZE_U8 in `flags`); per colour channel d = x - y, e = d * d (WS_ERROR_SQ) or |d| (WS_ERROR_ABS);
+ * plane[p] = ((e_r + e_g) + e_b) / 3.0f, every operation a separately rounded f32 one.  The SQ plane's mean is the pair's mse.
+ * Errors: those of ws_metrics_add for the views, sizes and flags; WS_ERR_INVALID for a null plane, a plane pitch below
+ * 4 * width or not a multiple of 4, a misaligned plane pointer, an unknown kind (WS_ERROR_DSSIM included: it has no kernel).
+ * ws_scene_accumulate_error: every camera of `split` (sorted by id) blamed on the Gaussians of `pc`.  Exactly one of ref_pc /
+ * gt_dir; cameras, frame sizes, targets, blend mode, background and PNG handling are exactly those of ws_scene_evaluate (the
+ * two drivers share that set-up).  Per camera: prepare with contributions enabled and render `pc` (image a); image b is the
+ * render of `ref_pc` (by a second renderer, as in ws_scene_evaluate) or the PNG; the error plane is ws_image_error_plane's,
+ * or for WS_ERROR_DSSIM the SSIM map of a private one-slot ws_metrics through scale -0.5, bias 0.5; the weighted sum is added
+ * to `err` and, if `weight` is not NULL, the plain contribution sum of the same prepared frame to `weight`.  One stream, one
+ * sync at the end (gt_dir: the upload of every PNG waits for the frame before it, as in ws_scene_evaluate).  *frames =
+ * cameras added.  WS_ERR_OVERFLOW when a frame overflowed its tile-entry list (read once, after the sync): the accumulators
+ * are then incomplete -- there is no second run, an accumulator cannot be rolled back (ws_scene_accumulate_contrib's rule).
+ * WS_ERR_INVALID for null handles, accumulators of another size than `pc`, an unknown kind, split or flag bit, both or neither
+ * of ref_pc / gt_dir; WS_ERR_IO naming the file for a PNG that cannot be opened. */
 /* ---- Image metrics: PSNR and SSIM between two resident images (no counterpart in the reference) ------------------------------
  * The two figures every 3DGS evaluation reports, as the INRIA / c3dgs metrics.py defines them, computed on the device between
  * two images of one size, per image pair.  The definition is bit-level up to the sums:
@@ -711,6 +748,21 @@ void ws_host_free(void* p);
  * flags: WS_METRICS_QUANTIZE_U8 or 0.  On an error `m` keeps the records it had before the call. */
 int  ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                        const char* gt_dir, uint32_t flags, ws_metrics* m, uint32_t* frames);
+/* "Attributing a pixel plane to Gaussians" (the text is above "Image metrics") */
+typedef struct ws_plane_view {
+    const float* d_values;      /* device memory: one f32 per viewport pixel */
+    size_t row_pitch_bytes;
+    float scale, bias;          /* E = clamp(scale * value + bias, 0, 1) */
+} ws_plane_view;
+int  ws_renderer_accumulate_weighted(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream); /* enqueues; counts as a frame of c */
+#define WS_ERROR_SQ  0
+#define WS_ERROR_ABS 1
+int  ws_image_error_plane(ws_context* ctx, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, int kind,
+                          uint32_t flags, float* d_plane, size_t plane_pitch_bytes, void* stream);                  /* enqueues only */
+#define WS_ERROR_DSSIM 2   /* scene driver only: ws_metrics_add's map through scale -0.5, bias 0.5 */
+int  ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                               const char* gt_dir, int kind, uint32_t flags, ws_contrib* err, ws_contrib* weight /* may be NULL */,
+                               uint32_t* frames);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

@@ -21,7 +21,26 @@ struct ContribParams {
     uint32_t* demand_mailbox;
     unsigned long long* sum_q32;  // [num_points]
     uint32_t* max_bits;           // [num_points] bits of the largest weight
+    // The weighted form (ws_renderer_accumulate_weighted; nullptr: the plain sums, and nothing below is read).  The members
+    // stay behind the plain ones: the unweighted kernels read their arguments at the offsets they always had.
+    const float* plane;           // f32 per viewport pixel
+    size_t plane_pitch;           // bytes
+    float scale, bias;
 };
+// k_contrib<qw, qh, plane != nullptr>.
+//
+// THE WEIGHTED FORM, to the bit (the ABI text is include/websplat.h, "Attributing a pixel plane").  Pairs, T and
+// termination are the plain form's: the cut-off rule, b, wgt = b * T, T <- T - wgt, the per-wave stop at T < T_MIN and the batch
+// vote read nothing of the plane.  Before the batch loop every lane inside the viewport loads its pixel's value once,
+//   E = fminf(fmaxf(fmaf(scale, plane[p], bias), 0.0f), 1.0f), NaN -> 0;
+// a lane outside the viewport loads nothing and has E = 0; nothing past a row's width-th value is read.  Per kept pair
+//   v = wgt * E                      one rounded f32 multiply (fp contract off, like wgt itself)
+//   q32 = (uint32_t)(v * 2^32)       exact product, truncating conversion
+//   mb = q32 ? bits(v) : 0
+// and q32 / mb go the way the plain form's go: DPP wave reductions, LDS partials per staged record, one 64-bit add and one 32-bit
+// max per (tile, entry) with a non-zero sum.  A wave whose 64 values of E are all 0 adds nothing whatever it walks: it skips its
+// walk, keeps staging and meeting the barriers, and votes "done" -- the other waves' walks are private to them, and the batch
+// loop ends early only when every wave has nothing left to add.
 int launch_contrib(const ContribParams& p, hipStream_t stream);
 
 // dst[i] += src[i] (u64), dst_max[i] = max(dst_max[i], src_max[i]) on the bits: ws_contrib_add

@@ -8,7 +8,8 @@
 //                     (one ds_add_u64 + one ds_max_u32 per (wave, record)), and after the batch's walk the staging threads
 //                     flush: one 64-bit add and one 32-bit max per (tile, entry) with a non-zero sum, through K1's
 //                     src_index, into the accumulators.  Integer sums and maxima commute: the result does not depend on
-//                     the order of anything.
+//                     the order of anything.  WEIGHTED (contrib.h): every weight is multiplied by the lane's value E of a
+//                     caller's f32 plane before the conversion; T, the kept pairs and the early exits do not see E.
 //   k_contrib_merge : accumulator += host arrays of another accumulator (ws_contrib_add)
 //   k_pc_gather     : the kept Gaussians' records, plane by plane
 #include <hip/hip_fp16.h>
@@ -48,7 +49,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-template <int QW, int QH>
+template <int QW, int QH, bool WEIGHTED>
 __global__ __launch_bounds__(64 * QW * QH) void k_contrib(const ContribParams p) {
     using G = tile::Geometry<QW, QH>;
     constexpr int NW = G::NW, NT = G::NT, STAGE = G::STAGE, SLOTS = G::SLOTS, LCAP = G::LCAP, TW = G::TW, TH = G::TH;
@@ -77,6 +78,16 @@ __global__ __launch_bounds__(64 * QW * QH) void k_contrib(const ContribParams p)
     const float W = (float)p.width, H = (float)p.height;
     const float tile_x0 = (float)(tx * TW), tile_y0 = (float)(ty * TH);
     uint32_t* my_list = s_list[wave];
+    // WEIGHTED: the lane's value of the plane, loaded once; a wave with nothing but zeros has no walk to do
+    float E = 0.0f;
+    bool idle = false;  // wave-uniform
+    if constexpr (WEIGHTED) {
+        if (px < p.width && py < p.height) {
+            const float e = fmaf(p.scale, *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.plane) + (size_t)py * p.plane_pitch + (size_t)px * 4), p.bias);
+            E = (e != e) ? 0.0f : fminf(fmaxf(e, 0.0f), 1.0f);
+        }
+        idle = __ballot(E > 0.0f) == 0ull;
+    }
 
     uint32_t hi = range.y;
     while (hi > range.x) {
@@ -92,7 +103,7 @@ __global__ __launch_bounds__(64 * QW * QH) void k_contrib(const ContribParams p)
         }
         __syncthreads();
         // a wave whose 64 pixels are saturated only keeps staging
-        for (uint32_t sub = 0; sub < nb && __ballot(T >= T_MIN) != 0ull; sub += (uint32_t)LCAP) {
+        for (uint32_t sub = 0; sub < nb && !(WEIGHTED && idle) && __ballot(T >= T_MIN) != 0ull; sub += (uint32_t)LCAP) {
             // wave-private compaction: records whose kept ellipse reaches this quadrant, near -> far
             const uint32_t n = tile::compact<LCAP, true>(s_m, my_list, sub, nb, lane, me.bit, tile::list_value(sub + (uint32_t)lane));
             for (uint32_t i = 0; i < n; ++i) {
@@ -113,6 +124,10 @@ __global__ __launch_bounds__(64 * QW * QH) void k_contrib(const ContribParams p)
                 }
                 // w < 1: w * 2^32 is exact in f32 and below 2^32; the conversion truncates (and takes anything negative to 0).
                 // A pair whose weight truncates to 0 (w < 2^-32) counts in neither result: sum == 0 <=> max == 0.
+                if constexpr (WEIGHTED) {
+#pragma clang fp contract(off)  // v = w E, one rounded multiply of the rounded w (T has already moved on by w itself)
+                    wgt = wgt * E;
+                }
                 const uint32_t q32 = (uint32_t)(wgt * 4294967296.0f);
                 const uint32_t mb = q32 ? __float_as_uint(wgt) : 0u;
                 // 64 values below 2^32 sum to less than 2^38: the low 26 bits and the high 6 bits as two 32-bit sums
@@ -126,7 +141,7 @@ __global__ __launch_bounds__(64 * QW * QH) void k_contrib(const ContribParams p)
                 if ((i & 3u) == 3u && __ballot(T >= T_MIN) == 0ull) break;
             }
         }
-        const int all_done = __syncthreads_and(T < T_MIN ? 1 : 0);  // (also: every wave's LDS atomics of this batch are done)
+        const int all_done = __syncthreads_and((WEIGHTED && idle) || T < T_MIN ? 1 : 0);  // (also: every wave's LDS atomics of this batch are done)
         // flush: one add + one max per (tile, entry) that drew anything, into the accumulators of its source Gaussian
         if (stager && (uint32_t)tid < nb) {
             const unsigned long long s = s_sum[tid];
@@ -170,10 +185,15 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_pc_gather(const uint32_t* __r
 int launch_contrib(const ContribParams& p, hipStream_t stream) {
     const uint32_t grid = p.tiles_x * p.tiles_y;
     if (grid == 0) return WS_OK;
-    if (p.qw == 4 && p.qh == 4) hipLaunchKernelGGL((k_contrib<4, 4>), dim3(grid), dim3(1024), 0, stream, p);
-    else if (p.qw == 4 && p.qh == 2) hipLaunchKernelGGL((k_contrib<4, 2>), dim3(grid), dim3(512), 0, stream, p);
-    else if (p.qw == 2 && p.qh == 2) hipLaunchKernelGGL((k_contrib<2, 2>), dim3(grid), dim3(256), 0, stream, p);
+    const bool weighted = p.plane != nullptr;
+#define WS_CONTRIB_LAUNCH(QW, QH)                                                                              \
+    if (weighted) hipLaunchKernelGGL((k_contrib<QW, QH, true>), dim3(grid), dim3(64 * QW * QH), 0, stream, p); \
+    else hipLaunchKernelGGL((k_contrib<QW, QH, false>), dim3(grid), dim3(64 * QW * QH), 0, stream, p)
+    if (p.qw == 4 && p.qh == 4) { WS_CONTRIB_LAUNCH(4, 4); }
+    else if (p.qw == 4 && p.qh == 2) { WS_CONTRIB_LAUNCH(4, 2); }
+    else if (p.qw == 2 && p.qh == 2) { WS_CONTRIB_LAUNCH(2, 2); }
     else return fail(WS_ERR_UNSUPPORTED, "launch_contrib: tile shape");
+#undef WS_CONTRIB_LAUNCH
     WS_HIP(hipGetLastError());
     return WS_OK;
 }

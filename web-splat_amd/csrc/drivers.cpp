@@ -262,22 +262,90 @@ int eval_render_checked(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     return rc;
 }
 
-int evaluate_against_cloud(ws_context* ctx, const ws_pointcloud* pc, const ws_pointcloud* ref_pc, const std::vector<ws_scene_camera>& cams,
-                           const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
-    size_t bytes = 0;
+// ---- the per-camera set-up of ws_scene_evaluate, shared with ws_scene_accumulate_error ------------------------------------------
+// a renderer as ws_render_views makes it: Rgba16Float, the context's render-views blend mode
+int eval_renderer(ws_context* ctx, const ws_pointcloud* pc, ws_renderer** r) {
+    const int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), r);
+    if (rc == WS_OK && !ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(*r, WS_BLEND_TARGET_PRECISION);
+    return rc;
+}
+
+// the largest Rgba16Float frame of the cameras at ws_render_views' sizes, in pixels; 0: a camera with an empty image
+size_t eval_max_pixels(const std::vector<ws_scene_camera>& cams, bool* ok) {
+    size_t px = 0;
+    *ok = true;
     for (const ws_scene_camera& c : cams) {
         uint32_t w, h;
-        if (!capped_size(c, &w, &h)) return fail(WS_ERR_INVALID, "ws_scene_evaluate: camera with an empty image");
-        bytes = std::max(bytes, (size_t)w * h * 8);
+        if (!capped_size(c, &w, &h)) *ok = false;
+        else px = std::max(px, (size_t)w * h);
     }
+    return px;
+}
+
+// <gt_dir>/<img_name>, ".png" appended unless the name ends in it: read as RGBA8 and checked against the camera's aspect.
+// *rgba is released with ws_host_free (nothing to release on an error).
+int truth_read(const char* who, const char* gt_dir, const ws_scene_camera& c, uint32_t* w, uint32_t* h, uint8_t** rgba) {
+    std::string name(c.img_name, strnlen(c.img_name, sizeof c.img_name));
+    const size_t L = name.size();
+    const bool has_ext = L >= 4 && name[L - 4] == '.' && (name[L - 3] | 0x20) == 'p' && (name[L - 2] | 0x20) == 'n' && (name[L - 1] | 0x20) == 'g';
+    const std::string path = std::string(gt_dir) + "/" + name + (has_ext ? "" : ".png");
+    *rgba = nullptr;
+    int rc = ws_png_read_rgba8(path.c_str(), w, h, rgba);  // (the message names the file)
+    if (rc) return rc;
+    const uint64_t skew = (uint64_t)*w * c.height > (uint64_t)*h * c.width ? (uint64_t)*w * c.height - (uint64_t)*h * c.width
+                                                                            : (uint64_t)*h * c.width - (uint64_t)*w * c.height;
+    if (c.width == 0 || c.height == 0 || skew > std::max(c.width, c.height)) {
+        rc = fail(WS_ERR_INVALID, std::string(who) + ": " + path + " (" + std::to_string(*w) + " x " + std::to_string(*h) + ") does not have the aspect of its camera (" +
+                                      std::to_string(c.width) + " x " + std::to_string(c.height) + ")");
+        ws_host_free(*rgba);
+        *rgba = nullptr;
+    }
+    return rc;
+}
+
+// the frame's Rgba16Float target and the image it is compared with (other_texel bytes per pixel), grown when a frame has more
+// pixels than both hold (every earlier frame has been waited for, or the free waits)
+struct EvalBuffers {
+    void *target = nullptr, *other = nullptr;
+    size_t capacity = 0;  // pixels both hold
+};
+int eval_buffers_reserve(ws_context* ctx, EvalBuffers* eb, size_t px, size_t other_texel) {
+    if (px <= eb->capacity) return WS_OK;
+    if (eb->target) ws_device_free(ctx, eb->target);
+    if (eb->other) ws_device_free(ctx, eb->other);
+    eb->target = eb->other = nullptr;
+    eb->capacity = 0;
+    int rc = ws_device_malloc(ctx, px * 8, &eb->target);
+    if (rc == WS_OK) rc = ws_device_malloc(ctx, px * other_texel, &eb->other);
+    if (rc == WS_OK) eb->capacity = px;
+    return rc;
+}
+void eval_buffers_free(ws_context* ctx, EvalBuffers* eb) {
+    if (eb->target) ws_device_free(ctx, eb->target);
+    if (eb->other) ws_device_free(ctx, eb->other);
+    eb->target = eb->other = nullptr;
+    eb->capacity = 0;
+}
+
+// the ground-truth image of a frame into eb->other: the comparison of the frame before still reads it, so that is waited for
+int truth_upload(ws_context* ctx, EvalBuffers* eb, const uint8_t* rgba, size_t px) {
+    int rc = ws_sync(ctx, nullptr);
+    if (rc == WS_OK) rc = ws_memcpy_h2d(ctx, eb->other, rgba, px * 4, nullptr);
+    return rc;
+}
+
+int evaluate_against_cloud(ws_context* ctx, const ws_pointcloud* pc, const ws_pointcloud* ref_pc, const std::vector<ws_scene_camera>& cams,
+                           const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
+    bool sizes_ok;
+    const size_t bytes = eval_max_pixels(cams, &sizes_ok) * 8;
+    if (!sizes_ok) return fail(WS_ERR_INVALID, "ws_scene_evaluate: camera with an empty image");
     const uint32_t base = ws_metrics_count(m);
     ws_renderer* rs[2] = {nullptr, nullptr};
     void* targets[2] = {nullptr, nullptr};
     const ws_pointcloud* clouds[2] = {pc, ref_pc};
     int rc = WS_OK;
     for (int k = 0; k < 2 && rc == WS_OK; ++k) {
-        rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(clouds[k]), ws_pointcloud_compressed(clouds[k]), &rs[k]);
-        if (rc == WS_OK && !ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(rs[k], WS_BLEND_TARGET_PRECISION);
+        rc = eval_renderer(ctx, clouds[k], &rs[k]);
         if (rc == WS_OK) rc = ws_device_malloc(ctx, bytes, &targets[k]);
     }
     const float clear[4] = {0, 0, 0, 0};
@@ -330,45 +398,25 @@ int evaluate_against_files(ws_context* ctx, const ws_pointcloud* pc, const char*
                            const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
     const uint32_t base = ws_metrics_count(m);
     ws_renderer* r = nullptr;
-    int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), &r);
+    int rc = eval_renderer(ctx, pc, &r);
     if (rc) return rc;
-    if (!ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(r, WS_BLEND_TARGET_PRECISION);
-    void *target = nullptr, *truth = nullptr;
-    size_t capacity = 0;  // pixels both buffers hold
+    EvalBuffers eb;
     for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
         const ws_scene_camera& c = cams[i];
-        std::string name(c.img_name, strnlen(c.img_name, sizeof c.img_name));
-        const size_t L = name.size();
-        const bool has_ext = L >= 4 && name[L - 4] == '.' && (name[L - 3] | 0x20) == 'p' && (name[L - 2] | 0x20) == 'n' && (name[L - 1] | 0x20) == 'g';
-        const std::string path = std::string(gt_dir) + "/" + name + (has_ext ? "" : ".png");
         uint32_t w = 0, h = 0;
         uint8_t* rgba = nullptr;
-        if ((rc = ws_png_read_rgba8(path.c_str(), &w, &h, &rgba))) break;  // (the message names the file)
-        const uint64_t skew = (uint64_t)w * c.height > (uint64_t)h * c.width ? (uint64_t)w * c.height - (uint64_t)h * c.width
-                                                                              : (uint64_t)h * c.width - (uint64_t)w * c.height;
-        if (c.width == 0 || c.height == 0 || skew > std::max(c.width, c.height))
-            rc = fail(WS_ERR_INVALID, "ws_scene_evaluate: " + path + " (" + std::to_string(w) + " x " + std::to_string(h) + ") does not have the aspect of its camera (" +
-                                          std::to_string(c.width) + " x " + std::to_string(c.height) + ")");
+        if ((rc = truth_read("ws_scene_evaluate", gt_dir, c, &w, &h, &rgba))) break;
         const size_t px = (size_t)w * h;
-        if (rc == WS_OK && px > capacity) {  // (every earlier frame has been waited for)
-            if (target) ws_device_free(ctx, target);
-            if (truth) ws_device_free(ctx, truth);
-            target = truth = nullptr;
-            capacity = 0;
-            rc = ws_device_malloc(ctx, px * 8, &target);
-            if (rc == WS_OK) rc = ws_device_malloc(ctx, px * 4, &truth);
-            if (rc == WS_OK) capacity = px;
-        }
+        rc = eval_buffers_reserve(ctx, &eb, px, 4);
         // no resampler: the camera's own field of view on the PNG's viewport (the renderer derives the focal length from both)
         ws_splatting_args a;
         if (rc == WS_OK) offline_args(c, pc, w, h, &a);
-        if (rc == WS_OK) rc = ws_sync(ctx, nullptr);  // the previous comparison still reads `truth`
-        if (rc == WS_OK) rc = ws_memcpy_h2d(ctx, truth, rgba, px * 4, nullptr);
+        if (rc == WS_OK) rc = truth_upload(ctx, &eb, rgba, px);
         ws_host_free(rgba);
-        if (rc == WS_OK) rc = eval_render_checked(r, pc, &a, target, (size_t)w * 8);
+        if (rc == WS_OK) rc = eval_render_checked(r, pc, &a, eb.target, (size_t)w * 8);
         if (rc != WS_OK) break;
-        const ws_image_view va = view_of(target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
-        const ws_image_view vb = view_of(truth, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr);  // opaque: alpha ignored
+        const ws_image_view va = view_of(eb.target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
+        const ws_image_view vb = view_of(eb.other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr);  // opaque: alpha ignored
         rc = ws_metrics_add(m, &va, &vb, w, h, flags, nullptr, 0, nullptr);
         if (rc == WS_OK) ++*done;
     }
@@ -378,10 +426,16 @@ int evaluate_against_files(ws_context* ctx, const ws_pointcloud* pc, const char*
         ws_internal_metrics_truncate(m, base);
         *done = 0;
     }
-    if (target) ws_device_free(ctx, target);
-    if (truth) ws_device_free(ctx, truth);
+    eval_buffers_free(ctx, &eb);
     ws_renderer_destroy(r);
     return rc;
+}
+
+// the cloud's own background colour, or black: what both images of a comparison go over
+void eval_background(const ws_pointcloud* pc, float bg[3]) {
+    bg[0] = bg[1] = bg[2] = 0.0f;
+    float pc_bg[3];
+    if (ws_pointcloud_background_color(pc, pc_bg) == 1) std::memcpy(bg, pc_bg, sizeof pc_bg);
 }
 
 }  // namespace
@@ -398,13 +452,122 @@ int ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* 
     const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
     std::vector<ws_scene_camera> cams(n);
     ws_scene_cameras(scene, split, n, cams.data());
-    float bg[3] = {0, 0, 0};  // the cloud's own background colour, or black
-    float pc_bg[3];
-    if (ws_pointcloud_background_color(pc, pc_bg) == 1) std::memcpy(bg, pc_bg, sizeof bg);
+    float bg[3];
+    eval_background(pc, bg);
     uint32_t done = 0;
     const int rc = ref_pc ? evaluate_against_cloud(ctx, pc, ref_pc, cams, bg, flags, m, &done)
                           : evaluate_against_files(ctx, pc, gt_dir, cams, bg, flags, m, &done);
     if (frames) *frames = done;
+    return rc;
+}
+
+// Every camera of `split` blamed on the Gaussians of `pc` (websplat.h "Attributing a pixel plane to Gaussians"): the frames of
+// ws_scene_evaluate, their per-pixel error against `ref_pc` or the ground-truth PNGs, and the weighted contribution sums.
+int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                              const char* gt_dir, int kind, uint32_t flags, ws_contrib* err, ws_contrib* weight, uint32_t* frames) {
+    if (!ctx || !pc || !scene || !err) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: null argument");
+    if (frames) *frames = 0;
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL)
+        return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: split must be train, test or all");
+    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: exactly one of ref_pc and gt_dir");
+    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: unknown flag bits");
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS && kind != WS_ERROR_DSSIM)
+        return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: kind must be WS_ERROR_SQ, WS_ERROR_ABS or WS_ERROR_DSSIM");
+    if (ws_contrib_num_points(err) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
+        return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: an accumulator was created for another number of points");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_error: the context stops its frames early (debug_cut)");
+    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
+    std::vector<ws_scene_camera> cams(n);
+    ws_scene_cameras(scene, split, n, cams.data());
+    float bg[3];
+    eval_background(pc, bg);
+    size_t cloud_px = 0;  // ref_pc: every frame's size is known up front, nothing is reallocated on the way
+    if (ref_pc) {
+        bool sizes_ok;
+        cloud_px = eval_max_pixels(cams, &sizes_ok);
+        if (!sizes_ok) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: camera with an empty image");
+    }
+    ws_renderer *r = nullptr, *rb = nullptr;
+    ws_metrics* ssim = nullptr;  // WS_ERROR_DSSIM: one slot, written again by every frame; only its map is used
+    EvalBuffers eb;
+    void* plane = nullptr;
+    size_t plane_px = 0;
+    int rc = eval_renderer(ctx, pc, &r);
+    if (rc == WS_OK) rc = ws_renderer_enable_contrib(r, 1);
+    if (rc == WS_OK && ref_pc) rc = eval_renderer(ctx, ref_pc, &rb);
+    if (rc == WS_OK && kind == WS_ERROR_DSSIM) rc = ws_metrics_create(ctx, 1, &ssim);
+    const float clear[4] = {0, 0, 0, 0};
+    uint32_t done = 0;
+    for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
+        const ws_scene_camera& c = cams[i];
+        uint32_t w = 0, h = 0;
+        uint8_t* rgba = nullptr;
+        if (ref_pc) capped_size(c, &w, &h);
+        else if ((rc = truth_read("ws_scene_accumulate_error", gt_dir, c, &w, &h, &rgba))) break;
+        const size_t px = (size_t)w * h;
+        rc = eval_buffers_reserve(ctx, &eb, ref_pc ? cloud_px : px, ref_pc ? 8 : 4);
+        if (rc == WS_OK && eb.capacity > plane_px) {
+            if (plane) ws_device_free(ctx, plane);
+            plane = nullptr;
+            plane_px = 0;
+            if ((rc = ws_device_malloc(ctx, eb.capacity * 4, &plane)) == WS_OK) plane_px = eb.capacity;
+        }
+        if (rc == WS_OK && !ref_pc) rc = truth_upload(ctx, &eb, rgba, px);
+        if (rgba) ws_host_free(rgba);
+        ws_splatting_args a;
+        if (rc == WS_OK) {
+            offline_args(c, pc, w, h, &a);
+            rc = ws_renderer_prepare(r, pc, &a, nullptr);
+        }
+        if (rc == WS_OK) rc = ws_renderer_render(r, pc, clear, eb.target, (size_t)w * 8, nullptr);
+        if (rc == WS_OK && ref_pc) {
+            ws_splatting_args ab;
+            offline_args(c, ref_pc, w, h, &ab);
+            rc = ws_renderer_prepare(rb, ref_pc, &ab, nullptr);
+            if (rc == WS_OK) rc = ws_renderer_render(rb, ref_pc, clear, eb.other, (size_t)w * 8, nullptr);
+        }
+        if (rc != WS_OK) break;
+        const ws_image_view va = view_of(eb.target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
+        const ws_image_view vb = ref_pc ? view_of(eb.other, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg)
+                                        : view_of(eb.other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr);  // opaque: alpha ignored
+        ws_plane_view pv;
+        pv.d_values = static_cast<const float*>(plane);
+        pv.row_pitch_bytes = (size_t)w * 4;
+        pv.scale = 1.0f;
+        pv.bias = 0.0f;
+        if (kind == WS_ERROR_DSSIM) {  // (1 - ssim) / 2 of the map
+            rc = ws_metrics_reset(ssim, nullptr);
+            if (rc == WS_OK) rc = ws_metrics_add(ssim, &va, &vb, w, h, flags, static_cast<float*>(plane), (size_t)w * 4, nullptr);
+            pv.scale = -0.5f;
+            pv.bias = 0.5f;
+        } else {
+            rc = ws_image_error_plane(ctx, &va, &vb, w, h, kind, flags, static_cast<float*>(plane), (size_t)w * 4, nullptr);
+        }
+        // (the next frame's renders and plane are ordered behind these on the stream: targets and plane are reused)
+        if (rc == WS_OK) rc = ws_renderer_accumulate_weighted(r, pc, err, &pv, nullptr);
+        if (rc == WS_OK && weight) rc = ws_renderer_accumulate_contrib(r, pc, weight, nullptr);
+        if (rc == WS_OK) ++done;
+    }
+    if (rc == WS_OK) {
+        uint32_t all_bits = 0;
+        ws_renderer* both[2] = {r, rb};
+        for (int k = 0; k < 2 && rc == WS_OK; ++k) {  // (the one sync)
+            uint32_t bits = 0;
+            if (both[k]) rc = ws_renderer_errors(both[k], &bits, nullptr, 1);
+            all_bits |= bits;
+        }
+        if (rc == WS_OK && all_bits)
+            rc = fail(WS_ERR_OVERFLOW, "ws_scene_accumulate_error: a frame reported device-side errors (tile-entry overflow or a look-back "
+                                       "time-out): the accumulators are incomplete");
+    } else {
+        (void)ws_sync(ctx, nullptr);
+    }
+    if (frames) *frames = done;
+    if (ssim) ws_metrics_destroy(ssim);
+    if (plane) ws_device_free(ctx, plane);
+    eval_buffers_free(ctx, &eb);
+    if (rb) ws_renderer_destroy(rb);
+    if (r) ws_renderer_destroy(r);
     return rc;
 }
 

@@ -42,6 +42,17 @@ struct MetricsParams {
 inline uint32_t metrics_num_tiles(uint32_t w, uint32_t h) {
     return ((w + METRICS_TILE_W - 1) / METRICS_TILE_W) * ((h + METRICS_TILE_H - 1) / METRICS_TILE_H);
 }
+// k_image_error: plane[p] = the mean over the three colour channels of e = d * d (WS_ERROR_SQ) or |d| (WS_ERROR_ABS), d = x - y on
+// the PIXEL VALUES k_image_metrics compares (the same device function), ((e_r + e_g) + e_b) / 3.0f in f32, one thread per pixel
+struct ImageErrorParams {
+    MetricsView a, b;
+    uint32_t width, height, flags;
+    int kind;                    // WS_ERROR_SQ / WS_ERROR_ABS
+    float* plane;                // W x H
+    size_t plane_pitch;          // bytes
+};
+int launch_image_error(const ImageErrorParams& p, hipStream_t stream);
+
 // k_image_metrics over the pair, then the one-workgroup sum of its slab into *record, both on `stream`
 int launch_image_metrics(const MetricsParams& p, MetricsRecord* record, hipStream_t stream);
 

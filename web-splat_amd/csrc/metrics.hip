@@ -17,6 +17,8 @@
 //   reduction          : no float atomics.  A thread sums its (at most six) values in a fixed order, a wave reduces by shuffles
 //                        in a fixed tree, the four waves meet in LDS and thread 0 adds them in wave order and stores ONE
 //                        partial record per workgroup with ordinary vector stores.
+//   k_image_error      : the per-pixel error plane of ws_image_error_plane: one thread per pixel, the two texels through the same
+//                        texel_load / pixel_value, no reduction and no atomics.
 //   k_metrics_finalize : one workgroup behind it: thread t adds records t, t + 256, ... in index order, the 256 sums are
 //                        folded by a fixed tree, and the image's record goes to the accumulator.  Bitwise reproducible.
 #include <hip/hip_fp16.h>
@@ -231,6 +233,22 @@ __global__ __launch_bounds__(NT) void k_image_metrics(const MetricsParams p) {
     }
 }
 
+constexpr int EW = 64, EH = 4;  // the pixels of one workgroup of k_image_error: a wave per row segment
+
+template <int FA, int FB>
+__global__ __launch_bounds__(EW * EH) void k_image_error(const ImageErrorParams p) {
+    const int x = (int)blockIdx.x * EW + (int)(threadIdx.x & (EW - 1)), y = (int)blockIdx.y * EH + (int)(threadIdx.x / EW);
+    if (x >= (int)p.width || y >= (int)p.height) return;
+    const bool quantize = (p.flags & WS_METRICS_QUANTIZE_U8) != 0u;
+    const uint4 ta = texel_load<FA>(p.a, x, y), tb = texel_load<FB>(p.b, x, y);
+    const float3 va = pixel_value<FA>(p.a, ta, quantize), vb = pixel_value<FB>(p.b, tb, quantize);
+    const float dr = __fsub_rn(va.x, vb.x), dg = __fsub_rn(va.y, vb.y), db = __fsub_rn(va.z, vb.z);
+    const bool sq = p.kind == WS_ERROR_SQ;
+    const float er = sq ? __fmul_rn(dr, dr) : fabsf(dr), eg = sq ? __fmul_rn(dg, dg) : fabsf(dg), eb = sq ? __fmul_rn(db, db) : fabsf(db);
+    *reinterpret_cast<float*>(reinterpret_cast<char*>(p.plane) + (size_t)y * p.plane_pitch + (size_t)x * 4) =
+        __fdiv_rn(__fadd_rn(__fadd_rn(er, eg), eb), 3.0f);
+}
+
 __global__ __launch_bounds__(NT) void k_metrics_finalize(const MetricsPartial* __restrict__ slab, uint32_t n,
                                                          MetricsRecord* __restrict__ record, uint32_t width, uint32_t height,
                                                          uint32_t flags) {
@@ -284,6 +302,21 @@ int launch_image_metrics(const MetricsParams& p, MetricsRecord* record, hipStrea
     hipLaunchKernelGGL(kernels[p.a.format][p.b.format], dim3(gx, gy), dim3(NT), 0, stream, p);
     WS_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_metrics_finalize, dim3(1), dim3(NT), 0, stream, p.slab, gx * gy, record, p.width, p.height, p.flags);
+    WS_HIP(hipGetLastError());
+    return WS_OK;
+}
+
+int launch_image_error(const ImageErrorParams& p, hipStream_t stream) {
+    const uint32_t gx = (p.width + EW - 1) / EW, gy = (p.height + EH - 1) / EH;
+    if (gx == 0 || gy == 0 || gy > 65535u) return fail(WS_ERR_INVALID, "launch_image_error: image size");
+    typedef void (*Kernel)(const ImageErrorParams);
+#define WS_ERROR_ROW(FA) \
+    {k_image_error<FA, WS_FORMAT_RGBA8_UNORM>, k_image_error<FA, WS_FORMAT_RGBA16_FLOAT>, k_image_error<FA, WS_FORMAT_RGBA32_FLOAT>}
+    static const Kernel kernels[3][3] = {WS_ERROR_ROW(WS_FORMAT_RGBA8_UNORM), WS_ERROR_ROW(WS_FORMAT_RGBA16_FLOAT),
+                                         WS_ERROR_ROW(WS_FORMAT_RGBA32_FLOAT)};
+#undef WS_ERROR_ROW
+    if (p.a.format < 0 || p.a.format > 2 || p.b.format < 0 || p.b.format > 2) return fail(WS_ERR_INVALID, "launch_image_error: colour format");
+    hipLaunchKernelGGL(kernels[p.a.format][p.b.format], dim3(gx, gy), dim3(EW * EH), 0, stream, p);
     WS_HIP(hipGetLastError());
     return WS_OK;
 }

@@ -2189,15 +2189,18 @@ int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
     return WS_OK;
 }
 
-int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, void* stream_v) {
-    if (!r || !pc || !c) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_contrib: null argument");
-    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_renderer_accumulate_contrib: the context stops its frames early (debug_cut)");
+// One attribution launch over the prepared frame: the plain sums (plane == nullptr) or the weighted ones
+static int accumulate_frame(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v,
+                            const char* who_c) {
+    const std::string who(who_c);
+    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
     if (c->num_points != pc->num_points)
-        return fail(WS_ERR_INVALID, "ws_renderer_accumulate_contrib: the accumulator was created for another number of points");
+        return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
     if (!r->prepared || r->prepared_pc != pc)
-        return fail(WS_ERR_STATE, "ws_renderer_accumulate_contrib: prepare() was not called for this point cloud");
+        return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
     if (!r->prepared_contrib)
-        return fail(WS_ERR_STATE, "ws_renderer_accumulate_contrib: needs ws_renderer_enable_contrib before prepare()");
+        return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
+    if (plane && plane->row_pitch_bytes < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": plane row pitch below 4 x the viewport's width");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     ContribParams cp;
     cp.splats = r->splats;
@@ -2215,15 +2218,33 @@ int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_c
     cp.demand_mailbox = r->demand_mailbox_dev;
     cp.sum_q32 = c->sum_q32;
     cp.max_bits = c->max_bits;
+    cp.plane = plane ? plane->d_values : nullptr;
+    cp.plane_pitch = plane ? plane->row_pitch_bytes : 0;
+    cp.scale = plane ? plane->scale : 1.0f;
+    cp.bias = plane ? plane->bias : 0.0f;
     KernelMarks* km = r->marks.active ? &r->marks : nullptr;
     if (km) km->begin(stream, false);
     const int rc = launch_contrib(cp, stream);
     if (rc) return rc;
-    km_mark(km, "k_contrib");
+    km_mark(km, plane ? "k_contrib_weighted" : "k_contrib");
     ++c->frames;
     c->last_stream = stream;
     r->last_stream = stream;
     return WS_OK;
+}
+
+int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, void* stream_v) {
+    if (!r || !pc || !c) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_contrib: null argument");
+    return accumulate_frame(r, pc, c, nullptr, stream_v, "ws_renderer_accumulate_contrib");
+}
+
+int ws_renderer_accumulate_weighted(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v) {
+    if (!r || !pc || !c || !plane || !plane->d_values) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: null argument");
+    if (!std::isfinite(plane->scale) || !std::isfinite(plane->bias))
+        return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: scale and bias must be finite");
+    if (plane->row_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(plane->d_values) % 4 != 0)
+        return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: plane pointer and row pitch must be multiples of 4");
+    return accumulate_frame(r, pc, c, plane, stream_v, "ws_renderer_accumulate_weighted");
 }
 
 int ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, float* max_weight) {
@@ -2331,8 +2352,8 @@ void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count) {
 }
 
 namespace {
-int metrics_view(const ws_image_view* v, uint32_t width, const char* which, MetricsView* out) {
-    const std::string who = std::string("ws_metrics_add: image ") + which;
+int metrics_view(const ws_image_view* v, uint32_t width, const char* which, MetricsView* out, const char* fn = "ws_metrics_add") {
+    const std::string who = std::string(fn) + ": image " + which;
     if (!v->d_pixels) return fail(WS_ERR_INVALID, who + ": null pixels");
     size_t texel;
     switch (v->format) {
@@ -2421,6 +2442,28 @@ int ws_metrics_add(ws_metrics* m, const ws_image_view* a, const ws_image_view* b
     ++m->count;
     m->last_stream = stream;
     return WS_OK;
+}
+
+int ws_image_error_plane(ws_context* ctx, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, int kind,
+                         uint32_t flags, float* d_plane, size_t plane_pitch_bytes, void* stream_v) {
+    if (!ctx || !a || !b || !d_plane) return fail(WS_ERR_INVALID, "ws_image_error_plane: null argument");
+    if (width == 0 || height == 0) return fail(WS_ERR_INVALID, "ws_image_error_plane: empty image");
+    if (width > 65536u || height > 65536u) return fail(WS_ERR_INVALID, "ws_image_error_plane: image larger than 65536 pixels on a side");
+    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_image_error_plane: unknown flag bits");
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, "ws_image_error_plane: kind must be WS_ERROR_SQ or WS_ERROR_ABS");
+    ImageErrorParams p;
+    int rc = metrics_view(a, width, "a", &p.a, "ws_image_error_plane");
+    if (rc == WS_OK) rc = metrics_view(b, width, "b", &p.b, "ws_image_error_plane");
+    if (rc) return rc;
+    if (plane_pitch_bytes < (size_t)width * 4 || plane_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(d_plane) % 4 != 0)
+        return fail(WS_ERR_INVALID, "ws_image_error_plane: plane pitch below 4 x width, or plane pointer / pitch not 4-B aligned");
+    p.width = width;
+    p.height = height;
+    p.flags = flags;
+    p.kind = kind;
+    p.plane = d_plane;
+    p.plane_pitch = plane_pitch_bytes;
+    return launch_image_error(p, static_cast<hipStream_t>(stream_v));
 }
 
 int ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out, uint32_t* count) {

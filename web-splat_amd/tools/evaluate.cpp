@@ -1,9 +1,14 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
+//                     [--blame N [--error sq|abs|dssim]]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
 // another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
+// --blame N: behind that table, the N Gaussians of the scene with the largest error sum over the split (websplat.h "Attributing a
+// pixel plane to Gaussians"): index, error sum, weight sum and their ratio, the mean error under the Gaussian.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -14,7 +19,9 @@ int main(int argc, char** argv) {
     const char *ref = nullptr, *gt = nullptr;
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
-    bool bad = argc < 3;
+    long blame = 0;
+    int kind = WS_ERROR_SQ;
+    bool bad = argc < 3, have_error = false;
     for (int i = 3; i < argc && !bad; ++i) {
         if (!std::strcmp(argv[i], "--ref") && i + 1 < argc) ref = argv[++i];
         else if (!std::strcmp(argv[i], "--gt") && i + 1 < argc) gt = argv[++i];
@@ -24,10 +31,23 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "test")) split = WS_SPLIT_TEST;
             else bad = true;
         } else if (!std::strcmp(argv[i], "--quantize")) flags |= WS_METRICS_QUANTIZE_U8;
-        else bad = true;
+        else if (!std::strcmp(argv[i], "--blame") && i + 1 < argc) {
+            char* end = nullptr;
+            blame = std::strtol(argv[++i], &end, 10);
+            if (*end || blame <= 0) bad = true;
+        } else if (!std::strcmp(argv[i], "--error") && i + 1 < argc) {
+            ++i;
+            have_error = true;
+            if (!std::strcmp(argv[i], "sq")) kind = WS_ERROR_SQ;
+            else if (!std::strcmp(argv[i], "abs")) kind = WS_ERROR_ABS;
+            else if (!std::strcmp(argv[i], "dssim")) kind = WS_ERROR_DSSIM;
+            else bad = true;
+        } else bad = true;
     }
+    if (have_error && blame == 0) bad = true;
     if (bad || (ref != nullptr) == (gt != nullptr)) {
-        std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
+                             "[--blame N [--error sq|abs|dssim]]\n", argv[0]);
         return 2;
     }
     ws_context* ctx = nullptr;
@@ -61,9 +81,37 @@ int main(int argc, char** argv) {
             ssim += recs[i].ssim;
         }
         std::printf("mean over %u images: PSNR %.4f  SSIM %.6f\n", count, psnr / count, ssim / count);
-    } else {
+    }
+    ws_contrib *err = nullptr, *weight = nullptr;
+    if (rc == WS_OK && blame > 0) {
+        const uint32_t np = ws_pointcloud_num_points(pc);
+        std::vector<uint64_t> e(np), w(np);
+        std::vector<uint32_t> order(np);
+        rc = ws_contrib_create(ctx, np, &err);
+        if (rc == WS_OK) rc = ws_contrib_create(ctx, np, &weight);
+        if (rc == WS_OK) rc = ws_scene_accumulate_error(ctx, pc, scene, split, ref_pc, gt, kind, flags, err, weight, &frames);
+        if (rc == WS_OK) rc = ws_contrib_download(err, np, e.data(), nullptr);
+        if (rc == WS_OK) rc = ws_contrib_download(weight, np, w.data(), nullptr);
+        if (rc == WS_OK) {
+            for (uint32_t i = 0; i < np; ++i) order[i] = i;
+            const size_t top = std::min<size_t>((size_t)blame, np);
+            std::partial_sort(order.begin(), order.begin() + top, order.end(),
+                              [&](uint32_t a, uint32_t b) { return e[a] != e[b] ? e[a] > e[b] : a < b; });
+            std::printf("blame (%s error over %u frames): %zu of %u Gaussians by error sum\n",
+                        kind == WS_ERROR_SQ ? "sq" : (kind == WS_ERROR_ABS ? "abs" : "dssim"), frames, top, np);
+            std::printf("%10s %16s %16s %12s\n", "index", "error sum", "weight sum", "error/weight");
+            for (size_t k = 0; k < top; ++k) {
+                const uint32_t i = order[k];
+                const double es = (double)e[i] / WS_CONTRIB_SUM_SCALE, wsum = (double)w[i] / WS_CONTRIB_SUM_SCALE;
+                std::printf("%10u %16.9f %16.6f %12.6g\n", i, es, wsum, w[i] ? es / wsum : 0.0);
+            }
+        }
+    }
+    if (rc != WS_OK) {
         std::fprintf(stderr, "error %d: %s\n", rc, ws_last_error());
     }
+    if (err) ws_contrib_destroy(err);
+    if (weight) ws_contrib_destroy(weight);
     if (m) ws_metrics_destroy(m);
     if (ref_pc) ws_pointcloud_destroy(ref_pc);
     if (pc) ws_pointcloud_destroy(pc);

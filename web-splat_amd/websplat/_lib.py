@@ -27,6 +27,9 @@ WS_ERR_IO = -6
 WS_ERR_OVERFLOW = -7
 WS_CONTRIB_SUM_SCALE = 4294967296.0  # sum_q32 / scale = sum of weights
 WS_METRICS_QUANTIZE_U8 = 1           # ws_metrics_add / ws_scene_evaluate flag: compare the 8-bit images a PNG would hold
+WS_ERROR_SQ = 0                      # ws_image_error_plane / ws_scene_accumulate_error kinds: mean over the channels of d * d,
+WS_ERROR_ABS = 1                     # of |d|,
+WS_ERROR_DSSIM = 2                   # (scene driver only) (1 - ssim map) / 2
 
 WS_FORMAT_RGBA8_UNORM = 0
 WS_FORMAT_RGBA16_FLOAT = 1
@@ -173,7 +176,12 @@ class ws_image_metrics(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ws_plane_view(C.Structure):
+    _fields_ = [("d_values", C.c_void_p), ("row_pitch_bytes", C.c_size_t), ("scale", C.c_float), ("bias", C.c_float)]
+
+
 assert C.sizeof(ws_image_view) == 40
+assert C.sizeof(ws_plane_view) == 24
 assert C.sizeof(ws_image_metrics) == 48
 assert C.sizeof(ws_camera_uniform) == 272
 assert C.sizeof(ws_settings_uniform) == 80
@@ -317,6 +325,10 @@ SIGNATURES = {
     "ws_png_read_rgba8": (C.c_int, [C.c_char_p, _u32p, _u32p, C.POINTER(C.POINTER(C.c_uint8))]),
     "ws_host_free": (None, [_P]),
     "ws_scene_evaluate": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_uint32, _P, _u32p]),
+    "ws_renderer_accumulate_weighted": (C.c_int, [_P, _P, _P, C.POINTER(ws_plane_view), _P]),
+    "ws_image_error_plane": (C.c_int, [_P, C.POINTER(ws_image_view), C.POINTER(ws_image_view), C.c_uint32, C.c_uint32, C.c_int,
+                                       C.c_uint32, _P, C.c_size_t, _P]),
+    "ws_scene_accumulate_error": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_uint32, _P, _P, _u32p]),
 }
 
 

@@ -793,6 +793,49 @@ def evaluate_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, m
     return n.value
 
 
+ERROR_KINDS = {"sq": L.WS_ERROR_SQ, "abs": L.WS_ERROR_ABS, "dssim": L.WS_ERROR_DSSIM}
+
+
+def image_error_plane(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, kind="sq", quantize_u8=False, background_a=None,
+                      background_b=None) -> np.ndarray:
+    """The per-pixel error plane (H x W float32) of two H x W x 4 numpy images (uint8, float16 or float32, each its own format):
+    the mean over the colour channels of d * d ("sq") or |d| ("abs") on the pixel values of image_metrics
+    (ws_image_error_plane): upload, one launch, download."""
+    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
+    for im in imgs:
+        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
+            raise ValueError("image_error_plane: two H x W x 4 arrays of one size, uint8 / float16 / float32")
+    h, w = imgs[0].shape[:2]
+    ptrs = []
+    try:
+        views = []
+        for im, bg in zip(imgs, (background_a, background_b)):
+            ptrs.append(ctx.malloc(im.nbytes))
+            ctx.upload(ptrs[-1], im)
+            views.append(ImageView(ptrs[-1], _NP_FORMATS[im.dtype], w * im.itemsize * 4, bg).to_c())
+        ptrs.append(ctx.malloc(w * h * 4))
+        check(lib.ws_image_error_plane(ctx.handle, C.byref(views[0]), C.byref(views[1]), w, h, ERROR_KINDS[kind],
+                                       L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, C.c_void_p(ptrs[-1]), w * 4, None))
+        return ctx.download(ptrs[-1], (h, w), np.float32)
+    finally:
+        ctx.sync()
+        for p in ptrs:
+            ctx.free(p)
+
+
+def accumulate_error_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, err: "Contrib", weight: "Contrib" = None,
+                           ref: "PointCloud" = None, gt_dir: str = None, kind="sq", quantize_u8=False) -> int:
+    """Every camera of `split`, set up as evaluate_scene sets it up: the per-pixel error of `pc` against the cloud `ref` or the
+    PNGs of `gt_dir` ("sq", "abs" or "dssim"), attributed to the Gaussians of `pc` into `err`; `weight` (optional) receives the
+    plain contribution sums of the same frames, so err / weight is the mean error under a Gaussian.  Returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_accumulate_error(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+                                        None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind],
+                                        L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, err.handle,
+                                        weight.handle if weight is not None else None, C.byref(n)))
+    return n.value
+
+
 class GaussianRenderer:
     """renderer.rs:33-283.  `prepare` + `render` enqueue on a HIP stream; nothing syncs except the
     read-back helpers (num_visible_points, frame_stats, stage_times, download_*)."""
@@ -965,6 +1008,31 @@ class GaussianRenderer:
     def accumulate_contrib(self, pc: PointCloud, contrib: "Contrib", stream=None):
         """Add the prepared frame's per-Gaussian weights to `contrib` (enqueues; render() is not needed)."""
         check(lib.ws_renderer_accumulate_contrib(self.handle, pc.handle, contrib.handle, C.c_void_p(stream or 0)))
+
+    def accumulate_weighted(self, pc: PointCloud, contrib: "Contrib", plane, scale=1.0, bias=0.0, pitch=None, stream=None):
+        """Add the prepared frame's per-Gaussian weights times E(p) = clamp(scale * plane[p] + bias, 0, 1) to `contrib`
+        (ws_renderer_accumulate_weighted).  `plane`: an H x W float32 numpy array of the viewport's shape (uploaded for the
+        call, which then waits for the launch), or a device pointer with its row `pitch` in bytes (enqueues only)."""
+        v = L.ws_plane_view()
+        v.scale, v.bias = float(scale), float(bias)
+        if isinstance(plane, np.ndarray):
+            a = np.ascontiguousarray(plane, dtype=np.float32)
+            view = getattr(self, "_viewport", None)  # (None: not prepared -- the library says so)
+            if a.ndim != 2 or (view is not None and (a.shape[0] != view[1] or a.shape[1] < view[0])):  # (wider rows: padding)
+                raise ValueError(f"accumulate_weighted: want an H x W float32 plane of the viewport {view}, got {a.shape}")
+            d = self.ctx.malloc(max(a.nbytes, 4))
+            try:
+                self.ctx.upload(d, a)
+                v.d_values, v.row_pitch_bytes = d, int(pitch) if pitch is not None else a.shape[1] * 4
+                check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
+            finally:
+                self.ctx.sync(stream)
+                self.ctx.free(d)
+        else:
+            if pitch is None:
+                raise ValueError("accumulate_weighted: a device plane needs its row pitch")
+            v.d_values, v.row_pitch_bytes = int(plane), int(pitch)
+            check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
 
     def _free_aux(self):
         for ptr in self._aux.values():
