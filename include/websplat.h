@@ -763,6 +763,48 @@ int  ws_image_error_plane(ws_context* ctx, const ws_image_view* a, const ws_imag
 int  ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                const char* gt_dir, int kind, uint32_t flags, ws_contrib* err, ws_contrib* weight /* may be NULL */,
                                uint32_t* frames);
+/* ---- Rendering per-Gaussian values to pixel planes, and the winner-id plane (no counterpart in the reference) ------------------
+ * The operator the two attribution passes above are the transpose of.  For a prepared frame and a caller's f32 values f[j][c]
+ * over the Gaussians of the point cloud (c < channels <= 4), per viewport pixel p
+ *   plane[c](p) = sum over the kept pairs (p, i), near to far, of w_i(p) * f[src(i)][c]
+ *   winner(p)   = src(i) of the kept pair with the largest w_i(p), 0xFFFFFFFF when no pair has w > 0
+ * with the pairs, the weights w and src(i) -- the index in the point cloud of splat i -- EXACTLY those of "Per-Gaussian
+ * contributions" above: whatever ws_renderer_accumulate_contrib sums for a frame in a context, this call draws.  So a blame
+ * score, a contribution sum, a keep / drop mask or a label per Gaussian becomes an image, and winner answers "which Gaussian is
+ * under this pixel".  To the bit:
+ *   the kept pairs, b, w = b * T, T <- T - w, the quadrant's stop at T < 2^-14 and everything else that decides which pairs are
+ *     walked are those of ws_renderer_accumulate_contrib in the same context; the values never influence them;
+ *   per pixel and channel acc = 0, and per kept pair in near-to-far order acc = fma(w, f[src][c], acc) in f32 (one fused
+ *     multiply-add); a pair that is not kept multiplies nothing, so a non-finite f[j] reaches only pixels Gaussian j reaches;
+ *   winner: best_w = 0, best = 0xFFFFFFFF, and per kept pair  if (w > best_w) { best_w = w; best = src; }  -- strict, so of
+ *     equal weights the nearest wins and a weight of 0 never does;
+ *   every pixel of the viewport of every plane asked for is written, 0.0f / 0xFFFFFFFF where nothing is listed; nothing past a
+ *     row's width-th value is written, nothing is read from the planes.
+ * Consequences that hold bitwise: for f one-hot at j (1.0f at j, 0.0f elsewhere) the plane holds j's weights themselves, so
+ * sum over p of (uint64_t)(plane(p) * 2^32) == sum_q32[j] and the largest value whose q32 is not 0 == max_weight[j] of
+ * ws_renderer_accumulate_contrib on the same frame; channels are independent of each other and of the stride; f scaled by a
+ * power of two scales the plane by it.  No normalisation: a channel of ones (= 1 - T, ws_renderer_render_aux's alpha up to
+ * rounding) is the normaliser.
+ * The call enqueues on `stream` behind the prepared frame (render() is not needed), makes no blend launch and changes no pixel
+ * of any target.  `values` may be NULL when only winner is asked for.
+ * Errors: WS_ERR_INVALID for null handles or targets, no output at all, channels of 0 or above 4, a plane that is not NULL at
+ * c >= channels, a stride below 4 * channels or a pitch below 4 * width or either not a multiple of 4, a pointer not 4-B
+ * aligned, num_points other than the point cloud's, a reserved word that is not 0 (all refused before anything touches a
+ * device); WS_ERR_STATE when the frame is not prepared for `pc` or was prepared with contributions off; WS_ERR_UNSUPPORTED in
+ * a context with debug_cut. */
+typedef struct ws_values_view {
+    const float* d_values;      /* device; value c of Gaussian j at (char*)d_values + j*stride_bytes + 4*c */
+    size_t stride_bytes;        /* >= 4*channels, multiple of 4; 4-B aligned pointer */
+    uint32_t num_points;        /* must equal the point cloud's */
+    uint32_t channels;          /* 1..4 */
+} ws_values_view;
+typedef struct ws_value_targets {
+    float* plane[4]; size_t pitch[4];     /* f32 per pixel; plane[c] may be NULL (not written); c >= channels must be NULL */
+    uint32_t* winner; size_t winner_pitch;/* u32 per pixel or NULL */
+    uint32_t reserved[4];                 /* zero */
+} ws_value_targets;
+int  ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_values_view* values /* may be NULL: winner only */,
+                               const ws_value_targets* out, void* stream);                                        /* enqueues only */
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

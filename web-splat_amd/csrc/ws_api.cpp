@@ -13,6 +13,7 @@
 
 #include "contrib.h"
 #include "metrics.h"
+#include "values.h"
 #include "ws_internal.h"
 
 namespace ws {
@@ -2245,6 +2246,75 @@ int ws_renderer_accumulate_weighted(ws_renderer* r, const ws_pointcloud* pc, ws_
     if (plane->row_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(plane->d_values) % 4 != 0)
         return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: plane pointer and row pitch must be multiples of 4");
     return accumulate_frame(r, pc, c, plane, stream_v, "ws_renderer_accumulate_weighted");
+}
+
+// The forward operator of the attribution pass: the caller's per-Gaussian values through the prepared frame's weights, to planes.
+// The descriptors are judged by themselves first, then the handles, then the descriptors against the frame; only then a launch.
+int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_values_view* values, const ws_value_targets* out,
+                              void* stream_v) {
+    const std::string who("ws_renderer_render_values");
+    if (!out) return fail(WS_ERR_INVALID, who + ": null targets");
+    for (uint32_t w : out->reserved)
+        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
+    const uint32_t channels = values ? values->channels : 0u;
+    if (values) {
+        if (!values->d_values) return fail(WS_ERR_INVALID, who + ": null d_values");
+        if (channels == 0 || channels > 4) return fail(WS_ERR_INVALID, who + ": channels must be 1..4");
+        if (values->stride_bytes < (size_t)4 * channels || values->stride_bytes % 4 != 0)
+            return fail(WS_ERR_INVALID, who + ": values stride below 4 x channels or not a multiple of 4");
+        if (reinterpret_cast<uintptr_t>(values->d_values) % 4 != 0) return fail(WS_ERR_INVALID, who + ": values pointer not 4-B aligned");
+    }
+    bool any = out->winner != nullptr;
+    for (uint32_t c = 0; c < 4; ++c) {
+        if (!out->plane[c]) continue;
+        if (c >= channels) return fail(WS_ERR_INVALID, who + ": a plane at or above the number of channels");
+        if (out->pitch[c] % 4 != 0 || reinterpret_cast<uintptr_t>(out->plane[c]) % 4 != 0)
+            return fail(WS_ERR_INVALID, who + ": plane pointer and row pitch must be multiples of 4");
+        any = true;
+    }
+    if (out->winner && (out->winner_pitch % 4 != 0 || reinterpret_cast<uintptr_t>(out->winner) % 4 != 0))
+        return fail(WS_ERR_INVALID, who + ": winner pointer and row pitch must be multiples of 4");
+    if (!any) return fail(WS_ERR_INVALID, who + ": no output plane");
+    if (!r || !pc) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
+    if (values && values->num_points != pc->num_points)
+        return fail(WS_ERR_INVALID, who + ": the values were laid out for another number of points");
+    if (!r->prepared || r->prepared_pc != pc) return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
+    if (!r->prepared_contrib) return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
+    for (uint32_t c = 0; c < 4; ++c)
+        if (out->plane[c] && out->pitch[c] < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": plane row pitch below 4 x the viewport's width");
+    if (out->winner && out->winner_pitch < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": winner row pitch below 4 x the viewport's width");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    ValuesParams vp;
+    vp.splats = r->splats;
+    vp.entry_vals = r->entries_sorted;
+    vp.tile_ranges = r->tile_ranges;
+    vp.src_index = r->src_index;
+    vp.width = r->vw;
+    vp.height = r->vh;
+    vp.tiles_x = r->tiles_x;
+    vp.tiles_y = r->tiles_y;
+    vp.qw = r->ctx->tile_qw;
+    vp.qh = r->ctx->tile_qh;
+    vp.counters = r->counters;
+    vp.sticky = r->sticky;
+    vp.demand_mailbox = r->demand_mailbox_dev;
+    vp.values = values ? values->d_values : nullptr;
+    vp.stride = values ? values->stride_bytes : 0;
+    vp.channels = channels;
+    for (uint32_t c = 0; c < 4; ++c) {
+        vp.plane[c] = out->plane[c];
+        vp.pitch[c] = out->pitch[c];
+    }
+    vp.winner = out->winner;
+    vp.winner_pitch = out->winner_pitch;
+    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
+    if (km) km->begin(stream, false);
+    const int rc = launch_values(vp, stream);
+    if (rc) return rc;
+    km_mark(km, "k_values");
+    r->last_stream = stream;
+    return WS_OK;
 }
 
 int ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, float* max_weight) {

@@ -180,7 +180,18 @@ class ws_plane_view(C.Structure):
     _fields_ = [("d_values", C.c_void_p), ("row_pitch_bytes", C.c_size_t), ("scale", C.c_float), ("bias", C.c_float)]
 
 
+class ws_values_view(C.Structure):
+    _fields_ = [("d_values", C.c_void_p), ("stride_bytes", C.c_size_t), ("num_points", C.c_uint32), ("channels", C.c_uint32)]
+
+
+class ws_value_targets(C.Structure):
+    _fields_ = [("plane", C.c_void_p * 4), ("pitch", C.c_size_t * 4), ("winner", C.c_void_p), ("winner_pitch", C.c_size_t),
+                ("reserved", C.c_uint32 * 4)]
+
+
 assert C.sizeof(ws_image_view) == 40
+assert C.sizeof(ws_values_view) == 24
+assert C.sizeof(ws_value_targets) == 96
 assert C.sizeof(ws_plane_view) == 24
 assert C.sizeof(ws_image_metrics) == 48
 assert C.sizeof(ws_camera_uniform) == 272
@@ -329,6 +340,7 @@ SIGNATURES = {
     "ws_image_error_plane": (C.c_int, [_P, C.POINTER(ws_image_view), C.POINTER(ws_image_view), C.c_uint32, C.c_uint32, C.c_int,
                                        C.c_uint32, _P, C.c_size_t, _P]),
     "ws_scene_accumulate_error": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_uint32, _P, _P, _u32p]),
+    "ws_renderer_render_values": (C.c_int, [_P, _P, C.POINTER(ws_values_view), C.POINTER(ws_value_targets), _P]),
 }
 
 

@@ -854,9 +854,13 @@ class GaussianRenderer:
         self._aux_last = ()       # the planes the last render_aux wrote
         self._occluder = None     # renderer-owned device copy (H x W f32) of render_composite's numpy occluder
         self._occluder_shape = None
+        self._val = {}            # plane index 0..3 / "winner" -> renderer-owned device buffer (H x W, 4 B) of render_values
+        self._val_shape = None
+        self._val_last = (0, False)  # (channels, winner) the last render_values wrote
 
     def close(self):
         self._free_aux()
+        self._free_values()
         self._free_occluder()
         if self._own_target:
             self.ctx.free(self._own_target)
@@ -1033,6 +1037,76 @@ class GaussianRenderer:
                 raise ValueError("accumulate_weighted: a device plane needs its row pitch")
             v.d_values, v.row_pitch_bytes = int(plane), int(pitch)
             check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
+
+    def _free_values(self):
+        for ptr in self._val.values():
+            self.ctx.free(ptr)
+        self._val = {}
+        self._val_shape = None
+        self._val_last = (0, False)
+
+    def render_values(self, pc: PointCloud, values=None, winner=False, stream=None, stride=None, channels=None):
+        """Draw per-Gaussian values through the prepared frame's weights (ws_renderer_render_values): per pixel and channel the sum
+        over the kept pairs of w * values[j][c], and with winner=True the index of the Gaussian with the largest w at the pixel
+        (0xFFFFFFFF: none).  Needs enable_contrib() before prepare(); render() is not needed and no target changes.
+
+        `values`: an (N,) or (N, C) float32 numpy array, C <= 4, over the cloud's Gaussians (uploaded for the call, which then
+        waits for the launch); or a device pointer with `stride` bytes per Gaussian and `channels` (enqueues only); or None with
+        winner=True.  The planes go to renderer-owned H x W buffers: download_values() reads them back."""
+        w, h = getattr(self, "_viewport", (0, 0))  # ((0, 0): not prepared -- the library says so)
+        if self._val_shape != (w, h):
+            self._free_values()
+            self._val_shape = (w, h)
+        v, staged = None, None
+        if isinstance(values, np.ndarray):
+            a = np.ascontiguousarray(values, dtype=np.float32)
+            if a.ndim == 1:
+                a = a[:, None]
+            if a.ndim != 2 or not 1 <= a.shape[1] <= 4:
+                raise ValueError(f"render_values: want (N,) or (N, C <= 4) float32 values, got {values.shape}")
+            v = L.ws_values_view()
+            v.stride_bytes, v.num_points, v.channels = a.shape[1] * 4, a.shape[0], a.shape[1]
+            staged = a
+        elif values is not None:
+            if stride is None or channels is None:
+                raise ValueError("render_values: device values need their stride in bytes and their number of channels")
+            v = L.ws_values_view()
+            v.d_values, v.stride_bytes, v.num_points, v.channels = int(values), int(stride), pc.num_points(), int(channels)
+        nch = int(v.channels) if v is not None else 0
+        t = L.ws_value_targets()
+        for key in list(range(min(nch, 4))) + (["winner"] if winner else []):
+            if key not in self._val:
+                self._val[key] = self.ctx.malloc(max(w * h * 4, 4))
+        for c in range(min(nch, 4)):
+            t.plane[c], t.pitch[c] = self._val[c], w * 4
+        if winner:
+            t.winner, t.winner_pitch = self._val["winner"], w * 4
+        vref = C.byref(v) if v is not None else None
+        if staged is not None:
+            d = self.ctx.malloc(max(staged.nbytes, 4))
+            try:
+                self.ctx.upload(d, staged)
+                v.d_values = d
+                check(lib.ws_renderer_render_values(self.handle, pc.handle, vref, C.byref(t), C.c_void_p(stream or 0)))
+            finally:
+                self.ctx.sync(stream)
+                self.ctx.free(d)
+        else:
+            check(lib.ws_renderer_render_values(self.handle, pc.handle, vref, C.byref(t), C.c_void_p(stream or 0)))
+        self._val_last = (nch, bool(winner))
+
+    def download_values(self) -> dict:
+        """{"values": H x W x C float32, "winner": H x W uint32} of what the last render_values() wrote (syncs); a key is
+        absent when the call did not ask for it."""
+        w, h = self._val_shape or (0, 0)
+        nch, winner = self._val_last
+        self.ctx.sync()
+        out = {}
+        if nch:
+            out["values"] = np.stack([self.ctx.download(self._val[c], (h, w), np.float32) for c in range(nch)], axis=-1)
+        if winner:
+            out["winner"] = self.ctx.download(self._val["winner"], (h, w), np.uint32)
+        return out
 
     def _free_aux(self):
         for ptr in self._aux.values():
