@@ -6,10 +6,25 @@ import numpy as np
 import scenes
 
 
-def composite_f64(frame, z, width, height, dst=None, occluder=None):
+def composite_f64(frame, z, width, height, dst=None, occluder=None, drop=None, swap=None, planes=None):
     """Returns (out [H, W, 4] = C + T dst, T, undecided): `undecided` marks pixels with a fragment within f32 rounding of the
-    cut-off.  dst: [H, W, 4] float (None = zeros); occluder: [H, W] view-space depths (None = no test)."""
-    order = frame["sorted"].astype(np.int64)[::-1]  # near -> far
+    cut-off.  dst: [H, W, 4] float (None = zeros); occluder: [H, W] view-space depths (None = no test).
+
+    The walk can be mutated (tests/blend_ref.py: what a kernel that loses or exchanges one record would draw): `drop` = a list
+    position, counted from the near end, whose record is skipped; `swap` = (i, j), two list positions that change places.
+    `planes`: a dict that receives what the depth forms of the blend accumulate (needs z): "wz" = sum of w z, "wsum" = sum of w,
+    "median" = the z of the record at which T crosses 0.5 (0 where it never does), "tcross" = how far from 0.5 the T on either
+    side of that crossing lies (inf where none), and "first_below" = the list position of the first record that MEETS a
+    T < T_MIN = 2^-14 at the pixel (the list's length where none does)."""
+    order = frame["sorted"].astype(np.int64)[::-1].copy()  # near -> far
+    if swap is not None:
+        i, j = swap
+        order[i], order[j] = order[j], order[i]
+    if drop is not None:
+        order = np.delete(order, drop)
+    if planes is not None:
+        planes.update(wz=np.zeros((height, width)), wsum=np.zeros((height, width)), median=np.zeros((height, width)),
+                      tcross=np.full((height, width), np.inf), first_below=np.full((height, width), len(order), dtype=np.int64))
     h = np.ascontiguousarray(frame["splats"]).view(np.float16).reshape(-1, 10).astype(np.float64)
     W, H = float(width), float(height)
     T = np.ones((height, width))
@@ -18,7 +33,9 @@ def composite_f64(frame, z, width, height, dst=None, occluder=None):
     D = None if occluder is None else np.asarray(occluder, dtype=np.float32)
     e = 2.0 ** -24
     rad = np.sqrt(scenes.CUT_A) * 1.001
-    for s in order:
+    for pos, s in enumerate(order):
+        if planes is not None:
+            np.minimum(planes["first_below"], np.where(T < 2.0 ** -14, pos, len(order)), out=planes["first_below"])
         m00, m01, m10, m11 = h[s, 0] * W, h[s, 2] * W, -h[s, 1] * H, -h[s, 3] * H
         det = m00 * m11 - m01 * m10
         if not np.isfinite(det) or det == 0:
@@ -51,6 +68,13 @@ def composite_f64(frame, z, width, height, dst=None, occluder=None):
         for c in range(3):
             C[y0:y1 + 1, x0:x1 + 1, c] += w * h[s, 6 + c]
         C[y0:y1 + 1, x0:x1 + 1, 3] += w
+        if planes is not None:
+            box = (slice(y0, y1 + 1), slice(x0, x1 + 1))
+            cross = keep & (Tb > 0.5) & (Tb - w <= 0.5)
+            planes["median"][box] = np.where(cross, z[s], planes["median"][box])
+            planes["tcross"][box] = np.where(cross, np.minimum(np.abs(Tb - 0.5), np.abs(Tb - w - 0.5)), planes["tcross"][box])
+            planes["wz"][box] += w * float(z[s])
+            planes["wsum"][box] += w
         T[y0:y1 + 1, x0:x1 + 1] = Tb - w
     d = np.zeros((height, width, 4)) if dst is None else np.asarray(dst, dtype=np.float64)
     return C + T[..., None] * d, T, undecided
