@@ -16,85 +16,11 @@ import pytest
 import attrib_ref
 import metrics_ref as mr
 import scenes
+from attrib_frames import VIEW, F, _c1_frame, _compressed, _ctx, _Frame, _ramp_checker, _stack_frame, _u32
 from websplat import _lib as L
 from websplat import synth
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-VIEW = (320, 240)  # 7.5 tile rows of 32 px: the last row's lower lanes are outside the viewport
-
-
-def _ctx(ws, **cfg):
-    return ws.Context(0, ws.config_from_env({}, **cfg))
-
-
-def _u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-class _Frame:
-    """One prepared frame with contributions on; accumulators come and go."""
-
-    def __init__(self, ws, c, gpc, args, compressed=False, fmt="rgba32float"):
-        self.ws, self.c = ws, c
-        self.pc = ws.PointCloud(c, gpc)
-        self.r = ws.GaussianRenderer(c, fmt, 3, compressed)
-        self.r.enable_contrib(True)
-        self.r.prepare(self.pc, args)
-        self.n = self.pc.num_points()
-
-    def plain(self):
-        acc = self.ws.Contrib(self.c, self.n)
-        try:
-            self.r.accumulate_contrib(self.pc, acc)
-            _, q, m = acc.download()
-            return q, m
-        finally:
-            acc.close()
-
-    def weighted(self, plane, scale=1.0, bias=0.0):
-        acc = self.ws.Contrib(self.c, self.n)
-        try:
-            self.r.accumulate_weighted(self.pc, acc, plane, scale=scale, bias=bias)
-            assert acc.frames == 1
-            _, q, m = acc.download()
-            return q, m
-        finally:
-            acc.close()
-
-    def frame(self):
-        assert self.r.frame_stats()["overflow"] == 0
-        return self.r.download_frame(with_src_index=True)
-
-    def close(self):
-        self.r.close()
-        self.pc.close()
-
-
-def _stack(k, opacity):
-    """test_gpu_contrib._stack: k isotropic Gaussians on the optical axis at distinct depths, index 0 nearest, each covering the
-    whole 32 x 32 viewport, so every tile lists all k and every quadrant's wave walks all of them until it saturates."""
-    z = np.linspace(-0.25, 0.25, k, dtype=np.float32) if k > 1 else np.zeros(1, dtype=np.float32)
-    xyz = np.stack([np.zeros(k, np.float32), np.zeros(k, np.float32), z], axis=1)
-    rng = np.random.default_rng(k)
-    f_dc = rng.uniform(-1.0, 1.0, size=(k, 3)).astype(np.float32)
-    rot = np.tile(np.array([1.0, 0.0, 0.0, 0.0], np.float32), (k, 1))
-    log_scale = np.full((k, 3), np.log(12.0 * 3.0 / 320.0), np.float32)
-    logit = np.full(k, np.log(opacity / (1.0 - opacity)), np.float32)
-    return synth._rows(xyz, f_dc, np.zeros((k, 45), np.float32), logit, log_scale, rot)
-
-
-def _stack_frame(ws, c, k, opacity):
-    gpc = ws.GenericGaussianPointCloud.from_ply_rows(_stack(k, opacity), 3)
-    cj = synth.look_at_camera(0, [0.0, 0.0, -3.0], [0.0, 0.0, 0.0], 32, 32, 320.0, 320.0)
-    cam = ws.PerspectiveCamera.from_scene_camera(cj.position, cj.rotation, cj.fx, cj.fy, 32, 32)
-    cam.fit_near_far(ws.Aabb([-1, -1, -1], [1, 1, 1]))
-    return _Frame(ws, c, gpc, ws.SplattingArgs(camera=cam, viewport=(32, 32), max_sh_deg=3))
-
-
-def _c1_frame(ws, oracle, c, seed=0):
-    sc = scenes.c1(ws, oracle, n=10_000, viewport=VIEW, seed=seed)
-    return _Frame(ws, c, sc.gpc, sc.args)
 
 
 # ---- 1. E == 1 ---------------------------------------------------------------------------------------------------------------
@@ -174,17 +100,6 @@ def test_partition_of_unity_is_exact_on_a_saturating_stack(ws):
 
 
 # ---- 3. against float64 ------------------------------------------------------------------------------------------------------
-def _ramp_checker(width, height, cell=5):
-    """A smooth ramp (exact zeros at the left, exact ones at the right) times a checker of 5-px cells."""
-    x = np.arange(width, dtype=np.float64)[None, :] / (width - 1)
-    y = np.arange(height, dtype=np.float64)[:, None] / (height - 1)
-    ramp = np.clip(1.5 * x + 0.2 * np.sin(6.0 * y) - 0.2, 0.0, 1.0)
-    checker = ((np.arange(width)[None, :] // cell + np.arange(height)[:, None] // cell) % 2).astype(np.float64)
-    e = (ramp * checker).astype(F)
-    assert (e == 0).any() and (e == 1).any() and ((e > 0) & (e < 1)).any()
-    return e
-
-
 def _compare(got_q, got_m, ref, min_drawn):
     tol_sum, tol_max = attrib_ref.bounds(ref)
     s = got_q.astype(np.float64) / L.WS_CONTRIB_SUM_SCALE
@@ -221,24 +136,6 @@ def test_against_f64_c1(ws, oracle, cfg):
             f.close()
     finally:
         c.close()
-
-
-def _compressed(ws, n=50_000, seed=41):
-    """The compressed cloud and view of test_gpu_contrib._compressed."""
-    blobs = synth.compressed_blobs(n=n, n_geometry=1024, n_sh=777, seed=seed, sh_deg=3)
-    q = ws.ws_gaussian_quantization()
-    for name in ("color_dc", "color_rest", "opacity", "scaling_factor"):
-        zp, s = blobs["quant"][name]
-        getattr(q, name).zero_point = int(zp)
-        getattr(q, name).scale = float(s)
-    g = blobs["gaussians"]
-    aabb, center, up = ws.pointcloud_stats(g, 24, ws.Aabb([-1, -1, -1], [1, 1, 1]))
-    gpc = ws.GenericGaussianPointCloud(g, blobs["sh"], blobs["sh_deg"], blobs["num_points"], aabb, center,
-                                       compressed=True, covars=blobs["covars"], quantization=q, up=up)
-    cj = synth.look_at_camera(0, [0.0, 0.0, -3.0], [0, 0, 0], 400, 300, 400.0, 400.0)
-    cam = ws.PerspectiveCamera.from_scene_camera(cj.position, cj.rotation, cj.fx, cj.fy, 400, 300)
-    cam.fit_near_far(gpc.aabb)
-    return gpc, ws.SplattingArgs(camera=cam, viewport=(400, 300), max_sh_deg=3)
 
 
 def test_against_f64_compressed(ws):

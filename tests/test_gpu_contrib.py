@@ -15,14 +15,11 @@ import pytest
 
 import contrib_ref
 import scenes
+from attrib_frames import _compressed, _ctx, _stack
 from websplat import _lib as L
 from websplat import synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _ctx(ws, **cfg):
-    return ws.Context(0, ws.config_from_env({}, **cfg))
 
 
 def _bits(a):
@@ -99,20 +96,6 @@ def test_against_f64_c1(ws, oracle, seed, cfg):
         c.close()
 
 
-def _stack(k, opacity):
-    """k isotropic Gaussians on the optical axis at distinct depths, each covering the whole 32 x 32 viewport (sigma ~ 12 px:
-    the cut-off ellipse reaches 26 px from the centre, the corners are 22.6 px away), so every tile lists all k and every
-    quadrant's wave walks all of them -- until it saturates."""
-    z = np.linspace(-0.25, 0.25, k, dtype=np.float32) if k > 1 else np.zeros(1, dtype=np.float32)
-    xyz = np.stack([np.zeros(k, np.float32), np.zeros(k, np.float32), z], axis=1)
-    rng = np.random.default_rng(k)
-    f_dc = rng.uniform(-1.0, 1.0, size=(k, 3)).astype(np.float32)
-    rot = np.tile(np.array([1.0, 0.0, 0.0, 0.0], np.float32), (k, 1))
-    log_scale = np.full((k, 3), np.log(12.0 * 3.0 / 320.0), np.float32)
-    logit = np.full(k, np.log(opacity / (1.0 - opacity)), np.float32)
-    return synth._rows(xyz, f_dc, np.zeros((k, 45), np.float32), logit, log_scale, rot)
-
-
 # list lengths around the batch size (STAGE = 512 at the 4x4 tile, 256 at 2x2) and the sub-round size (LCAP), one and two batches
 BOUNDARY_CASES = [({}, k) for k in (1, 511, 512, 513, 1024, 1025)] + [({"tile_qw": 2, "tile_qh": 2}, k) for k in (255, 256, 257, 513)]
 
@@ -147,24 +130,6 @@ def test_list_lengths_at_staging_boundaries(ws, cfg, k, opacity):
         _compare(got, contrib_ref.contrib_f64(got["frame"], 32, 32, k), min_drawn=0)
     finally:
         c.close()
-
-
-def _compressed(ws, n=50_000, seed=41):
-    """The compressed cloud and view of test_gpu_aux._compressed."""
-    blobs = synth.compressed_blobs(n=n, n_geometry=1024, n_sh=777, seed=seed, sh_deg=3)
-    q = ws.ws_gaussian_quantization()
-    for name in ("color_dc", "color_rest", "opacity", "scaling_factor"):
-        zp, s = blobs["quant"][name]
-        getattr(q, name).zero_point = int(zp)
-        getattr(q, name).scale = float(s)
-    g = blobs["gaussians"]
-    aabb, center, up = ws.pointcloud_stats(g, 24, ws.Aabb([-1, -1, -1], [1, 1, 1]))
-    gpc = ws.GenericGaussianPointCloud(g, blobs["sh"], blobs["sh_deg"], blobs["num_points"], aabb, center,
-                                       compressed=True, covars=blobs["covars"], quantization=q, up=up)
-    cj = synth.look_at_camera(0, [0.0, 0.0, -3.0], [0, 0, 0], 400, 300, 400.0, 400.0)
-    cam = ws.PerspectiveCamera.from_scene_camera(cj.position, cj.rotation, cj.fx, cj.fy, 400, 300)
-    cam.fit_near_far(gpc.aabb)
-    return gpc, ws.SplattingArgs(camera=cam, viewport=(400, 300), max_sh_deg=3)
 
 
 def test_against_f64_compressed(ws):

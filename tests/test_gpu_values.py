@@ -15,97 +15,12 @@ import attrib_ref
 import contrib_ref
 import scenes
 import values_ref
+from attrib_frames import VIEW, F, _c1_frame, _compressed, _ctx, _Frame, _ramp_checker, _stack_frame, _u32
 from websplat import _lib as L
-from websplat import synth
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-VIEW = (320, 240)  # 7.5 tile rows of 32 px: the last row's lower lanes are outside the viewport
 NONE = 0xFFFFFFFF
 T_MIN = 2.0 ** -14
-
-
-def _ctx(ws, **cfg):
-    return ws.Context(0, ws.config_from_env({}, **cfg))
-
-
-def _u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-class _Frame:
-    """One prepared frame with contributions on (test_gpu_attrib._Frame), and the planes of render_values."""
-
-    def __init__(self, ws, c, gpc, args, compressed=False, fmt="rgba32float"):
-        self.ws, self.c = ws, c
-        self.pc = ws.PointCloud(c, gpc)
-        self.r = ws.GaussianRenderer(c, fmt, 3, compressed)
-        self.r.enable_contrib(True)
-        self.r.prepare(self.pc, args)
-        self.n = self.pc.num_points()
-        self.view = (int(args.viewport[0]), int(args.viewport[1]))
-
-    def plain(self):
-        acc = self.ws.Contrib(self.c, self.n)
-        try:
-            self.r.accumulate_contrib(self.pc, acc)
-            _, q, m = acc.download()
-            return q, m
-        finally:
-            acc.close()
-
-    def weighted(self, plane):
-        acc = self.ws.Contrib(self.c, self.n)
-        try:
-            self.r.accumulate_weighted(self.pc, acc, plane)
-            _, q, m = acc.download()
-            return q, m
-        finally:
-            acc.close()
-
-    def values(self, f, winner=False):
-        """H x W x C float32 (None without values) and, with winner, H x W uint32."""
-        self.r.render_values(self.pc, f, winner=winner)
-        got = self.r.download_values()
-        assert ("values" in got) == (f is not None) and ("winner" in got) == bool(winner)
-        return (got.get("values"), got["winner"]) if winner else got["values"]
-
-    def frame(self):
-        assert self.r.frame_stats()["overflow"] == 0
-        return self.r.download_frame(with_src_index=True)
-
-    def close(self):
-        self.r.close()
-        self.pc.close()
-
-
-def _stack(k, opacity):
-    """test_gpu_contrib._stack: k isotropic Gaussians on the optical axis at distinct depths, index 0 nearest, each covering the
-    whole 32 x 32 viewport (kept radius ~26 px around the centre), so every tile lists all k and every quadrant's wave walks all of
-    them until it saturates.  `opacity`: one value or one per Gaussian."""
-    z = np.linspace(-0.25, 0.25, k, dtype=np.float32) if k > 1 else np.zeros(1, dtype=np.float32)
-    xyz = np.stack([np.zeros(k, np.float32), np.zeros(k, np.float32), z], axis=1)
-    rng = np.random.default_rng(k)
-    f_dc = rng.uniform(-1.0, 1.0, size=(k, 3)).astype(np.float32)
-    rot = np.tile(np.array([1.0, 0.0, 0.0, 0.0], np.float32), (k, 1))
-    log_scale = np.full((k, 3), np.log(12.0 * 3.0 / 320.0), np.float32)
-    op = np.broadcast_to(np.asarray(opacity, np.float64), (k,))
-    logit = np.log(op / (1.0 - op)).astype(np.float32)
-    return synth._rows(xyz, f_dc, np.zeros((k, 45), np.float32), logit, log_scale, rot)
-
-
-def _stack_frame(ws, c, k, opacity, viewport=(32, 32)):
-    gpc = ws.GenericGaussianPointCloud.from_ply_rows(_stack(k, opacity), 3)
-    w, h = viewport
-    cj = synth.look_at_camera(0, [0.0, 0.0, -3.0], [0.0, 0.0, 0.0], w, h, 320.0, 320.0)
-    cam = ws.PerspectiveCamera.from_scene_camera(cj.position, cj.rotation, cj.fx, cj.fy, w, h)
-    cam.fit_near_far(ws.Aabb([-1, -1, -1], [1, 1, 1]))
-    return _Frame(ws, c, gpc, ws.SplattingArgs(camera=cam, viewport=viewport, max_sh_deg=3))
-
-
-def _c1_frame(ws, oracle, c, seed=0, viewport=VIEW):
-    sc = scenes.c1(ws, oracle, n=10_000, viewport=viewport, seed=seed)
-    return _Frame(ws, c, sc.gpc, sc.args)
 
 
 def _one_hot(n, picks):
@@ -240,24 +155,6 @@ def test_against_f64_c1(ws, oracle, cfg):
         c.close()
 
 
-def _compressed(ws, n=50_000, seed=41):
-    """The compressed cloud and view of test_gpu_contrib._compressed."""
-    blobs = synth.compressed_blobs(n=n, n_geometry=1024, n_sh=777, seed=seed, sh_deg=3)
-    q = ws.ws_gaussian_quantization()
-    for name in ("color_dc", "color_rest", "opacity", "scaling_factor"):
-        zp, s = blobs["quant"][name]
-        getattr(q, name).zero_point = int(zp)
-        getattr(q, name).scale = float(s)
-    g = blobs["gaussians"]
-    aabb, center, up = ws.pointcloud_stats(g, 24, ws.Aabb([-1, -1, -1], [1, 1, 1]))
-    gpc = ws.GenericGaussianPointCloud(g, blobs["sh"], blobs["sh_deg"], blobs["num_points"], aabb, center,
-                                       compressed=True, covars=blobs["covars"], quantization=q, up=up)
-    cj = synth.look_at_camera(0, [0.0, 0.0, -3.0], [0, 0, 0], 400, 300, 400.0, 400.0)
-    cam = ws.PerspectiveCamera.from_scene_camera(cj.position, cj.rotation, cj.fx, cj.fy, 400, 300)
-    cam.fit_near_far(gpc.aabb)
-    return gpc, ws.SplattingArgs(camera=cam, viewport=(400, 300), max_sh_deg=3)
-
-
 def test_against_f64_compressed(ws):
     c = _ctx(ws)
     try:
@@ -274,17 +171,6 @@ def test_against_f64_compressed(ws):
 
 
 # ---- 4. the adjoint identity --------------------------------------------------------------------------------------------------
-def _ramp_checker(width, height, cell=5):
-    """test_gpu_attrib._ramp_checker: a smooth ramp (exact zeros at the left, exact ones at the right) times a checker of 5-px cells."""
-    x = np.arange(width, dtype=np.float64)[None, :] / (width - 1)
-    y = np.arange(height, dtype=np.float64)[:, None] / (height - 1)
-    ramp = np.clip(1.5 * x + 0.2 * np.sin(6.0 * y) - 0.2, 0.0, 1.0)
-    checker = ((np.arange(width)[None, :] // cell + np.arange(height)[:, None] // cell) % 2).astype(np.float64)
-    e = (ramp * checker).astype(F)
-    assert (e == 0).any() and (e == 1).any() and ((e > 0) & (e < 1)).any()
-    return e
-
-
 def test_adjoint_identity_against_accumulate_weighted(ws, oracle):
     """<E, A f> on the pixels against <A^T E, f> on the Gaussians, from one prepared frame.  The weights w are bit-identical on both
     sides; per kept pair the left side rounds one fma (at most 2^-24 fmax), the right side rounds w E once (at most 2^-25) and

@@ -1,6 +1,5 @@
 """Float64 reference of ws_renderer_render_values (include/websplat.h "Rendering per-Gaussian values"; values.h): the walk of
-contrib_ref.contrib_f64 -- the same decode, cut-off and undecided band, front to back, no early termination -- kept per PIXEL
-instead of per Gaussian.
+contrib_ref.contrib_f64 (weight_ref.records: front to back, no early termination) kept per PIXEL instead of per Gaussian.
 
 Per pixel p:
   out[p, c]   sum over kept pairs of w * values[src, c]
@@ -20,7 +19,7 @@ CUT_STEP * fmax) plus what it moves behind it (at most the same)."""
 import numpy as np
 
 import contrib_ref
-import scenes
+import weight_ref
 
 
 def values_f64(frame, width, height, values, watch=None):
@@ -28,10 +27,6 @@ def values_f64(frame, width, height, values, watch=None):
     if values.ndim == 1:
         values = values[:, None]
     C = values.shape[1]
-    order = frame["sorted"].astype(np.int64)[::-1]  # near -> far
-    src = frame["src_index"].astype(np.int64)
-    h = np.ascontiguousarray(frame["splats"]).view(np.float16).reshape(-1, 10).astype(np.float64)
-    W, H = float(width), float(height)
     T = np.ones((height, width))
     out = np.zeros((height, width, C))
     wmax = np.zeros((height, width))
@@ -39,36 +34,9 @@ def values_f64(frame, width, height, values, watch=None):
     n = np.zeros((height, width), dtype=np.int64)
     und_count = np.zeros((height, width), dtype=np.int64)
     wwatch = np.zeros((height, width)) if watch is not None else None
-    e = 2.0 ** -24
-    rad = np.sqrt(scenes.CUT_A) * 1.001
-    for s in order:
-        m00, m01, m10, m11 = h[s, 0] * W, h[s, 2] * W, -h[s, 1] * H, -h[s, 3] * H
-        det = m00 * m11 - m01 * m10
-        if not np.isfinite(det) or det == 0:
-            continue
-        i00, i01, i10, i11 = m11 / det, -m01 / det, -m10 / det, m00 / det
-        cx, cy = (h[s, 4] * 0.5 + 0.5) * W, (0.5 - h[s, 5] * 0.5) * H
-        ex, ey = rad * np.hypot(m00, m01) + 2, rad * np.hypot(m10, m11) + 2
-        x0, x1 = max(int(np.floor(cx - ex)), 0), min(int(np.ceil(cx + ex)), width - 1)
-        y0, y1 = max(int(np.floor(cy - ey)), 0), min(int(np.ceil(cy + ey)), height - 1)
-        if x0 > x1 or y0 > y1:
-            continue
-        xs = np.arange(x0, x1 + 1) + 0.5 - cx
-        ys = np.arange(y0, y1 + 1)[:, None] + 0.5 - cy
-        t00, t01, t10, t11 = i00 * xs, i01 * ys, i10 * xs, i11 * ys
-        p0, p1 = t00 + t01, t10 + t11
-        a = p0 * p0 + p1 * p1
-        e0 = 6 * e * (np.abs(t00) + np.abs(t01)) + 4 * e * 64.0 * (abs(i00) + abs(i01))
-        e1 = 6 * e * (np.abs(t10) + np.abs(t11)) + 4 * e * 64.0 * (abs(i10) + abs(i11))
-        tol = 4.0 * (2 * np.abs(p0) * e0 + 2 * np.abs(p1) * e1 + 2 * e * a) + 1e-7
-        keep = a <= scenes.CUT_A
-        und = np.abs(a - scenes.CUT_A) <= tol
-        if not (keep.any() or und.any()):
-            continue
-        j = src[s]
-        blk = (slice(y0, y1 + 1), slice(x0, x1 + 1))
+    for j, blk, a, keep, und, alpha in weight_ref.records(frame, width, height):
         Tb = T[blk]
-        w = np.where(keep, np.minimum(0.99, np.exp(-a) * h[s, 9]) * Tb, 0.0)
+        w = weight_ref.weights(a, keep, alpha, Tb)
         with np.errstate(invalid="ignore"):  # (a non-finite value times the 0 of a pair that is not kept: discarded)
             out[blk] += np.where(keep[..., None], w[..., None] * values[j], 0.0)
         better = w > wmax[blk]

@@ -2,7 +2,9 @@
 // ws_pointcloud_create_subset (k_pc_gather).  Internal: the ABI is include/websplat.h, "Per-Gaussian contributions".
 #pragma once
 
-#include "ws_internal.h"
+#include <cstddef>
+
+#include "weight_walk.h"
 
 namespace ws {
 
@@ -10,15 +12,7 @@ namespace ws {
 // it writes no pixel.  One workgroup per blend tile (qw x qh quadrants, one wave each), whatever the blend's own scheduling
 // (split halves, longest-first order, tiles per workgroup) would be.
 struct ContribParams {
-    const uint8_t* splats;        // [V] x SPLAT_STRIDE
-    const uint32_t* entry_vals;   // sorted by tile, far -> near inside a tile (store indices)
-    const uint2* tile_ranges;     // (0xFFFFFFFF - begin, end) per binning tile, (0, 0) = empty
-    const uint32_t* src_index;    // [V] store slot -> index into the point cloud (K1, contributions enabled)
-    uint32_t width, height, tiles_x, tiles_y;
-    uint32_t qw, qh;
-    const FrameCounters* counters;  // bin_shift of the frame; its error bits are folded into *sticky (no blend may follow)
-    uint32_t* sticky;
-    uint32_t* demand_mailbox;
+    FrameLists frame;             // (its counters' error bits are folded into *sticky: no blend may follow)
     unsigned long long* sum_q32;  // [num_points]
     uint32_t* max_bits;           // [num_points] bits of the largest weight
     // The weighted form (ws_renderer_accumulate_weighted; nullptr: the plain sums, and nothing below is read).  The members
@@ -27,11 +21,11 @@ struct ContribParams {
     size_t plane_pitch;           // bytes
     float scale, bias;
 };
+static_assert(offsetof(ContribParams, sum_q32) == 80 && sizeof(ContribParams) == 120, "kernarg segment of k_contrib: 376 B");
 // k_contrib<qw, qh, plane != nullptr>.
 //
 // THE WEIGHTED FORM, to the bit (the ABI text is include/websplat.h, "Attributing a pixel plane").  Pairs, T and
-// termination are the plain form's: the cut-off rule, b, wgt = b * T, T <- T - wgt, the per-wave stop at T < T_MIN and the batch
-// vote read nothing of the plane.  Before the batch loop every lane inside the viewport loads its pixel's value once,
+// termination are tile::walk_weights' (weight_walk.h), which reads nothing of the plane.  Before the batch loop every lane inside the viewport loads its pixel's value once,
 //   E = fminf(fmaxf(fmaf(scale, plane[p], bias), 0.0f), 1.0f), NaN -> 0;
 // a lane outside the viewport loads nothing and has E = 0; nothing past a row's width-th value is read.  Per kept pair
 //   v = wgt * E                      one rounded f32 multiply (fp contract off, like wgt itself)

@@ -2,7 +2,9 @@
 // Internal: the ABI is include/websplat.h, "Rendering per-Gaussian values".
 #pragma once
 
-#include "ws_internal.h"
+#include <cstddef>
+
+#include "weight_walk.h"
 
 namespace ws {
 
@@ -10,15 +12,7 @@ namespace ws {
 // A sibling of k_contrib, not a form of the blend: one workgroup per blend tile (qw x qh quadrants, one wave each), whatever the
 // blend's own scheduling (split halves, longest-first order, tiles per workgroup) would be.
 struct ValuesParams {
-    const uint8_t* splats;        // [V] x SPLAT_STRIDE
-    const uint32_t* entry_vals;   // sorted by tile, far -> near inside a tile (store indices)
-    const uint2* tile_ranges;     // (0xFFFFFFFF - begin, end) per binning tile, (0, 0) = empty
-    const uint32_t* src_index;    // [V] store slot -> index into the point cloud (K1, contributions enabled)
-    uint32_t width, height, tiles_x, tiles_y;
-    uint32_t qw, qh;
-    const FrameCounters* counters;  // bin_shift of the frame; its error bits are folded into *sticky (no blend need follow)
-    uint32_t* sticky;
-    uint32_t* demand_mailbox;
+    FrameLists frame;             // (its counters' error bits are folded into *sticky: no blend need follow)
     const float* values;          // value c of Gaussian j at (char*)values + j * stride + 4 c; nullptr with channels == 0
     size_t stride;                // bytes
     uint32_t channels;            // 0..4
@@ -27,11 +21,11 @@ struct ValuesParams {
     uint32_t* winner;             // u32 per viewport pixel, or nullptr
     size_t winner_pitch;
 };
+static_assert(offsetof(ValuesParams, values) == 80 && sizeof(ValuesParams) == 184, "kernarg segment of k_values: 440 B");
 // k_values<qw, qh, winner != nullptr>.
 //
-// TO THE BIT.  The pairs, p0, p1, a, the cut-off test, b, wgt = b * T (fp contract off), T <- T - wgt, the sub-round loop
-// condition, the look at the quadrant's T after every fourth record of the wave's list and the batch vote are k_contrib's
-// (contrib.hip), token for token: in one context the pairs that contribute are exactly the pairs k_contrib sums.  The staging
+// TO THE BIT.  The pairs, the weights wgt = b * T and the stops are tile::walk_weights' (weight_walk.h), the one function k_contrib
+// (contrib.hip) runs too: in one context the pairs that contribute are exactly the pairs k_contrib sums.  The staging
 // thread of a slot also loads src = src_index[idx] and the `channels` values of Gaussian src, zero-padded to four, into a third
 // 16-B record plane (and src itself into a fourth plane when the winner is asked for).  Per kept pair, in list order:
 //   acc[c] = fmaf(wgt, val[c], acc[c])                           c < 4 (val[c] == 0 for c >= channels)

@@ -2190,33 +2190,45 @@ int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
     return WS_OK;
 }
 
+// What a launch over the prepared frame's weights (k_contrib, k_values) reads of the renderer
+static FrameLists frame_lists(const ws_renderer* r) {
+    FrameLists f;
+    f.splats = r->splats;
+    f.entry_vals = r->entries_sorted;
+    f.tile_ranges = r->tile_ranges;
+    f.src_index = r->src_index;
+    f.width = r->vw;
+    f.height = r->vh;
+    f.tiles_x = r->tiles_x;
+    f.tiles_y = r->tiles_y;
+    f.qw = r->ctx->tile_qw;
+    f.qh = r->ctx->tile_qh;
+    f.counters = r->counters;
+    f.sticky = r->sticky;
+    f.demand_mailbox = r->demand_mailbox_dev;
+    return f;
+}
+
+// ... and whether the renderer holds such a frame for `pc`.  points_match: the caller's own per-Gaussian array fits the cloud.
+static int check_weights_frame(const ws_renderer* r, const ws_pointcloud* pc, const std::string& who, bool points_match,
+                               const char* points_text) {
+    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
+    if (!points_match) return fail(WS_ERR_INVALID, who + ": " + points_text);
+    if (!r->prepared || r->prepared_pc != pc) return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
+    if (!r->prepared_contrib) return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
+    return WS_OK;
+}
+
 // One attribution launch over the prepared frame: the plain sums (plane == nullptr) or the weighted ones
 static int accumulate_frame(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v,
                             const char* who_c) {
     const std::string who(who_c);
-    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
-    if (c->num_points != pc->num_points)
-        return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
-    if (!r->prepared || r->prepared_pc != pc)
-        return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
-    if (!r->prepared_contrib)
-        return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
+    const int state = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
+    if (state) return state;
     if (plane && plane->row_pitch_bytes < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": plane row pitch below 4 x the viewport's width");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     ContribParams cp;
-    cp.splats = r->splats;
-    cp.entry_vals = r->entries_sorted;
-    cp.tile_ranges = r->tile_ranges;
-    cp.src_index = r->src_index;
-    cp.width = r->vw;
-    cp.height = r->vh;
-    cp.tiles_x = r->tiles_x;
-    cp.tiles_y = r->tiles_y;
-    cp.qw = r->ctx->tile_qw;
-    cp.qh = r->ctx->tile_qh;
-    cp.counters = r->counters;
-    cp.sticky = r->sticky;
-    cp.demand_mailbox = r->demand_mailbox_dev;
+    cp.frame = frame_lists(r);
     cp.sum_q32 = c->sum_q32;
     cp.max_bits = c->max_bits;
     cp.plane = plane ? plane->d_values : nullptr;
@@ -2276,29 +2288,14 @@ int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_
         return fail(WS_ERR_INVALID, who + ": winner pointer and row pitch must be multiples of 4");
     if (!any) return fail(WS_ERR_INVALID, who + ": no output plane");
     if (!r || !pc) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
-    if (values && values->num_points != pc->num_points)
-        return fail(WS_ERR_INVALID, who + ": the values were laid out for another number of points");
-    if (!r->prepared || r->prepared_pc != pc) return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
-    if (!r->prepared_contrib) return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
+    const int state = check_weights_frame(r, pc, who, !values || values->num_points == pc->num_points, "the values were laid out for another number of points");
+    if (state) return state;
     for (uint32_t c = 0; c < 4; ++c)
         if (out->plane[c] && out->pitch[c] < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": plane row pitch below 4 x the viewport's width");
     if (out->winner && out->winner_pitch < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": winner row pitch below 4 x the viewport's width");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     ValuesParams vp;
-    vp.splats = r->splats;
-    vp.entry_vals = r->entries_sorted;
-    vp.tile_ranges = r->tile_ranges;
-    vp.src_index = r->src_index;
-    vp.width = r->vw;
-    vp.height = r->vh;
-    vp.tiles_x = r->tiles_x;
-    vp.tiles_y = r->tiles_y;
-    vp.qw = r->ctx->tile_qw;
-    vp.qh = r->ctx->tile_qh;
-    vp.counters = r->counters;
-    vp.sticky = r->sticky;
-    vp.demand_mailbox = r->demand_mailbox_dev;
+    vp.frame = frame_lists(r);
     vp.values = values ? values->d_values : nullptr;
     vp.stride = values ? values->stride_bytes : 0;
     vp.channels = channels;
