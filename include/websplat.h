@@ -805,6 +805,68 @@ typedef struct ws_value_targets {
 } ws_value_targets;
 int  ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_values_view* values /* may be NULL: winner only */,
                                const ws_value_targets* out, void* stream);                                        /* enqueues only */
+/* ---- Removal effect: what deleting each Gaussian alone would do to the frames (no counterpart in the reference) ---------------
+ * The contribution sum says how much a Gaussian drew, blame how much of a given error map lies under it; both are proxies for
+ * the question a pruner asks.  This call answers it without a second image: per Gaussian j, the change of the frame itself if j
+ * alone were deleted.  Call F the image the FAST blend's pairs produce over `background`.  With splat i taken out, every weight
+ * behind it at pixel p grows by 1 / (1 - b_i) and everything in front stays; the pixel moves by
+ *   D_i(p) = r_i * S_i(p) - w_i * c_i,   r_i = w_i / T_after_i = b_i / (1 - b_i),   S_i(p) = F(p) - P_i(p)
+ * where P_i is the colour accumulated near to far through i, itself included: S_i is what lies behind i, background included,
+ * and D_i = w_i * (B_i - c_i), the splat's weight times the difference between the normalised colour behind it and its own.
+ * The form is exact, not first order, as long as no stop at T < 2^-14 intervenes.
+ * Preconditions as for ws_renderer_accumulate_contrib: a prepared frame, ws_renderer_enable_contrib(r, 1) before prepare().
+ * The call enqueues two launches on `stream` behind the prepared frame, makes no blend launch and changes no target.
+ * PAIRS AND WEIGHTS.  The pairs walked, b, w = b * T, T <- T - w, the quadrant's stop and the batch loop's stop are exactly those
+ * of "Per-Gaussian contributions" in the same context.  No argument of this call influences them.
+ * PASS 1, THE BASE IMAGE, for every viewport pixel, empty tiles included.  acc_ch = 0; per kept pair, near to far,
+ *   acc_ch = fma(w, c_ch, acc_ch)      one fused multiply-add; c_ch the f16 colour of the Splat record taken to f32;
+ * at the end F_ch = fma(T_end, background_ch, acc_ch) and base(p) = (F_r, F_g, F_b, T_end) as one float4; (background, 1)
+ * where nothing is listed.  With d_base it is written there -- the FAST image in f32 over that background, useful by itself;
+ * nothing past a row's width-th float4 is written -- otherwise to renderer-owned scratch, grown on demand.
+ * PASS 2, PER WALKED PAIR.  P_ch = 0 and a copy of T of its own (1; 0 outside the viewport), kept with the walk's arithmetic:
+ *   Tb = T;  T = Tb - w                (w == 0 for a pair outside the cut-off)
+ *   kept:  P_ch = fma(w, c_ch, P_ch)   the sequence of pass 1: P equals pass 1's acc at the last walked pair
+ *   the pair COUNTS iff it is kept, w > 0 and Tb >= 2^-14: a pair at an already saturated pixel scores 0 whether or not its
+ *     wave was still walking, and so does every pair at a pixel outside the viewport;
+ *   r    = w / T                       IEEE division (T > 0: b <= 0.99)
+ *   s_ch = F_ch - P_ch                 one rounded subtraction
+ *   t_ch = w * c_ch                    one rounded multiply
+ *   d_ch = fma(r, s_ch, -t_ch)         one fused multiply-add
+ *   e_ch = d_ch * d_ch (WS_ERROR_SQ) or |d_ch| (WS_ERROR_ABS);  m = ((e_r + e_g) + e_b) / 3, each operation rounded by itself
+ *   v    = min(scale * m, 0x1.fffffep-1f), NaN -> 0: one rounded multiply; the cap sits below 1 so that v * 2^32 fits 32 bits
+ *   with a weight plane  v = v * E(p), one rounded multiply; E is formed exactly as ws_renderer_accumulate_weighted forms it
+ *     (the same ws_plane_view: scale and bias in one fma, clamp to [0, 1], NaN -> 0, read once per pixel, nothing past a row's
+ *     width-th value read).  A quadrant whose 64 values of E are all 0 is idle in pass 2; pass 1 is never idle.
+ * ACCUMULATION.  sum_q32[j] += (uint64_t)(v * 2^32), truncating; max_weight[j] = max(max_weight[j], v) over pairs whose q32 is
+ * not 0; both into an ordinary ws_contrib through the source index, and the call counts as a frame of it.  Integer reductions
+ * as in ws_renderer_accumulate_contrib: bitwise reproducible, mergeable with ws_contrib_add, exact across ranks.  The pairs add
+ * exactly: a 0/1 mask and its complement sum to the unweighted result bit for bit, and a plane with E == 1 everywhere equals
+ * weight == NULL bit for bit.
+ * THE STOPS.  In a frame where no stop occurs, sum[j] / scale with WS_ERROR_SQ is the sum over p of mean_ch (F_without_j - F)^2
+ * up to f32 rounding: the squared error the frame would gain if j were deleted alone.  Where quadrants saturate, F is the FAST
+ * blend's own image, which ignores what lies behind the stop: a deletion that would un-saturate a pixel is under-reported by at
+ * most r * 2^-14 * colour per pair.
+ * Out of scope: gradients, a per-Gaussian image of D, and the joint effect of deleting several Gaussians (it is not additive).
+ * Errors: state and size errors as ws_renderer_accumulate_contrib; WS_ERR_INVALID for null params, an unknown kind
+ * (WS_ERROR_DSSIM included), a scale that is not finite and above 0, a non-finite background, a weight view with a null
+ * d_values, a non-finite scale or bias, a pointer or pitch not a multiple of 4 or a pitch below 4 * width, a d_base or
+ * base_pitch_bytes that is not a multiple of 16 or a pitch below 16 * width, a reserved word that is not 0.  Everything that can
+ * be judged from the descriptor alone is refused before a handle is looked at.
+ * ws_scene_accumulate_removal: every camera of `split` (sorted by id), set up exactly as ws_scene_accumulate_contrib sets it up
+ * (the two share that function), over the cloud's own background colour, or black when it has none; the effect is added to
+ * `effect` and, if `weight` is not NULL, the plain contribution sums of the same prepared frames to `weight`.  One renderer, one
+ * stream, one sync at the end; *frames = cameras added; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule. */
+typedef struct ws_removal_params {
+    float background[3];            /* the frames are judged over this colour */
+    int32_t kind;                   /* WS_ERROR_SQ | WS_ERROR_ABS */
+    float scale;                    /* finite, > 0 */
+    const ws_plane_view* weight;    /* may be NULL: E = 1 */
+    float* d_base; size_t base_pitch_bytes;   /* may be NULL; float4 per pixel, 16-B aligned pointer and pitch >= 16 * width, multiple of 16 */
+    uint32_t reserved[4];           /* zero */
+} ws_removal_params;
+int  ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_removal_params* p, void* stream); /* enqueues; counts as a frame of c */
+int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, int kind, float scale,
+                                 ws_contrib* effect, ws_contrib* weight /* may be NULL: the plain contribution sums of the same frames */, uint32_t* frames);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

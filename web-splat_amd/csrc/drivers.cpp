@@ -171,16 +171,14 @@ int ws_render_views(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* sc
     return rc;
 }
 
-// Every camera of `split` into a contribution accumulator, set up exactly as ws_render_views sets its frames up.  No target and
-// no blend: prepare() + the attribution launch per camera on one stream, one sync at the end, then one look at the error bits.
-int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c,
-                                uint32_t* frames) {
-    if (!ctx || !pc || !scene || !c) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: null argument");
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: split must be train or test");
-    if (frames) *frames = 0;
-    if (ws_contrib_num_points(c) != ws_pointcloud_num_points(pc))
-        return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: the accumulator was created for another number of points");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_contrib: the context stops its frames early (debug_cut)");
+// Every camera of `split` into per-Gaussian accumulators, set up exactly as ws_render_views sets its frames up.  No target and
+// no blend: prepare() + per_camera's attribution launches on one stream, one sync at the end, then one look at the error bits.
+// The camera set-up of ws_scene_accumulate_contrib and ws_scene_accumulate_removal.
+extern "C++" {
+namespace {
+template <class PerCamera>
+int accumulate_over_cameras(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const std::string& who,
+                            const char* incomplete, uint32_t* frames, PerCamera&& per_camera) {
     const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
     std::vector<ws_scene_camera> cams(n);
     ws_scene_cameras(scene, split, n, cams.data());
@@ -197,25 +195,64 @@ int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const 
             h = (uint32_t)((float)h / s);
         }
         if (w == 0 || h == 0) {
-            rc = fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: camera with an empty image");
+            rc = fail(WS_ERR_INVALID, who + ": camera with an empty image");
             break;
         }
         ws_splatting_args a;
         offline_args(cams[i], pc, w, h, &a);
         if ((rc = ws_renderer_prepare(r, pc, &a, nullptr))) break;
-        if ((rc = ws_renderer_accumulate_contrib(r, pc, c, nullptr))) break;
+        if ((rc = per_camera(r))) break;
         ++done;
     }
     if (rc == WS_OK) {
         uint32_t bits = 0;
         rc = ws_renderer_errors(r, &bits, nullptr, 1);  // (the one sync)
         if (rc == WS_OK && bits)
-            rc = fail(WS_ERR_OVERFLOW, "ws_scene_accumulate_contrib: a frame reported device-side errors (tile-entry overflow or a look-back "
-                                       "time-out): the accumulator is incomplete");
+            rc = fail(WS_ERR_OVERFLOW, who + ": a frame reported device-side errors (tile-entry overflow or a look-back time-out): " + incomplete);
     }
     if (frames) *frames = done;
     ws_renderer_destroy(r);
     return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c,
+                                uint32_t* frames) {
+    if (!ctx || !pc || !scene || !c) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: null argument");
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: split must be train or test");
+    if (frames) *frames = 0;
+    if (ws_contrib_num_points(c) != ws_pointcloud_num_points(pc))
+        return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: the accumulator was created for another number of points");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_contrib: the context stops its frames early (debug_cut)");
+    return accumulate_over_cameras(ctx, pc, scene, split, "ws_scene_accumulate_contrib", "the accumulator is incomplete", frames,
+                                   [&](ws_renderer* r) { return ws_renderer_accumulate_contrib(r, pc, c, nullptr); });
+}
+
+// ... and what deleting each Gaussian alone would do to them (websplat.h "Removal effect"), over the cloud's own background
+// colour, or black; `weight`: the plain contribution sums of the same prepared frames.
+int ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, int kind, float scale,
+                                ws_contrib* effect, ws_contrib* weight, uint32_t* frames) {
+    const std::string who("ws_scene_accumulate_removal");
+    if (frames) *frames = 0;
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
+    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, who + ": split must be train or test");
+    if (!ctx || !pc || !scene || !effect) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (ws_contrib_num_points(effect) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
+        return fail(WS_ERR_INVALID, who + ": an accumulator was created for another number of points");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
+    ws_removal_params rp;
+    std::memset(&rp, 0, sizeof rp);
+    float pc_bg[3];
+    if (ws_pointcloud_background_color(pc, pc_bg) == 1) std::memcpy(rp.background, pc_bg, sizeof pc_bg);  // (else black)
+    rp.kind = kind;
+    rp.scale = scale;
+    return accumulate_over_cameras(ctx, pc, scene, split, who, "the accumulators are incomplete", frames, [&](ws_renderer* r) {
+        int rc = ws_renderer_accumulate_removal(r, pc, effect, &rp, nullptr);
+        if (rc == WS_OK && weight) rc = ws_renderer_accumulate_contrib(r, pc, weight, nullptr);
+        return rc;
+    });
 }
 
 // Every camera of `split` compared on the device (websplat.h "Image metrics"): `pc` against another cloud, or against

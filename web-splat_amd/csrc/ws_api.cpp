@@ -13,6 +13,7 @@
 
 #include "contrib.h"
 #include "metrics.h"
+#include "removal.h"
 #include "values.h"
 #include "ws_internal.h"
 
@@ -209,6 +210,8 @@ struct ws_renderer {
     bool blend_timing = false;           // ws_renderer_enable_blend_timing: render() launches the time-stamped blend
     uint32_t* debug_timing = nullptr;    // [tiles][16][BLEND_TIMING_WORDS], allocated on first use
     uint32_t debug_timing_tiles = 0;
+    float4* removal_base = nullptr;      // [removal_base_px]: the base plane of ws_renderer_accumulate_removal without d_base, grown on first use
+    size_t removal_base_px = 0;
     bool timers = false;
     KernelMarks marks;               // per-kernel events, timers level 2
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -294,6 +297,8 @@ static void renderer_free_scratch(ws_renderer* r) {
     dfree(r->debug_walked);
     dfree(r->debug_timing);
     r->debug_timing_tiles = 0;
+    dfree(r->removal_base);
+    r->removal_base_px = 0;
     dfree(r->blend_order);
     r->blend_order_valid = false;
     if (r->zero) (void)hipFree(r->zero);
@@ -2310,6 +2315,71 @@ int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_
     const int rc = launch_values(vp, stream);
     if (rc) return rc;
     km_mark(km, "k_values");
+    r->last_stream = stream;
+    return WS_OK;
+}
+
+// What deleting each Gaussian alone would do to the prepared frame (websplat.h "Removal effect"; removal.h).  The descriptor is
+// judged by itself first, then the handles, then the descriptor against the frame; only then the two launches.
+int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_removal_params* p, void* stream_v) {
+    const std::string who("ws_renderer_accumulate_removal");
+    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
+    for (uint32_t w : p->reserved)
+        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
+    if (p->kind == WS_ERROR_DSSIM) return fail(WS_ERR_INVALID, who + ": kind WS_ERROR_DSSIM has no removal effect (sq or abs)");
+    if (p->kind != WS_ERROR_SQ && p->kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": unknown kind");
+    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
+    for (float b : p->background)
+        if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
+    if (const ws_plane_view* e = p->weight) {
+        if (!e->d_values) return fail(WS_ERR_INVALID, who + ": weight: null d_values");
+        if (!std::isfinite(e->scale) || !std::isfinite(e->bias)) return fail(WS_ERR_INVALID, who + ": weight: scale and bias must be finite");
+        if (e->row_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(e->d_values) % 4 != 0)
+            return fail(WS_ERR_INVALID, who + ": weight: plane pointer and row pitch must be multiples of 4");
+    }
+    if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
+        return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
+    if (!r || !pc || !c) return fail(WS_ERR_INVALID, who + ": null argument");
+    const int state = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
+    if (state) return state;
+    if (p->weight && p->weight->row_pitch_bytes < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": weight: plane row pitch below 4 x the viewport's width");
+    if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    RemovalParams rp;
+    rp.frame = frame_lists(r);
+    if (p->d_base) {
+        rp.base = reinterpret_cast<float4*>(p->d_base);
+        rp.base_pitch = p->base_pitch_bytes;
+    } else {
+        const size_t px = (size_t)r->vw * r->vh;
+        if (px > r->removal_base_px) {
+            // (an earlier call's launches may still read the plane, on any stream: as the frame scratch, it is replaced behind a device sync)
+            WS_HIP(hipDeviceSynchronize());
+            dfree(r->removal_base);
+            r->removal_base_px = 0;
+            const int rc_ = dmalloc(&r->removal_base, px);
+            if (rc_) return rc_;
+            r->removal_base_px = px;
+        }
+        rp.base = r->removal_base;
+        rp.base_pitch = (size_t)r->vw * 16;
+    }
+    for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
+    rp.scale = p->scale;
+    rp.kind = p->kind;
+    rp.sum_q32 = c->sum_q32;
+    rp.max_bits = c->max_bits;
+    rp.plane = p->weight ? p->weight->d_values : nullptr;
+    rp.plane_pitch = p->weight ? p->weight->row_pitch_bytes : 0;
+    rp.plane_scale = p->weight ? p->weight->scale : 1.0f;
+    rp.plane_bias = p->weight ? p->weight->bias : 0.0f;
+    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
+    if (km) km->begin(stream, false);
+    const int rc = launch_removal(rp, stream);
+    if (rc) return rc;
+    km_mark(km, "k_removal_base+k_removal");
+    ++c->frames;
+    c->last_stream = stream;
     r->last_stream = stream;
     return WS_OK;
 }

@@ -1,10 +1,13 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
-//                     [--blame N [--error sq|abs|dssim]]
+//                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
 // another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
 // --blame N: behind that table, the N Gaussians of the scene with the largest error sum over the split (websplat.h "Attributing a
 // pixel plane to Gaussians"): index, error sum, weight sum and their ratio, the mean error under the Gaussian.
+// --removal N: behind all that, the N Gaussians whose deletion alone would change the split's frames most (websplat.h "Removal
+// effect"): index, effect sum, plain contribution sum and their ratio, then how many drawn Gaussians have an effect of exactly 0.
+// It needs no second image: --ref / --gt may be left out, and then only this table is printed.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -19,7 +22,7 @@ int main(int argc, char** argv) {
     const char *ref = nullptr, *gt = nullptr;
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
-    long blame = 0;
+    long blame = 0, removal = 0;
     int kind = WS_ERROR_SQ;
     bool bad = argc < 3, have_error = false;
     for (int i = 3; i < argc && !bad; ++i) {
@@ -35,6 +38,10 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             blame = std::strtol(argv[++i], &end, 10);
             if (*end || blame <= 0) bad = true;
+        } else if (!std::strcmp(argv[i], "--removal") && i + 1 < argc) {
+            char* end = nullptr;
+            removal = std::strtol(argv[++i], &end, 10);
+            if (*end || removal <= 0) bad = true;
         } else if (!std::strcmp(argv[i], "--error") && i + 1 < argc) {
             ++i;
             have_error = true;
@@ -44,10 +51,13 @@ int main(int argc, char** argv) {
             else bad = true;
         } else bad = true;
     }
-    if (have_error && blame == 0) bad = true;
-    if (bad || (ref != nullptr) == (gt != nullptr)) {
+    if (have_error && blame == 0 && removal == 0) bad = true;
+    if (removal > 0 && kind == WS_ERROR_DSSIM) bad = true;
+    const bool compare = ref != nullptr || gt != nullptr;  // (--removal alone needs no second image)
+    if (blame > 0 && !compare) bad = true;
+    if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0)) {
         std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
-                             "[--blame N [--error sq|abs|dssim]]\n", argv[0]);
+                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]]\n", argv[0]);
         return 2;
     }
     ws_context* ctx = nullptr;
@@ -69,10 +79,10 @@ int main(int argc, char** argv) {
         rc = WS_ERR_INVALID;
     }
     if (rc == WS_OK) ws_scene_cameras(scene, split, n, cams.data());
-    if (rc == WS_OK) rc = ws_metrics_create(ctx, n, &m);
-    if (rc == WS_OK) rc = ws_scene_evaluate(ctx, pc, scene, split, ref_pc, gt, flags, m, &frames);
-    if (rc == WS_OK) rc = ws_metrics_download(m, n, recs.data(), &count);
-    if (rc == WS_OK) {
+    if (rc == WS_OK && compare) rc = ws_metrics_create(ctx, n, &m);
+    if (rc == WS_OK && compare) rc = ws_scene_evaluate(ctx, pc, scene, split, ref_pc, gt, flags, m, &frames);
+    if (rc == WS_OK && compare) rc = ws_metrics_download(m, n, recs.data(), &count);
+    if (rc == WS_OK && compare) {
         double psnr = 0.0, ssim = 0.0;
         for (uint32_t i = 0; i < count; ++i) {
             std::printf("%5u %-32s %4ux%-4u PSNR %8.4f  SSIM %.6f\n", cams[i].id, cams[i].img_name, recs[i].width, recs[i].height, recs[i].psnr,
@@ -107,9 +117,41 @@ int main(int argc, char** argv) {
             }
         }
     }
+    ws_contrib *effect = nullptr, *drawn = nullptr;
+    if (rc == WS_OK && removal > 0) {
+        const uint32_t np = ws_pointcloud_num_points(pc);
+        std::vector<uint64_t> e(np), w(np);
+        std::vector<uint32_t> order(np);
+        rc = ws_contrib_create(ctx, np, &effect);
+        if (rc == WS_OK) rc = ws_contrib_create(ctx, np, &drawn);
+        if (rc == WS_OK) rc = ws_scene_accumulate_removal(ctx, pc, scene, split, kind, 1.0f, effect, drawn, &frames);
+        if (rc == WS_OK) rc = ws_contrib_download(effect, np, e.data(), nullptr);
+        if (rc == WS_OK) rc = ws_contrib_download(drawn, np, w.data(), nullptr);
+        if (rc == WS_OK) {
+            for (uint32_t i = 0; i < np; ++i) order[i] = i;
+            const size_t top = std::min<size_t>((size_t)removal, np);
+            std::partial_sort(order.begin(), order.begin() + top, order.end(),
+                              [&](uint32_t a, uint32_t b) { return e[a] != e[b] ? e[a] > e[b] : a < b; });
+            std::printf("removal (%s effect over %u frames): %zu of %u Gaussians by effect sum\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, top, np);
+            std::printf("%10s %16s %16s %12s\n", "index", "effect sum", "weight sum", "effect/weight");
+            for (size_t k = 0; k < top; ++k) {
+                const uint32_t i = order[k];
+                const double es = (double)e[i] / WS_CONTRIB_SUM_SCALE, wsum = (double)w[i] / WS_CONTRIB_SUM_SCALE;
+                std::printf("%10u %16.9g %16.6f %12.6g\n", i, es, wsum, w[i] ? es / wsum : 0.0);
+            }
+            uint32_t drawn_n = 0, zero_n = 0;
+            for (uint32_t i = 0; i < np; ++i) {
+                drawn_n += w[i] != 0;
+                zero_n += w[i] != 0 && e[i] == 0;
+            }
+            std::printf("removal: %u of %u drawn Gaussians have an effect of exactly 0\n", zero_n, drawn_n);
+        }
+    }
     if (rc != WS_OK) {
         std::fprintf(stderr, "error %d: %s\n", rc, ws_last_error());
     }
+    if (effect) ws_contrib_destroy(effect);
+    if (drawn) ws_contrib_destroy(drawn);
     if (err) ws_contrib_destroy(err);
     if (weight) ws_contrib_destroy(weight);
     if (m) ws_metrics_destroy(m);

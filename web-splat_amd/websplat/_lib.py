@@ -189,6 +189,12 @@ class ws_value_targets(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class ws_removal_params(C.Structure):
+    _fields_ = [("background", C.c_float * 3), ("kind", C.c_int32), ("scale", C.c_float), ("weight", C.POINTER(ws_plane_view)),
+                ("d_base", C.c_void_p), ("base_pitch_bytes", C.c_size_t), ("reserved", C.c_uint32 * 4)]
+
+
+assert C.sizeof(ws_removal_params) == 64
 assert C.sizeof(ws_image_view) == 40
 assert C.sizeof(ws_values_view) == 24
 assert C.sizeof(ws_value_targets) == 96
@@ -341,6 +347,8 @@ SIGNATURES = {
                                        C.c_uint32, _P, C.c_size_t, _P]),
     "ws_scene_accumulate_error": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_uint32, _P, _P, _u32p]),
     "ws_renderer_render_values": (C.c_int, [_P, _P, C.POINTER(ws_values_view), C.POINTER(ws_value_targets), _P]),
+    "ws_renderer_accumulate_removal": (C.c_int, [_P, _P, _P, C.POINTER(ws_removal_params), _P]),
+    "ws_scene_accumulate_removal": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _u32p]),
 }
 
 

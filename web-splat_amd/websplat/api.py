@@ -836,6 +836,17 @@ def accumulate_error_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split
     return n.value
 
 
+def accumulate_removal_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, effect: "Contrib", weight: "Contrib" = None,
+                             kind="sq", scale=1.0) -> int:
+    """Every camera of `split`, set up as accumulate_contrib_scene sets it up: what deleting each Gaussian of `pc` alone would do
+    to the frames ("sq" or "abs", ws_scene_accumulate_removal), over the cloud's own background colour or black, into `effect`;
+    `weight` (optional) receives the plain contribution sums of the same frames.  Returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_accumulate_removal(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ERROR_KINDS[kind], float(scale),
+                                          effect.handle, weight.handle if weight is not None else None, C.byref(n)))
+    return n.value
+
+
 class GaussianRenderer:
     """renderer.rs:33-283.  `prepare` + `render` enqueue on a HIP stream; nothing syncs except the
     read-back helpers (num_visible_points, frame_stats, stage_times, download_*)."""
@@ -857,10 +868,13 @@ class GaussianRenderer:
         self._val = {}            # plane index 0..3 / "winner" -> renderer-owned device buffer (H x W, 4 B) of render_values
         self._val_shape = None
         self._val_last = (0, False)  # (channels, winner) the last render_values wrote
+        self._rm_base = None      # renderer-owned device buffer (H x W float4) of accumulate_removal(base=True)
+        self._rm_base_shape = None
 
     def close(self):
         self._free_aux()
         self._free_values()
+        self._free_removal_base()
         self._free_occluder()
         if self._own_target:
             self.ctx.free(self._own_target)
@@ -1037,6 +1051,72 @@ class GaussianRenderer:
                 raise ValueError("accumulate_weighted: a device plane needs its row pitch")
             v.d_values, v.row_pitch_bytes = int(plane), int(pitch)
             check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
+
+    def _free_removal_base(self):
+        if self._rm_base:
+            self.ctx.free(self._rm_base)
+        self._rm_base = None
+        self._rm_base_shape = None
+
+    def accumulate_removal(self, pc: PointCloud, contrib: "Contrib", background=(0.0, 0.0, 0.0), kind="sq", scale=1.0, weight=None,
+                           weight_scale=1.0, weight_bias=0.0, base=False, stream=None, weight_pitch=None, base_ptr=None,
+                           base_pitch=None):
+        """Add to `contrib`, per Gaussian, what deleting it alone would do to the prepared frame over `background`
+        (ws_renderer_accumulate_removal): the sum over its pairs of min(scale * mean_ch e(D), 1 - 2^-24), e = D * D ("sq") or |D|
+        ("abs"), D the change of the pixel.  Needs enable_contrib() before prepare(); render() is not needed, no target changes.
+
+        `weight`: None, an H x W float32 numpy plane (uploaded for the call, which then waits for the launches) or a device
+        pointer with `weight_pitch` bytes per row; every pair counts times E(p) = clamp(weight_scale * weight[p] + weight_bias, 0, 1).
+        base=True: the frame's f32 image over `background` and the final transmittance go to a renderer-owned H x W float4
+        buffer that download_removal_base() reads back; `base_ptr` / `base_pitch`: a caller's device plane instead."""
+        p = L.ws_removal_params()
+        for i in range(3):
+            p.background[i] = float(background[i])
+        p.kind = ERROR_KINDS[kind] if isinstance(kind, str) else int(kind)
+        p.scale = float(scale)
+        w, h = getattr(self, "_viewport", (0, 0))  # ((0, 0): not prepared -- the library says so)
+        if base_ptr is not None:
+            p.d_base, p.base_pitch_bytes = int(base_ptr), int(base_pitch if base_pitch is not None else w * 16)
+        elif base:
+            if self._rm_base_shape != (w, h):
+                self._free_removal_base()
+                self._rm_base = self.ctx.malloc(max(w * h * 16, 16))
+                self._rm_base_shape = (w, h)
+            p.d_base, p.base_pitch_bytes = self._rm_base, w * 16
+        v, staged = None, None
+        if weight is not None:
+            v = L.ws_plane_view()
+            v.scale, v.bias = float(weight_scale), float(weight_bias)
+            if isinstance(weight, np.ndarray):
+                a = np.ascontiguousarray(weight, dtype=np.float32)
+                if a.ndim != 2 or (w and (a.shape[0] != h or a.shape[1] < w)):  # (wider rows: padding)
+                    raise ValueError(f"accumulate_removal: want an H x W float32 weight plane of the viewport {(w, h)}, got {a.shape}")
+                staged = a
+                v.row_pitch_bytes = int(weight_pitch) if weight_pitch is not None else a.shape[1] * 4
+            else:
+                if weight_pitch is None:
+                    raise ValueError("accumulate_removal: a device weight plane needs its row pitch")
+                v.d_values, v.row_pitch_bytes = int(weight), int(weight_pitch)
+            p.weight = C.pointer(v)
+        if staged is not None:
+            d = self.ctx.malloc(max(staged.nbytes, 4))
+            try:
+                self.ctx.upload(d, staged)
+                v.d_values = d
+                check(lib.ws_renderer_accumulate_removal(self.handle, pc.handle, contrib.handle, C.byref(p), C.c_void_p(stream or 0)))
+            finally:
+                self.ctx.sync(stream)
+                self.ctx.free(d)
+        else:
+            check(lib.ws_renderer_accumulate_removal(self.handle, pc.handle, contrib.handle, C.byref(p), C.c_void_p(stream or 0)))
+
+    def download_removal_base(self) -> np.ndarray:
+        """H x W x 4 float32 (F_r, F_g, F_b, T_end) of what the last accumulate_removal(base=True) wrote (syncs)."""
+        if not self._rm_base:
+            raise ValueError("download_removal_base: no accumulate_removal(base=True) since the viewport changed")
+        w, h = self._rm_base_shape
+        self.ctx.sync()
+        return self.ctx.download(self._rm_base, (h, w, 4), np.float32)
 
     def _free_values(self):
         for ptr in self._val.values():
