@@ -1,15 +1,18 @@
-"""k_contrib, k_contrib_weighted and k_values of this tree against a library built from the parent commit: same bits, same speed?
+"""The launches over a prepared frame's weights (k_contrib, k_contrib_weighted, k_values, k_removal_base + k_removal) of this tree
+against a library built from the parent commit: same bits, same speed?
 
 Fresh child processes, alternately with the parent's library (WEBSPLAT_LIB) and with this tree's; the script stops at the first
 child that does not exit with status 0 (a fault in a child: nothing more is started on the device).
   * parity: one child per side.  On c1 (10 000 Gaussians, 320 x 240; default tiles and 2x2) and on the stack of the staging
     boundaries (tests/attrib_frames._stack; k = 513 and 1025 at 32 x 32, faint and opaque), SHA-256 of accumulate_contrib's sums
-    and maxima, of accumulate_weighted's with a ramp-checker plane, and of render_values' 4 channels + winner.  Integer sums and
-    atomics-free planes are deterministic: every digest has to be equal.
+    and maxima, of accumulate_weighted's with a ramp-checker plane, of render_values' 4 channels + winner, and of
+    accumulate_removal's sums and maxima ("sq" and "abs", each without and with the ramp-checker plane as the weight) with its
+    base plane.  Integer sums and atomics-free planes are deterministic: every digest has to be equal.
   * speed: REPS children per side on hd1m (bench.py), one frame in flight, per-kernel times from enable_timers(2): the medians
-    over the frames of k_contrib, k_contrib_weighted (a plane in (0, 1] everywhere) and k_values (4 channels + winner).  Per kernel
-    the verdict compares the two medians over the repetitions with the spread (max - min) of the parent's own repetitions
-    (attrib_cost.py's rule).
+    over the frames of k_contrib, k_contrib_weighted (a plane in (0, 1] everywhere), k_values (4 channels + winner), and the
+    arms removal and removal_weighted ("sq"; the same plane), both of the mark k_removal_base+k_removal.  Per arm the verdict
+    compares the two medians over the repetitions with the spread (max - min) of the parent's own repetitions (attrib_cost.py's
+    rule).
 Writes profiles/weight_walk/ab.json.  Exit status 0: every digest equal and no kernel slower beyond the spread; 1: not so;
 2: a child failed or ran out of time.
 
@@ -26,7 +29,9 @@ sys.path[:0] = [os.path.join(ROOT, "web-splat_amd"), os.path.join(ROOT, "tests")
 import numpy as np  # noqa: E402
 
 WORKLOAD = "hd1m"
-KERNELS = ("k_contrib", "k_contrib_weighted", "k_values")
+ARMS = {"k_contrib": "k_contrib", "k_contrib_weighted": "k_contrib_weighted", "k_values": "k_values",  # arm: its kernel mark
+        "removal": "k_removal_base+k_removal", "removal_weighted": "k_removal_base+k_removal"}
+KERNELS = tuple(ARMS)
 CHILD_TIMEOUT = 300  # seconds
 
 
@@ -52,8 +57,11 @@ def child_parity():
             try:
                 vals = np.random.default_rng(5).uniform(-1, 1, size=(f.n, 4)).astype(np.float32)
                 planes, winner = f.values(vals, winner=True)
-                out[name] = {"contrib": _sha(*f.plain()), "weighted": _sha(*f.weighted(A._ramp_checker(*f.view))),
-                             "values": _sha(planes, winner)}
+                E = A._ramp_checker(*f.view)
+                out[name] = {"contrib": _sha(*f.plain()), "weighted": _sha(*f.weighted(E)), "values": _sha(planes, winner)}
+                for kind in ("sq", "abs"):
+                    out[name][f"removal-{kind}"] = _sha(*f.removal(kind=kind, base=True))
+                    out[name][f"removal-{kind}-weighted"] = _sha(*f.removal(kind=kind, weight=E, base=True))
             finally:
                 f.close()
         finally:
@@ -81,7 +89,9 @@ def child_speed(frames, warmup):
             r.enable_contrib(True)
             launch = {"k_contrib": lambda: r.accumulate_contrib(pc, acc),
                       "k_contrib_weighted": lambda: r.accumulate_weighted(pc, acc, d_plane, pitch=w * 4),
-                      "k_values": lambda: r.render_values(pc, d_values, winner=True, stride=16, channels=4)}
+                      "k_values": lambda: r.render_values(pc, d_values, winner=True, stride=16, channels=4),
+                      "removal": lambda: r.accumulate_removal(pc, acc),
+                      "removal_weighted": lambda: r.accumulate_removal(pc, acc, weight=d_plane, weight_pitch=w * 4)}
             out = {}
             for label in KERNELS:
                 def frame(i):
@@ -96,7 +106,7 @@ def child_speed(frames, warmup):
                 times = []
                 for i in range(frames):
                     frame(i)
-                    times += [ms for name, ms in r.kernel_times() if name == label]
+                    times += [ms for name, ms in r.kernel_times() if name == ARMS[label]]
                 assert len(times) == frames and r.frame_stats()["overflow"] == 0
                 out[label] = float(np.median(times))
         finally:

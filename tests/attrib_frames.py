@@ -1,4 +1,4 @@
-"""The frames of test_gpu_contrib, test_gpu_attrib and test_gpu_values: a context, one prepared frame with contributions on, and
+"""The frames of test_gpu_contrib, test_gpu_attrib, test_gpu_values and test_gpu_removal: a context, one prepared frame with contributions on, and
 the scenes the three files share (the stack of the staging boundaries, c1, the compressed cloud, the ramp-checker plane)."""
 import numpy as np
 
@@ -8,6 +8,7 @@ from websplat import synth
 
 F = np.float32
 VIEW = (320, 240)  # 7.5 tile rows of 32 px: the last row's lower lanes are outside the viewport
+BG = (0.25, 0.5, 0.75)  # the background of the removal effect
 
 
 def _ctx(ws, **cfg):
@@ -45,6 +46,11 @@ class _Frame:
 
     def weighted(self, plane, scale=1.0, bias=0.0):
         return self._download(lambda acc: self.r.accumulate_weighted(self.pc, acc, plane, scale=scale, bias=bias))
+
+    def removal(self, background=BG, kind="sq", scale=1.0, weight=None, base=False, **kw):
+        got = self._download(lambda acc: self.r.accumulate_removal(self.pc, acc, background=background, kind=kind, scale=scale,
+                                                                    weight=weight, base=base, **kw))
+        return got + (self.r.download_removal_base(),) if base else got
 
     def values(self, f, winner=False):
         """H x W x C float32 (None without values) and, with winner, H x W uint32."""

@@ -22,14 +22,13 @@ import blend_ref
 import removal_ref
 import scenes
 import weight_ref
-from attrib_frames import VIEW, F, _compressed, _ctx, _Frame, _ramp_checker, _stack, _u32
+from attrib_frames import BG, VIEW, F, _compressed, _ctx, _Frame, _ramp_checker, _stack_frame, _u32
 from websplat import _lib as L
 from websplat import synth
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BG = (0.25, 0.5, 0.75)
 SCALE = float(L.WS_CONTRIB_SUM_SCALE)
 REPORT = []
 
@@ -42,19 +41,6 @@ def _report():
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, "removal_report.json"), "w") as f:
             json.dump(REPORT, f, indent=1)
-
-
-class _RFrame(_Frame):
-    """attrib_frames._Frame with the removal call."""
-
-    def removal(self, background=BG, kind="sq", scale=1.0, weight=None, base=False, **kw):
-        got = self._download(lambda acc: self.r.accumulate_removal(self.pc, acc, background=background, kind=kind, scale=scale,
-                                                                    weight=weight, base=base, **kw))
-        return got + (self.r.download_removal_base(),) if base else got
-
-
-def _stack_frame(ws, c, k, opacity, viewport=(32, 32)):
-    return _RFrame(ws, c, *blend_ref.device_scene(ws, _stack(k, opacity), viewport))
 
 
 def _compare(case, got_q, got_m, ref, min_drawn=0):
@@ -132,7 +118,7 @@ def _cloud_rows(n=3000, seed=17):
 
 
 def _cloud_frame(ws, c):
-    return _RFrame(ws, c, *blend_ref.device_scene(ws, _cloud_rows(), VIEW))
+    return _Frame(ws, c, *blend_ref.device_scene(ws, _cloud_rows(), VIEW))
 
 
 _REF = {}  # K1 and the depth sort do not depend on the tile configuration: one float64 walk serves the cases that share a frame
@@ -178,7 +164,7 @@ def test_against_f64_compressed_cloud(ws):
     c = _ctx(ws)
     try:
         gpc, args = _compressed(ws, n=3000)   # (4000 points leave 1.8 % of the view saturated, 6000 14 %; 3000: 0.13 %)
-        f = _RFrame(ws, c, gpc, args, compressed=True)
+        f = _Frame(ws, c, gpc, args, compressed=True)
         try:
             frame = f.frame()
             plain = removal_ref.base_f64(frame, 400, 300, BG)
@@ -202,7 +188,7 @@ def test_delete_one_on_the_device(ws):
     try:
         rows = _cloud_rows()
         gpc, args = blend_ref.device_scene(ws, rows, VIEW)
-        f = _RFrame(ws, c, gpc, args)
+        f = _Frame(ws, c, gpc, args)
         try:
             frame, _, ok, _ = _cloud_ref(f)
             mask = ok.astype(F)
@@ -408,7 +394,7 @@ def test_a_decoy_in_front_of_a_wall_of_its_colour(ws):
         op = np.concatenate([[0.5, 0.5], np.full(layers, 1.0 - 1e-6)])
         rot = np.tile(np.array([1.0, 0.0, 0.0, 0.0], F), (layers + 2, 1))
         rows = synth._rows(xyz, f_dc, np.zeros((layers + 2, 45), F), np.log(op / (1.0 - op)).astype(F), log_scale, rot)
-        f = _RFrame(ws, c, *blend_ref.device_scene(ws, rows, (64, 64)))
+        f = _Frame(ws, c, *blend_ref.device_scene(ws, rows, (64, 64)))
         try:
             qc, _ = f.plain()
             q, m = f.removal(background=(0.0, 0.0, 0.0))

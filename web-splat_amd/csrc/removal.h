@@ -4,6 +4,7 @@
 
 #include <cstddef>
 
+#include "accum_q32.h"
 #include "weight_walk.h"
 
 namespace ws {
@@ -17,15 +18,12 @@ struct RemovalParams {
     float background[3];
     float scale;                  // of the effect: v = min(scale * m, 1 - 2^-24)
     int kind;                     // WS_ERROR_SQ | WS_ERROR_ABS
-    unsigned long long* sum_q32;  // [num_points]
-    uint32_t* max_bits;           // [num_points] bits of the largest v
-    const float* plane;           // the weight plane, f32 per viewport pixel; nullptr: E = 1, and nothing below is read
-    size_t plane_pitch;           // bytes
-    float plane_scale, plane_bias;
+    Accum acc;                    // acc.plane: the weight plane; nullptr: every pair counts in full
 };
 static_assert(offsetof(RemovalParams, base) == 80, "the frame's lists first, as in ContribParams and ValuesParams");
+static_assert(offsetof(RemovalParams, acc) == 120 && sizeof(RemovalParams) == 160, "kernarg segment of k_removal: 416 B");
 
-// k_removal_base<qw, qh>, then k_removal<qw, qh, plane != nullptr, kind> on the same stream.
+// k_removal_base<qw, qh>, then k_removal<qw, qh, acc.plane != nullptr, kind> on the same stream.
 //
 // TO THE BIT.  The pairs, the weights wgt = b * T and the stops are tile::walk_weights' (weight_walk.h), the one function k_contrib
 // and k_values run: nothing here influences them.  The staging thread of a slot also copies words 3 and 4 of its Splat record
@@ -35,8 +33,8 @@ static_assert(offsetof(RemovalParams, base) == 80, "the frame's lists first, as 
 //   acc_ch = fmaf(wgt, c_ch, acc_ch);  T = T - wgt                     (the walk's own subtraction of its rounded wgt)
 // and at the end base(p) = (fmaf(T, background_ch, acc_ch), T): (background, 1) where nothing is listed.
 //
-// Pass 2.  Every lane inside the viewport loads base(p) = (F, .) and, with a plane, E(p) exactly as k_contrib's weighted form
-// does (contrib.h); P_ch = 0, T = 1 (0 outside the viewport).  Per walked pair:
+// Pass 2.  Every lane inside the viewport loads base(p) = (F, .) and, with a plane, the accumulator's E(p) (accum_q32.h);
+// P_ch = 0, T = 1 (0 outside the viewport).  Per walked pair:
 //   Tb = T;  T = Tb - wgt                                              (wgt == 0 for a pair outside the cut-off)
 //   kept:  P_ch = fmaf(wgt, c_ch, P_ch)
 //   counted = kept && wgt > 0 && Tb >= 2^-14;  not counted: v = 0
@@ -48,10 +46,8 @@ static_assert(offsetof(RemovalParams, base) == 80, "the frame's lists first, as 
 //   m    = ((e_r + e_g) + e_b) / 3.0f                                  two rounded additions, IEEE division
 //   v    = fminf(scale * m, 0x1.fffffep-1f), NaN -> 0                  one rounded multiply
 //   plane:  v = v * E                                                  one rounded multiply
-//   q32 = (uint32_t)(v * 2^32)  exact product, truncating;  mb = q32 ? bits(v) : 0
-// and q32 / mb go the way k_contrib's go: DPP wave reductions, LDS partials per staged record, one 64-bit add and one 32-bit max
-// per (tile, entry) with a non-zero sum, through src_index.  A wave whose 64 values of E are all 0 skips its walk (as in
-// k_contrib); pass 1 never does.
+// and everything from v on is the accumulator's (accum_q32.h), the one k_contrib feeds too.  A wave whose 64 values of E are
+// all 0 skips its walk there; pass 1 never does.
 int launch_removal(const RemovalParams& p, hipStream_t stream);
 
 }  // namespace ws

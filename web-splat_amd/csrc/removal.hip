@@ -5,10 +5,8 @@
 //
 //   k_removal_base : F and the final T per pixel -- k_values with the colour taken from the Splat record.  Every lane keeps
 //                    acc = sum of w c and its own copy of T; no atomics, no wave reductions; empty tiles get (background, 1).
-//   k_removal      : per walked pair the lane's v = min(scale * mean_ch e(d), 1 - 2^-24) (times E of a weight plane), reduced
-//                    exactly as k_contrib reduces its weights: q32 = (uint32_t)(v 2^32), DPP wave sums of the split q32 and a DPP
-//                    max of the bits, one ds_add_u64 + one ds_max_u32 per (wave, record), and behind the batch's walk one 64-bit
-//                    add and one 32-bit max per (tile, entry) with a non-zero sum, through K1's src_index.
+//   k_removal      : per walked pair the lane's v = min(scale * mean_ch e(d), 1 - 2^-24) (times E of a weight plane), into the
+//                    per-Gaussian accumulator k_contrib feeds with its weights (accum_q32.h).
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -69,69 +67,34 @@ __global__ __launch_bounds__(64 * QW * QH) void k_removal_base(const RemovalPara
     tile::walk_weights<QW, QH>(p.frame, sink);
 }
 
-// Wave reductions over 64 lanes with DPP, result in lane 63 (contrib.hip's, copied: that file's code object stays as it is).
-// row_shr 1 / 2 / 4 / 8 leave every row's total in its lane 15, row_bcast:15 adds it into the next row (rows 1 and 3),
-// row_bcast:31 adds lane 31 into rows 2 and 3.  Lanes a step does not reach read 0, the identity of unsigned add and max.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-__device__ __forceinline__ uint32_t wave_add_u32(uint32_t v) {
-    v += dpp0<0x111, 0xF>(v);
-    v += dpp0<0x112, 0xF>(v);
-    v += dpp0<0x114, 0xF>(v);
-    v += dpp0<0x118, 0xF>(v);
-    v += dpp0<0x142, 0xA>(v);
-    v += dpp0<0x143, 0xC>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    v = umax(v, dpp0<0x111, 0xF>(v));
-    v = umax(v, dpp0<0x112, 0xF>(v));
-    v = umax(v, dpp0<0x114, 0xF>(v));
-    v = umax(v, dpp0<0x118, 0xF>(v));
-    v = umax(v, dpp0<0x142, 0xA>(v));
-    v = umax(v, dpp0<0x143, 0xC>(v));
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 constexpr float V_CAP = 0x1.fffffep-1f;  // the largest f32 below 1: v * 2^32 fits 32 bits
 
-// Pass 2 (removal.h).  LDS per staged record: its colour words, the sum of q32 over the tile's pixels and the bits of its largest v.
+// Pass 2 (removal.h): v per walked pair, into the accumulator (accum_q32.h).  LDS per staged record: its colour words beside the
+// accumulator's partials.
 template <bool WEIGHTED, int KIND>
 struct RemovalSink {
     static constexpr bool WRITES_EMPTY_TILES = false;
-    static constexpr bool PAIR_IS_WAVE_WIDE = true;  // the DPP reductions must not sit under a divergent branch
+    static constexpr bool PAIR_IS_WAVE_WIDE = true;
     const RemovalParams& p;
     uint2* s_col;
-    unsigned long long* s_sum;
-    uint32_t* s_max;
-    const int lane = threadIdx.x & 63;
+    AccumQ32 acc;
     float F0 = 0.0f, F1 = 0.0f, F2 = 0.0f;  // base(p)
     float P0 = 0.0f, P1 = 0.0f, P2 = 0.0f;  // the colour accumulated through the pair at hand
     float T = 0.0f;                         // the walk's T again
-    float E = 0.0f;                         // WEIGHTED: the lane's value of the plane, loaded once
-    bool none = false;                      // wave-uniform: nothing but zeros -- no walk to do
+    PlaneValue<WEIGHTED> plane;
 
     __device__ __forceinline__ void begin(uint32_t px, uint32_t py, bool inside) {
         if (inside) {
             const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.base) + (size_t)py * p.base_pitch + (size_t)px * 16);
             F0 = b.x, F1 = b.y, F2 = b.z;
             T = 1.0f;
+            plane.load(p.acc, px, py);
         }
-        if constexpr (WEIGHTED) {
-            if (inside) {
-                const float e = fmaf(p.plane_scale, *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.plane) + (size_t)py * p.plane_pitch + (size_t)px * 4), p.plane_bias);
-                E = (e != e) ? 0.0f : fminf(fmaxf(e, 0.0f), 1.0f);
-            }
-            none = __ballot(E > 0.0f) == 0ull;
-        }
+        plane.vote();
     }
-    __device__ __forceinline__ bool idle() const { return WEIGHTED && none; }
+    __device__ __forceinline__ bool idle() const { return plane.idle(); }
     __device__ __forceinline__ void stage(int tid, uint32_t idx, bool live) {
-        s_sum[tid] = 0ull;
-        s_max[tid] = 0u;
+        acc.clear(tid);
         if (live) s_col[tid] = splat_colour_words(p.frame.splats, idx);
     }
     __device__ __forceinline__ void pair(uint32_t off, float wgt, bool kept) {
@@ -157,31 +120,13 @@ struct RemovalSink {
                     const float m = ((e0 + e1) + e2) / 3.0f;
                     const float sm = p.scale * m;
                     v = (sm != sm) ? 0.0f : fminf(sm, V_CAP);
-                    if constexpr (WEIGHTED) v = v * E;
+                    if constexpr (WEIGHTED) v = v * plane.E;
                 }
             }
         }
-        // v < 1: v * 2^32 is exact in f32 and below 2^32; the conversion truncates.  A pair whose v truncates to 0 counts in
-        // neither result: sum == 0 <=> max == 0.
-        const uint32_t q32 = (uint32_t)(v * 4294967296.0f);
-        const uint32_t mb = q32 ? __float_as_uint(v) : 0u;
-        // 64 values below 2^32 sum to less than 2^38: the low 26 bits and the high 6 bits as two 32-bit sums
-        const uint32_t lo = wave_add_u32(q32 & 0x03FFFFFFu), hi6 = wave_add_u32(q32 >> 26), mx = wave_max_u32(mb);
-        const unsigned long long sum = (unsigned long long)lo + ((unsigned long long)hi6 << 26);
-        if (sum != 0ull && lane == 0) {  // (sum is wave-uniform)
-            atomicAdd(&s_sum[off >> 4], sum);
-            atomicMax(&s_max[off >> 4], mx);
-        }
+        acc.add(off, v);
     }
-    // one add + one max per (tile, entry) with any effect, into the accumulators of its source Gaussian
-    __device__ __forceinline__ void flush(int tid, uint32_t idx) {
-        const unsigned long long s = s_sum[tid];
-        if (s != 0ull) {
-            const uint32_t src = p.frame.src_index[idx];
-            atomicAdd(p.sum_q32 + src, s);
-            atomicMax(p.max_bits + src, s_max[tid]);
-        }
-    }
+    __device__ __forceinline__ void flush(int tid, uint32_t idx) { acc.flush(p.frame.src_index, tid, idx); }
     __device__ __forceinline__ void finish(uint32_t, uint32_t, bool) {}
 };
 
@@ -191,7 +136,7 @@ __global__ __launch_bounds__(64 * QW * QH) void k_removal(const RemovalParams p)
     __shared__ uint2 s_col[STAGE];
     __shared__ unsigned long long s_sum[STAGE];
     __shared__ uint32_t s_max[STAGE];
-    RemovalSink<WEIGHTED, KIND> sink{p, s_col, s_sum, s_max};
+    RemovalSink<WEIGHTED, KIND> sink{p, s_col, {p.acc, s_sum, s_max}};
     tile::walk_weights<QW, QH>(p.frame, sink);
 }
 
@@ -200,7 +145,7 @@ __global__ __launch_bounds__(64 * QW * QH) void k_removal(const RemovalParams p)
 int launch_removal(const RemovalParams& p, hipStream_t stream) {
     const uint32_t grid = p.frame.tiles_x * p.frame.tiles_y;
     if (grid == 0) return WS_OK;
-    const bool weighted = p.plane != nullptr;
+    const bool weighted = p.acc.plane != nullptr;
     const bool sq = p.kind == WS_ERROR_SQ;
     const bool shaped = with_tile_shape(p.frame.qw, p.frame.qh, [&](auto qw, auto qh) {
         constexpr int QW = decltype(qw)::value, QH = decltype(qh)::value;

@@ -1,7 +1,8 @@
 // weight_walk.h -- the weights of a prepared frame, w = b T pair by pair, near -> far, once: what a launch over the frame's binned
 // lists reads (FrameLists) and the walk of one tile's list through the staged batches of blend_tile.h (tile::walk_weights).
-// k_contrib (contrib.hip) and k_values (values.hip) are two sinks of this one function: in one context they see the same pairs,
-// the same weights and the same stops because there is no second copy of the arithmetic.  k_blend (raster.hip) keeps its own.
+// k_contrib (contrib.hip), k_values (values.hip), k_removal_base and k_removal (removal.hip) are four sinks of this one function:
+// in one context they see the same pairs, the same weights and the same stops because there is no second copy of the arithmetic.
+// What k_contrib and k_removal do with a value per pair is accum_q32.h's.  k_blend (raster.hip) keeps its own walk.
 #pragma once
 
 #include <type_traits>
@@ -10,7 +11,7 @@
 
 namespace ws {
 
-// A prepared frame's binned, depth-ordered tile lists, as a kernel argument.  ContribParams and ValuesParams start with it.
+// A prepared frame's binned, depth-ordered tile lists, as a kernel argument.  ContribParams, ValuesParams and RemovalParams start with it.
 struct FrameLists {
     const uint8_t* splats;        // [V] x SPLAT_STRIDE
     const uint32_t* entry_vals;   // sorted by tile, far -> near inside a tile (store indices)

@@ -2195,7 +2195,7 @@ int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
     return WS_OK;
 }
 
-// What a launch over the prepared frame's weights (k_contrib, k_values) reads of the renderer
+// What a launch over the prepared frame's weights (k_contrib, k_values, k_removal_base, k_removal) reads of the renderer
 static FrameLists frame_lists(const ws_renderer* r) {
     FrameLists f;
     f.splats = r->splats;
@@ -2224,31 +2224,52 @@ static int check_weights_frame(const ws_renderer* r, const ws_pointcloud* pc, co
     return WS_OK;
 }
 
+// A caller's plane of 4-B values (`what`: "plane" | "winner"; nullptr: nothing to judge).  r == nullptr: by itself, pointer and
+// pitch; else against r's prepared frame, the pitch.  who: the text's prefix.
+static int check_plane(const ws_renderer* r, const std::string& who, const char* what, const void* ptr, size_t pitch) {
+    if (ptr && !r && (pitch % 4 != 0 || reinterpret_cast<uintptr_t>(ptr) % 4 != 0))
+        return fail(WS_ERR_INVALID, who + ": " + what + " pointer and row pitch must be multiples of 4");
+    if (ptr && r && pitch < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": " + what + " row pitch below 4 x the viewport's width");
+    return WS_OK;
+}
+static int check_plane_view(const ws_renderer* r, const std::string& who, const ws_plane_view* v) {
+    if (!v) return WS_OK;
+    if (!r && (!std::isfinite(v->scale) || !std::isfinite(v->bias))) return fail(WS_ERR_INVALID, who + ": scale and bias must be finite");
+    return check_plane(r, who, "plane", v->d_values, v->row_pitch_bytes);
+}
+
+// The accumulator as the kernels' argument: the plain sums (plane == nullptr) or the weighted ones
+static Accum accum_arg(const ws_contrib* c, const ws_plane_view* plane) {
+    if (!plane) return {c->sum_q32, c->max_bits, nullptr, 0, 1.0f, 0.0f};
+    return {c->sum_q32, c->max_bits, plane->d_values, plane->row_pitch_bytes, plane->scale, plane->bias};
+}
+
+// The bracket of a launch over the prepared frame: the timers' begin before it; behind it, with its status, the mark and the
+// streams to wait for.  c: the accumulator the launch added a frame to, or nullptr
+static KernelMarks* launch_begin(ws_renderer* r, hipStream_t stream) {
+    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
+    if (km) km->begin(stream, false);
+    return km;
+}
+static int launch_done(int rc, ws_renderer* r, ws_contrib* c, hipStream_t stream, KernelMarks* km, const char* mark) {
+    if (rc) return rc;
+    km_mark(km, mark);
+    if (c) ++c->frames, c->last_stream = stream;
+    r->last_stream = stream;
+    return WS_OK;
+}
+
 // One attribution launch over the prepared frame: the plain sums (plane == nullptr) or the weighted ones
 static int accumulate_frame(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v,
                             const char* who_c) {
     const std::string who(who_c);
-    const int state = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
-    if (state) return state;
-    if (plane && plane->row_pitch_bytes < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": plane row pitch below 4 x the viewport's width");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    ContribParams cp;
-    cp.frame = frame_lists(r);
-    cp.sum_q32 = c->sum_q32;
-    cp.max_bits = c->max_bits;
-    cp.plane = plane ? plane->d_values : nullptr;
-    cp.plane_pitch = plane ? plane->row_pitch_bytes : 0;
-    cp.scale = plane ? plane->scale : 1.0f;
-    cp.bias = plane ? plane->bias : 0.0f;
-    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
-    if (km) km->begin(stream, false);
-    const int rc = launch_contrib(cp, stream);
+    int rc = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
+    if (rc == WS_OK) rc = check_plane_view(r, who, plane);
     if (rc) return rc;
-    km_mark(km, plane ? "k_contrib_weighted" : "k_contrib");
-    ++c->frames;
-    c->last_stream = stream;
-    r->last_stream = stream;
-    return WS_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const ContribParams cp{frame_lists(r), accum_arg(c, plane)};
+    KernelMarks* km = launch_begin(r, stream);
+    return launch_done(launch_contrib(cp, stream), r, c, stream, km, plane ? "k_contrib_weighted" : "k_contrib");
 }
 
 int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, void* stream_v) {
@@ -2258,10 +2279,7 @@ int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_c
 
 int ws_renderer_accumulate_weighted(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v) {
     if (!r || !pc || !c || !plane || !plane->d_values) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: null argument");
-    if (!std::isfinite(plane->scale) || !std::isfinite(plane->bias))
-        return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: scale and bias must be finite");
-    if (plane->row_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(plane->d_values) % 4 != 0)
-        return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: plane pointer and row pitch must be multiples of 4");
+    if (const int rc = check_plane_view(nullptr, "ws_renderer_accumulate_weighted", plane)) return rc;
     return accumulate_frame(r, pc, c, plane, stream_v, "ws_renderer_accumulate_weighted");
 }
 
@@ -2285,20 +2303,17 @@ int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_
     for (uint32_t c = 0; c < 4; ++c) {
         if (!out->plane[c]) continue;
         if (c >= channels) return fail(WS_ERR_INVALID, who + ": a plane at or above the number of channels");
-        if (out->pitch[c] % 4 != 0 || reinterpret_cast<uintptr_t>(out->plane[c]) % 4 != 0)
-            return fail(WS_ERR_INVALID, who + ": plane pointer and row pitch must be multiples of 4");
+        if (const int rc = check_plane(nullptr, who, "plane", out->plane[c], out->pitch[c])) return rc;
         any = true;
     }
-    if (out->winner && (out->winner_pitch % 4 != 0 || reinterpret_cast<uintptr_t>(out->winner) % 4 != 0))
-        return fail(WS_ERR_INVALID, who + ": winner pointer and row pitch must be multiples of 4");
+    if (const int rc = check_plane(nullptr, who, "winner", out->winner, out->winner_pitch)) return rc;
     if (!any) return fail(WS_ERR_INVALID, who + ": no output plane");
     if (!r || !pc) return fail(WS_ERR_INVALID, who + ": null argument");
     const int state = check_weights_frame(r, pc, who, !values || values->num_points == pc->num_points, "the values were laid out for another number of points");
     if (state) return state;
     for (uint32_t c = 0; c < 4; ++c)
-        if (out->plane[c] && out->pitch[c] < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": plane row pitch below 4 x the viewport's width");
-    if (out->winner && out->winner_pitch < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": winner row pitch below 4 x the viewport's width");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+        if (const int rc = check_plane(r, who, "plane", out->plane[c], out->pitch[c])) return rc;
+    if (const int rc = check_plane(r, who, "winner", out->winner, out->winner_pitch)) return rc;
     ValuesParams vp;
     vp.frame = frame_lists(r);
     vp.values = values ? values->d_values : nullptr;
@@ -2310,13 +2325,9 @@ int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_
     }
     vp.winner = out->winner;
     vp.winner_pitch = out->winner_pitch;
-    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
-    if (km) km->begin(stream, false);
-    const int rc = launch_values(vp, stream);
-    if (rc) return rc;
-    km_mark(km, "k_values");
-    r->last_stream = stream;
-    return WS_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    KernelMarks* km = launch_begin(r, stream);
+    return launch_done(launch_values(vp, stream), r, nullptr, stream, km, "k_values");
 }
 
 // What deleting each Gaussian alone would do to the prepared frame (websplat.h "Removal effect"; removal.h).  The descriptor is
@@ -2331,20 +2342,15 @@ int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_c
     if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
     for (float b : p->background)
         if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
-    if (const ws_plane_view* e = p->weight) {
-        if (!e->d_values) return fail(WS_ERR_INVALID, who + ": weight: null d_values");
-        if (!std::isfinite(e->scale) || !std::isfinite(e->bias)) return fail(WS_ERR_INVALID, who + ": weight: scale and bias must be finite");
-        if (e->row_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(e->d_values) % 4 != 0)
-            return fail(WS_ERR_INVALID, who + ": weight: plane pointer and row pitch must be multiples of 4");
-    }
+    if (p->weight && !p->weight->d_values) return fail(WS_ERR_INVALID, who + ": weight: null d_values");
+    if (const int rc = check_plane_view(nullptr, who + ": weight", p->weight)) return rc;
     if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
         return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
     if (!r || !pc || !c) return fail(WS_ERR_INVALID, who + ": null argument");
     const int state = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
     if (state) return state;
-    if (p->weight && p->weight->row_pitch_bytes < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": weight: plane row pitch below 4 x the viewport's width");
+    if (const int rc = check_plane_view(r, who + ": weight", p->weight)) return rc;
     if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
     RemovalParams rp;
     rp.frame = frame_lists(r);
     if (p->d_base) {
@@ -2367,21 +2373,10 @@ int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_c
     for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
     rp.scale = p->scale;
     rp.kind = p->kind;
-    rp.sum_q32 = c->sum_q32;
-    rp.max_bits = c->max_bits;
-    rp.plane = p->weight ? p->weight->d_values : nullptr;
-    rp.plane_pitch = p->weight ? p->weight->row_pitch_bytes : 0;
-    rp.plane_scale = p->weight ? p->weight->scale : 1.0f;
-    rp.plane_bias = p->weight ? p->weight->bias : 0.0f;
-    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
-    if (km) km->begin(stream, false);
-    const int rc = launch_removal(rp, stream);
-    if (rc) return rc;
-    km_mark(km, "k_removal_base+k_removal");
-    ++c->frames;
-    c->last_stream = stream;
-    r->last_stream = stream;
-    return WS_OK;
+    rp.acc = accum_arg(c, p->weight);
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    KernelMarks* km = launch_begin(r, stream);
+    return launch_done(launch_removal(rp, stream), r, c, stream, km, "k_removal_base+k_removal");
 }
 
 int ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, float* max_weight) {

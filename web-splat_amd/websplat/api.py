@@ -10,6 +10,7 @@ Names follow the reference so that tests read like web-splat code:
   GPURSSorter         (src/gpu_rs.rs:63-885)     -> GPURSSorter
 No compute happens here; every method is one call into libwebsplat_hip.so.
 """
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass, field
@@ -1027,29 +1028,45 @@ class GaussianRenderer:
         """Add the prepared frame's per-Gaussian weights to `contrib` (enqueues; render() is not needed)."""
         check(lib.ws_renderer_accumulate_contrib(self.handle, pc.handle, contrib.handle, C.c_void_p(stream or 0)))
 
+    @contextlib.contextmanager
+    def _staged(self, v, array, stream):
+        """For the calls of the body, v.d_values points at a device copy of `array`; behind them: wait for `stream`, free the
+        copy.  array None: v is left as it is, nothing is uploaded or waited for."""
+        if array is None:
+            yield
+            return
+        d = self.ctx.malloc(max(array.nbytes, 4))
+        try:
+            self.ctx.upload(d, array)
+            v.d_values = d
+            yield
+        finally:
+            self.ctx.sync(stream)
+            self.ctx.free(d)
+
+    def _plane_view(self, who, what, plane, pitch, scale, bias, view):
+        """(ws_plane_view, array to stage | None) of an H x W float32 numpy plane of the viewport `view` -- its d_values is
+        _staged()'s to set -- or of a device pointer with its row `pitch` in bytes."""
+        v = L.ws_plane_view()
+        v.scale, v.bias = float(scale), float(bias)
+        if not isinstance(plane, np.ndarray):
+            if pitch is None:
+                raise ValueError(f"{who}: a device {what} needs its row pitch")
+            v.d_values, v.row_pitch_bytes = int(plane), int(pitch)
+            return v, None
+        a = np.ascontiguousarray(plane, dtype=np.float32)
+        if a.ndim != 2 or (view is not None and view[0] and (a.shape[0] != view[1] or a.shape[1] < view[0])):  # (wider rows: padding)
+            raise ValueError(f"{who}: want an H x W float32 {what} of the viewport {view}, got {a.shape}")
+        v.row_pitch_bytes = int(pitch) if pitch is not None else a.shape[1] * 4
+        return v, a
+
     def accumulate_weighted(self, pc: PointCloud, contrib: "Contrib", plane, scale=1.0, bias=0.0, pitch=None, stream=None):
         """Add the prepared frame's per-Gaussian weights times E(p) = clamp(scale * plane[p] + bias, 0, 1) to `contrib`
         (ws_renderer_accumulate_weighted).  `plane`: an H x W float32 numpy array of the viewport's shape (uploaded for the
         call, which then waits for the launch), or a device pointer with its row `pitch` in bytes (enqueues only)."""
-        v = L.ws_plane_view()
-        v.scale, v.bias = float(scale), float(bias)
-        if isinstance(plane, np.ndarray):
-            a = np.ascontiguousarray(plane, dtype=np.float32)
-            view = getattr(self, "_viewport", None)  # (None: not prepared -- the library says so)
-            if a.ndim != 2 or (view is not None and (a.shape[0] != view[1] or a.shape[1] < view[0])):  # (wider rows: padding)
-                raise ValueError(f"accumulate_weighted: want an H x W float32 plane of the viewport {view}, got {a.shape}")
-            d = self.ctx.malloc(max(a.nbytes, 4))
-            try:
-                self.ctx.upload(d, a)
-                v.d_values, v.row_pitch_bytes = d, int(pitch) if pitch is not None else a.shape[1] * 4
-                check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
-            finally:
-                self.ctx.sync(stream)
-                self.ctx.free(d)
-        else:
-            if pitch is None:
-                raise ValueError("accumulate_weighted: a device plane needs its row pitch")
-            v.d_values, v.row_pitch_bytes = int(plane), int(pitch)
+        view = getattr(self, "_viewport", None)  # (None: not prepared -- the library says so)
+        v, staged = self._plane_view("accumulate_weighted", "plane", plane, pitch, scale, bias, view)
+        with self._staged(v, staged, stream):
             check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
 
     def _free_removal_base(self):
@@ -1085,29 +1102,9 @@ class GaussianRenderer:
             p.d_base, p.base_pitch_bytes = self._rm_base, w * 16
         v, staged = None, None
         if weight is not None:
-            v = L.ws_plane_view()
-            v.scale, v.bias = float(weight_scale), float(weight_bias)
-            if isinstance(weight, np.ndarray):
-                a = np.ascontiguousarray(weight, dtype=np.float32)
-                if a.ndim != 2 or (w and (a.shape[0] != h or a.shape[1] < w)):  # (wider rows: padding)
-                    raise ValueError(f"accumulate_removal: want an H x W float32 weight plane of the viewport {(w, h)}, got {a.shape}")
-                staged = a
-                v.row_pitch_bytes = int(weight_pitch) if weight_pitch is not None else a.shape[1] * 4
-            else:
-                if weight_pitch is None:
-                    raise ValueError("accumulate_removal: a device weight plane needs its row pitch")
-                v.d_values, v.row_pitch_bytes = int(weight), int(weight_pitch)
+            v, staged = self._plane_view("accumulate_removal", "weight plane", weight, weight_pitch, weight_scale, weight_bias, (w, h))
             p.weight = C.pointer(v)
-        if staged is not None:
-            d = self.ctx.malloc(max(staged.nbytes, 4))
-            try:
-                self.ctx.upload(d, staged)
-                v.d_values = d
-                check(lib.ws_renderer_accumulate_removal(self.handle, pc.handle, contrib.handle, C.byref(p), C.c_void_p(stream or 0)))
-            finally:
-                self.ctx.sync(stream)
-                self.ctx.free(d)
-        else:
+        with self._staged(v, staged, stream):
             check(lib.ws_renderer_accumulate_removal(self.handle, pc.handle, contrib.handle, C.byref(p), C.c_void_p(stream or 0)))
 
     def download_removal_base(self) -> np.ndarray:
@@ -1162,16 +1159,7 @@ class GaussianRenderer:
         if winner:
             t.winner, t.winner_pitch = self._val["winner"], w * 4
         vref = C.byref(v) if v is not None else None
-        if staged is not None:
-            d = self.ctx.malloc(max(staged.nbytes, 4))
-            try:
-                self.ctx.upload(d, staged)
-                v.d_values = d
-                check(lib.ws_renderer_render_values(self.handle, pc.handle, vref, C.byref(t), C.c_void_p(stream or 0)))
-            finally:
-                self.ctx.sync(stream)
-                self.ctx.free(d)
-        else:
+        with self._staged(v, staged, stream):
             check(lib.ws_renderer_render_values(self.handle, pc.handle, vref, C.byref(t), C.c_void_p(stream or 0)))
         self._val_last = (nch, bool(winner))
 
