@@ -17,7 +17,8 @@ uint32_t fat_sort_grid(uint32_t n, int num_cus, int grid_request) {
 
 int launch_depth_sort_fat(const FatSortScratch& sc, uint32_t* keys, uint32_t* vals, uint32_t* aux, const uint32_t* d_count,
                           uint32_t n, bool implicit_iota, bool coop, uint32_t epoch, int num_cus, hipStream_t stream,
-                          KernelMarks* km) {
+                          KernelMarks* km, SortResult* res) {
+    *res = SortResult{keys, vals, aux};  // A -> B -> A -> B -> A: everything ends where it started, no pass is ever skipped
     if (n == 0) return WS_OK;
     if (n > sc.cap) return fail(WS_ERR_INVALID, "depth sort: n exceeds the scratch capacity");
     if (aux && !sc.aux_alt) return fail(WS_ERR_INVALID, "depth sort: companion values without a companion scratch buffer");
@@ -68,7 +69,8 @@ int launch_depth_sort_fat(const FatSortScratch& sc, uint32_t* keys, uint32_t* va
 }
 
 int launch_tile_sort_wide(const SortScratch& sc, const uint32_t* keys16, const uint32_t* vals, const uint32_t* d_count,
-                          uint32_t n, int bits, hipStream_t stream, KernelMarks* km, uint2* ranges, uint32_t nranges) {
+                          uint32_t n, int bits, hipStream_t stream, KernelMarks* km, uint2* ranges, uint32_t nranges, SortResult* res) {
+    *res = SortResult{nullptr, sc.vals_alt};  // the values only: the ranges stand for the sorted tile ids
     if (n == 0) return WS_OK;
     if (bits < 7) bits = 7;
     const uint32_t bins = 1u << bits;

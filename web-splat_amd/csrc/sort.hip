@@ -22,6 +22,8 @@
 // The fat-tile one-sweep below (k_dsort_fat) is the form of that idea that does not chain; it is a measured variant too.
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 #ifdef WS_EXPERIMENTAL
 #include "experimental/grid_barrier.h"  // (the single-launch depth sort's device-wide barrier)
 #endif
@@ -620,26 +622,28 @@ __global__ __launch_bounds__(SORT_THREADS) void k_dsort_copy_back(const uint32_t
     }
 }
 
+// The digit passes of one SortJob (ws_internal.h), ping-ponging between the caller's arrays and the scratch partners.
 template <int KPT, int BITS, bool KEY16>
-int run_passes_scan(const SortScratch& sc, uint32_t* kin, uint32_t* vin, uint32_t* kout, uint32_t* vout, uint32_t* ain,
-                    uint32_t* aout,
-                    const uint32_t* d_count, uint32_t n, int begin_bit, int npass, bool implicit_iota,
-                    bool first_tile_hist_ready, hipStream_t stream, uint32_t** fk, uint32_t** fv,
-                    KernelMarks* km, const char* const* names, uint2* ranges, uint32_t nranges, FrameCounters* skip_top,
-                    uint32_t** fk_skipped, uint32_t** fv_skipped) {
+int run_passes_scan(const SortScratch& sc, const SortJob& job, int npass, hipStream_t stream, KernelMarks* km,
+                    const char* const* names, SortResult* res) {
+    uint32_t *kin = job.keys, *vin = job.vals, *ain = job.aux, *kout = sc.keys_alt, *vout = sc.vals_alt, *aout = job.aux_alt;
+    const uint32_t* const d_count = job.d_count;
+    const uint32_t n = job.n;
+    FrameCounters* const skip_top = job.skip_top;
     constexpr uint32_t TILE_N = SORT_THREADS * KPT;
     const uint32_t tiles = sort_grid((n + TILE_N - 1) / TILE_N);
     for (int p = 0; p < npass; ++p) {
-        const int shift = begin_bit + p * BITS;
-        const int iota = (implicit_iota && p == 0) ? 1 : 0;
+        const int shift = job.begin_bit + p * BITS;
+        const int iota = (job.implicit_iota && p == 0) ? 1 : 0;
         // the depth sort of a frame: its first kernel decides whether the last pass has anything to do, the kernels of the last
         // pass ask (ws_internal.h depth_range_decide)
         FrameCounters* fold = (skip_top && p == 0) ? skip_top : nullptr;
         const uint32_t* skip = (skip_top && p == npass - 1) ? &skip_top->depth_skip_top : nullptr;
         const uint32_t* kbase = (skip_top && p > 0) ? &skip_top->depth_key_base : nullptr;
         if (skip) {
-            if (fk_skipped) *fk_skipped = kin;
-            if (fv_skipped) *fv_skipped = vin;
+            res->keys_skipped = kin;
+            res->vals_skipped = vin;
+            res->aux_skipped = ain;
         }
         uint32_t* const hist_p = sc.hist + (size_t)p * sc.hist_pitch;
         if constexpr (BITS == 9) {  // the depth sort's 9-bit form: its own kernels (above)
@@ -653,7 +657,7 @@ int run_passes_scan(const SortScratch& sc, uint32_t* kin, uint32_t* vin, uint32_
                                n, shift, iota, hist_p, sc.tile_sums, sc.tiles_cap, skip, kbase);
             km_mark(km, names[2]);
         } else {
-        if (!(p == 0 && first_tile_hist_ready)) {
+        if (!(p == 0 && job.first_tile_hist_ready)) {
             hipLaunchKernelGGL((k_sort_tile_hist<KPT, KEY16>), dim3(tiles), dim3(SORT_THREADS), 0, stream, kin, d_count, n, shift,
                                (1u << BITS) - 1u, sc.tile_sums, sc.tiles_cap, fold, skip, kbase);
             km_mark(km, names[0]);
@@ -661,10 +665,10 @@ int run_passes_scan(const SortScratch& sc, uint32_t* kin, uint32_t* vin, uint32_
         hipLaunchKernelGGL(k_sort_col_scan, dim3(1u << BITS), dim3(SORT_THREADS), 0, stream, d_count, n, TILE_N,
                            sc.tile_sums, sc.tiles_cap, hist_p, skip, fold);
         km_mark(km, names[1]);
-        if (ranges && p == npass - 1)
+        if (job.ranges && p == npass - 1)
             hipLaunchKernelGGL((k_sort_scatter<KPT, true, BITS, false, KEY16>), dim3(tiles), dim3(SORT_THREADS), 0, stream, kin, vin,
                                kout, vout, (const uint32_t*)nullptr, (uint32_t*)nullptr, d_count, n, shift, iota,
-                               hist_p, sc.tile_sums, sc.tiles_cap, ranges, nranges, skip, kbase);
+                               hist_p, sc.tile_sums, sc.tiles_cap, job.ranges, job.nranges, skip, kbase);
         else if (ain)
             hipLaunchKernelGGL((k_sort_scatter<KPT, false, BITS, true>), dim3(tiles), dim3(SORT_THREADS), 0, stream, kin,
                                vin, kout, vout, ain, aout, d_count, n, shift, iota, hist_p, sc.tile_sums,
@@ -676,21 +680,28 @@ int run_passes_scan(const SortScratch& sc, uint32_t* kin, uint32_t* vin, uint32_
         km_mark(km, names[2]);
         }
         WS_HIP(hipGetLastError());
-        uint32_t* tk = kin;
-        kin = kout;
-        kout = tk;
-        uint32_t* tv = vin;
-        vin = vout;
-        vout = tv;
-        uint32_t* ta = ain;
-        ain = aout;
-        aout = ta;
+        std::swap(kin, kout);
+        std::swap(vin, vout);
+        std::swap(ain, aout);
     }
-    *fk = kin;
-    *fv = vin;
+    res->keys = kin;
+    res->vals = vin;
+    res->aux = job.aux ? ain : nullptr;
     return WS_OK;
 }
 
+// One digit width of the scan path: the large or the small tile, 16- or 32-bit keys (9-bit digits: 32-bit keys only).
+template <int BITS>
+int run_scan(bool big, const SortScratch& sc, const SortJob& job, int npass, hipStream_t stream, KernelMarks* km,
+             const char* const* names, SortResult* res) {
+    if constexpr (BITS != 9) {
+        if (job.key16)
+            return big ? run_passes_scan<SORT_KPT, BITS, true>(sc, job, npass, stream, km, names, res)
+                       : run_passes_scan<SORT_KPT_SMALL, BITS, true>(sc, job, npass, stream, km, names, res);
+    }
+    return big ? run_passes_scan<SORT_KPT, BITS, false>(sc, job, npass, stream, km, names, res)
+               : run_passes_scan<SORT_KPT_SMALL, BITS, false>(sc, job, npass, stream, km, names, res);
+}
 
 #ifdef WS_EXPERIMENTAL  // measured-and-lost variants: compiled by `make experimental` only
 #include "experimental/sort_variants_kernels.hip"
@@ -724,77 +735,48 @@ int launch_depth_copy_back(const uint32_t* skip, const uint32_t* d_count, uint32
 size_t fat_sort_status_words() { return 0; }
 uint32_t fat_sort_grid(uint32_t, int, int) { return 0u; }
 int launch_depth_sort_fat(const FatSortScratch&, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, uint32_t, bool, bool, uint32_t, int,
-                          hipStream_t, KernelMarks*) {
+                          hipStream_t, KernelMarks*, SortResult*) {
     return fail(WS_ERR_UNSUPPORTED, "the fat-tile one-sweep depth sort is only in the experimental build");
 }
 int launch_tile_sort_wide(const SortScratch&, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, hipStream_t, KernelMarks*,
-                          uint2*, uint32_t) {
+                          uint2*, uint32_t, SortResult*) {
     return fail(WS_ERR_UNSUPPORTED, "the single-pass tile-id sort is only in the experimental build");
 }
 #endif  // WS_EXPERIMENTAL
 
-int launch_sort_pairs(const SortScratch& sc, uint32_t* keys, uint32_t* vals, const uint32_t* d_count, uint32_t n,
-                      int begin_bit, int end_bit, bool implicit_iota, bool first_tile_hist_ready, hipStream_t stream,
-                      uint32_t** out_keys, uint32_t** out_vals, KernelMarks* km, const char* tag, uint2* ranges,
-                      uint32_t nranges, int digit_bits, bool key16, uint32_t* aux, uint32_t* aux_alt, FrameCounters* skip_top,
-                      uint32_t** out_keys_skipped, uint32_t** out_vals_skipped, int kpt9) {
-    // labels of the per-kernel timers: "<tag>k_sort_..." with tag = "depth:" / "tiles:"
-    const bool depth = tag && tag[0] == 'd';
+int launch_sort_pairs(const SortScratch& sc, const SortJob& job, hipStream_t stream, KernelMarks* km, SortResult* res) {
     static const char* const N_DEPTH[3] = {"depth:k_sort_tile_hist", "depth:k_sort_col_scan", "depth:k_sort_scatter"};
     static const char* const N_TILES[3] = {"tiles:k_sort_tile_hist", "tiles:k_sort_col_scan", "tiles:k_sort_scatter"};
-    const char* const* names = depth ? N_DEPTH : N_TILES;
-    if (out_keys) *out_keys = keys;
-    if (out_vals) *out_vals = vals;
+    const char* const* names = job.kind == SORT_DEPTH ? N_DEPTH : N_TILES;  // labels of the per-kernel timers
+    const uint32_t n = job.n;
+    const int begin_bit = job.begin_bit, end_bit = job.end_bit, digit_bits = job.digit_bits;
+    const bool key16 = job.key16, first_tile_hist_ready = job.first_tile_hist_ready;
+    *res = SortResult{job.keys, job.vals, job.aux};
     if (n == 0) return WS_OK;
     if (n > sc.cap) return fail(WS_ERR_INVALID, "sort: n exceeds the scratch capacity");
-    if (aux && (ranges || !aux_alt)) return fail(WS_ERR_INVALID, "sort: companion values need a scratch partner and no range recording");
+    if (job.aux && (job.ranges || !job.aux_alt)) return fail(WS_ERR_INVALID, "sort: companion values need a scratch partner and no range recording");
     if (key16 && end_bit > 16) return fail(WS_ERR_INVALID, "sort: 16-bit keys with more than 16 key bits");
-    if (key16 && aux) return fail(WS_ERR_INVALID, "sort: companion values travel with 32-bit keys only");
+    if (key16 && job.aux) return fail(WS_ERR_INVALID, "sort: companion values travel with 32-bit keys only");
     if (digit_bits < 6 || digit_bits > 9) return fail(WS_ERR_INVALID, "sort: digit width must be 6, 7, 8 or (depth sort) 9 bits");
-    if (digit_bits == 9 && (key16 || ranges || first_tile_hist_ready || sc.rows < 512u || sc.hist_pitch < 512u))
+    if (digit_bits == 9 && (key16 || job.ranges || first_tile_hist_ready || sc.rows < 512u || sc.hist_pitch < 512u))
         return fail(WS_ERR_INVALID, "sort: 9-bit digits belong to the depth sort (32-bit keys, a scratch with 512 count rows)");
     if (begin_bit < 0 || end_bit > 32 || begin_bit >= end_bit)
         return fail(WS_ERR_INVALID, "sort: bit range must be non-empty and within [0,32]");
-    if ((reinterpret_cast<uintptr_t>(keys) & 15u) != 0) return fail(WS_ERR_INVALID, "sort: keys must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(job.keys) & 15u) != 0) return fail(WS_ERR_INVALID, "sort: keys must be 16-byte aligned");
     const int npass = (end_bit - begin_bit + digit_bits - 1) / digit_bits;
     if (npass > 4) return fail(WS_ERR_INVALID, "sort: more than four digit passes");
-    if (skip_top && (npass != 4 || begin_bit != 0 || (digit_bits != RADIX_BITS && digit_bits != 9) || first_tile_hist_ready || ranges))
+    if (job.skip_top && (npass != 4 || begin_bit != 0 || (digit_bits != RADIX_BITS && digit_bits != 9) || first_tile_hist_ready || job.ranges))
         return fail(WS_ERR_INVALID, "sort: the top-byte skip belongs to the four-pass depth sort");
 
-    uint32_t* kin = keys;
-    uint32_t* vin = vals;
-    uint32_t* kout = sc.keys_alt;
-    uint32_t* vout = sc.vals_alt;
-    int rc;
     const bool big = sort_tile_size(n) == SORT_TILE;
-#define WS_RUN_SCAN(KPT_, BITS_)                                                                                       \
-    rc = key16 ? run_passes_scan<KPT_, BITS_, true>(sc, kin, vin, kout, vout, aux, aux_alt, d_count, n, begin_bit, npass,   \
-                                                    implicit_iota, first_tile_hist_ready, stream, &kin, &vin, km, names,   \
-                                                    ranges, nranges, skip_top, out_keys_skipped, out_vals_skipped)         \
-               : run_passes_scan<KPT_, BITS_, false>(sc, kin, vin, kout, vout, aux, aux_alt, d_count, n, begin_bit, npass,  \
-                                                     implicit_iota, first_tile_hist_ready, stream, &kin, &vin, km, names,  \
-                                                     ranges, nranges, skip_top, out_keys_skipped, out_vals_skipped)
-    if (digit_bits == 9) {  // (never key16: checked above)
-        // (1024-pair tiles only up to SORT_SMALL_MAX keys: the count rows' pitch is sized for that, alloc_sort_scratch)
-        const bool big9 = (kpt9 == SORT_KPT_SMALL && n <= SORT_SMALL_MAX) ? false : (kpt9 ? true : big);
-        if (big9) rc = run_passes_scan<SORT_KPT, 9, false>(sc, kin, vin, kout, vout, aux, aux_alt, d_count, n, begin_bit, npass, implicit_iota,
-                                                          false, stream, &kin, &vin, km, names, nullptr, 0u, skip_top, out_keys_skipped,
-                                                          out_vals_skipped);
-        else rc = run_passes_scan<SORT_KPT_SMALL, 9, false>(sc, kin, vin, kout, vout, aux, aux_alt, d_count, n, begin_bit, npass,
-                                                            implicit_iota, false, stream, &kin, &vin, km, names, nullptr, 0u, skip_top,
-                                                            out_keys_skipped, out_vals_skipped);
-    } else if (digit_bits == 8) {
-        if (big) WS_RUN_SCAN(SORT_KPT, 8); else WS_RUN_SCAN(SORT_KPT_SMALL, 8);
-    } else if (digit_bits == 7) {
-        if (big) WS_RUN_SCAN(SORT_KPT, 7); else WS_RUN_SCAN(SORT_KPT_SMALL, 7);
-    } else {
-        if (big) WS_RUN_SCAN(SORT_KPT, 6); else WS_RUN_SCAN(SORT_KPT_SMALL, 6);
+    // (9-bit digits, 1024-pair tiles only up to SORT_SMALL_MAX keys: the count rows' pitch is sized for that, alloc_sort_scratch)
+    const bool big9 = (job.kpt9 == SORT_KPT_SMALL && n <= SORT_SMALL_MAX) ? false : (job.kpt9 ? true : big);
+    switch (digit_bits) {
+        case 9: return run_scan<9>(big9, sc, job, npass, stream, km, names, res);
+        case 8: return run_scan<8>(big, sc, job, npass, stream, km, names, res);
+        case 7: return run_scan<7>(big, sc, job, npass, stream, km, names, res);
+        default: return run_scan<6>(big, sc, job, npass, stream, km, names, res);
     }
-#undef WS_RUN_SCAN
-    if (rc) return rc;
-    if (out_keys) *out_keys = kin;
-    if (out_vals) *out_vals = vin;
-    return WS_OK;
 }
 
 }  // namespace ws

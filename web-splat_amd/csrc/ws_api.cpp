@@ -112,6 +112,16 @@ struct ws_sorter {
     hipStream_t last_stream = nullptr;
 };
 
+// Where the prepared frame's arrays are: one value, so that the frame graph's capture and replay cannot forget a member.
+struct FrameArrays {
+    // the depth sort's result: vals = the draw-ordered store indices, aux = their footprint words; the *_skipped members are
+    // where they are when the sort's last pass had nothing to do (FrameCounters::depth_skip_top, decided on the device per
+    // frame), nullptr: this frame's sort cannot skip
+    SortResult depth;
+    uint32_t* entries = nullptr;     // the tile-sorted entry values (store indices)
+    bool blend_order_valid = false;  // the frame wrote ws_renderer::blend_order (it ran k_blend_order)
+};
+
 struct ws_renderer {
     ws_context* ctx = nullptr;
     ws_color_format format = WS_FORMAT_RGBA32_FLOAT;
@@ -140,7 +150,6 @@ struct ws_renderer {
     FrameCounters* counters = nullptr;  // = &zero->counters
     SortScratch sort_depth, sort_tiles;
     FatSortScratch fat;              // fat-tile one-sweep depth sort (WS_DEPTH_SORT=onesweep | coop): chunk-count rows
-    uint32_t* fp_sorted = nullptr;  // where the last frame's draw-ordered footprint words are
     int footprint_mode = FP_RECT_PACKED;  // of the current scratch (chosen by the viewport and WS_FOOTPRINT)
     uint32_t epoch = 0;
     uint32_t* sticky = nullptr;      // two device words that survive the per-frame memset (ws_renderer_errors): [0] error bits
@@ -170,23 +179,15 @@ struct ws_renderer {
         uint64_t generation = 0;   // scratch generation the graph was captured for
         uint32_t next = 0;
         bool valid = false;
-        uint32_t *sorted_idx = nullptr, *sorted_keys = nullptr, *fp_sorted = nullptr, *entries_sorted = nullptr;
-        uint32_t *sorted_idx_skipped = nullptr, *sorted_keys_skipped = nullptr;
+        FrameArrays arrays;              // of the captured frame
         int order_mode = 0;              // decide_blend_order() of the captured frame: a change re-captures
-        bool blend_order_valid = false;  // the captured frame contains k_blend_order
     } fg;
     uint64_t scratch_generation = 0;
 
     // last prepared frame
     bool prepared = false;
     const ws_pointcloud* prepared_pc = nullptr;
-    uint32_t* sorted_idx = nullptr;
-    uint32_t* sorted_keys = nullptr;
-    // where the sorted arrays are when the depth sort's last pass had nothing to do (FrameCounters::depth_skip_top, decided on
-    // the device per frame); nullptr: this frame's sort cannot skip
-    uint32_t* sorted_idx_skipped = nullptr;
-    uint32_t* sorted_keys_skipped = nullptr;
-    uint32_t* entries_sorted = nullptr;
+    FrameArrays arrays;
     hipStream_t last_stream = nullptr;
 
     int blend_mode = WS_BLEND_FAST;  // ws_renderer_set_blend_mode
@@ -200,7 +201,6 @@ struct ws_renderer {
     uint32_t* debug_consumed = nullptr;  // [tiles], capture mode only
     uint32_t* debug_walked = nullptr;    // [tiles][17], capture mode only
     uint4* blend_order = nullptr;        // [blend_order_blocks]: the blend's tiles, longest list first (k_blend_order)
-    bool blend_order_valid = false;      // the last prepared frame wrote it
     int order_mode_this_frame = 0;       // decide_blend_order() of the prepare() in progress
     int depth_bits_this_frame = 8;       // digit width the last enqueued depth sort used (8 | 9)
     int graph_depth_bits = 0;            // != 0 while a frame graph is captured / valid: its depth sort's digit width
@@ -300,7 +300,7 @@ static void renderer_free_scratch(ws_renderer* r) {
     dfree(r->removal_base);
     r->removal_base_px = 0;
     dfree(r->blend_order);
-    r->blend_order_valid = false;
+    r->arrays.blend_order_valid = false;
     if (r->zero) (void)hipFree(r->zero);
     r->zero = nullptr;
     r->tile_ranges = nullptr;
@@ -1004,7 +1004,7 @@ int ws_renderer_enable_capture(ws_renderer* r, int enable) {
 int ws_renderer_download_blend_order(ws_renderer* r, uint32_t capacity_blocks, uint32_t* order4, uint32_t* num_blocks) {
     if (!r || !num_blocks) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_order: null argument");
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_blend_order: no prepared frame");
-    const uint32_t nb = r->blend_order_valid ? blend_order_blocks(r->tiles_x, r->tiles_y) : 0u;
+    const uint32_t nb = r->arrays.blend_order_valid ? blend_order_blocks(r->tiles_x, r->tiles_y) : 0u;
     *num_blocks = nb;
     if (!order4 || nb == 0) return WS_OK;
     if (capacity_blocks < nb) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_order: capacity smaller than the block count");
@@ -1131,20 +1131,20 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
                                         // (the single-launch form needs all its workgroups resident at once: never beside other
                                         // frames' kernels -- a slot of a view batch falls back to the one-sweep form)
                                         r->ctx->depth_sort_mode == DS_COOP && !r->throughput_mode, r->epoch, r->ctx->num_cus, stream,
-                                        km)))
+                                        km, &r->arrays.depth)))
             return rc;
-        r->sorted_idx = r->vals_a;
-        r->sorted_keys = r->keys_a;
-        r->fp_sorted = r->fpw_a;
-        r->sorted_idx_skipped = r->sorted_keys_skipped = nullptr;
     } else {
         // Four 8-bit passes over the 32-bit keys (gpu_rs.rs:865-884), of which the last one leaves at once on frames whose keys
         // span less than 2^24 (decided on the device from the key range the sort's first histogram kernel leaves: ws_internal.h
         // depth_range_decide; WS_DEPTH_SKIP_TOP=0 switches it off).  (K1c's keys are NOT confined to 24 bits: preprocess_compressed.wgsl:325 scales
         // clip z, which is below znear for the nearest splats.)
-        uint32_t *sk = nullptr, *sv = nullptr, *sk2 = nullptr, *sv2 = nullptr;
-        const int key_bits = 32;
-        FrameCounters* skip_top = r->ctx->depth_skip_top ? r->counters : nullptr;
+        SortJob job;
+        job.kind = SORT_DEPTH;
+        job.keys = r->keys_a, job.vals = r->vals_a, job.d_count = &r->counters->num_visible, job.n = pc->num_points;
+        job.implicit_iota = true;
+        job.aux = r->fpw_a, job.aux_alt = r->fpw_b;
+        job.skip_top = r->ctx->depth_skip_top ? r->counters : nullptr;
+        job.kpt9 = r->ctx->depth_tile_kpt ? r->ctx->depth_tile_kpt : 8;
         // Digit width (round 6): three 8-bit passes when the renderer's previous frame says its keys span < 2^24 (the cheapest
         // form), three 9-bit passes when it says they do not (c5: every frame; hd1m: the views that see the cloud end on) --
         // the answer of the last frame whose blend has started, read from pinned memory without a sync.  Either width yields
@@ -1152,20 +1152,13 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         int dbits = r->ctx->depth_digit_bits;
         if (dbits != 8 && dbits != 9) {
             dbits = WS_DEPTH_DIGIT_BITS_DEFAULT;
-            if (WS_DEPTH_DIGIT_BITS_ADAPTIVE && skip_top && r->demand_mailbox && r->graph_depth_bits == 0)
+            if (WS_DEPTH_DIGIT_BITS_ADAPTIVE && job.skip_top && r->demand_mailbox && r->graph_depth_bits == 0)
                 dbits = *reinterpret_cast<volatile const uint32_t*>(r->demand_mailbox + 2) == 2u ? 9 : 8;
         }
         if (r->graph_depth_bits) dbits = r->graph_depth_bits;  // (a captured frame graph keeps the width it was captured with)
         r->depth_bits_this_frame = dbits;
-        if ((rc = launch_sort_pairs(r->sort_depth, r->keys_a, r->vals_a, &r->counters->num_visible, pc->num_points, 0, key_bits,
-                                    true, false, stream, &sk, &sv, km, "depth:", nullptr, 0, dbits, false, r->fpw_a,
-                                    r->fpw_b, skip_top, &sk2, &sv2, r->ctx->depth_tile_kpt ? r->ctx->depth_tile_kpt : 8)))
-            return rc;
-        r->sorted_idx = sv;
-        r->sorted_keys = sk;
-        r->fp_sorted = (sv == r->vals_a) ? r->fpw_a : r->fpw_b;  // where the payload went
-        r->sorted_idx_skipped = skip_top ? sv2 : nullptr;
-        r->sorted_keys_skipped = skip_top ? sk2 : nullptr;
+        job.digit_bits = dbits;
+        if ((rc = launch_sort_pairs(r->sort_depth, job, stream, km, &r->arrays.depth))) return rc;
     }
     if (r->timers) WS_HIP(hipEventRecord(r->ev[2], stream));
     if (cut == 2) {  // analysis only (WS_DEBUG_CUT): the image is NOT produced
@@ -1177,10 +1170,10 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
 
     // tile binning
     BinBuffers bb;
-    bb.sorted_idx = r->sorted_idx;
-    bb.fp_sorted = r->fp_sorted;
-    bb.sorted_idx_alt = r->sorted_idx_skipped;
-    bb.fp_sorted_alt = r->sorted_idx_skipped ? ((r->sorted_idx_skipped == r->vals_a) ? r->fpw_a : r->fpw_b) : nullptr;
+    bb.sorted_idx = r->arrays.depth.vals;
+    bb.fp_sorted = r->arrays.depth.aux;
+    bb.sorted_idx_alt = r->arrays.depth.vals_skipped;
+    bb.fp_sorted_alt = r->arrays.depth.aux_skipped;
     bb.footprint_mode = r->footprint_mode;
     bb.splats = r->splats;
     bb.vw = kp.cam.viewport[0];
@@ -1238,17 +1231,21 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         r->last_stream = stream;
         return WS_OK;
     }
-    uint32_t *ek = nullptr, *evv = nullptr;
+    SortResult tiles;
     if (wide_sort) {
         if ((rc = launch_tile_sort_wide(r->sort_tiles, r->ekeys_a, r->evals_a, &r->counters->num_entries, r->entry_cap,
-                                        wide_bits, stream, km, r->tile_ranges, ntiles)))
+                                        wide_bits, stream, km, r->tile_ranges, ntiles, &tiles)))
             return rc;
-        evv = r->sort_tiles.vals_alt;
-    } else if ((rc = launch_sort_pairs(r->sort_tiles, r->ekeys_a, r->evals_a, &r->counters->num_entries, r->entry_cap, 0,
-                                       tile_bits, false, fused_hist, stream, &ek, &evv, km,
-                                       "tiles:", r->tile_ranges, ntiles, digit_bits, key16)))
-        return rc;
-    r->entries_sorted = evv;  // the last pass wrote the per-tile ranges instead of the sorted tile ids
+    } else {
+        SortJob job;
+        job.kind = SORT_TILE_IDS;
+        job.keys = r->ekeys_a, job.vals = r->evals_a, job.d_count = &r->counters->num_entries, job.n = r->entry_cap;
+        job.end_bit = tile_bits, job.digit_bits = digit_bits;
+        job.first_tile_hist_ready = fused_hist, job.key16 = key16;
+        job.ranges = r->tile_ranges, job.nranges = ntiles;
+        if ((rc = launch_sort_pairs(r->sort_tiles, job, stream, km, &tiles))) return rc;
+    }
+    r->arrays.entries = tiles.vals;  // the last pass wrote the per-tile ranges instead of the sorted tile ids
     // the compositing workgroups in longest-list-first order (one tile per workgroup at the 32x32 tile: every frame up to
     // 1080p-class tile counts; 4K-class frames composite several tiles per workgroup and keep the image order)
     // Longest first is what a frame drawn ALONE wants (blend -12 % hd1m, -18 % c3 / c2: no tail of idle slots).  With several
@@ -1259,14 +1256,14 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
     // whose prepare() calls change stream from call to call (frames in flight on a ring of streams do; a renderer that draws
     // one frame at a time stays on its stream: after four consecutive calls on one stream it orders its tiles).
     // (the decision itself is taken once per prepare(), OUTSIDE any captured region: ws_renderer_prepare -> decide_blend_order)
-    r->blend_order_valid = false;
+    r->arrays.blend_order_valid = false;
     const int order_mode = r->order_mode_this_frame;
     // (up to 4096 tiles = eight rounds of workgroups on this chip: beyond that the tail is a small share of the kernel and the
     // one-workgroup ordering kernel, 3 us at 2040 tiles and 7.6 us at 8160, costs what it saves -- c5, 4K: measured)
     if (order_mode && r->ctx->tile_qw == 4 && r->ctx->tile_qh == 4 && ntiles <= 4096u && r->ctx->blend_tpw_log2 <= 0) {
         if ((rc = launch_blend_order(r->tile_ranges, r->counters, r->tiles_x, r->tiles_y, r->blend_order, order_mode, stream))) return rc;
         km_mark(km, "k_blend_order");
-        r->blend_order_valid = true;
+        r->arrays.blend_order_valid = true;
     }
     if (r->timers) {
         WS_HIP(hipEventRecord(r->ev[3], stream));
@@ -1434,14 +1431,8 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         }
         g.pc = pc;
         g.generation = r->scratch_generation;
-        g.sorted_idx = r->sorted_idx;
-        g.sorted_keys = r->sorted_keys;
-        g.fp_sorted = r->fp_sorted;
-        g.entries_sorted = r->entries_sorted;
-        g.sorted_idx_skipped = r->sorted_idx_skipped;
-        g.sorted_keys_skipped = r->sorted_keys_skipped;
+        g.arrays = r->arrays;  // (with: did the captured frame run k_blend_order?)
         g.order_mode = r->order_mode_this_frame;
-        g.blend_order_valid = r->blend_order_valid;  // did the captured frame run k_blend_order?
         g.valid = true;
     }
     const int slot = (int)(g.next++ % ws_renderer::GRAPH_RING);
@@ -1456,13 +1447,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     WS_HIP(hipGraphLaunch(g.exec[slot], stream));
     WS_HIP(hipEventRecord(g.done[slot], stream));
     g.used[slot] = true;
-    r->sorted_idx = g.sorted_idx;
-    r->sorted_keys = g.sorted_keys;
-    r->fp_sorted = g.fp_sorted;
-    r->entries_sorted = g.entries_sorted;
-    r->sorted_idx_skipped = g.sorted_idx_skipped;
-    r->sorted_keys_skipped = g.sorted_keys_skipped;
-    r->blend_order_valid = g.blend_order_valid;  // what THIS graph's frames write, whatever a launch-by-launch frame left behind
+    r->arrays = g.arrays;  // what THIS graph's frames write, whatever a launch-by-launch frame left behind
     r->prepared = true;
     r->prepared_depth = r->k1_depths != nullptr;
     r->prepared_pc = pc;
@@ -1565,11 +1550,11 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     fr.target_precision = r->blend_mode == WS_BLEND_TARGET_PRECISION, fr.exact_mode = r->blend_mode == WS_BLEND_FAST_EXACT_CUT;
     fr.variant = r->ctx->blend_variant, fr.capture = r->capture, fr.timing = r->blend_timing;
     fr.split_wanted = r->ctx->blend_split >= 0 ? r->ctx->blend_split != 0 : (r->tiles_x * r->tiles_y < 2u * (uint32_t)r->ctx->num_cus);
-    fr.order_valid = r->blend_order_valid, fr.qw = r->ctx->tile_qw, fr.qh = r->ctx->tile_qh;
+    fr.order_valid = r->arrays.blend_order_valid, fr.qw = r->ctx->tile_qw, fr.qh = r->ctx->tile_qh;
     const BlendFrameChoice form = blend_frame_choice(fr);
     BlendParams bp;
     bp.splats = r->splats;
-    bp.entry_vals = r->entries_sorted;
+    bp.entry_vals = r->arrays.entries;
     bp.tile_ranges = r->tile_ranges;
     bp.width = r->vw;
     bp.height = r->vh;
@@ -1609,8 +1594,7 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
         if (r->debug_timing_tiles != nt) {
             WS_HIP(hipStreamSynchronize(stream));
             dfree(r->debug_timing);
-            int rc_ = dmalloc(&r->debug_timing, (size_t)nt * 16 * BLEND_TIMING_WORDS);
-            if (rc_) return rc_;
+            WS_TRY(dmalloc(&r->debug_timing, (size_t)nt * 16 * BLEND_TIMING_WORDS));
             r->debug_timing_tiles = nt;
         }
         WS_HIP(hipMemsetAsync(r->debug_timing, 0, (size_t)nt * 16 * BLEND_TIMING_WORDS * sizeof(uint32_t), stream));
@@ -1754,7 +1738,7 @@ int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out) {
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_frame_stats: no prepared frame");
     WS_HIP(hipStreamSynchronize(r->last_stream));
     FrameCounters fc;
-    { int rc_ = copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream); if (rc_) return rc_; }
+    WS_TRY(copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream));
     out->num_visible = fc.num_visible;
     out->num_tile_entries = fc.num_entries;
     out->tile_entries_capacity = r->entry_cap;
@@ -1764,10 +1748,10 @@ int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out) {
 
 // Number of tile LISTS of the last prepared frame and the shift from blend tiles to binning tiles: the device decides per
 // frame (bin_shift_decide, k_bin_prefix) whether a list serves one blend tile or a 2x2 block of them.
-static int frame_lists(ws_renderer* r, uint32_t* shift, uint32_t* lists_x, uint32_t* lists_y) {
+static int frame_list_counts(ws_renderer* r, uint32_t* shift, uint32_t* lists_x, uint32_t* lists_y) {
     WS_HIP(hipStreamSynchronize(r->last_stream));
     FrameCounters fc;
-    { int rc_ = copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream); if (rc_) return rc_; }
+    WS_TRY(copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream));
     const uint32_t s = fc.bin_shift;
     *shift = s;
     *lists_x = (r->tiles_x + s) >> s;
@@ -1779,22 +1763,34 @@ int ws_renderer_binning_tile(ws_renderer* r, uint32_t* width, uint32_t* height) 
     if (!r || !width || !height) return fail(WS_ERR_INVALID, "ws_renderer_binning_tile: null argument");
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_binning_tile: no prepared frame");
     uint32_t s, lx, ly;
-    { int rc_ = frame_lists(r, &s, &lx, &ly); if (rc_) return rc_; }
+    WS_TRY(frame_list_counts(r, &s, &lx, &ly));
     *width = (QUAD * r->ctx->tile_qw) << s;
     *height = (QUAD * r->ctx->tile_qh) << s;
+    return WS_OK;
+}
+
+// Which depth-sorted arrays hold the prepared frame's order: where the sort's last pass left them, or -- decided on the device,
+// read back here only when the frame could skip -- where pass 2 did (*skipped).
+static int frame_depth_order(ws_renderer* r, const uint32_t** keys, const uint32_t** vals, bool* skipped) {
+    const SortResult& d = r->arrays.depth;
+    uint32_t skip = 0;
+    if (d.vals_skipped) {
+        WS_HIP(hipStreamSynchronize(r->last_stream));
+        WS_TRY(copy_d2h(&skip, &r->counters->depth_skip_top, sizeof skip, r->last_stream));
+    }
+    *keys = skip ? d.keys_skipped : d.keys;
+    *vals = skip ? d.vals_skipped : d.vals;
+    *skipped = skip != 0;
     return WS_OK;
 }
 
 int ws_renderer_depth_sort_passes(ws_renderer* r, uint32_t* passes) {
     if (!r || !passes) return fail(WS_ERR_INVALID, "ws_renderer_depth_sort_passes: null argument");
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_depth_sort_passes: no prepared frame");
-    *passes = 4u;
-    if (r->sorted_idx_skipped) {
-        WS_HIP(hipStreamSynchronize(r->last_stream));
-        uint32_t skipped = 0;
-        { int rc_ = copy_d2h(&skipped, &r->counters->depth_skip_top, sizeof skipped, r->last_stream); if (rc_) return rc_; }
-        if (skipped) *passes = 3u;
-    }
+    const uint32_t *keys, *vals;
+    bool skipped;
+    WS_TRY(frame_depth_order(r, &keys, &vals, &skipped));
+    *passes = skipped ? 3u : 4u;
     return WS_OK;
 }
 
@@ -1814,10 +1810,10 @@ int ws_renderer_errors(ws_renderer* r, uint32_t* bits, uint32_t* entries_needed,
     // frames left must not disappear behind them.  Only the per-frame counter needs a prepared frame.
     WS_HIP(hipStreamSynchronize(r->last_stream));
     uint32_t both[2] = {0u, 0u};
-    { int rc_ = copy_d2h(both, r->sticky, sizeof(both), r->last_stream); if (rc_) return rc_; }
+    WS_TRY(copy_d2h(both, r->sticky, sizeof(both), r->last_stream));
     *bits = both[0];
     if (both[1] > r->needed_seen) r->needed_seen = both[1];  // an overflowed frame's demand: the next prepare() allocates it
-    if (entries_needed && r->prepared && r->counters) { int rc_ = copy_d2h(entries_needed, &r->counters->entries_needed, sizeof(uint32_t), r->last_stream); if (rc_) return rc_; }
+    if (entries_needed && r->prepared && r->counters) WS_TRY(copy_d2h(entries_needed, &r->counters->entries_needed, sizeof(uint32_t), r->last_stream));
     if (reset && *bits) {
         WS_HIP(hipMemsetAsync(r->sticky, 0, sizeof(uint32_t), r->last_stream));
         WS_HIP(hipStreamSynchronize(r->last_stream));
@@ -1869,7 +1865,7 @@ int ws_renderer_download_tile_stats(ws_renderer* r, uint32_t capacity, uint32_t*
     if (!r) return fail(WS_ERR_INVALID, "ws_renderer_download_tile_stats: null renderer");
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_tile_stats: no prepared frame");
     uint32_t bs, lx, ly;
-    { int rc_ = frame_lists(r, &bs, &lx, &ly); if (rc_) return rc_; }
+    WS_TRY(frame_list_counts(r, &bs, &lx, &ly));
     const uint32_t nt = lx * ly;  // one entry per LIST (= per binning tile; capture keeps them at the blend tile)
     if (num_tiles) *num_tiles = nt;
     if (!list_len && !consumed) return WS_OK;
@@ -1879,10 +1875,10 @@ int ws_renderer_download_tile_stats(ws_renderer* r, uint32_t capacity, uint32_t*
     WS_HIP(hipStreamSynchronize(r->last_stream));
     if (list_len) {
         std::vector<uint2> rg(nt);
-        { int rc_ = copy_d2h(rg.data(), r->tile_ranges, (size_t)nt * sizeof(uint2), r->last_stream); if (rc_) return rc_; }
+        WS_TRY(copy_d2h(rg.data(), r->tile_ranges, (size_t)nt * sizeof(uint2), r->last_stream));
         for (uint32_t i = 0; i < nt; ++i) list_len[i] = rg[i].y ? rg[i].y - (0xFFFFFFFFu - rg[i].x) : 0u;
     }
-    if (consumed) { int rc_ = copy_d2h(consumed, r->debug_consumed, (size_t)nt * 4, r->last_stream); if (rc_) return rc_; }
+    if (consumed) WS_TRY(copy_d2h(consumed, r->debug_consumed, (size_t)nt * 4, r->last_stream));
     return WS_OK;
 }
 
@@ -1893,7 +1889,7 @@ int ws_renderer_download_wave_stats(ws_renderer* r, uint32_t tile_capacity, uint
     const uint32_t nt = r->tiles_x * r->tiles_y;
     if (tile_capacity < nt) return fail(WS_ERR_INVALID, "ws_renderer_download_wave_stats: capacity smaller than the tile count");
     WS_HIP(hipStreamSynchronize(r->last_stream));
-    { int rc_ = copy_d2h(walked, r->debug_walked, (size_t)nt * 17 * sizeof(uint32_t), r->last_stream); if (rc_) return rc_; }
+    WS_TRY(copy_d2h(walked, r->debug_walked, (size_t)nt * 17 * sizeof(uint32_t), r->last_stream));
     return WS_OK;
 }
 
@@ -1904,7 +1900,7 @@ int ws_renderer_download_tile_lists(ws_renderer* r, uint32_t tile_capacity, uint
     int rc = ws_renderer_frame_stats(r, &st);
     if (rc) return rc;
     uint32_t bs, lx, ly;
-    { int rc_ = frame_lists(r, &bs, &lx, &ly); if (rc_) return rc_; }
+    WS_TRY(frame_list_counts(r, &bs, &lx, &ly));
     const uint32_t nt = lx * ly;  // one range per LIST (= per binning tile, ws_renderer_binning_tile)
     if (num_entries) *num_entries = st.num_tile_entries;
     if ((begin || end) && tile_capacity < nt) return fail(WS_ERR_INVALID, "ws_renderer_download_tile_lists: tile capacity too small");
@@ -1912,14 +1908,14 @@ int ws_renderer_download_tile_lists(ws_renderer* r, uint32_t tile_capacity, uint
         return fail(WS_ERR_INVALID, "ws_renderer_download_tile_lists: entry capacity too small");
     if (begin || end) {
         std::vector<uint2> rg(nt);
-        { int rc_ = copy_d2h(rg.data(), r->tile_ranges, (size_t)nt * sizeof(uint2), r->last_stream); if (rc_) return rc_; }
+        WS_TRY(copy_d2h(rg.data(), r->tile_ranges, (size_t)nt * sizeof(uint2), r->last_stream));
         for (uint32_t i = 0; i < nt; ++i) {
             if (begin) begin[i] = rg[i].y ? 0xFFFFFFFFu - rg[i].x : 0u;
             if (end) end[i] = rg[i].y;
         }
     }
     if (entries && st.num_tile_entries)
-        { int rc_ = copy_d2h(entries, r->entries_sorted, (size_t)st.num_tile_entries * 4, r->last_stream); if (rc_) return rc_; }
+        WS_TRY(copy_d2h(entries, r->arrays.entries, (size_t)st.num_tile_entries * 4, r->last_stream));
     return WS_OK;
 }
 
@@ -1936,36 +1932,26 @@ int ws_renderer_download_frame(ws_renderer* r, uint32_t capacity, void* splats, 
     if (src_index && !r->capture && !r->prepared_contrib)
         return fail(WS_ERR_STATE, "ws_renderer_download_frame: src_index needs ws_renderer_enable_capture before prepare");
     if (v == 0) return WS_OK;
-    // where the frame's depth sort left its result: behind its last pass, or -- decided on the device -- behind pass 2
-    const uint32_t* sorted_idx = r->sorted_idx;
-    const uint32_t* sorted_keys = r->sorted_keys;
-    if (r->sorted_idx_skipped) {
-        uint32_t skipped = 0;
-        { int rc_ = copy_d2h(&skipped, &r->counters->depth_skip_top, sizeof skipped, r->last_stream); if (rc_) return rc_; }
-        if (skipped) {
-            sorted_idx = r->sorted_idx_skipped;
-            sorted_keys = r->sorted_keys_skipped;
-        }
-    }
+    const uint32_t *sorted_keys, *sorted_idx;
+    bool skipped;
+    WS_TRY(frame_depth_order(r, &sorted_keys, &sorted_idx, &skipped));
     if (splats) {  // the caller gets the reference's 20-B records whatever stride the device keeps them at
         if (SPLAT_STRIDE == 20u) {
-            int rc_ = copy_d2h(splats, r->splats, (size_t)v * 20, r->last_stream);
-            if (rc_) return rc_;
+            WS_TRY(copy_d2h(splats, r->splats, (size_t)v * 20, r->last_stream));
         } else {
             std::vector<uint8_t> padded((size_t)v * SPLAT_STRIDE);
-            int rc_ = copy_d2h(padded.data(), r->splats, padded.size(), r->last_stream);
-            if (rc_) return rc_;
+            WS_TRY(copy_d2h(padded.data(), r->splats, padded.size(), r->last_stream));
             for (size_t i = 0; i < (size_t)v; ++i) std::memcpy(static_cast<uint8_t*>(splats) + i * 20, padded.data() + i * SPLAT_STRIDE, 20);
         }
     }
-    if (src_index) { int rc_ = copy_d2h(src_index, r->src_index, (size_t)v * 4, r->last_stream); if (rc_) return rc_; }
-    if (sorted) { int rc_ = copy_d2h(sorted, sorted_idx, (size_t)v * 4, r->last_stream); if (rc_) return rc_; }
+    if (src_index) WS_TRY(copy_d2h(src_index, r->src_index, (size_t)v * 4, r->last_stream));
+    if (sorted) WS_TRY(copy_d2h(sorted, sorted_idx, (size_t)v * 4, r->last_stream));
     if (keys) {
         // the sort permutes the keys in place; un-permute them with the sorted indices so that the caller
         // gets keys in STORE order (what preprocess wrote)
         std::vector<uint32_t> ks(v), idx(v);
-        { int rc_ = copy_d2h(ks.data(), sorted_keys, (size_t)v * 4, r->last_stream); if (rc_) return rc_; }
-        { int rc_ = copy_d2h(idx.data(), sorted_idx, (size_t)v * 4, r->last_stream); if (rc_) return rc_; }
+        WS_TRY(copy_d2h(ks.data(), sorted_keys, (size_t)v * 4, r->last_stream));
+        WS_TRY(copy_d2h(idx.data(), sorted_idx, (size_t)v * 4, r->last_stream));
         for (uint32_t i = 0; i < v; ++i)
             if (idx[i] < v) keys[idx[i]] = ks[i];
     }
@@ -2028,10 +2014,11 @@ int ws_sorter_sort(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, const ui
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     s->folded = false;  // (the memset below clears what a ws_sorter_sort_depth decided)
     WS_HIP(hipMemsetAsync(s->zero, 0, sizeof(SorterZero), stream));
-    uint32_t *ok = nullptr, *ov = nullptr;
-    int rc = launch_sort_pairs(s->sc, d_keys, d_payload, d_count, n, 0, 32, false, false, stream, &ok, &ov);
-    if (rc) return rc;
-    if (ok != d_keys) return fail(WS_ERR_STATE, "ws_sorter_sort: internal ping-pong parity error");
+    SortJob job;
+    job.keys = d_keys, job.vals = d_payload, job.d_count = d_count, job.n = n;
+    SortResult res;
+    WS_TRY(launch_sort_pairs(s->sc, job, stream, nullptr, &res));
+    if (res.keys != d_keys) return fail(WS_ERR_STATE, "ws_sorter_sort: internal ping-pong parity error");
     return WS_OK;
 }
 
@@ -2061,22 +2048,25 @@ int ws_sorter_sort_depth(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, ui
     FrameCounters* skip_top = (s->ctx->depth_skip_top && !fat) ? &s->zero->counters : nullptr;
     s->folded = skip_top != nullptr;
     if (n == 0) return WS_OK;
+    SortResult res;
     if (fat)
         return launch_depth_sort_fat(s->fat, d_keys, d_payload, d_aux, d_count, n, false, s->ctx->depth_sort_mode == DS_COOP,
-                                     s->epoch, s->ctx->num_cus, stream, nullptr);
-    uint32_t *ok = nullptr, *ov = nullptr, *sk = nullptr, *sv = nullptr;
-    int rc = launch_sort_pairs(s->sc, d_keys, d_payload, d_count, n, 0, 32, false, false, stream, &ok, &ov, nullptr, "depth:",
-                               nullptr, 0, depth_digit_bits(s->ctx), false, d_aux, d_aux ? s->aux_alt : nullptr, skip_top, &sk, &sv,
-                               s->ctx->depth_tile_kpt ? s->ctx->depth_tile_kpt : 8);
-    if (rc) return rc;
-    if (ok != d_keys) return fail(WS_ERR_STATE, "ws_sorter_sort_depth: internal ping-pong parity error");
-    if (skip_top) {  // three passes when the fourth was skipped: the result is in the scratch partners -> back in place
-        if (sk != s->sc.keys_alt || sv != s->sc.vals_alt)
-            return fail(WS_ERR_STATE, "ws_sorter_sort_depth: internal ping-pong parity error (skipped pass)");
-        rc = launch_depth_copy_back(&skip_top->depth_skip_top, d_count, n, sk, sv, d_aux ? s->aux_alt : nullptr, d_keys, d_payload, d_aux,
-                                    stream);
-    }
-    return rc;
+                                     s->epoch, s->ctx->num_cus, stream, nullptr, &res);
+    SortJob job;
+    job.kind = SORT_DEPTH;
+    job.keys = d_keys, job.vals = d_payload, job.d_count = d_count, job.n = n;
+    job.digit_bits = depth_digit_bits(s->ctx);
+    job.aux = d_aux, job.aux_alt = d_aux ? s->aux_alt : nullptr;
+    job.skip_top = skip_top;
+    job.kpt9 = s->ctx->depth_tile_kpt ? s->ctx->depth_tile_kpt : 8;
+    WS_TRY(launch_sort_pairs(s->sc, job, stream, nullptr, &res));
+    if (res.keys != d_keys) return fail(WS_ERR_STATE, "ws_sorter_sort_depth: internal ping-pong parity error");
+    if (!skip_top) return WS_OK;
+    // three passes when the fourth was skipped: the result is in the scratch partners -> back in place
+    if (res.keys_skipped != s->sc.keys_alt || res.vals_skipped != s->sc.vals_alt)
+        return fail(WS_ERR_STATE, "ws_sorter_sort_depth: internal ping-pong parity error (skipped pass)");
+    return launch_depth_copy_back(&skip_top->depth_skip_top, d_count, n, res.keys_skipped, res.vals_skipped, res.aux_skipped, d_keys,
+                                  d_payload, d_aux, stream);
 }
 
 int ws_sorter_depth_range(ws_sorter* s, uint32_t* base, uint32_t* skip, uint32_t* span_class) {
@@ -2088,7 +2078,7 @@ int ws_sorter_depth_range(ws_sorter* s, uint32_t* base, uint32_t* skip, uint32_t
     static_assert(offsetof(FrameCounters, depth_key_base) == offsetof(FrameCounters, depth_skip_top) + 4 &&
                       offsetof(FrameCounters, depth_span_class) == offsetof(FrameCounters, depth_skip_top) + 8,
                   "FrameCounters layout");
-    { int rc_ = copy_d2h(w, &s->zero->counters.depth_skip_top, sizeof w, s->last_stream); if (rc_) return rc_; }
+    WS_TRY(copy_d2h(w, &s->zero->counters.depth_skip_top, sizeof w, s->last_stream));
     *skip = w[0];
     *base = w[1];
     *span_class = w[2];
@@ -2199,7 +2189,7 @@ int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
 static FrameLists frame_lists(const ws_renderer* r) {
     FrameLists f;
     f.splats = r->splats;
-    f.entry_vals = r->entries_sorted;
+    f.entry_vals = r->arrays.entries;
     f.tile_ranges = r->tile_ranges;
     f.src_index = r->src_index;
     f.width = r->vw;
@@ -2363,8 +2353,7 @@ int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_c
             WS_HIP(hipDeviceSynchronize());
             dfree(r->removal_base);
             r->removal_base_px = 0;
-            const int rc_ = dmalloc(&r->removal_base, px);
-            if (rc_) return rc_;
+            WS_TRY(dmalloc(&r->removal_base, px));
             r->removal_base_px = px;
         }
         rp.base = r->removal_base;

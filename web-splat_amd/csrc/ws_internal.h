@@ -59,6 +59,12 @@ int hip_fail(hipError_t e, const char* what);
         hipError_t _e = (expr);                               \
         if (_e != hipSuccess) return ::ws::hip_fail(_e, #expr); \
     } while (0)
+// the same for a call of this library that returns a WS_* code
+#define WS_TRY(expr)             \
+    do {                         \
+        const int rc_ = (expr);  \
+        if (rc_) return rc_;     \
+    } while (0)
 
 // ---- geometry of the rasteriser ----------------------------------------------------------------
 // Binning tiles are QW x QH quadrants of 8x8 pixels (one wave each): 2x2 = the north star's 16x16 tile; 4x2 / 4x4
@@ -332,27 +338,39 @@ struct SortScratch {
     uint32_t* wide_hist = nullptr;    // [wide_bins] totals per bin, written by the wide column scan
 };
 
-// Launch an ascending stable LSD radix sort of (key, value) pairs on `stream`.
-//   d_count == nullptr -> sort n pairs; else the count is read on the device (clamped to n).
-//   begin_bit/end_bit: key bits that participate; digit_bits (6..8): digit width, passes = ceil(bits / digit_bits).
-//   implicit_iota: values of the first pass are the element positions (vals in is not read).
-//   first_tile_hist_ready: the producer of the keys already wrote the first pass's per-tile digit
-//     counts into sc.tile_sums (layout [digit][tiles_cap], tile = sort_tile_size(n) consecutive keys).
-//   ranges != nullptr: the LAST pass does not write the sorted keys; instead ranges[key] (key < nranges, zero on
-//     entry) receives (0xFFFFFFFF - begin, end) of that key's run in the sorted order (see k_sort_scatter).
-// The result lands in (keys, vals) if the pass count is even, else in (scratch.keys_alt, vals_alt);
-// *out_keys / *out_vals receive the final pointers.
-int launch_sort_pairs(const SortScratch& sc, uint32_t* keys, uint32_t* vals, const uint32_t* d_count, uint32_t n,
-                      int begin_bit, int end_bit, bool implicit_iota, bool first_tile_hist_ready, hipStream_t stream,
-                      uint32_t** out_keys, uint32_t** out_vals, KernelMarks* km = nullptr, const char* tag = "", uint2* ranges = nullptr, uint32_t nranges = 0,
-                      int digit_bits = RADIX_BITS, bool key16 = false, uint32_t* aux = nullptr, uint32_t* aux_alt = nullptr,
-                      FrameCounters* skip_top = nullptr, uint32_t** out_keys_skipped = nullptr, uint32_t** out_vals_skipped = nullptr,
-                      int kpt9 = 0);  // kpt9 (9-bit digits only): 0 = the tile size the input size selects, 4 / 8 = keys per thread (A/B)
-//   skip_top (four passes of 8- or 9-bit digits from bit 0 only: the depth sort of a frame): the first histogram kernel leaves the key range, the column scan behind it folds it into
-//     skip_top->depth_skip_top (depth_range_decide); when it is set the three kernels of the LAST pass return at once and the
-//     result is what pass 2 wrote: *out_keys_skipped / *out_vals_skipped (the companion values next to the payload).
-//   aux / aux_alt: a 4-byte companion value per pair travels with the payload; the result lands where
-//     the payload lands (aux for an even pass count, aux_alt for an odd one).
+// One ascending stable LSD radix sort of (key, value) pairs: what is sorted and how.  The defaults are a plain sort of n
+// pairs over all 32 key bits.
+enum SortKind { SORT_TILE_IDS = 0, SORT_DEPTH = 1 };  // which label triple the per-kernel timers get ("tiles:" / "depth:")
+struct SortJob {
+    uint32_t *keys = nullptr, *vals = nullptr;  // (keys: 16-byte aligned)
+    const uint32_t* d_count = nullptr;   // nullptr -> sort n pairs; else the count is read on the device (clamped to n)
+    uint32_t n = 0;
+    // key bits that participate; digit_bits (6..8, the depth sort also 9): digit width, passes = ceil(bits / digit_bits) <= 4
+    int begin_bit = 0, end_bit = 32, digit_bits = RADIX_BITS;
+    int kpt9 = 0;                        // 9-bit digits only: 0 = the tile size the input size selects, 4 / 8 = keys per thread (A/B)
+    bool implicit_iota = false;          // values of the first pass are the element positions (vals in is not read)
+    // the producer of the keys already wrote the first pass's per-tile digit counts into sc.tile_sums (layout
+    // [digit][tiles_cap], tile = sort_tile_size(n) consecutive keys)
+    bool first_tile_hist_ready = false;
+    bool key16 = false;                  // the key arrays hold uint16_t (tile ids, at most 16 key bits)
+    uint32_t *aux = nullptr, *aux_alt = nullptr;  // a 4-byte companion value per pair travels with the payload (aux_alt: its scratch partner)
+    // ranges != nullptr: the LAST pass does not write the sorted keys; instead ranges[key] (key < nranges, zero on entry)
+    // receives (0xFFFFFFFF - begin, end) of that key's run in the sorted order (see k_sort_scatter)
+    uint2* ranges = nullptr;
+    uint32_t nranges = 0;
+    // skip_top (four passes of 8- or 9-bit digits from bit 0 only: the depth sort of a frame): the first histogram kernel
+    // leaves the key range, the column scan behind it folds it into skip_top->depth_skip_top (depth_range_decide); when it is
+    // set the three kernels of the LAST pass return at once and the result is what pass 2 wrote (SortResult::*_skipped)
+    FrameCounters* skip_top = nullptr;
+    SortKind kind = SORT_TILE_IDS;
+};
+// Where a sort's result ended: the caller's arrays for an even pass count, else the scratch partners.
+struct SortResult {
+    uint32_t *keys = nullptr, *vals = nullptr, *aux = nullptr;
+    // when the last pass was skipped (SortJob::skip_top); nullptr: the job had no skip_top
+    uint32_t *keys_skipped = nullptr, *vals_skipped = nullptr, *aux_skipped = nullptr;
+};
+int launch_sort_pairs(const SortScratch& sc, const SortJob& job, hipStream_t stream, KernelMarks* km, SortResult* res);
 // After a skip_top sort, for callers that need the result in place (ws_sorter_sort_depth): when *skip is set, copy [0, count)
 // of (keys, vals, aux) from where pass 2 left them (the scratch partners) to the caller's arrays; a no-op otherwise.  aux_dst
 // may be null (no companion).
@@ -368,14 +386,16 @@ int launch_depth_copy_back(const uint32_t* skip, const uint32_t* d_count, uint32
 // begin, end) for non-empty ids (zero on entry), no atomics.  Against the two 6-bit passes it replaces: 2 launches instead
 // of 5, the pairs are read once instead of twice and never written back as pairs -- but the count rows are 4 B x bins per
 // 2048 pairs, at 2048 bins as many bytes as the pairs: faster alone, slower with frames in flight (WS_TILE_SORT=wide).
+// *res: vals only (sc.vals_alt).
 int launch_tile_sort_wide(const SortScratch& sc, const uint32_t* keys16, const uint32_t* vals, const uint32_t* d_count,
-                          uint32_t n, int bits, hipStream_t stream, KernelMarks* km, uint2* ranges, uint32_t nranges);
+                          uint32_t n, int bits, hipStream_t stream, KernelMarks* km, uint2* ranges, uint32_t nranges, SortResult* res);
 
 // ---- fat-tile one-sweep depth sort (sort.hip k_dsort_fat) -----------------------------------------------------------
 // The same result as launch_sort_pairs over bits 0..32 with a companion value: four 8-bit passes, A -> B -> A -> B -> A, the
 // sorted arrays end where they started.  At most FAT_MAX_GRID workgroups of 1024 threads rank chunks of up to 8192 pairs;
 // the cross-chunk prefix is a consumer-side sum over epoch-tagged count rows (no chain).  Per-pass launches (one histogram
 // launch + four) or, coop = true, ONE launch with device-wide barriers between the passes (needs grid <= CUs resident).
+// *res: the caller's arrays, nothing skipped.
 constexpr uint32_t FAT_MAX_GRID = 256;
 constexpr uint32_t FAT_CHUNK_MAX = 1024u * 8u;
 struct FatSortScratch {
@@ -397,7 +417,7 @@ size_t fat_sort_status_words();
 uint32_t fat_sort_grid(uint32_t n, int num_cus, int grid_request);
 int launch_depth_sort_fat(const FatSortScratch& sc, uint32_t* keys, uint32_t* vals, uint32_t* aux, const uint32_t* d_count,
                           uint32_t n, bool implicit_iota, bool coop, uint32_t epoch, int num_cus, hipStream_t stream,
-                          KernelMarks* km = nullptr);
+                          KernelMarks* km, SortResult* res);
 
 // ---- preprocess ---------------------------------------------------------------------------------
 struct K1Buffers {
