@@ -457,6 +457,21 @@ def test_tile_shapes_odd_viewports(ws, oracle, shape, viewport, monkeypatch):
         c.close()
 
 
+@pytest.mark.parametrize("viewport", [(256, 256), (416, 160), (512, 512), (1376, 192), (8192, 32), (8224, 32)])
+def test_image_at_the_frame_plans_boundaries(ws, ctx, oracle, viewport):
+    """Frames on both sides of the tile counts at which the frame's plan (csrc/frame_plan.h; tests/test_frame_plan.py checks the
+    plan itself) changes the launch sequence, at the default 32x32 tile: 64 tiles (the tile-id sort is one 6-bit pass) and 65 (two
+    6-bit passes), 256 tiles and 258 (9 key bits), 256 tiles on an axis (packed footprint rectangles) and 257 (tile counts)."""
+    sc = scenes.c1(ws, oracle, n=3000, viewport=viewport, seed=17)
+    pc, img, stats = _render(ws, ctx, sc)
+    try:
+        ref, ofr_ = sc.oracle_image(pc)
+        _assert_close(img, ref, proof=sc.proof(ofr_))
+        assert stats["overflow"] == 0
+    finally:
+        pc.close()
+
+
 def _coverage_tiles(splats_f16, viewport, tile=(16, 16)):
     """For every splat: the set of tiles holding at least one pixel centre with a <= 2*CUTOFF, evaluated as the
     oracle does (oracle/ws_oracle.c setup_splat + wso_render), in float64 with a small slack towards 'covered'."""

@@ -716,8 +716,6 @@ uint32_t sort_grid(uint32_t tiles) {
     return g < 2048u ? (g ? g : 8u) : 2048u;
 }
 
-uint32_t sort_tile_size(uint32_t n) { return n <= SORT_SMALL_MAX ? SORT_THREADS * SORT_KPT_SMALL : SORT_TILE; }
-
 int launch_depth_copy_back(const uint32_t* skip, const uint32_t* d_count, uint32_t n, const uint32_t* keys_src, const uint32_t* vals_src,
                            const uint32_t* aux_src, uint32_t* keys_dst, uint32_t* vals_dst, uint32_t* aux_dst, hipStream_t stream) {
     if (n == 0) return WS_OK;

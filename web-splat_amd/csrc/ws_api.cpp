@@ -130,9 +130,9 @@ struct ws_renderer {
 
     // scratch, (re)created when num_points or the viewport changes (renderer.rs:200-211)
     uint32_t cap_points = 0;
-    uint32_t vw = 0, vh = 0, tiles_x = 0, tiles_y = 0;
+    uint32_t vw = 0, vh = 0;
     uint64_t entry_cap_request = 0;
-    uint32_t entry_cap = 0;
+    FramePlan plan{};                // of the last prepare(): the scratch is sized by it, the frame's launches are filled from it (frame_plan.h)
     uint32_t *fpw_a = nullptr, *fpw_b = nullptr;  // footprint words (FootprintMode): store order / ping-pong of the depth sort
     uint8_t* splats = nullptr;      // Splat[N], 20 B each (pointcloud.rs:103-108 allocates it in PointCloud;
                                     // here it is per renderer so that renderers never share scratch)
@@ -150,7 +150,6 @@ struct ws_renderer {
     FrameCounters* counters = nullptr;  // = &zero->counters
     SortScratch sort_depth, sort_tiles;
     FatSortScratch fat;              // fat-tile one-sweep depth sort (WS_DEPTH_SORT=onesweep | coop): chunk-count rows
-    int footprint_mode = FP_RECT_PACKED;  // of the current scratch (chosen by the viewport and WS_FOOTPRINT)
     uint32_t epoch = 0;
     uint32_t* sticky = nullptr;      // two device words that survive the per-frame memset (ws_renderer_errors): [0] error bits
                                      // of all frames since the last reset, [1] the largest entries_needed of an overflowed frame
@@ -181,6 +180,7 @@ struct ws_renderer {
         bool valid = false;
         FrameArrays arrays;              // of the captured frame
         int order_mode = 0;              // decide_blend_order() of the captured frame: a change re-captures
+        int depth_bits = 0;              // != 0 while the graph is valid: the digit width its depth sort was captured with
     } fg;
     uint64_t scratch_generation = 0;
 
@@ -201,9 +201,7 @@ struct ws_renderer {
     uint32_t* debug_consumed = nullptr;  // [tiles], capture mode only
     uint32_t* debug_walked = nullptr;    // [tiles][17], capture mode only
     uint4* blend_order = nullptr;        // [blend_order_blocks]: the blend's tiles, longest list first (k_blend_order)
-    int order_mode_this_frame = 0;       // decide_blend_order() of the prepare() in progress
-    int depth_bits_this_frame = 8;       // digit width the last enqueued depth sort used (8 | 9)
-    int graph_depth_bits = 0;            // != 0 while a frame graph is captured / valid: its depth sort's digit width
+    int order_mode = 0;                  // decide_blend_order() of the last prepare(): a captured graph replays only under its own
     unsigned long long* frame_trace = nullptr;  // [trace_cap][4]: {K1 start, K1 end, blend start, blend end} per frame (ws_renderer_enable_frame_trace)
     uint32_t trace_cap = 0, trace_count = 0;
     unsigned long long* trace_slot = nullptr;   // the slot of the frame being prepared / rendered (nullptr: not traced)
@@ -229,10 +227,8 @@ static void free_sort_scratch(SortScratch& sc, bool own_alt) {
     sc = SortScratch();
 }
 
-// wide_bins != 0: also room for the [tiles][wide_bins] count rows of the single-pass tile-id sort (launch_tile_sort_wide)
-// digit width of the depth sort: ws_context_config::depth_digit_bits, 0 = the default
-static int depth_digit_bits(const ws_context* c) { return c->depth_digit_bits == 9 ? 9 : (c->depth_digit_bits == 8 ? 8 : WS_DEPTH_DIGIT_BITS_DEFAULT); }
-
+// wide_bins != 0: also room for the [tiles][wide_bins] count rows of the single-pass tile-id sort (launch_tile_sort_wide;
+// FramePlan::wide_bins, which has weighed their size)
 static int alloc_sort_scratch(SortScratch& sc, uint32_t cap, bool own_alt, uint32_t wide_bins = 0, uint32_t rows = RADIX) {
     sc.cap = cap;
     sc.rows = rows;
@@ -247,9 +243,7 @@ static int alloc_sort_scratch(SortScratch& sc, uint32_t cap, bool own_alt, uint3
     const uint32_t small_tiles = (small_n + SORT_THREADS * SORT_KPT_SMALL - 1) / (SORT_THREADS * SORT_KPT_SMALL);
     sc.tiles_cap = std::max<uint32_t>(std::max<uint32_t>(small_tiles, sc.tiles), 1u);
     size_t sum_words = (size_t)sc.tiles_cap * rows;
-    // (4 B x tiles x bins: 8 KiB per 2048 entries of capacity at 2048 bins, 1.3 x the entry lists themselves; beyond 1 GiB
-    // -- 250 M entries -- the tile sort stays with its digit passes)
-    if (wide_bins && (size_t)sc.tiles * wide_bins * sizeof(uint32_t) <= ((size_t)1 << 30)) {
+    if (wide_bins) {
         sc.wide_bins = wide_bins;
         sum_words = std::max(sum_words, (size_t)sc.tiles * wide_bins);
         if ((rc = dmalloc(&sc.wide_hist, (size_t)wide_bins))) return rc;
@@ -258,6 +252,14 @@ static int alloc_sort_scratch(SortScratch& sc, uint32_t cap, bool own_alt, uint3
     return WS_OK;
 }
 
+// FrameCounters::depth_span_class of the renderer's last frame whose blend has started: the blend posts it to pinned memory,
+// read here without a sync (0: none yet, or no mailbox)
+static uint32_t renderer_span_class(const ws_renderer* r) {
+    return r->demand_mailbox ? *reinterpret_cast<volatile const uint32_t*>(r->demand_mailbox + 2) : 0u;
+}
+
+// Frees the captured frame graph.  The depth sort's digit width is the plan's one rule that reads the graph (a valid graph keeps
+// the width it was captured with): it is asked again, so that a plan made while the graph stood chooses its own width.
 static void renderer_free_graph(ws_renderer* r) {
     ws_renderer::FrameGraph& g = r->fg;
     for (int i = 0; i < ws_renderer::GRAPH_RING; ++i) {
@@ -266,7 +268,7 @@ static void renderer_free_graph(ws_renderer* r) {
     }
     if (g.graph) (void)hipGraphDestroy(g.graph);
     g = ws_renderer::FrameGraph();
-    r->graph_depth_bits = 0;
+    r->plan.depth_digit_bits = depth_sort_digit_bits(r->ctx->depth_digit_bits, r->ctx->depth_skip_top != 0, renderer_span_class(r), 0);
 }
 
 static void renderer_free_scratch(ws_renderer* r) {
@@ -312,35 +314,30 @@ static void renderer_free_scratch(ws_renderer* r) {
     r->prepared = false;
 }
 
-static int renderer_ensure_scratch(ws_renderer* r, uint32_t n, uint32_t vw, uint32_t vh) {
-    uint64_t want_cap = r->entry_cap_request;
-    if (want_cap == 0) {
-        // automatic: 4 tile entries per Gaussian at ~1 Mpixel, growing with the pixel count (a splat's footprint in tiles
-        // scales with the resolution), at least 8 M: twice what the BASELINE scenes need at the 32-px tile (hd1m 4.1 per
-        // Gaussian at 2.2 Mpixel, c3 1.2), 16 B per entry -- c3 0.7 GB instead of the 4.1 GB of rounds 1-3 (24 per Gaussian;
-        // round-3 verdict).  The safety net: an overflow is always flagged, the blend leaves the overflowed frame's demand
-        // in the sticky words, and once a read-back (ws_renderer_errors) has seen it the next prepare() allocates 1.25 x that.
-        const double mpix = (double)vw * (double)vh / (1200.0 * 800.0);
-        want_cap = std::max<uint64_t>(8ull << 20, (uint64_t)(4.0 * (double)n * std::max(1.0, mpix)));
-        // an overflowed frame's demand arrives by the mailbox (no sync, no polling by the caller) or by ws_renderer_errors.
-        // It belongs to THIS point-cloud size and viewport: another scene or target size starts from the formula again
-        // (one heavy frame must not inflate the scratch for the renderer's lifetime).
-        if (r->zero && (r->cap_points != n || r->vw != vw || r->vh != vh)) {
-            r->needed_seen = 0;
-            if (r->demand_mailbox) {
-                WS_HIP(hipDeviceSynchronize());
-                *reinterpret_cast<volatile uint32_t*>(r->demand_mailbox) = 0u;
-                WS_HIP(hipMemset(r->sticky + 1, 0, sizeof(uint32_t)));
-            }
-        } else if (r->demand_mailbox) {
-            const uint32_t posted = *reinterpret_cast<volatile uint32_t*>(r->demand_mailbox);
-            if (posted > r->needed_seen) r->needed_seen = posted;
+// What the automatic entry capacity of a frame of n points at vw x vh may grow to (FramePlanRequest::demand): an overflowed
+// frame's demand arrives by the mailbox (no sync, no polling by the caller) or by ws_renderer_errors.
+// It belongs to THIS point-cloud size and viewport: another scene or target size starts from the formula again
+// (one heavy frame must not inflate the scratch for the renderer's lifetime).
+static int renderer_refresh_demand(ws_renderer* r, uint32_t n, uint32_t vw, uint32_t vh) {
+    if (r->zero && (r->cap_points != n || r->vw != vw || r->vh != vh)) {
+        r->needed_seen = 0;
+        if (r->demand_mailbox) {
+            WS_HIP(hipDeviceSynchronize());
+            *reinterpret_cast<volatile uint32_t*>(r->demand_mailbox) = 0u;
+            WS_HIP(hipMemset(r->sticky + 1, 0, sizeof(uint32_t)));
         }
-        if (r->needed_seen) want_cap = std::max<uint64_t>(want_cap, (uint64_t)r->needed_seen + r->needed_seen / 4 + 4096);
+    } else if (r->demand_mailbox) {
+        const uint32_t posted = *reinterpret_cast<volatile uint32_t*>(r->demand_mailbox);
+        if (posted > r->needed_seen) r->needed_seen = posted;
     }
-    // look-back words carry 30-bit counts (lookback.h): keep D below 2^30
-    want_cap = std::min<uint64_t>(want_cap, (1ull << 30) - 2 * EMIT_TILE);
-    if (r->cap_points == n && r->vw == vw && r->vh == vh && r->entry_cap == (uint32_t)want_cap && r->zero) return WS_OK;
+    return WS_OK;
+}
+
+// The scratch of frames of n points at vw x vh laid out by `plan`; kept while those three and the entry capacity stay.
+static int renderer_ensure_scratch(ws_renderer* r, uint32_t n, uint32_t vw, uint32_t vh, const FramePlan& plan) {
+    const bool keep = r->cap_points == n && r->vw == vw && r->vh == vh && r->plan.entry_cap == plan.entry_cap && r->zero;
+    r->plan = plan;
+    if (keep) return WS_OK;
     WS_HIP(hipDeviceSynchronize());
     renderer_free_scratch(r);
     int rc;
@@ -359,21 +356,17 @@ static int renderer_ensure_scratch(ws_renderer* r, uint32_t n, uint32_t vw, uint
     if ((rc = dmalloc(&r->bin_status, bin_words))) return rc;
     WS_HIP(hipMemset(r->k1_status, 0, k1_words * sizeof(uint64_t)));
     WS_HIP(hipMemset(r->bin_status, 0, bin_words * sizeof(uint64_t)));
-    r->entry_cap = (uint32_t)want_cap;
-    const size_t ne = (size_t)r->entry_cap + 8;
+    const size_t ne = (size_t)plan.entry_cap + 8;
     if ((rc = dmalloc(&r->ekeys_a, ne))) return rc;
     if ((rc = dmalloc(&r->ekeys_b, ne))) return rc;
     if ((rc = dmalloc(&r->evals_a, ne))) return rc;
     if ((rc = dmalloc(&r->evals_b, ne))) return rc;
-    if ((rc = dmalloc(&r->emit_start, (size_t)r->entry_cap / EMIT_TILE + 4))) return rc;
-    const uint32_t tile_w = QUAD * r->ctx->tile_qw, tile_h = QUAD * r->ctx->tile_qh;
-    r->tiles_x = (vw + tile_w - 1) / tile_w;
-    r->tiles_y = (vh + tile_h - 1) / tile_h;
-    if ((rc = dmalloc(&r->blend_order, (size_t)blend_order_blocks(r->tiles_x, r->tiles_y) + 8))) return rc;
-    if ((rc = dmalloc(&r->debug_consumed, (size_t)r->tiles_x * r->tiles_y))) return rc;
-    if ((rc = dmalloc(&r->debug_walked, (size_t)r->tiles_x * r->tiles_y * 17))) return rc;
+    if ((rc = dmalloc(&r->emit_start, (size_t)plan.entry_cap / EMIT_TILE + 4))) return rc;
+    if ((rc = dmalloc(&r->blend_order, (size_t)blend_order_blocks(plan.tiles_x, plan.tiles_y) + 8))) return rc;
+    if ((rc = dmalloc(&r->debug_consumed, (size_t)plan.ntiles))) return rc;
+    if ((rc = dmalloc(&r->debug_walked, (size_t)plan.ntiles * 17))) return rc;
     // the per-frame zero arena: counters | depth histograms | tile histograms | tile ranges
-    r->zero_bytes = sizeof(FrameZero) + (size_t)r->tiles_x * r->tiles_y * sizeof(uint2);
+    r->zero_bytes = sizeof(FrameZero) + (size_t)plan.ntiles * sizeof(uint2);
     WS_HIP(hipMalloc(reinterpret_cast<void**>(&r->zero), r->zero_bytes));
     WS_HIP(hipMemset(r->zero, 0, r->zero_bytes));
     r->counters = &r->zero->counters;
@@ -383,17 +376,7 @@ static int renderer_ensure_scratch(ws_renderer* r, uint32_t n, uint32_t vw, uint
     r->sort_depth.vals_alt = r->vals_b;
     r->sort_depth.hist = r->zero->depth_hist;
     r->sort_depth.hist_pitch = 512;
-    // WS_TILE_SORT=wide: the tile-id sort is ONE counting pass when the viewport has at most 2048 binning tiles
-    uint32_t wide_bins = 0;
-    {
-        const uint32_t ntiles = r->tiles_x * r->tiles_y;
-        if (r->ctx->tile_sort_wide && ntiles > 64u && ntiles <= (uint32_t)TILE_SORT_WIDE_MAX_BINS &&
-            sort_tile_size(r->entry_cap) == (uint32_t)EMIT_TILE) {
-            wide_bins = 128u;
-            while (wide_bins < ntiles) wide_bins <<= 1;
-        }
-    }
-    if ((rc = alloc_sort_scratch(r->sort_tiles, r->entry_cap, false, wide_bins))) return rc;
+    if ((rc = alloc_sort_scratch(r->sort_tiles, plan.entry_cap, false, plan.wide_bins))) return rc;
     r->sort_tiles.keys_alt = r->ekeys_b;
     r->sort_tiles.vals_alt = r->evals_b;
     r->sort_tiles.hist = r->zero->tile_hist;
@@ -1004,7 +987,7 @@ int ws_renderer_enable_capture(ws_renderer* r, int enable) {
 int ws_renderer_download_blend_order(ws_renderer* r, uint32_t capacity_blocks, uint32_t* order4, uint32_t* num_blocks) {
     if (!r || !num_blocks) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_order: null argument");
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_blend_order: no prepared frame");
-    const uint32_t nb = r->arrays.blend_order_valid ? blend_order_blocks(r->tiles_x, r->tiles_y) : 0u;
+    const uint32_t nb = r->arrays.blend_order_valid ? blend_order_blocks(r->plan.tiles_x, r->plan.tiles_y) : 0u;
     *num_blocks = nb;
     if (!order4 || nb == 0) return WS_OK;
     if (capacity_blocks < nb) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_order: capacity smaller than the block count");
@@ -1055,7 +1038,7 @@ int ws_renderer_enable_blend_timing(ws_renderer* r, int enable) {
 
 int ws_renderer_download_blend_timing(ws_renderer* r, uint32_t tile_capacity, uint32_t* times, uint32_t* num_tiles) {
     if (!r) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_timing: null renderer");
-    const uint32_t nt = r->tiles_x * r->tiles_y;
+    const uint32_t nt = r->plan.ntiles;
     if (num_tiles) *num_tiles = nt;
     if (!times) return WS_OK;
     if (!r->prepared || !r->blend_timing || !r->debug_timing || r->debug_timing_tiles != nt)
@@ -1080,6 +1063,13 @@ enum FramePhase { FRAME_ALL = 0, FRAME_CLEAR = 1, FRAME_REST = 2 };
 // 2 / 3 the measured experiments.  Decided ONCE per prepare() and outside any stream capture (a frame graph captured
 // under one decision and replayed under another composited with a stale order table): the graph path re-captures when the
 // decision changes.
+// Longest first is what a frame drawn ALONE wants (blend -12 % hd1m, -18 % c3 / c2: no tail of idle slots).  With several
+// frames in flight it is the wrong order, measured (profiles/r05/blend_order_ab.txt: hd1m -9 %, c3 -17 % frames/s): the first
+// 512 workgroups are then the longest tiles, no slot retires for 40 (hd1m) to 120 us (c3), and the other frames' small
+// dependent kernels, which live on the slots the blend's short tiles keep freeing, starve behind it.
+// "In flight" = a slot of a view batch with several slots, or -- for renderers driven by the caller's own loop -- a context
+// whose prepare() calls change stream from call to call (frames in flight on a ring of streams do; a renderer that draws
+// one frame at a time stays on its stream: after four consecutive calls on one stream it orders its tiles).
 static int decide_blend_order(ws_renderer* r, hipStream_t stream) {
     bool in_flight = r->throughput_mode;
     if (!in_flight) {
@@ -1093,9 +1083,18 @@ static int decide_blend_order(ws_renderer* r, hipStream_t stream) {
     return r->ctx->blend_order < 0 ? (in_flight ? 0 : 1) : r->ctx->blend_order;
 }
 
+// the renderer holds a prepared frame of pc, enqueued on stream
+static int frame_prepared(ws_renderer* r, const ws_pointcloud* pc, hipStream_t stream) {
+    r->prepared = true;
+    r->prepared_pc = pc;
+    r->last_stream = stream;
+    return WS_OK;
+}
+
 static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params& kp, const K1Buffers& kb, hipStream_t stream,
                          int phase = FRAME_ALL) {
     int rc;
+    const FramePlan& plan = r->plan;
     KernelMarks* km = r->marks.active ? &r->marks : nullptr;
     if (phase != FRAME_REST) {
         // GPURSSorter::record_reset_indirect_buffer (gpu_rs.rs:720-727): keys_size = 0, dispatch = 0 -- here ONE
@@ -1104,7 +1103,7 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         if (phase == FRAME_CLEAR) return WS_OK;
         if (km) km->begin(stream, true);
         if (r->timers) WS_HIP(hipEventRecord(r->ev[0], stream));
-        if ((rc = launch_preprocess(kp, kb, pc->compressed, r->footprint_mode, stream, r->k1_depths))) return rc;
+        if ((rc = launch_preprocess(kp, kb, pc->compressed, plan.footprint_mode, stream, r->k1_depths))) return rc;
         km_mark(km, pc->compressed ? "k_preprocess<compressed>" : "k_preprocess");
         if (r->timers) WS_HIP(hipEventRecord(r->ev[1], stream));
         if (km) {  // calibration interval between two kernels: the dispatch latency of a dependent launch
@@ -1114,12 +1113,7 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
     }
 
     const int cut = r->ctx->debug_cut;
-    if (cut == 1) {  // analysis only (WS_DEBUG_CUT): the image is NOT produced
-        r->prepared = true;
-        r->prepared_pc = pc;
-        r->last_stream = stream;
-        return WS_OK;
-    }
+    if (cut == 1) return frame_prepared(r, pc, stream);  // analysis only (WS_DEBUG_CUT): the image is NOT produced
     // depth sort: V (key, store index) pairs, values start as iota (preprocess.wgsl:274), the splat's footprint word
     // (packed tile rectangle, or tile count) rides along as a companion value.  Default: the generic 4 x 8-bit sorter
     // (GPURSSorter's shape); WS_DEPTH_SORT=onesweep | coop: the fat-tile one-sweep (measured variants).
@@ -1145,28 +1139,11 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         job.aux = r->fpw_a, job.aux_alt = r->fpw_b;
         job.skip_top = r->ctx->depth_skip_top ? r->counters : nullptr;
         job.kpt9 = r->ctx->depth_tile_kpt ? r->ctx->depth_tile_kpt : 8;
-        // Digit width (round 6): three 8-bit passes when the renderer's previous frame says its keys span < 2^24 (the cheapest
-        // form), three 9-bit passes when it says they do not (c5: every frame; hd1m: the views that see the cloud end on) --
-        // the answer of the last frame whose blend has started, read from pinned memory without a sync.  Either width yields
-        // the same stable order, so the image does not depend on which frame's answer was the latest.
-        int dbits = r->ctx->depth_digit_bits;
-        if (dbits != 8 && dbits != 9) {
-            dbits = WS_DEPTH_DIGIT_BITS_DEFAULT;
-            if (WS_DEPTH_DIGIT_BITS_ADAPTIVE && job.skip_top && r->demand_mailbox && r->graph_depth_bits == 0)
-                dbits = *reinterpret_cast<volatile const uint32_t*>(r->demand_mailbox + 2) == 2u ? 9 : 8;
-        }
-        if (r->graph_depth_bits) dbits = r->graph_depth_bits;  // (a captured frame graph keeps the width it was captured with)
-        r->depth_bits_this_frame = dbits;
-        job.digit_bits = dbits;
+        job.digit_bits = plan.depth_digit_bits;  // (8 | 9, per frame: frame_plan.h depth_sort_digit_bits)
         if ((rc = launch_sort_pairs(r->sort_depth, job, stream, km, &r->arrays.depth))) return rc;
     }
     if (r->timers) WS_HIP(hipEventRecord(r->ev[2], stream));
-    if (cut == 2) {  // analysis only (WS_DEBUG_CUT): the image is NOT produced
-        r->prepared = true;
-        r->prepared_pc = pc;
-        r->last_stream = stream;
-        return WS_OK;
-    }
+    if (cut == 2) return frame_prepared(r, pc, stream);  // analysis only (WS_DEBUG_CUT): the image is NOT produced
 
     // tile binning
     BinBuffers bb;
@@ -1174,94 +1151,55 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
     bb.fp_sorted = r->arrays.depth.aux;
     bb.sorted_idx_alt = r->arrays.depth.vals_skipped;
     bb.fp_sorted_alt = r->arrays.depth.aux_skipped;
-    bb.footprint_mode = r->footprint_mode;
+    bb.footprint_mode = plan.footprint_mode;
     bb.splats = r->splats;
     bb.vw = kp.cam.viewport[0];
     bb.vh = kp.cam.viewport[1];
-    bb.tile_w_log2 = kp.tile_w_log2;
-    bb.tile_h_log2 = kp.tile_h_log2;
+    bb.tile_w_log2 = plan.tile_w_log2;
+    bb.tile_h_log2 = plan.tile_h_log2;
     bb.offsets = r->bin_offsets;
     bb.emit_start = r->emit_start;
     bb.block_status = r->bin_status;
     bb.entry_keys = r->ekeys_a;
     bb.entry_vals = r->evals_a;
-    bb.entry_cap = r->entry_cap;
+    bb.entry_cap = plan.entry_cap;
     bb.tile_ranges = r->tile_ranges;
     bb.counters = r->counters;
     bb.max_points = pc->num_points;
-    bb.tiles_x = r->tiles_x;
-    bb.tiles_y = r->tiles_y;
-    // the emit kernel cuts the entry list into the same 4096-entry tiles the radix sort uses, so it can hand
-    // the sort the digit counts of its first pass for free
-    const bool fused_hist = sort_tile_size(r->entry_cap) == (uint32_t)EMIT_TILE;
-    bb.tile_hist = fused_hist ? r->sort_tiles.tile_sums : nullptr;
-    bb.tile_hist_pitch = r->sort_tiles.tiles_cap;
-    // The tile-id sort is "segmented": only the bits a tile id can have take part, split evenly over the passes
-    // (3750 tiles -> 12 bits -> 6 + 6; 8160 tiles -> 13 bits -> 7 + 6(7); 32400 tiles -> 15 bits -> 8 + 7(8)).
-    const uint32_t ntiles = r->tiles_x * r->tiles_y;
-    int tile_bits = 1;
-    while ((1ull << tile_bits) < ntiles) ++tile_bits;
-    int tile_passes = (tile_bits + RADIX_BITS - 1) / RADIX_BITS;
-    int digit_bits = (tile_bits + tile_passes - 1) / tile_passes;
-    // A single pass (at most 256 tiles) would let EVERY sort workgroup end runs of EVERY tile: the last pass records the
-    // tile ranges with two atomics per (workgroup, tile) run, the whole range table is then 16 cache lines, and atomics on
-    // one line serialise -- measured 127 us for 247 tiles x 413 workgroups.  Two 6-bit passes instead: behind the first one
-    // a workgroup holds a handful of tiles.
-    if (tile_passes == 1 && ntiles > 64) digit_bits = 6;
-    if (digit_bits < 6) digit_bits = 6;
-    bb.tile_hist_mask = (1u << digit_bits) - 1u;
-    // ONE counting pass over the whole tile id when the scratch was sized for it (at most 2048 binning tiles): the emit
-    // kernel leaves [sort tile][bin] counts, a column scan and a scatter follow -- two launches instead of five, the
-    // entries are read once, and the tile ranges are prefix sums of the bin totals (launch_tile_sort_wide)
-    const bool wide_sort = fused_hist && r->sort_tiles.wide_bins >= ntiles && ntiles > 64u && r->sort_tiles.wide_bins != 0u;
-    int wide_bits = 7;
-    while ((1u << wide_bits) < ntiles) ++wide_bits;
-    bb.tile_hist_wide = wide_sort ? 1 : 0;
-    if (wide_sort) bb.tile_hist_pitch = 1u << wide_bits;
-    // tile ids fit 16 bits up to 65534 tiles (4096 x 4080 px): the key arrays of the tile sort then hold uint16_t
-    const bool key16 = ntiles < 65535u;
-    bb.key16 = key16 ? 1 : 0;
+    bb.tiles_x = plan.tiles_x;
+    bb.tiles_y = plan.tiles_y;
+    // the tile-id sort's shape (frame_plan.h): k_bin_emit writes the counts of its first pass -- or of its only pass, as
+    // [sort tile][bin] rows of wide_bins words -- and the sort below reads them with the same digit width and key width
+    bb.tile_hist = plan.fused_hist ? r->sort_tiles.tile_sums : nullptr;
+    bb.tile_hist_pitch = plan.wide_sort() ? plan.wide_bins : r->sort_tiles.tiles_cap;
+    bb.tile_hist_mask = plan.tile_hist_mask;
+    bb.tile_hist_wide = plan.wide_sort() ? 1 : 0;
+    bb.key16 = plan.key16 ? 1 : 0;
     if ((rc = launch_bin_prefix(bb, stream))) return rc;
     km_mark(km, "k_bin_prefix");
     if ((rc = launch_bin_emit(bb, stream))) return rc;
     km_mark(km, "k_bin_emit");
-    if (cut == 3) {
-        r->prepared = true;
-        r->prepared_pc = pc;
-        r->last_stream = stream;
-        return WS_OK;
-    }
+    if (cut == 3) return frame_prepared(r, pc, stream);
     SortResult tiles;
-    if (wide_sort) {
-        if ((rc = launch_tile_sort_wide(r->sort_tiles, r->ekeys_a, r->evals_a, &r->counters->num_entries, r->entry_cap,
-                                        wide_bits, stream, km, r->tile_ranges, ntiles, &tiles)))
+    if (plan.wide_sort()) {
+        if ((rc = launch_tile_sort_wide(r->sort_tiles, r->ekeys_a, r->evals_a, &r->counters->num_entries, plan.entry_cap,
+                                        plan.wide_bits(), stream, km, r->tile_ranges, plan.ntiles, &tiles)))
             return rc;
     } else {
         SortJob job;
         job.kind = SORT_TILE_IDS;
-        job.keys = r->ekeys_a, job.vals = r->evals_a, job.d_count = &r->counters->num_entries, job.n = r->entry_cap;
-        job.end_bit = tile_bits, job.digit_bits = digit_bits;
-        job.first_tile_hist_ready = fused_hist, job.key16 = key16;
-        job.ranges = r->tile_ranges, job.nranges = ntiles;
+        job.keys = r->ekeys_a, job.vals = r->evals_a, job.d_count = &r->counters->num_entries, job.n = plan.entry_cap;
+        job.end_bit = plan.tile_bits, job.digit_bits = plan.digit_bits;
+        job.first_tile_hist_ready = plan.fused_hist, job.key16 = plan.key16;
+        job.ranges = r->tile_ranges, job.nranges = plan.ntiles;
         if ((rc = launch_sort_pairs(r->sort_tiles, job, stream, km, &tiles))) return rc;
     }
     r->arrays.entries = tiles.vals;  // the last pass wrote the per-tile ranges instead of the sorted tile ids
-    // the compositing workgroups in longest-list-first order (one tile per workgroup at the 32x32 tile: every frame up to
-    // 1080p-class tile counts; 4K-class frames composite several tiles per workgroup and keep the image order)
-    // Longest first is what a frame drawn ALONE wants (blend -12 % hd1m, -18 % c3 / c2: no tail of idle slots).  With several
-    // frames in flight it is the wrong order, measured (profiles/r05/blend_order_ab.txt: hd1m -9 %, c3 -17 % frames/s): the first
-    // 512 workgroups are then the longest tiles, no slot retires for 40 (hd1m) to 120 us (c3), and the other frames' small
-    // dependent kernels, which live on the slots the blend's short tiles keep freeing, starve behind it.
-    // "In flight" = a slot of a view batch with several slots, or -- for renderers driven by the caller's own loop -- a context
-    // whose prepare() calls change stream from call to call (frames in flight on a ring of streams do; a renderer that draws
-    // one frame at a time stays on its stream: after four consecutive calls on one stream it orders its tiles).
-    // (the decision itself is taken once per prepare(), OUTSIDE any captured region: ws_renderer_prepare -> decide_blend_order)
+    // the compositing workgroups in longest-list-first order, where the plan says so (the order mode itself is decided once
+    // per prepare(), OUTSIDE any captured region: decide_blend_order)
     r->arrays.blend_order_valid = false;
-    const int order_mode = r->order_mode_this_frame;
-    // (up to 4096 tiles = eight rounds of workgroups on this chip: beyond that the tail is a small share of the kernel and the
-    // one-workgroup ordering kernel, 3 us at 2040 tiles and 7.6 us at 8160, costs what it saves -- c5, 4K: measured)
-    if (order_mode && r->ctx->tile_qw == 4 && r->ctx->tile_qh == 4 && ntiles <= 4096u && r->ctx->blend_tpw_log2 <= 0) {
-        if ((rc = launch_blend_order(r->tile_ranges, r->counters, r->tiles_x, r->tiles_y, r->blend_order, order_mode, stream))) return rc;
+    if (plan.blend_order) {
+        if ((rc = launch_blend_order(r->tile_ranges, r->counters, plan.tiles_x, plan.tiles_y, r->blend_order, plan.blend_order, stream))) return rc;
         km_mark(km, "k_blend_order");
         r->arrays.blend_order_valid = true;
     }
@@ -1269,10 +1207,7 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         WS_HIP(hipEventRecord(r->ev[3], stream));
         r->ev_prepare_valid = true;
     }
-    r->prepared = true;
-    r->prepared_pc = pc;
-    r->last_stream = stream;
-    return WS_OK;
+    return frame_prepared(r, pc, stream);
 }
 
 // Validation, scratch, uniforms, buffers and the frame's look-back epoch: everything of prepare() in front of the first
@@ -1282,37 +1217,36 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     if (!r || !pc || !args) return fail(WS_ERR_INVALID, "ws_renderer_prepare: null argument");
     if (pc->compressed != r->compressed)
         return fail(WS_ERR_INVALID, "ws_renderer_prepare: renderer and point cloud disagree on `compressed`");
-    // Tile coordinates are 16-bit (ws_internal.h): 65535 binning tiles per axis, i.e. any target the reference can create
-    // (it asks for the adapter's own max_texture_dimension_2d, src/lib.rs:99-110: 16384 or 32768 on today's adapters).
-    // Pixel coordinates are converted through f32 (exact below 2^24).
-    if (args->viewport[0] == 0 || args->viewport[1] == 0 ||
-        (uint64_t)args->viewport[0] > (uint64_t)MAX_TILES_PER_AXIS * QUAD * r->ctx->tile_qw ||
-        (uint64_t)args->viewport[1] > (uint64_t)MAX_TILES_PER_AXIS * QUAD * r->ctx->tile_qh ||
-        args->viewport[0] > (1u << 24) || args->viewport[1] > (1u << 24))
+    if (!frame_viewport_ok(args->viewport[0], args->viewport[1], r->ctx->tile_qw, r->ctx->tile_qh))
         return fail(WS_ERR_INVALID, "ws_renderer_prepare: bad viewport (at most 65535 binning tiles per axis)");
     if (args->max_sh_deg > 3) return fail(WS_ERR_UNSUPPORTED, "ws_renderer_prepare: max_sh_deg > 3");
-    if (!pc->compressed && args->max_sh_deg > pc->sh_deg) {
-        // the 96-B record always holds 16 coefficients (zeros above the file's degree): harmless, as in the reference
-    }
+    // (uncompressed, max_sh_deg above the point cloud's degree: the 96-B record always holds 16 coefficients, zeros above the
+    // file's degree -- harmless, as in the reference)
     if (pc->compressed && args->max_sh_deg > r->sh_deg)
         return fail(WS_ERR_INVALID, "ws_renderer_prepare: max_sh_deg exceeds the renderer's SH layout degree");
     if (pc->compressed && pc->sh_deg > r->sh_deg)
         return fail(WS_ERR_INVALID, "ws_renderer_prepare: compressed point cloud has a higher SH degree than the renderer was created for");
     r->prepared = false;
-    int rc = renderer_ensure_scratch(r, pc->num_points, args->viewport[0], args->viewport[1]);
-    if (rc) return rc;
+    int rc;
+    // an automatic capacity follows the demand of this scene's and viewport's overflowed frames
+    if (r->entry_cap_request == 0 && (rc = renderer_refresh_demand(r, pc->num_points, args->viewport[0], args->viewport[1]))) return rc;
+    // the frame's plan (frame_plan.h): everything below -- scratch, K1's parameters, the launches of enqueue_frame -- reads it
+    const ws_context* c = r->ctx;
+    FramePlanRequest q{};
+    q.tile_qw = c->tile_qw, q.tile_qh = c->tile_qh, q.footprint = c->footprint, q.tile_sort_wide = c->tile_sort_wide;
+    q.bin_request = c->bin_request, q.blend_tpw_log2 = c->blend_tpw_log2, q.blend_split = c->blend_split, q.num_cus = c->num_cus;
+    q.depth_digit_bits = c->depth_digit_bits, q.depth_skip_top = c->depth_skip_top;
+    q.num_points = pc->num_points, q.viewport[0] = args->viewport[0], q.viewport[1] = args->viewport[1], q.capture = r->capture;
+    q.entry_cap_request = r->entry_cap_request, q.demand = r->needed_seen;
+    q.order_mode = r->order_mode = decide_blend_order(r, stream);
+    q.span_class = renderer_span_class(r);
+    q.graph_depth_bits = r->fg.depth_bits;
+    if ((rc = renderer_ensure_scratch(r, pc->num_points, args->viewport[0], args->viewport[1], frame_plan(q)))) return rc;
+    const FramePlan& plan = r->plan;
     // the z plane: 4 B per splat, allocated with the scratch (and freed with it) while depth is on
     if (r->depth && !r->depths && (rc = dmalloc(&r->depths, (size_t)pc->num_points + 8))) return rc;
     r->k1_depths = r->depth ? r->depths : nullptr;
     r->prepared_depth = false;
-    // the footprint word K1 leaves per splat (ws_internal.h): the packed rectangle while the viewport has at most 256
-    // binning tiles per axis, the rectangle's tile count beyond that; WS_FOOTPRINT=ellipse: the ellipse's own tile count
-    const int fp_mode = r->ctx->footprint == FP_ELLIPSE ? FP_ELLIPSE
-                        : ((r->tiles_x > RECT_PACKED_MAX_TILES_PER_AXIS || r->tiles_y > RECT_PACKED_MAX_TILES_PER_AXIS) ? FP_RECT_COUNT : FP_RECT_PACKED);
-    if (fp_mode != r->footprint_mode) {
-        renderer_free_graph(r);  // (a captured frame graph holds the other mode's kernels)
-        r->footprint_mode = fp_mode;
-    }
 
     K1Params kp;
     std::memset(&kp, 0, sizeof kp);
@@ -1323,15 +1257,11 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     // stride of the packed int8 SH records: the POINT CLOUD's degree (the records were laid out by its loader); a
     // renderer created for another degree must not re-interpret them (WebGPU would clamp the reads, HIP would not)
     kp.sh_deg_layout = (pc->sh_deg + 1) * (pc->sh_deg + 1);
-    kp.tiles_x = r->tiles_x;
-    kp.tiles_y = r->tiles_y;
-    kp.tile_w_log2 = r->ctx->tile_qw == 4 ? 5u : 4u;
-    kp.tile_h_log2 = r->ctx->tile_qh == 4 ? 5u : 4u;
-    // Coarse binning (2 x 2 blend tiles per binning tile, decided per frame on the device: ws_internal.h bin_shift_decide) is
-    // offered to frames of the default 32x32 shape whose rectangles travel packed; parity tooling that reads per-tile
-    // lists back (capture mode) always sees the blend's own tiles.
-    kp.bin_request = (r->footprint_mode == FP_RECT_PACKED && !r->capture && r->ctx->tile_qw == 4 && r->ctx->tile_qh == 4)
-                         ? (uint32_t)r->ctx->bin_request : (uint32_t)BIN_NEVER;
+    kp.tiles_x = plan.tiles_x;
+    kp.tiles_y = plan.tiles_y;
+    kp.tile_w_log2 = plan.tile_w_log2;
+    kp.tile_h_log2 = plan.tile_h_log2;
+    kp.bin_request = plan.bin_request;
     kp.znear = -kp.cam.proj[3 * 4 + 2] / kp.cam.proj[2 * 4 + 2];
     kp.zfar = -kp.cam.proj[3 * 4 + 2] / (kp.cam.proj[2 * 4 + 2] - 1.0f);
     r->prepared_znear = kp.znear;
@@ -1383,19 +1313,16 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     // when the caller gave a real stream and no per-launch instrumentation is on.  The legacy NULL stream cannot be captured.
     const bool use_graph = r->ctx->use_graph && stream != nullptr && !r->marks.active && !r->timers && !r->capture &&
                            !r->contrib && cut_mode == 0;
-    r->order_mode_this_frame = decide_blend_order(r, stream);
     if (!use_graph) {
         rc = enqueue_frame(r, pc, kp, kb, stream);
         if (rc == WS_OK) r->prepared_depth = r->k1_depths != nullptr;
         return rc;
     }
     ws_renderer::FrameGraph& g = r->fg;
-    if (!(g.valid && g.pc == pc && g.generation == r->scratch_generation && g.order_mode == r->order_mode_this_frame)) {
-        renderer_free_graph(r);
-        r->graph_depth_bits = 0;
+    if (!(g.valid && g.pc == pc && g.generation == r->scratch_generation && g.order_mode == r->order_mode)) {
+        renderer_free_graph(r);  // (with it the digit width it kept: this capture's depth sort chooses its own)
         WS_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
         rc = enqueue_frame(r, pc, kp, kb, stream);
-        r->graph_depth_bits = r->depth_bits_this_frame;
         hipGraph_t graph = nullptr;
         const hipError_t ce = hipStreamEndCapture(stream, &graph);
         if (rc) {
@@ -1410,7 +1337,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         WS_HIP(hipGraphGetNodes(graph, nullptr, &nn));
         std::vector<hipGraphNode_t> nodes(nn);
         WS_HIP(hipGraphGetNodes(graph, nodes.data(), &nn));
-        const void* k1_func = preprocess_kernel_func(pc->compressed, r->footprint_mode, r->k1_depths != nullptr);
+        const void* k1_func = preprocess_kernel_func(pc->compressed, r->plan.footprint_mode, r->k1_depths != nullptr);
         for (size_t i = 0; i < nn && !g.k1_node; ++i) {
             hipGraphNodeType ty;
             if (hipGraphNodeGetType(nodes[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
@@ -1432,7 +1359,8 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         g.pc = pc;
         g.generation = r->scratch_generation;
         g.arrays = r->arrays;  // (with: did the captured frame run k_blend_order?)
-        g.order_mode = r->order_mode_this_frame;
+        g.order_mode = r->order_mode;
+        g.depth_bits = r->plan.depth_digit_bits;
         g.valid = true;
     }
     const int slot = (int)(g.next++ % ws_renderer::GRAPH_RING);
@@ -1448,11 +1376,8 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     WS_HIP(hipEventRecord(g.done[slot], stream));
     g.used[slot] = true;
     r->arrays = g.arrays;  // what THIS graph's frames write, whatever a launch-by-launch frame left behind
-    r->prepared = true;
     r->prepared_depth = r->k1_depths != nullptr;
-    r->prepared_pc = pc;
-    r->last_stream = stream;
-    return WS_OK;
+    return frame_prepared(r, pc, stream);
 }
 
 }  // extern "C"
@@ -1498,12 +1423,11 @@ int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_point
     int rc;
     for (uint32_t i = 0; i < n; ++i) {
         if ((rc = prepare_setup(rs[i], pc, &views[i], streams[i], &kp[i], &kb[i]))) return rc;
-        rs[i]->order_mode_this_frame = decide_blend_order(rs[i], streams[i]);
         for (int e = 0; e < 2; ++e)
             if (!rs[i]->ev_group[e]) WS_HIP(hipEventCreateWithFlags(&rs[i]->ev_group[e], hipEventDisableTiming));
     }
     for (uint32_t i = 1; i < n; ++i)
-        if (rs[i]->footprint_mode != rs[0]->footprint_mode) {  // (cannot happen within one batch: same viewport class)
+        if (rs[i]->plan.footprint_mode != rs[0]->plan.footprint_mode) {  // (cannot happen within one batch: same viewport class)
             for (uint32_t k = 0; k < n; ++k)  // fall back in place: the set-up is done, finish every frame on its own
                 if ((rc = enqueue_frame(rs[k], pc, kp[k], kb[k], streams[k]))) return rc;
             return WS_OK;
@@ -1516,7 +1440,7 @@ int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_point
             WS_HIP(hipStreamWaitEvent(streams[0], rs[i]->ev_group[0], 0));
         }
     }
-    if ((rc = launch_preprocess_multi(kp, kb, n, pc->compressed, rs[0]->footprint_mode, streams[0]))) return rc;
+    if ((rc = launch_preprocess_multi(kp, kb, n, pc->compressed, rs[0]->plan.footprint_mode, streams[0]))) return rc;
     WS_HIP(hipEventRecord(rs[0]->ev_group[1], streams[0]));
     // (Measured and removed: starting the frames of a group one after another behind events, so that they do not run the
     // same stage in lock-step -- 3781 instead of 5155 frames/s; every cross-stream wait costs more than the lock-step does.)
@@ -1542,14 +1466,10 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
         (reinterpret_cast<uintptr_t>(d_rgba_out) % texel) != 0)
         return fail(WS_ERR_INVALID, "ws_renderer_render: row pitch / alignment does not fit the colour format");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    // Split: two 512-thread workgroups (32x16 halves) per 32x32 binning tile, both reading the tile's list.  Automatic: when the
-    // frame has fewer binning tiles than the chip holds 1024-thread blend workgroups (two per CU) -- small viewports --
-    // the halves fill the chip and balance the long tiles (800x600, 0.5 M Gaussians: +24 % frames/s); above that the
-    // doubled staging costs more with frames in flight than the finer synchronisation saves.
     BlendFrameRequest fr{};
     fr.target_precision = r->blend_mode == WS_BLEND_TARGET_PRECISION, fr.exact_mode = r->blend_mode == WS_BLEND_FAST_EXACT_CUT;
     fr.variant = r->ctx->blend_variant, fr.capture = r->capture, fr.timing = r->blend_timing;
-    fr.split_wanted = r->ctx->blend_split >= 0 ? r->ctx->blend_split != 0 : (r->tiles_x * r->tiles_y < 2u * (uint32_t)r->ctx->num_cus);
+    fr.split_wanted = r->plan.split_wanted;
     fr.order_valid = r->arrays.blend_order_valid, fr.qw = r->ctx->tile_qw, fr.qh = r->ctx->tile_qh;
     const BlendFrameChoice form = blend_frame_choice(fr);
     BlendParams bp;
@@ -1558,8 +1478,8 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     bp.tile_ranges = r->tile_ranges;
     bp.width = r->vw;
     bp.height = r->vh;
-    bp.tiles_x = r->tiles_x;
-    bp.tiles_y = r->tiles_y;
+    bp.tiles_x = r->plan.tiles_x;
+    bp.tiles_y = r->plan.tiles_y;
     bp.qw = r->ctx->tile_qw;
     bp.qh = r->ctx->tile_qh;
     for (int i = 0; i < 4; ++i) bp.background[i] = background ? background[i] : 0.0f;
@@ -1573,7 +1493,7 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     bp.async_staging = r->ctx->blend_async < 0 ? WS_BLEND_ASYNC_DEFAULT : (r->ctx->blend_async ? 1 : 0);
     bp.num_cus = r->ctx->num_cus;
     bp.range_row_shift = 0;
-    bp.bin_tiles_x = r->tiles_x;
+    bp.bin_tiles_x = r->plan.tiles_x;
     if (form.split) {
         bp.qh = 2;
         bp.tiles_y = (r->vh + 15u) / 16u;
@@ -1590,7 +1510,7 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     bp.debug_timing = nullptr;
     bp.trace = r->trace_slot ? r->trace_slot + 2 : nullptr;
     if (r->blend_timing && !r->capture) {
-        const uint32_t nt = r->tiles_x * r->tiles_y;
+        const uint32_t nt = r->plan.ntiles;
         if (r->debug_timing_tiles != nt) {
             WS_HIP(hipStreamSynchronize(stream));
             dfree(r->debug_timing);
@@ -1601,8 +1521,8 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
         bp.debug_timing = r->debug_timing;
     }
     if (bp.debug_consumed) {
-        WS_HIP(hipMemsetAsync(r->debug_consumed, 0, (size_t)r->tiles_x * r->tiles_y * sizeof(uint32_t), stream));
-        WS_HIP(hipMemsetAsync(r->debug_walked, 0, (size_t)r->tiles_x * r->tiles_y * 17 * sizeof(uint32_t), stream));
+        WS_HIP(hipMemsetAsync(r->debug_consumed, 0, (size_t)r->plan.ntiles * sizeof(uint32_t), stream));
+        WS_HIP(hipMemsetAsync(r->debug_walked, 0, (size_t)r->plan.ntiles * 17 * sizeof(uint32_t), stream));
     }
     KernelMarks* km = r->marks.active ? &r->marks : nullptr;
     if (km) km->begin(stream, false);
@@ -1741,7 +1661,7 @@ int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out) {
     WS_TRY(copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream));
     out->num_visible = fc.num_visible;
     out->num_tile_entries = fc.num_entries;
-    out->tile_entries_capacity = r->entry_cap;
+    out->tile_entries_capacity = r->plan.entry_cap;
     out->overflow = fc.overflow;
     return WS_OK;
 }
@@ -1754,8 +1674,8 @@ static int frame_list_counts(ws_renderer* r, uint32_t* shift, uint32_t* lists_x,
     WS_TRY(copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream));
     const uint32_t s = fc.bin_shift;
     *shift = s;
-    *lists_x = (r->tiles_x + s) >> s;
-    *lists_y = (r->tiles_y + s) >> s;
+    *lists_x = (r->plan.tiles_x + s) >> s;
+    *lists_y = (r->plan.tiles_y + s) >> s;
     return WS_OK;
 }
 
@@ -1797,7 +1717,7 @@ int ws_renderer_depth_sort_passes(ws_renderer* r, uint32_t* passes) {
 int ws_renderer_depth_sort_digit_bits(ws_renderer* r, uint32_t* digit_bits) {
     if (!r || !digit_bits) return fail(WS_ERR_INVALID, "ws_renderer_depth_sort_digit_bits: null argument");
     if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_depth_sort_digit_bits: no prepared frame");
-    *digit_bits = (uint32_t)r->depth_bits_this_frame;
+    *digit_bits = (uint32_t)r->plan.depth_digit_bits;
     return WS_OK;
 }
 
@@ -1886,7 +1806,7 @@ int ws_renderer_download_wave_stats(ws_renderer* r, uint32_t tile_capacity, uint
     if (!r || !walked) return fail(WS_ERR_INVALID, "ws_renderer_download_wave_stats: null argument");
     if (!r->prepared || !r->capture)
         return fail(WS_ERR_STATE, "ws_renderer_download_wave_stats: needs ws_renderer_enable_capture and a rendered frame");
-    const uint32_t nt = r->tiles_x * r->tiles_y;
+    const uint32_t nt = r->plan.ntiles;
     if (tile_capacity < nt) return fail(WS_ERR_INVALID, "ws_renderer_download_wave_stats: capacity smaller than the tile count");
     WS_HIP(hipStreamSynchronize(r->last_stream));
     WS_TRY(copy_d2h(walked, r->debug_walked, (size_t)nt * 17 * sizeof(uint32_t), r->last_stream));
@@ -2055,7 +1975,7 @@ int ws_sorter_sort_depth(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, ui
     SortJob job;
     job.kind = SORT_DEPTH;
     job.keys = d_keys, job.vals = d_payload, job.d_count = d_count, job.n = n;
-    job.digit_bits = depth_digit_bits(s->ctx);
+    job.digit_bits = depth_sort_digit_bits(s->ctx->depth_digit_bits, false, 0u, 0);  // (no previous frame, no graph: forced, or the default)
     job.aux = d_aux, job.aux_alt = d_aux ? s->aux_alt : nullptr;
     job.skip_top = skip_top;
     job.kpt9 = s->ctx->depth_tile_kpt ? s->ctx->depth_tile_kpt : 8;
@@ -2194,8 +2114,8 @@ static FrameLists frame_lists(const ws_renderer* r) {
     f.src_index = r->src_index;
     f.width = r->vw;
     f.height = r->vh;
-    f.tiles_x = r->tiles_x;
-    f.tiles_y = r->tiles_y;
+    f.tiles_x = r->plan.tiles_x;
+    f.tiles_y = r->plan.tiles_y;
     f.qw = r->ctx->tile_qw;
     f.qh = r->ctx->tile_qh;
     f.counters = r->counters;

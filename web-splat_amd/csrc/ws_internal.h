@@ -9,6 +9,7 @@
 #include <string>
 
 #include "blend_form.h"
+#include "frame_plan.h"
 #include "websplat.h"
 
 #if defined(_OPENMP) && !defined(__HIP_DEVICE_COMPILE__)
@@ -66,12 +67,7 @@ int hip_fail(hipError_t e, const char* what);
         if (rc_) return rc_;     \
     } while (0)
 
-// ---- geometry of the rasteriser ----------------------------------------------------------------
-// Binning tiles are QW x QH quadrants of 8x8 pixels (one wave each): 2x2 = the north star's 16x16 tile; 4x2 / 4x4
-// bin two / four such tiles into one list (ws_context::tile_qw/qh, WS_TILE_SHAPE).  Default 4x4, by measurement:
-// a 24-px splat touches 8.3 16x16 tiles but 3.7 32x32 ones, so the (tile, splat) entry list -- emit, tile sort,
-// gather -- shrinks 2.2x while the per-quadrant compositing work is unchanged.
-constexpr int QUAD = 8;
+// ---- geometry of the rasteriser (the tile grid: frame_plan.h) ----------------------------------
 constexpr float CUTOFF = 2.3539888583335364f; // gaussian.wgsl:2  sqrt(ln 255)
 constexpr float CUT_A = 2.0f * CUTOFF;        // gaussian.wgsl:61 discard if a > 2*CUTOFF
 constexpr float T_MIN = 1.0f / 16384.0f;      // front-to-back early-out (6.1e-5; DESIGN.md section Blend)
@@ -104,14 +100,6 @@ __device__ __forceinline__ void ws_trace_end(unsigned long long* t) {
 #ifndef WS_BLEND_ASYNC_DEFAULT
 #define WS_BLEND_ASYNC_DEFAULT 0
 #endif
-#ifndef WS_DEPTH_DIGIT_BITS_DEFAULT
-#define WS_DEPTH_DIGIT_BITS_DEFAULT 8
-#endif
-#ifndef WS_DEPTH_DIGIT_BITS_ADAPTIVE   // 1: a renderer picks 8 or 9 bits per frame from its previous frame's key range (ws_api.cpp)
-#define WS_DEPTH_DIGIT_BITS_ADAPTIVE 1
-#endif
-constexpr int RADIX_BITS = 8;
-constexpr int RADIX = 1 << RADIX_BITS;
 
 struct FrameCounters {
     uint32_t num_visible;    // V  (reference: SortInfos.keys_size, preprocess.wgsl:262)
@@ -155,23 +143,8 @@ struct FrameZero {
     // uint2 tile_ranges[tiles] follows
 };
 
-// ---- binning footprint of a splat: the companion value of the depth sort ----------------------------------------
-// K1 stores one 32-bit word per visible splat that says which binning tiles the splat is listed in; it rides through the
-// depth sort with the splat index (sort.hip), so the binning prefix streams it in draw order.  Three forms:
-//   FP_RECT_PACKED (default)  the bounding rectangle of the kept ellipse, x0 | y0 << 8 | (w - 1) << 16 | (h - 1) << 24
-//                  in binning tiles: at most 256 tiles per axis (8192 px at the default 32-px tile); RECT_EMPTY = no
-//                  tile.  k_bin_emit derives a tile from the word alone.
-//   FP_RECT_COUNT  the NUMBER of tiles of the same rectangle; k_bin_emit re-derives the rectangle from the 12 geometry
-//                  bytes of the Splat record (footprint.h).  Taken automatically for viewports beyond 256 tiles per axis:
-//                  any target the reference can create (it asks for the adapter's own max_texture_dimension_2d,
-//                  src/lib.rs:99-110) is accepted, at the price of a slower emit kernel.
-//   FP_ELLIPSE     the number of tiles the kept ELLIPSE reaches (per tile row the exact column span, footprint.h):
-//                  15 % fewer entries on the 1 M / 1080p scene, but the span arithmetic costs more VALU time in K1 and
-//                  k_bin_emit than the entries cost downstream (profiles/r03/footprint_*) -- WS_FOOTPRINT=ellipse.
-enum FootprintMode { FP_RECT_PACKED = 0, FP_RECT_COUNT = 1, FP_ELLIPSE = 2 };
+// ---- the footprint word of a splat (FootprintMode, frame_plan.h) ----------------------------------------------------
 constexpr uint32_t RECT_EMPTY = 0xFFFFFFFFu;
-constexpr uint32_t RECT_PACKED_MAX_TILES_PER_AXIS = 256u;
-constexpr uint32_t MAX_TILES_PER_AXIS = 65535u;  // tile coordinates are 16-bit (the blend packs tx | ty << 16)
 __host__ __device__ inline uint32_t rect_pack(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
     return x0 | (y0 << 8) | ((x1 - x0) << 16) | ((y1 - y0) << 24);
 }
@@ -179,15 +152,7 @@ __host__ __device__ inline uint32_t rect_tiles(uint32_t r) {
     return r == RECT_EMPTY ? 0u : (((r >> 16) & 0xFFu) + 1u) * ((r >> 24) + 1u);
 }
 
-// ---- binning granularity, decided PER FRAME ON THE DEVICE -----------------------------------------------------------
-// The blend composites 32x32-px tiles (default shape).  Binning may use those tiles, or 2 x 2 blocks of them (64x64 px):
-// four blend workgroups then share one binned list -- half the (tile, splat) entries to emit and sort when splats span
-// several tiles, at the price of every entry being staged by up to four workgroups.  Measured (profiles/r03/bin64_*):
-// +16..+20 % frames/s where the rectangles shrink 2.07x (hd1m, c4), +3..+5 % at 1.75x (c2), -14 % / -23 % at 1.14x / 1.10x
-// (c5, c3: pixel-sized splats); an N x resolution sweep (profiles/r03/sweep_bin_auto_v24.json) has 64 px ahead (+1..+63 %) at
-// all ratios 1.75..2.63 and by +4 % on average (-3..+13 %) at 1.53: the threshold sits just below the smallest ratio measured to win.  K1 sums both tile counts while it writes the rectangles; the binning prefix derives
-// the decision from the two sums (a pure function of the frame: ranks and renderers agree), no host round trip.
-enum BinRequest { BIN_NEVER = 0, BIN_AUTO = 1, BIN_ALWAYS = 2 };
+// ---- binning granularity, decided PER FRAME ON THE DEVICE (BinRequest, frame_plan.h) ----------------------------------
 #ifndef WS_BIN64_RATIO_PERCENT
 #define WS_BIN64_RATIO_PERCENT 150
 #endif
@@ -306,23 +271,7 @@ inline void km_mark(KernelMarks* km, const char* what) {
     if (km && km->active) km->mark(what);
 }
 
-// ---- sort ---------------------------------------------------------------------------------------
-constexpr int SORT_THREADS = 256;
-#ifndef WS_SORT_KPT
-#define WS_SORT_KPT 8
-#endif
-constexpr int SORT_KPT = WS_SORT_KPT;                 // keys per thread
-constexpr int SORT_TILE = SORT_THREADS * SORT_KPT;    // keys per work tile
-constexpr int SORT_KPT_SMALL = 4;                     // small inputs: 1024-key tiles -> 4x the workgroups
-#ifndef WS_SORT_SMALL_MAX
-#define WS_SORT_SMALL_MAX (2u << 20)
-#endif
-constexpr uint32_t SORT_SMALL_MAX = WS_SORT_SMALL_MAX;  // host-side bound n up to which the small tile is used
-uint32_t sort_tile_size(uint32_t n);                  // tile size the scan path (the production sort) uses for bound n
-
-// Single-pass tile-id sort (launch_tile_sort_wide): the whole tile id is ONE digit of up to 11 bits.
-constexpr int TILE_SORT_WIDE_MAX_BITS = 11;
-constexpr int TILE_SORT_WIDE_MAX_BINS = 1 << TILE_SORT_WIDE_MAX_BITS;
+// ---- sort (tile sizes and digit widths: frame_plan.h) -------------------------------------------
 
 struct SortScratch {
     uint32_t* keys_alt = nullptr;     // ping-pong partner of the caller's key buffer   [cap]
@@ -451,8 +400,6 @@ const void* preprocess_kernel_func(bool compressed, int footprint_mode, bool dep
 uint32_t preprocess_blocks(uint32_t n);
 
 // ---- binning + blend ----------------------------------------------------------------------------
-constexpr int EMIT_TILE = SORT_TILE;  // tile entries produced per workgroup of the emit kernel (= the sort's tile)
-
 struct BinBuffers {
     const uint32_t* sorted_idx;  // [V] store indices in draw order (far -> near)
     const uint32_t* fp_sorted;   // [N] footprint words by draw position (carried through the depth sort)
