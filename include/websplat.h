@@ -846,7 +846,8 @@ int  ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws
  * up to f32 rounding: the squared error the frame would gain if j were deleted alone.  Where quadrants saturate, F is the FAST
  * blend's own image, which ignores what lies behind the stop: a deletion that would un-saturate a pixel is under-reported by at
  * most r * 2^-14 * colour per pair.
- * Out of scope: gradients, a per-Gaussian image of D, and the joint effect of deleting several Gaussians (it is not additive).
+ * Out of scope: a per-Gaussian image of D, and the joint effect of deleting several Gaussians (it is not additive; the additive
+ * first-order score is the opacity sum of "Gradients of an image loss" below).
  * Errors: state and size errors as ws_renderer_accumulate_contrib; WS_ERR_INVALID for null params, an unknown kind
  * (WS_ERROR_DSSIM included), a scale that is not finite and above 0, a non-finite background, a weight view with a null
  * d_values, a non-finite scale or bias, a pointer or pitch not a multiple of 4 or a pitch below 4 * width, a d_base or
@@ -867,6 +868,84 @@ typedef struct ws_removal_params {
 int  ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_removal_params* p, void* stream); /* enqueues; counts as a frame of c */
 int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, int kind, float scale,
                                  ws_contrib* effect, ws_contrib* weight /* may be NULL: the plain contribution sums of the same frames */, uint32_t* frames);
+/* ---- Gradients of an image loss: dL/d(colour) and dL/d(ln opacity) per Gaussian (no counterpart in the reference) --------------
+ * What a refit of the colours and opacities of a (pruned) cloud needs.  The prepared frame is LINEAR in each splat's colour and
+ * AFFINE in each splat's per-pixel opacity b_i(p): with F, T_end, w, r, D, P of "Removal effect",
+ *   dF(p) / dc_i = w_i(p),     b_i * dF(p) / db_i = -D_i(p),     b_i * dT_end(p) / db_i = -r_i * T_end(p)
+ * (taking b_i out moves the pixel by D_i = r_i S_i - w_i c_i, and F is affine in b_i, so D_i = -b_i dF/db_i; T_end carries the
+ * factor 1 - b_i, and b_i / (1 - b_i) = r_i).  The caller supplies a plane g of one float4 per viewport pixel,
+ *   g(p) = (dL/dF_r, dL/dF_g, dL/dF_b, dL/dT_end),   F and T_end those of "Removal effect", pass 1, over `background`,
+ * and per source Gaussian j the call adds four sums over the pairs (p, i) with src(i) = j:
+ *   colour[j][ch] += sum_p w_i(p) * G_ch(p)          ch = r, g, b: the loss's derivative with respect to an offset added to the
+ *                                                    Gaussian's colour BEFORE K1's clamp at 0 (preprocess.wgsl:258): a pair whose
+ *                                                    staged c_ch is exactly 0 adds nothing to channel ch
+ *   opacity[j]    += -sum_p (G_r D_r + G_g D_g + G_b D_b + G_T r T_end(p))
+ *                                                    the derivative with respect to ln of a common factor on every b_i(p) of the
+ *                                                    Gaussian, dL/d ln(alpha); pairs whose b sits on the 0.99 clamp add nothing
+ * Preconditions as for ws_renderer_accumulate_removal: a prepared frame, ws_renderer_enable_contrib(r, 1) before prepare().  The
+ * call enqueues two launches on `stream` behind the prepared frame, makes no blend launch and changes no target.
+ * PAIRS AND WEIGHTS.  The pairs walked, b, w = b * T, T <- T - w, the quadrant's stop and the batch loop's stop are exactly those
+ * of "Per-Gaussian contributions" in the same context.  No argument of this call influences them.
+ * THE PLANE.  G_k(p) = min(max(scale * g_k(p), -1), 1) in f32: one rounded multiply, NaN -> 0, read once per pixel as one 16-byte
+ * load; nothing past a row's width-th float4 is read; scale is finite and > 0.  A quadrant whose 64 x 4 values of G are all 0 is
+ * idle in pass 2; pass 1 is never idle.
+ * PASS 1.  Removal's base image, unchanged (the same kernel): base(p) = (F_r, F_g, F_b, T_end), to d_base or to the renderer's
+ * scratch, which the two calls share.
+ * PASS 2, PER WALKED PAIR.  Tb, T, P_ch as "Removal effect" pass 2 keeps them: the same operations in the same order.  Then
+ *   colour, per ch:  v_ch = w * G_ch, one rounded multiply; counted iff the pair is kept, w > 0 and c_ch > 0; |v_ch| < 1 (b <= 0.99)
+ *   opacity:  counted iff the pair is kept, w > 0, Tb >= 2^-14 (removal's rule) and the pair is NOT CLAMPED; it is clamped iff
+ *     w == 0x1.fae148p-1f * Tb (one rounded f32 multiply): the only way min(0.99, ...) shows in b * T
+ *     r, s_ch, t_ch, d_ch exactly removal's
+ *     a = G_r * d_r (rounded);  a = fma(G_g, d_g, a);  a = fma(G_b, d_b, a);  u = r * T_end (rounded);  a = fma(G_T, u, a)
+ *     v_o = -min(max(opacity_scale * a, -0x1.fffffep-1f), 0x1.fffffep-1f), NaN -> 0; opacity_scale finite and > 0 (|d| can reach
+ *     r * colour with r up to 99); the cap is removal's and silent, as there
+ * every step a separately rounded f32 operation except the fused ones named.
+ * ACCUMULATION.  q = (int64_t)(v * 2^32): the product is exact, |q| < 2^32, the conversion truncates TOWARD ZERO.  Four int64
+ * sums per Gaussian, added through the source index; integer sums commute, so the result depends on the order of nothing:
+ * bitwise reproducible, mergeable with ws_grad_add, exact across ranks.  sum / (2^32 * scale) is the colour gradient,
+ * sum / (2^32 * scale * opacity_scale) the opacity gradient.  Bit for bit: (a) g and -g give exactly negated sums; (b) a plane
+ * restricted to a 0/1 mask and to its complement add up to the whole; (c) with g = (E, 0, 0, 0), E in [0, 1], scale 1,
+ * colour[j][r] equals sum_q32[j] of ws_renderer_accumulate_weighted with that E through scale 1, bias 0, for every Gaussian whose
+ * red is above 0 in the frame -- with E == 1 everywhere, ws_renderer_accumulate_contrib's sum.
+ * THE STOPS.  As "Removal effect": F ignores what lies behind a stop, so a pair's opacity term is under-reported by at most
+ * r * 2^-14 * colour * |G|.
+ * Out of scope: gradients with respect to position, covariance and the higher SH coefficients; an optimiser; writing a refitted
+ * cloud to disk.
+ * Errors: as ws_renderer_accumulate_removal, judged from the descriptor before a handle is looked at; in addition
+ * WS_ERR_INVALID for a null d_grad, a gradient pointer or pitch that is not a multiple of 16, a pitch below 16 * width, a scale
+ * or opacity_scale that is not finite and above 0.
+ * ws_grad: four int64 sums per Gaussian in device memory, zeroed at creation and by ws_grad_reset; ws_grad_download syncs and
+ * copies [num_points][4] (colour r, g, b; ln-opacity); ws_grad_add adds another accumulator's (or rank's) downloaded sums, exactly.
+ * ws_image_error_gradient: kernel beside ws_image_error_plane's, one thread per pixel (enqueues only).  Both pixel values are as
+ * "Image metrics" defines them, WS_METRICS_QUANTIZE_U8 is refused; per colour channel d = x - y, g = (2 * d) / 3.0f (WS_ERROR_SQ:
+ * one rounded multiply, IEEE division) or copysign(1 / 3.0f, d), 0 at d == 0 (WS_ERROR_ABS); g = 0 where a's value before the
+ * clamp lay outside [0, 1] or was NaN; the fourth component is 0.  So sum g * dx is the first-order change of the sum of
+ * ws_image_error_plane's plane.  Image a may be the base plane itself: rgba32float, over_background = 0 (the alpha slot holds
+ * T_end and is ignored).  d_grad: float4 per pixel, pointer and pitch multiples of 16, pitch >= 16 * width.
+ * ws_scene_accumulate_gradient: cameras, image b and PNG handling exactly those of ws_scene_accumulate_error (they share that
+ * set-up); per camera: prepare, the base image over the cloud's background (black if none), ws_image_error_gradient(base, b),
+ * accumulate.  One stream, one sync at the end; *frames = cameras added; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule. */
+typedef struct ws_grad ws_grad;                 /* four int64 sums per Gaussian, device memory, zeroed */
+#define WS_GRAD_CHANNELS 4                      /* colour r, g, b; ln-opacity */
+#define WS_GRAD_SUM_SCALE 4294967296.0
+int  ws_grad_create(ws_context* ctx, uint32_t num_points, ws_grad** out);
+void ws_grad_destroy(ws_grad* g);
+int  ws_grad_reset(ws_grad* g, void* stream);
+uint32_t ws_grad_num_points(const ws_grad* g);
+uint32_t ws_grad_frames(const ws_grad* g);
+int  ws_grad_download(ws_grad* g, uint32_t capacity, int64_t* q32 /* [capacity][4] */);   /* syncs */
+int  ws_grad_add(ws_grad* g, const int64_t* q32, uint32_t n);                             /* exact merge of another rank's */
+typedef struct ws_gradient_params {
+    float background[3]; float scale; float opacity_scale; uint32_t reserved0;   /* scales finite, > 0; reserved0 zero */
+    const float* d_grad; size_t grad_pitch_bytes;      /* float4 per pixel, 16-B aligned pointer and pitch >= 16 * width, multiple of 16 */
+    float* d_base; size_t base_pitch_bytes;            /* may be NULL, as ws_removal_params */
+    uint32_t reserved[4];                              /* zero */
+} ws_gradient_params;
+int  ws_renderer_accumulate_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream); /* enqueues; counts as a frame of g */
+int  ws_image_error_gradient(ws_context* ctx, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, int kind,
+                             uint32_t flags, float* d_grad, size_t grad_pitch_bytes, void* stream);
+int  ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                                  const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

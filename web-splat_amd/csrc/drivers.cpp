@@ -498,6 +498,103 @@ int ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* 
     return rc;
 }
 
+// The frames of ws_scene_accumulate_error and ws_scene_accumulate_gradient: every camera of `split` set up as ws_scene_evaluate
+// sets it up -- `pc` prepared with contributions on (and, render_a, drawn into an Rgba16Float target), image b the render of
+// `ref_pc` or the ground-truth PNG, a scratch plane of plane_texel bytes per pixel -- then per_frame, all on one stream; one sync
+// and one look at the error bits at the end.
+extern "C++" {
+namespace {
+struct ErrorFrame {
+    ws_renderer* r;
+    uint32_t w, h;
+    ws_image_view va, vb;  // pc's render over the background (render_a only), and what it is compared with
+    void* plane;
+};
+template <class PerFrame>
+int over_error_frames(const std::string& who, ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split,
+                      const ws_pointcloud* ref_pc, const char* gt_dir, size_t plane_texel, bool render_a, uint32_t* frames,
+                      PerFrame&& per_frame) {
+    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
+    std::vector<ws_scene_camera> cams(n);
+    ws_scene_cameras(scene, split, n, cams.data());
+    float bg[3];
+    eval_background(pc, bg);
+    size_t cloud_px = 0;  // ref_pc: every frame's size is known up front, nothing is reallocated on the way
+    if (ref_pc) {
+        bool sizes_ok;
+        cloud_px = eval_max_pixels(cams, &sizes_ok);
+        if (!sizes_ok) return fail(WS_ERR_INVALID, who + ": camera with an empty image");
+    }
+    ws_renderer *r = nullptr, *rb = nullptr;
+    EvalBuffers eb;
+    void* plane = nullptr;
+    size_t plane_px = 0;
+    int rc = eval_renderer(ctx, pc, &r);
+    if (rc == WS_OK) rc = ws_renderer_enable_contrib(r, 1);
+    if (rc == WS_OK && ref_pc) rc = eval_renderer(ctx, ref_pc, &rb);
+    const float clear[4] = {0, 0, 0, 0};
+    uint32_t done = 0;
+    for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
+        const ws_scene_camera& c = cams[i];
+        uint32_t w = 0, h = 0;
+        uint8_t* rgba = nullptr;
+        if (ref_pc) capped_size(c, &w, &h);
+        else if ((rc = truth_read(who.c_str(), gt_dir, c, &w, &h, &rgba))) break;
+        const size_t px = (size_t)w * h;
+        rc = eval_buffers_reserve(ctx, &eb, ref_pc ? cloud_px : px, ref_pc ? 8 : 4);
+        if (rc == WS_OK && eb.capacity > plane_px) {
+            if (plane) ws_device_free(ctx, plane);
+            plane = nullptr;
+            plane_px = 0;
+            if ((rc = ws_device_malloc(ctx, eb.capacity * plane_texel, &plane)) == WS_OK) plane_px = eb.capacity;
+        }
+        if (rc == WS_OK && !ref_pc) rc = truth_upload(ctx, &eb, rgba, px);
+        if (rgba) ws_host_free(rgba);
+        ws_splatting_args a;
+        if (rc == WS_OK) {
+            offline_args(c, pc, w, h, &a);
+            rc = ws_renderer_prepare(r, pc, &a, nullptr);
+        }
+        if (rc == WS_OK && render_a) rc = ws_renderer_render(r, pc, clear, eb.target, (size_t)w * 8, nullptr);
+        if (rc == WS_OK && ref_pc) {
+            ws_splatting_args ab;
+            offline_args(c, ref_pc, w, h, &ab);
+            rc = ws_renderer_prepare(rb, ref_pc, &ab, nullptr);
+            if (rc == WS_OK) rc = ws_renderer_render(rb, ref_pc, clear, eb.other, (size_t)w * 8, nullptr);
+        }
+        if (rc != WS_OK) break;
+        const ErrorFrame f{r, w, h, view_of(eb.target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg),
+                           ref_pc ? view_of(eb.other, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg)
+                                  : view_of(eb.other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr),  // opaque: alpha ignored
+                           plane};
+        // (the next frame's renders and plane are ordered behind these on the stream: targets and plane are reused)
+        rc = per_frame(f);
+        if (rc == WS_OK) ++done;
+    }
+    if (rc == WS_OK) {
+        uint32_t all_bits = 0;
+        ws_renderer* both[2] = {r, rb};
+        for (int k = 0; k < 2 && rc == WS_OK; ++k) {  // (the one sync)
+            uint32_t bits = 0;
+            if (both[k]) rc = ws_renderer_errors(both[k], &bits, nullptr, 1);
+            all_bits |= bits;
+        }
+        if (rc == WS_OK && all_bits)
+            rc = fail(WS_ERR_OVERFLOW, who + ": a frame reported device-side errors (tile-entry overflow or a look-back "
+                                             "time-out): the accumulators are incomplete");
+    } else {
+        (void)ws_sync(ctx, nullptr);
+    }
+    if (frames) *frames = done;
+    if (plane) ws_device_free(ctx, plane);
+    eval_buffers_free(ctx, &eb);
+    if (rb) ws_renderer_destroy(rb);
+    if (r) ws_renderer_destroy(r);
+    return rc;
+}
+}  // namespace
+}  // extern "C++"
+
 // Every camera of `split` blamed on the Gaussians of `pc` (websplat.h "Attributing a pixel plane to Gaussians"): the frames of
 // ws_scene_evaluate, their per-pixel error against `ref_pc` or the ground-truth PNGs, and the weighted contribution sums.
 int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
@@ -513,99 +610,67 @@ int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws
     if (ws_contrib_num_points(err) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
         return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: an accumulator was created for another number of points");
     if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_error: the context stops its frames early (debug_cut)");
-    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
-    std::vector<ws_scene_camera> cams(n);
-    ws_scene_cameras(scene, split, n, cams.data());
-    float bg[3];
-    eval_background(pc, bg);
-    size_t cloud_px = 0;  // ref_pc: every frame's size is known up front, nothing is reallocated on the way
-    if (ref_pc) {
-        bool sizes_ok;
-        cloud_px = eval_max_pixels(cams, &sizes_ok);
-        if (!sizes_ok) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: camera with an empty image");
-    }
-    ws_renderer *r = nullptr, *rb = nullptr;
     ws_metrics* ssim = nullptr;  // WS_ERROR_DSSIM: one slot, written again by every frame; only its map is used
-    EvalBuffers eb;
-    void* plane = nullptr;
-    size_t plane_px = 0;
-    int rc = eval_renderer(ctx, pc, &r);
-    if (rc == WS_OK) rc = ws_renderer_enable_contrib(r, 1);
-    if (rc == WS_OK && ref_pc) rc = eval_renderer(ctx, ref_pc, &rb);
-    if (rc == WS_OK && kind == WS_ERROR_DSSIM) rc = ws_metrics_create(ctx, 1, &ssim);
-    const float clear[4] = {0, 0, 0, 0};
-    uint32_t done = 0;
-    for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
-        const ws_scene_camera& c = cams[i];
-        uint32_t w = 0, h = 0;
-        uint8_t* rgba = nullptr;
-        if (ref_pc) capped_size(c, &w, &h);
-        else if ((rc = truth_read("ws_scene_accumulate_error", gt_dir, c, &w, &h, &rgba))) break;
-        const size_t px = (size_t)w * h;
-        rc = eval_buffers_reserve(ctx, &eb, ref_pc ? cloud_px : px, ref_pc ? 8 : 4);
-        if (rc == WS_OK && eb.capacity > plane_px) {
-            if (plane) ws_device_free(ctx, plane);
-            plane = nullptr;
-            plane_px = 0;
-            if ((rc = ws_device_malloc(ctx, eb.capacity * 4, &plane)) == WS_OK) plane_px = eb.capacity;
-        }
-        if (rc == WS_OK && !ref_pc) rc = truth_upload(ctx, &eb, rgba, px);
-        if (rgba) ws_host_free(rgba);
-        ws_splatting_args a;
-        if (rc == WS_OK) {
-            offline_args(c, pc, w, h, &a);
-            rc = ws_renderer_prepare(r, pc, &a, nullptr);
-        }
-        if (rc == WS_OK) rc = ws_renderer_render(r, pc, clear, eb.target, (size_t)w * 8, nullptr);
-        if (rc == WS_OK && ref_pc) {
-            ws_splatting_args ab;
-            offline_args(c, ref_pc, w, h, &ab);
-            rc = ws_renderer_prepare(rb, ref_pc, &ab, nullptr);
-            if (rc == WS_OK) rc = ws_renderer_render(rb, ref_pc, clear, eb.other, (size_t)w * 8, nullptr);
-        }
-        if (rc != WS_OK) break;
-        const ws_image_view va = view_of(eb.target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
-        const ws_image_view vb = ref_pc ? view_of(eb.other, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg)
-                                        : view_of(eb.other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr);  // opaque: alpha ignored
-        ws_plane_view pv;
-        pv.d_values = static_cast<const float*>(plane);
-        pv.row_pitch_bytes = (size_t)w * 4;
-        pv.scale = 1.0f;
-        pv.bias = 0.0f;
-        if (kind == WS_ERROR_DSSIM) {  // (1 - ssim) / 2 of the map
-            rc = ws_metrics_reset(ssim, nullptr);
-            if (rc == WS_OK) rc = ws_metrics_add(ssim, &va, &vb, w, h, flags, static_cast<float*>(plane), (size_t)w * 4, nullptr);
-            pv.scale = -0.5f;
-            pv.bias = 0.5f;
-        } else {
-            rc = ws_image_error_plane(ctx, &va, &vb, w, h, kind, flags, static_cast<float*>(plane), (size_t)w * 4, nullptr);
-        }
-        // (the next frame's renders and plane are ordered behind these on the stream: targets and plane are reused)
-        if (rc == WS_OK) rc = ws_renderer_accumulate_weighted(r, pc, err, &pv, nullptr);
-        if (rc == WS_OK && weight) rc = ws_renderer_accumulate_contrib(r, pc, weight, nullptr);
-        if (rc == WS_OK) ++done;
-    }
-    if (rc == WS_OK) {
-        uint32_t all_bits = 0;
-        ws_renderer* both[2] = {r, rb};
-        for (int k = 0; k < 2 && rc == WS_OK; ++k) {  // (the one sync)
-            uint32_t bits = 0;
-            if (both[k]) rc = ws_renderer_errors(both[k], &bits, nullptr, 1);
-            all_bits |= bits;
-        }
-        if (rc == WS_OK && all_bits)
-            rc = fail(WS_ERR_OVERFLOW, "ws_scene_accumulate_error: a frame reported device-side errors (tile-entry overflow or a look-back "
-                                       "time-out): the accumulators are incomplete");
-    } else {
-        (void)ws_sync(ctx, nullptr);
-    }
-    if (frames) *frames = done;
+    int rc = kind == WS_ERROR_DSSIM ? ws_metrics_create(ctx, 1, &ssim) : WS_OK;
+    if (rc == WS_OK)
+        rc = over_error_frames("ws_scene_accumulate_error", ctx, pc, scene, split, ref_pc, gt_dir, 4, true, frames, [&](const ErrorFrame& f) {
+            ws_plane_view pv;
+            pv.d_values = static_cast<const float*>(f.plane);
+            pv.row_pitch_bytes = (size_t)f.w * 4;
+            pv.scale = 1.0f;
+            pv.bias = 0.0f;
+            int frc;
+            if (kind == WS_ERROR_DSSIM) {  // (1 - ssim) / 2 of the map
+                frc = ws_metrics_reset(ssim, nullptr);
+                if (frc == WS_OK) frc = ws_metrics_add(ssim, &f.va, &f.vb, f.w, f.h, flags, static_cast<float*>(f.plane), (size_t)f.w * 4, nullptr);
+                pv.scale = -0.5f;
+                pv.bias = 0.5f;
+            } else {
+                frc = ws_image_error_plane(ctx, &f.va, &f.vb, f.w, f.h, kind, flags, static_cast<float*>(f.plane), (size_t)f.w * 4, nullptr);
+            }
+            if (frc == WS_OK) frc = ws_renderer_accumulate_weighted(f.r, pc, err, &pv, nullptr);
+            if (frc == WS_OK && weight) frc = ws_renderer_accumulate_contrib(f.r, pc, weight, nullptr);
+            return frc;
+        });
     if (ssim) ws_metrics_destroy(ssim);
-    if (plane) ws_device_free(ctx, plane);
-    eval_buffers_free(ctx, &eb);
-    if (rb) ws_renderer_destroy(rb);
-    if (r) ws_renderer_destroy(r);
     return rc;
+}
+
+// ... and the colour and ln-opacity gradients of that error (websplat.h "Gradients of an image loss"): image a is the frame's
+// f32 base plane over the cloud's background, the first half of the scratch plane; the loss gradient is the second half.
+int ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                                 const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames) {
+    const std::string who("ws_scene_accumulate_gradient");
+    if (frames) *frames = 0;
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
+    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
+    if (!std::isfinite(opacity_scale) || !(opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL) return fail(WS_ERR_INVALID, who + ": split must be train, test or all");
+    if (!ctx || !pc || !scene || !grad) return fail(WS_ERR_INVALID, who + ": null argument");
+    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, who + ": exactly one of ref_pc and gt_dir");
+    if (ws_grad_num_points(grad) != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
+    ws_gradient_params gp;
+    std::memset(&gp, 0, sizeof gp);
+    eval_background(pc, gp.background);
+    gp.scale = scale;
+    gp.opacity_scale = opacity_scale;
+    return over_error_frames(who, ctx, pc, scene, split, ref_pc, gt_dir, 32, false, frames, [&](const ErrorFrame& f) {
+        const size_t pitch = (size_t)f.w * 16;
+        float* base = static_cast<float*>(f.plane);
+        float* g = base + (size_t)f.w * f.h * 4;
+        ws_gradient_params p = gp;
+        p.d_base = base;
+        p.base_pitch_bytes = pitch;
+        p.d_grad = g;
+        p.grad_pitch_bytes = pitch;
+        // the call in its two steps: the plane is made of pass 1's image
+        int frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 1u);
+        const ws_image_view va = view_of(base, WS_FORMAT_RGBA32_FLOAT, pitch, nullptr);  // (the alpha slot holds T_end: ignored)
+        if (frc == WS_OK) frc = ws_image_error_gradient(ctx, &va, &f.vb, f.w, f.h, kind, 0, g, pitch, nullptr);
+        if (frc == WS_OK) frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 2u);
+        return frc;
+    });
 }
 
 int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, uint32_t num_samples,

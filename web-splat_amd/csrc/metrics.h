@@ -44,12 +44,16 @@ inline uint32_t metrics_num_tiles(uint32_t w, uint32_t h) {
 }
 // k_image_error: plane[p] = the mean over the three colour channels of e = d * d (WS_ERROR_SQ) or |d| (WS_ERROR_ABS), d = x - y on
 // the PIXEL VALUES k_image_metrics compares (the same device function), ((e_r + e_g) + e_b) / 3.0f in f32, one thread per pixel
+// k_image_error_grad (gradient != 0): per pixel the float4 (g_r, g_g, g_b, 0), g_ch the derivative of that plane's value with
+// respect to a's pixel value: d = x - y; (2 * d) / 3.0f (SQ: one rounded multiply, IEEE division) or copysign(1 / 3.0f, d), 0 at
+// d == 0 (ABS); 0 where a's value before the clamp lay outside [0, 1] or was NaN.  No quantisation.
 struct ImageErrorParams {
     MetricsView a, b;
     uint32_t width, height, flags;
     int kind;                    // WS_ERROR_SQ / WS_ERROR_ABS
     float* plane;                // W x H
     size_t plane_pitch;          // bytes
+    int gradient = 0;            // k_image_error_grad instead: plane holds one float4 per pixel
 };
 int launch_image_error(const ImageErrorParams& p, hipStream_t stream);
 

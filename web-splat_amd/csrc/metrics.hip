@@ -19,6 +19,8 @@
 //                        partial record per workgroup with ordinary vector stores.
 //   k_image_error      : the per-pixel error plane of ws_image_error_plane: one thread per pixel, the two texels through the same
 //                        texel_load / pixel_value, no reduction and no atomics.
+//   k_image_error_grad : beside it, the derivative of that plane's value with respect to image a's pixel value, one float4
+//                        per pixel (ws_image_error_gradient): the loss gradient k_gradient (gradient.hip) takes.
 //   k_metrics_finalize : one workgroup behind it: thread t adds records t, t + 256, ... in index order, the 256 sums are
 //                        folded by a fixed tree, and the image's record goes to the accumulator.  Bitwise reproducible.
 #include <hip/hip_fp16.h>
@@ -48,13 +50,17 @@ __device__ __forceinline__ float h2f(uint32_t bits) { return __half2float(__usho
 
 // The pixel value of websplat.h, one channel: three separately rounded operations over the background, clamp with NaN -> 0,
 // optional quantisation by truncation
-__device__ __forceinline__ float channel_value(float c, float a, const MetricsView& v, int ch, bool quantize) {
+__device__ __forceinline__ float channel_over(float c, float a, const MetricsView& v, int ch) {  // (before the clamp)
     float r = c;
     if (v.over_bg) {
         const float k = __fsub_rn(1.0f, a);
         const float t = __fmul_rn(v.bg[ch], k);
         r = __fadd_rn(c, t);
     }
+    return r;
+}
+__device__ __forceinline__ float channel_value(float c, float a, const MetricsView& v, int ch, bool quantize) {
+    float r = channel_over(c, a, v, ch);
     r = (r != r) ? 0.0f : fminf(fmaxf(r, 0.0f), 1.0f);
     if (quantize) {
         const uint32_t q = (uint32_t)__fmul_rn(r, 255.0f);  // truncation: ws_download_texture_rgba8's rule
@@ -79,7 +85,7 @@ __device__ __forceinline__ uint4 texel_load(const MetricsView& v, int x, int y) 
     }
 }
 template <int FORMAT>
-__device__ __forceinline__ float3 pixel_value(const MetricsView& v, uint4 t, bool quantize) {
+__device__ __forceinline__ float4 texel_decode(uint4 t) {
     float r, g, b, a;
     if constexpr (FORMAT == WS_FORMAT_RGBA32_FLOAT) {
         r = __uint_as_float(t.x); g = __uint_as_float(t.y); b = __uint_as_float(t.z); a = __uint_as_float(t.w);
@@ -89,7 +95,12 @@ __device__ __forceinline__ float3 pixel_value(const MetricsView& v, uint4 t, boo
         r = (float)(t.x & 255u) / 255.0f; g = (float)((t.x >> 8) & 255u) / 255.0f;
         b = (float)((t.x >> 16) & 255u) / 255.0f; a = (float)(t.x >> 24) / 255.0f;
     }
-    return make_float3(channel_value(r, a, v, 0, quantize), channel_value(g, a, v, 1, quantize), channel_value(b, a, v, 2, quantize));
+    return make_float4(r, g, b, a);
+}
+template <int FORMAT>
+__device__ __forceinline__ float3 pixel_value(const MetricsView& v, uint4 t, bool quantize) {
+    const float4 c = texel_decode<FORMAT>(t);
+    return make_float3(channel_value(c.x, c.w, v, 0, quantize), channel_value(c.y, c.w, v, 1, quantize), channel_value(c.z, c.w, v, 2, quantize));
 }
 
 // fixed trees over the wave's 64 lanes: the total ends in lane 0
@@ -249,6 +260,27 @@ __global__ __launch_bounds__(EW * EH) void k_image_error(const ImageErrorParams 
         __fdiv_rn(__fadd_rn(__fadd_rn(er, eg), eb), 3.0f);
 }
 
+// One channel of k_image_error_grad: the derivative of k_image_error's plane value with respect to image a's pixel value
+__device__ __forceinline__ float error_grad(float raw, float x, float y, bool sq) {
+    if (!(raw >= 0.0f && raw <= 1.0f)) return 0.0f;  // a's value sits on the clamp (or was NaN): it does not move with the texel
+    const float d = __fsub_rn(x, y);
+    if (sq) return __fdiv_rn(__fmul_rn(2.0f, d), 3.0f);
+    return d == 0.0f ? 0.0f : copysignf(__fdiv_rn(1.0f, 3.0f), d);
+}
+
+template <int FA, int FB>
+__global__ __launch_bounds__(EW * EH) void k_image_error_grad(const ImageErrorParams p) {
+    const int x = (int)blockIdx.x * EW + (int)(threadIdx.x & (EW - 1)), y = (int)blockIdx.y * EH + (int)(threadIdx.x / EW);
+    if (x >= (int)p.width || y >= (int)p.height) return;
+    const uint4 ta = texel_load<FA>(p.a, x, y), tb = texel_load<FB>(p.b, x, y);
+    const float4 ca = texel_decode<FA>(ta);
+    const float3 va = pixel_value<FA>(p.a, ta, false), vb = pixel_value<FB>(p.b, tb, false);
+    const bool sq = p.kind == WS_ERROR_SQ;
+    const float4 g = make_float4(error_grad(channel_over(ca.x, ca.w, p.a, 0), va.x, vb.x, sq), error_grad(channel_over(ca.y, ca.w, p.a, 1), va.y, vb.y, sq),
+                                 error_grad(channel_over(ca.z, ca.w, p.a, 2), va.z, vb.z, sq), 0.0f);
+    *reinterpret_cast<float4*>(reinterpret_cast<char*>(p.plane) + (size_t)y * p.plane_pitch + (size_t)x * 16) = g;
+}
+
 __global__ __launch_bounds__(NT) void k_metrics_finalize(const MetricsPartial* __restrict__ slab, uint32_t n,
                                                          MetricsRecord* __restrict__ record, uint32_t width, uint32_t height,
                                                          uint32_t flags) {
@@ -310,13 +342,13 @@ int launch_image_error(const ImageErrorParams& p, hipStream_t stream) {
     const uint32_t gx = (p.width + EW - 1) / EW, gy = (p.height + EH - 1) / EH;
     if (gx == 0 || gy == 0 || gy > 65535u) return fail(WS_ERR_INVALID, "launch_image_error: image size");
     typedef void (*Kernel)(const ImageErrorParams);
-#define WS_ERROR_ROW(FA) \
-    {k_image_error<FA, WS_FORMAT_RGBA8_UNORM>, k_image_error<FA, WS_FORMAT_RGBA16_FLOAT>, k_image_error<FA, WS_FORMAT_RGBA32_FLOAT>}
-    static const Kernel kernels[3][3] = {WS_ERROR_ROW(WS_FORMAT_RGBA8_UNORM), WS_ERROR_ROW(WS_FORMAT_RGBA16_FLOAT),
-                                         WS_ERROR_ROW(WS_FORMAT_RGBA32_FLOAT)};
+#define WS_ERROR_ROW(K, FA) {K<FA, WS_FORMAT_RGBA8_UNORM>, K<FA, WS_FORMAT_RGBA16_FLOAT>, K<FA, WS_FORMAT_RGBA32_FLOAT>}
+#define WS_ERROR_TABLE(K) {WS_ERROR_ROW(K, WS_FORMAT_RGBA8_UNORM), WS_ERROR_ROW(K, WS_FORMAT_RGBA16_FLOAT), WS_ERROR_ROW(K, WS_FORMAT_RGBA32_FLOAT)}
+    static const Kernel kernels[2][3][3] = {WS_ERROR_TABLE(k_image_error), WS_ERROR_TABLE(k_image_error_grad)};
+#undef WS_ERROR_TABLE
 #undef WS_ERROR_ROW
     if (p.a.format < 0 || p.a.format > 2 || p.b.format < 0 || p.b.format > 2) return fail(WS_ERR_INVALID, "launch_image_error: colour format");
-    hipLaunchKernelGGL(kernels[p.a.format][p.b.format], dim3(gx, gy), dim3(EW * EH), 0, stream, p);
+    hipLaunchKernelGGL(kernels[p.gradient ? 1 : 0][p.a.format][p.b.format], dim3(gx, gy), dim3(EW * EH), 0, stream, p);
     WS_HIP(hipGetLastError());
     return WS_OK;
 }

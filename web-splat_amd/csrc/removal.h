@@ -50,4 +50,30 @@ static_assert(offsetof(RemovalParams, acc) == 120 && sizeof(RemovalParams) == 16
 // all 0 skips its walk there; pass 1 never does.
 int launch_removal(const RemovalParams& p, hipStream_t stream);
 
+// Pass 1 alone: k_removal_base<qw, qh>.  Reads frame, base, base_pitch and background of p and nothing else -- the launch the
+// gradient's pass 1 makes too (gradient.h).
+int launch_removal_base(const RemovalParams& p, hipStream_t stream);
+
 }  // namespace ws
+
+#if defined(__HIPCC__)
+namespace ws {
+
+// The staged colours of k_removal_base, k_removal and k_gradient (gradient.hip).
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+
+// Words 3 and 4 of the 20-B Splat record: the f16 colour (r, g | b) and opacity.  Kept raw in LDS, 8 B per slot: decoded float4s
+// would take the 4x4 tile's static LDS to 64.6 KB of 64 (profiles/removal/resources.txt).
+__device__ __forceinline__ uint2 splat_colour_words(const uint8_t* splats, uint32_t idx) {
+    const char* sp = reinterpret_cast<const char*>(splats) + (size_t)idx * SPLAT_STRIDE + 12;
+    uint2 c;
+    __builtin_memcpy(&c.x, sp, 4);
+    __builtin_memcpy(&c.y, sp + 4, 4);
+    return c;
+}
+__device__ __forceinline__ f16x4_t staged_colour(const uint2* s_col, uint32_t off) {  // off = slot * 16
+    return *reinterpret_cast<const f16x4_t*>(reinterpret_cast<const char*>(s_col) + (off >> 1));
+}
+
+}  // namespace ws
+#endif  // __HIPCC__

@@ -16,21 +16,6 @@ namespace ws {
 
 namespace {
 
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-
-// Words 3 and 4 of the 20-B Splat record: the f16 colour (r, g | b) and opacity.  Kept raw in LDS, 8 B per slot: decoded float4s
-// would take the 4x4 tile's static LDS to 64.6 KB of 64 (profiles/removal/resources.txt).
-__device__ __forceinline__ uint2 splat_colour_words(const uint8_t* splats, uint32_t idx) {
-    const char* sp = reinterpret_cast<const char*>(splats) + (size_t)idx * SPLAT_STRIDE + 12;
-    uint2 c;
-    __builtin_memcpy(&c.x, sp, 4);
-    __builtin_memcpy(&c.y, sp + 4, 4);
-    return c;
-}
-__device__ __forceinline__ f16x4_t staged_colour(const uint2* s_col, uint32_t off) {  // off = slot * 16
-    return *reinterpret_cast<const f16x4_t*>(reinterpret_cast<const char*>(s_col) + (off >> 1));
-}
-
 // Pass 1 (removal.h): F = sum of w c + T_end * background, and T_end.
 struct RemovalBaseSink {
     static constexpr bool WRITES_EMPTY_TILES = true;  // the lanes of a tile with nothing listed store (background, 1)
@@ -142,15 +127,27 @@ __global__ __launch_bounds__(64 * QW * QH) void k_removal(const RemovalParams p)
 
 }  // namespace
 
+int launch_removal_base(const RemovalParams& p, hipStream_t stream) {
+    const uint32_t grid = p.frame.tiles_x * p.frame.tiles_y;
+    if (grid == 0) return WS_OK;
+    const bool shaped = with_tile_shape(p.frame.qw, p.frame.qh, [&](auto qw, auto qh) {
+        constexpr int QW = decltype(qw)::value, QH = decltype(qh)::value;
+        hipLaunchKernelGGL((k_removal_base<QW, QH>), dim3(grid), dim3(64 * QW * QH), 0, stream, p);
+    });
+    if (!shaped) return fail(WS_ERR_UNSUPPORTED, "launch_removal_base: tile shape");
+    WS_HIP(hipGetLastError());
+    return WS_OK;
+}
+
 int launch_removal(const RemovalParams& p, hipStream_t stream) {
     const uint32_t grid = p.frame.tiles_x * p.frame.tiles_y;
     if (grid == 0) return WS_OK;
+    if (const int rc = launch_removal_base(p, stream)) return rc;
     const bool weighted = p.acc.plane != nullptr;
     const bool sq = p.kind == WS_ERROR_SQ;
     const bool shaped = with_tile_shape(p.frame.qw, p.frame.qh, [&](auto qw, auto qh) {
         constexpr int QW = decltype(qw)::value, QH = decltype(qh)::value;
         const dim3 g(grid), b(64 * QW * QH);
-        hipLaunchKernelGGL((k_removal_base<QW, QH>), g, b, 0, stream, p);
         if (weighted && sq) hipLaunchKernelGGL((k_removal<QW, QH, true, WS_ERROR_SQ>), g, b, 0, stream, p);
         else if (weighted) hipLaunchKernelGGL((k_removal<QW, QH, true, WS_ERROR_ABS>), g, b, 0, stream, p);
         else if (sq) hipLaunchKernelGGL((k_removal<QW, QH, false, WS_ERROR_SQ>), g, b, 0, stream, p);

@@ -13,6 +13,7 @@
 
 #include "contrib.h"
 #include "metrics.h"
+#include "gradient.h"
 #include "removal.h"
 #include "values.h"
 #include "ws_internal.h"
@@ -208,7 +209,7 @@ struct ws_renderer {
     bool blend_timing = false;           // ws_renderer_enable_blend_timing: render() launches the time-stamped blend
     uint32_t* debug_timing = nullptr;    // [tiles][16][BLEND_TIMING_WORDS], allocated on first use
     uint32_t debug_timing_tiles = 0;
-    float4* removal_base = nullptr;      // [removal_base_px]: the base plane of ws_renderer_accumulate_removal without d_base, grown on first use
+    float4* removal_base = nullptr;      // [removal_base_px]: the base plane of ws_renderer_accumulate_removal / _gradient without d_base, grown on first use
     size_t removal_base_px = 0;
     bool timers = false;
     KernelMarks marks;               // per-kernel events, timers level 2
@@ -2240,6 +2241,28 @@ int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_
     return launch_done(launch_values(vp, stream), r, nullptr, stream, km, "k_values");
 }
 
+// The base plane (F, T_end) of ws_renderer_accumulate_removal and ws_renderer_accumulate_gradient: the caller's, or the
+// renderer's scratch, grown on demand
+static int base_plane(ws_renderer* r, float* d_base, size_t pitch, float4** base, size_t* base_pitch) {
+    if (d_base) {
+        *base = reinterpret_cast<float4*>(d_base);
+        *base_pitch = pitch;
+        return WS_OK;
+    }
+    const size_t px = (size_t)r->vw * r->vh;
+    if (px > r->removal_base_px) {
+        // (an earlier call's launches may still read the plane, on any stream: as the frame scratch, it is replaced behind a device sync)
+        WS_HIP(hipDeviceSynchronize());
+        dfree(r->removal_base);
+        r->removal_base_px = 0;
+        WS_TRY(dmalloc(&r->removal_base, px));
+        r->removal_base_px = px;
+    }
+    *base = r->removal_base;
+    *base_pitch = (size_t)r->vw * 16;
+    return WS_OK;
+}
+
 // What deleting each Gaussian alone would do to the prepared frame (websplat.h "Removal effect"; removal.h).  The descriptor is
 // judged by itself first, then the handles, then the descriptor against the frame; only then the two launches.
 int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_removal_params* p, void* stream_v) {
@@ -2263,22 +2286,7 @@ int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_c
     if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
     RemovalParams rp;
     rp.frame = frame_lists(r);
-    if (p->d_base) {
-        rp.base = reinterpret_cast<float4*>(p->d_base);
-        rp.base_pitch = p->base_pitch_bytes;
-    } else {
-        const size_t px = (size_t)r->vw * r->vh;
-        if (px > r->removal_base_px) {
-            // (an earlier call's launches may still read the plane, on any stream: as the frame scratch, it is replaced behind a device sync)
-            WS_HIP(hipDeviceSynchronize());
-            dfree(r->removal_base);
-            r->removal_base_px = 0;
-            WS_TRY(dmalloc(&r->removal_base, px));
-            r->removal_base_px = px;
-        }
-        rp.base = r->removal_base;
-        rp.base_pitch = (size_t)r->vw * 16;
-    }
+    if (const int rc = base_plane(r, p->d_base, p->base_pitch_bytes, &rp.base, &rp.base_pitch)) return rc;
     for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
     rp.scale = p->scale;
     rp.kind = p->kind;
@@ -2538,6 +2546,165 @@ int ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out,
         o.reserved = 0;
     }
     return WS_OK;
+}
+
+}  // extern "C"
+
+// ---- gradients of an image loss (include/websplat.h "Gradients of an image loss"; gradient.hip) ----------------
+struct ws_grad {
+    ws_context* ctx = nullptr;
+    uint32_t num_points = 0;
+    unsigned long long* sums = nullptr;  // [num_points][WS_GRAD_CHANNELS] two's-complement q32 sums
+    uint32_t frames = 0;
+    hipStream_t last_stream = nullptr;
+};
+static_assert(WS_GRAD_CHANNELS == GRAD_CHANNELS, "the ABI's channel count is the kernel's");
+
+extern "C" {
+
+int ws_grad_create(ws_context* ctx, uint32_t num_points, ws_grad** out) {
+    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_grad_create: null argument");
+    *out = nullptr;
+    if (num_points == 0) return fail(WS_ERR_INVALID, "ws_grad_create: no points");
+    ws_grad* g = new (std::nothrow) ws_grad();
+    if (!g) return fail(WS_ERR_OOM, "ws_grad_create: host allocation failed");
+    g->ctx = ctx;
+    g->num_points = num_points;
+    int rc = dmalloc(&g->sums, (size_t)num_points * GRAD_CHANNELS);
+    if (rc == WS_OK) rc = ws_grad_reset(g, nullptr);
+    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_grad_create: device sync failed");
+    if (rc != WS_OK) {
+        ws_grad_destroy(g);
+        return rc;
+    }
+    *out = g;
+    return WS_OK;
+}
+
+void ws_grad_destroy(ws_grad* g) {
+    if (!g) return;
+    (void)hipDeviceSynchronize();
+    dfree(g->sums);
+    delete g;
+}
+
+int ws_grad_reset(ws_grad* g, void* stream_v) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_grad_reset: null accumulator");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    WS_HIP(hipMemsetAsync(g->sums, 0, (size_t)g->num_points * GRAD_CHANNELS * sizeof(unsigned long long), stream));
+    g->frames = 0;
+    g->last_stream = stream;
+    return WS_OK;
+}
+
+uint32_t ws_grad_num_points(const ws_grad* g) { return g ? g->num_points : 0u; }
+uint32_t ws_grad_frames(const ws_grad* g) { return g ? g->frames : 0u; }
+
+int ws_grad_download(ws_grad* g, uint32_t capacity, int64_t* q32) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_grad_download: null accumulator");
+    if (q32 && capacity < g->num_points) return fail(WS_ERR_INVALID, "ws_grad_download: capacity smaller than the number of points");
+    WS_HIP(hipStreamSynchronize(g->last_stream));
+    if (!q32) return WS_OK;
+    return copy_d2h(q32, g->sums, (size_t)g->num_points * GRAD_CHANNELS * sizeof(int64_t), g->last_stream);
+}
+
+int ws_grad_add(ws_grad* g, const int64_t* q32, uint32_t n) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_grad_add: null accumulator");
+    if (n < g->num_points) return fail(WS_ERR_INVALID, "ws_grad_add: fewer values than the accumulator has points");
+    if (!q32) return WS_OK;
+    const size_t words = (size_t)g->num_points * GRAD_CHANNELS;
+    unsigned long long* d_other = nullptr;
+    hipStream_t stream = g->last_stream;
+    int rc = dmalloc(&d_other, words);
+    if (rc == WS_OK) {
+        const hipError_t e = hipMemcpyAsync(d_other, q32, words * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) rc = hip_fail(e, "ws_grad_add: upload");
+    }
+    if (rc == WS_OK) rc = launch_grad_merge(g->sums, d_other, words, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_grad_add: stream sync failed");
+    dfree(d_other);
+    return rc;
+}
+
+// The descriptor is judged by itself first, then the handles, then the descriptor against the frame; only then the two launches:
+// removal's pass 1 through launch_removal_base, then k_gradient.
+int ws_renderer_accumulate_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream) {
+    return ws_internal_gradient_passes(r, pc, g, p, stream, 3u);
+}
+
+}  // extern "C"
+
+int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
+    const std::string who("ws_renderer_accumulate_gradient");
+    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
+    if (p->reserved0 != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
+    for (uint32_t w : p->reserved)
+        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
+    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
+    if (!std::isfinite(p->opacity_scale) || !(p->opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
+    for (float b : p->background)
+        if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
+    if (!p->d_grad) return fail(WS_ERR_INVALID, who + ": null d_grad");
+    if (p->grad_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_grad) % 16 != 0)
+        return fail(WS_ERR_INVALID, who + ": d_grad: pointer and grad_pitch_bytes must be multiples of 16");
+    if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
+        return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
+    if (!r || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
+    const int state = check_weights_frame(r, pc, who, g->num_points == pc->num_points, "the accumulator was created for another number of points");
+    if (state) return state;
+    if (p->grad_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_grad: grad_pitch_bytes below 16 x the viewport's width");
+    if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
+    RemovalParams rp;
+    rp.frame = frame_lists(r);
+    if (const int rc = base_plane(r, p->d_base, p->base_pitch_bytes, &rp.base, &rp.base_pitch)) return rc;
+    for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
+    rp.scale = 1.0f;  // (pass 1 reads neither of the three)
+    rp.kind = WS_ERROR_SQ;
+    rp.acc = Accum{nullptr, nullptr, nullptr, 0, 1.0f, 0.0f};
+    GradientParams gp;
+    gp.frame = rp.frame;
+    gp.base = rp.base;
+    gp.base_pitch = rp.base_pitch;
+    gp.grad = reinterpret_cast<const float4*>(p->d_grad);
+    gp.grad_pitch = p->grad_pitch_bytes;
+    gp.scale = p->scale;
+    gp.opacity_scale = p->opacity_scale;
+    gp.sums = g->sums;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    KernelMarks* km = launch_begin(r, stream);
+    int rc = (passes & 1u) ? launch_removal_base(rp, stream) : WS_OK;
+    if (rc == WS_OK && (passes & 2u)) rc = launch_gradient(gp, stream);
+    rc = launch_done(rc, r, nullptr, stream, km, passes == 1u ? "k_removal_base" : passes == 2u ? "k_gradient" : "k_removal_base+k_gradient");
+    if (rc == WS_OK && (passes & 2u)) ++g->frames, g->last_stream = stream;
+    return rc;
+}
+
+extern "C" {
+
+int ws_image_error_gradient(ws_context* ctx, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, int kind,
+                            uint32_t flags, float* d_grad, size_t grad_pitch_bytes, void* stream_v) {
+    const char* fn = "ws_image_error_gradient";
+    const std::string who(fn);
+    if (!ctx || !a || !b || !d_grad) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (width == 0 || height == 0) return fail(WS_ERR_INVALID, who + ": empty image");
+    if (width > 65536u || height > 65536u) return fail(WS_ERR_INVALID, who + ": image larger than 65536 pixels on a side");
+    if (flags & WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, who + ": WS_METRICS_QUANTIZE_U8 has no gradient");
+    if (flags) return fail(WS_ERR_INVALID, who + ": unknown flag bits");
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
+    ImageErrorParams p;
+    int rc = metrics_view(a, width, "a", &p.a, fn);
+    if (rc == WS_OK) rc = metrics_view(b, width, "b", &p.b, fn);
+    if (rc) return rc;
+    if (grad_pitch_bytes < (size_t)width * 16 || grad_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(d_grad) % 16 != 0)
+        return fail(WS_ERR_INVALID, who + ": gradient pitch below 16 x width, or gradient pointer / pitch not 16-B aligned");
+    p.width = width;
+    p.height = height;
+    p.flags = 0;
+    p.kind = kind;
+    p.plane = d_grad;
+    p.plane_pitch = grad_pitch_bytes;
+    p.gradient = 1;
+    return launch_image_error(p, static_cast<hipStream_t>(stream_v));
 }
 
 }  // extern "C"

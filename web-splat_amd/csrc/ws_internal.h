@@ -531,6 +531,11 @@ void ws_internal_renderer_set_throughput_mode(ws_renderer* r, bool on);
 // ws_scene_evaluate gives back the records of a pass it has to repeat (ws_api.cpp): the host counter only
 struct ws_metrics;
 void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count);
+// ws_renderer_accumulate_gradient in two steps, for ws_scene_accumulate_gradient, which makes the plane from pass 1's image
+// (ws_api.cpp): passes = 1: the base image only, nothing is accumulated; 2: k_gradient on a base plane already there; 3: the call
+struct ws_grad;
+struct ws_gradient_params;
+int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream, unsigned passes);
 
 // opaque handle definitions -------------------------------------------------------------------------
 // The depth sort of a frame (V keys + store index + footprint word):

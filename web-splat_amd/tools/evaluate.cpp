@@ -1,6 +1,6 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
-//                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]]
+//                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
 // another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
 // --blame N: behind that table, the N Gaussians of the scene with the largest error sum over the split (websplat.h "Attributing a
@@ -8,6 +8,9 @@
 // --removal N: behind all that, the N Gaussians whose deletion alone would change the split's frames most (websplat.h "Removal
 // effect"): index, effect sum, plain contribution sum and their ratio, then how many drawn Gaussians have an effect of exactly 0.
 // It needs no second image: --ref / --gt may be left out, and then only this table is printed.
+// --gradient N: behind all that, the N Gaussians with the largest |d error / d ln opacity| over the split (websplat.h "Gradients
+// of an image loss"; the error is --blame's, sq or abs, against --ref / --gt): index, opacity gradient, the three colour
+// gradients, then how many drawn Gaussians have all four sums 0.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -22,7 +25,7 @@ int main(int argc, char** argv) {
     const char *ref = nullptr, *gt = nullptr;
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
-    long blame = 0, removal = 0;
+    long blame = 0, removal = 0, gradient = 0;
     int kind = WS_ERROR_SQ;
     bool bad = argc < 3, have_error = false;
     for (int i = 3; i < argc && !bad; ++i) {
@@ -42,6 +45,10 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             removal = std::strtol(argv[++i], &end, 10);
             if (*end || removal <= 0) bad = true;
+        } else if (!std::strcmp(argv[i], "--gradient") && i + 1 < argc) {
+            char* end = nullptr;
+            gradient = std::strtol(argv[++i], &end, 10);
+            if (*end || gradient <= 0) bad = true;
         } else if (!std::strcmp(argv[i], "--error") && i + 1 < argc) {
             ++i;
             have_error = true;
@@ -51,13 +58,13 @@ int main(int argc, char** argv) {
             else bad = true;
         } else bad = true;
     }
-    if (have_error && blame == 0 && removal == 0) bad = true;
-    if (removal > 0 && kind == WS_ERROR_DSSIM) bad = true;
+    if (have_error && blame == 0 && removal == 0 && gradient == 0) bad = true;
+    if ((removal > 0 || gradient > 0) && kind == WS_ERROR_DSSIM) bad = true;
     const bool compare = ref != nullptr || gt != nullptr;  // (--removal alone needs no second image)
-    if (blame > 0 && !compare) bad = true;
+    if ((blame > 0 || gradient > 0) && !compare) bad = true;
     if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0)) {
         std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
-                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]]\n", argv[0]);
+                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]\n", argv[0]);
         return 2;
     }
     ws_context* ctx = nullptr;
@@ -147,9 +154,46 @@ int main(int argc, char** argv) {
             std::printf("removal: %u of %u drawn Gaussians have an effect of exactly 0\n", zero_n, drawn_n);
         }
     }
+    ws_grad* grad = nullptr;
+    ws_contrib* grad_drawn = nullptr;
+    if (rc == WS_OK && gradient > 0) {
+        const uint32_t np = ws_pointcloud_num_points(pc);
+        std::vector<int64_t> q((size_t)np * WS_GRAD_CHANNELS);
+        std::vector<uint64_t> w(np);
+        std::vector<uint32_t> order(np);
+        rc = ws_grad_create(ctx, np, &grad);
+        if (rc == WS_OK) rc = ws_contrib_create(ctx, np, &grad_drawn);
+        if (rc == WS_OK) rc = ws_scene_accumulate_gradient(ctx, pc, scene, split, ref_pc, gt, kind, 1.0f, 1.0f, grad, &frames);
+        if (rc == WS_OK) rc = ws_scene_accumulate_contrib(ctx, pc, scene, split, grad_drawn, nullptr);
+        if (rc == WS_OK) rc = ws_grad_download(grad, np, q.data());
+        if (rc == WS_OK) rc = ws_contrib_download(grad_drawn, np, w.data(), nullptr);
+        if (rc == WS_OK) {
+            for (uint32_t i = 0; i < np; ++i) order[i] = i;
+            const size_t top = std::min<size_t>((size_t)gradient, np);
+            auto mag = [&](uint32_t i) { return q[(size_t)i * 4 + 3] < 0 ? 0ull - (uint64_t)q[(size_t)i * 4 + 3] : (uint64_t)q[(size_t)i * 4 + 3]; };
+            std::partial_sort(order.begin(), order.begin() + top, order.end(),
+                              [&](uint32_t a, uint32_t b) { return mag(a) != mag(b) ? mag(a) > mag(b) : a < b; });
+            std::printf("gradient (%s error over %u frames): %zu of %u Gaussians by |opacity gradient|\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, top, np);
+            std::printf("%10s %16s %16s %16s %16s\n", "index", "d/d ln opacity", "d/d red", "d/d green", "d/d blue");
+            for (size_t k = 0; k < top; ++k) {
+                const int64_t* g = &q[(size_t)order[k] * 4];
+                std::printf("%10u %16.9g %16.9g %16.9g %16.9g\n", order[k], (double)g[3] / WS_GRAD_SUM_SCALE, (double)g[0] / WS_GRAD_SUM_SCALE,
+                            (double)g[1] / WS_GRAD_SUM_SCALE, (double)g[2] / WS_GRAD_SUM_SCALE);
+            }
+            uint32_t drawn_n = 0, zero_n = 0;
+            for (uint32_t i = 0; i < np; ++i) {
+                const int64_t* g = &q[(size_t)i * 4];
+                drawn_n += w[i] != 0;
+                zero_n += w[i] != 0 && g[0] == 0 && g[1] == 0 && g[2] == 0 && g[3] == 0;
+            }
+            std::printf("gradient: %u of %u drawn Gaussians have all four sums exactly 0\n", zero_n, drawn_n);
+        }
+    }
     if (rc != WS_OK) {
         std::fprintf(stderr, "error %d: %s\n", rc, ws_last_error());
     }
+    if (grad) ws_grad_destroy(grad);
+    if (grad_drawn) ws_contrib_destroy(grad_drawn);
     if (effect) ws_contrib_destroy(effect);
     if (drawn) ws_contrib_destroy(drawn);
     if (err) ws_contrib_destroy(err);

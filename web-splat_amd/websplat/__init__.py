@@ -6,5 +6,6 @@ from ._lib import (LIB_PATH, WebSplatError, lib, check, ws_gaussian_quantization
 from .api import (Aabb, Context, GaussianRenderer, GenericGaussianPointCloud, GPURSSorter, PerspectiveCamera,  # noqa: F401
                   PointCloud, SplattingArgs, pointcloud_stats, FORMATS, Scene, SceneCamera, read_npz, read_ply, write_png,
                   render_views, measure, ViewBatch, config_from_env, stage_splat, footprint_tiles, packed_rect, binning_decision, Contrib, accumulate_contrib_scene,
-                  ImageView, Metrics, image_metrics, read_png, evaluate_scene, image_error_plane, accumulate_error_scene, accumulate_removal_scene)
+                  ImageView, Metrics, image_metrics, read_png, evaluate_scene, image_error_plane, accumulate_error_scene, accumulate_removal_scene,
+                  Grad, image_error_gradient, accumulate_gradient_scene)
 from . import synth  # noqa: F401

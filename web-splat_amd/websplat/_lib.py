@@ -26,6 +26,8 @@ WS_ERR_STATE = -5
 WS_ERR_IO = -6
 WS_ERR_OVERFLOW = -7
 WS_CONTRIB_SUM_SCALE = 4294967296.0  # sum_q32 / scale = sum of weights
+WS_GRAD_SUM_SCALE = 4294967296.0     # ws_grad: q32 / (scale * the call's scales) = the gradient
+WS_GRAD_CHANNELS = 4                 # colour r, g, b; ln-opacity
 WS_METRICS_QUANTIZE_U8 = 1           # ws_metrics_add / ws_scene_evaluate flag: compare the 8-bit images a PNG would hold
 WS_ERROR_SQ = 0                      # ws_image_error_plane / ws_scene_accumulate_error kinds: mean over the channels of d * d,
 WS_ERROR_ABS = 1                     # of |d|,
@@ -194,6 +196,13 @@ class ws_removal_params(C.Structure):
                 ("d_base", C.c_void_p), ("base_pitch_bytes", C.c_size_t), ("reserved", C.c_uint32 * 4)]
 
 
+class ws_gradient_params(C.Structure):
+    _fields_ = [("background", C.c_float * 3), ("scale", C.c_float), ("opacity_scale", C.c_float), ("reserved0", C.c_uint32),
+                ("d_grad", C.c_void_p), ("grad_pitch_bytes", C.c_size_t), ("d_base", C.c_void_p), ("base_pitch_bytes", C.c_size_t),
+                ("reserved", C.c_uint32 * 4)]
+
+
+assert C.sizeof(ws_gradient_params) == 72
 assert C.sizeof(ws_removal_params) == 64
 assert C.sizeof(ws_image_view) == 40
 assert C.sizeof(ws_values_view) == 24
@@ -349,6 +358,17 @@ SIGNATURES = {
     "ws_renderer_render_values": (C.c_int, [_P, _P, C.POINTER(ws_values_view), C.POINTER(ws_value_targets), _P]),
     "ws_renderer_accumulate_removal": (C.c_int, [_P, _P, _P, C.POINTER(ws_removal_params), _P]),
     "ws_scene_accumulate_removal": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _u32p]),
+    "ws_grad_create": (C.c_int, [_P, C.c_uint32, _PP]),
+    "ws_grad_destroy": (None, [_P]),
+    "ws_grad_reset": (C.c_int, [_P, _P]),
+    "ws_grad_num_points": (C.c_uint32, [_P]),
+    "ws_grad_frames": (C.c_uint32, [_P]),
+    "ws_grad_download": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int64)]),
+    "ws_grad_add": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_uint32]),
+    "ws_renderer_accumulate_gradient": (C.c_int, [_P, _P, _P, C.POINTER(ws_gradient_params), _P]),
+    "ws_image_error_gradient": (C.c_int, [_P, C.POINTER(ws_image_view), C.POINTER(ws_image_view), C.c_uint32, C.c_uint32, C.c_int,
+                                          C.c_uint32, _P, C.c_size_t, _P]),
+    "ws_scene_accumulate_gradient": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, C.c_float, _P, _u32p]),
 }
 
 

@@ -648,6 +648,47 @@ class Contrib:
                                  m.ctypes.data_as(C.POINTER(C.c_float)) if m is not None else None, n))
 
 
+class Grad:
+    """Per-Gaussian gradient accumulators over frames (websplat.h "Gradients of an image loss"): for every Gaussian of a cloud
+    of num_points, four signed q32 sums -- dL/d(colour r, g, b) and dL/d(ln opacity) times 2^32 and the calls' scales."""
+
+    def __init__(self, ctx: Context, num_points: int):
+        self.ctx = ctx
+        h = C.c_void_p()
+        check(lib.ws_grad_create(ctx.handle, int(num_points), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            lib.ws_grad_destroy(self.handle)
+            self.handle = None
+
+    def reset(self, stream=None):
+        check(lib.ws_grad_reset(self.handle, C.c_void_p(stream or 0)))
+
+    def num_points(self) -> int:
+        return lib.ws_grad_num_points(self.handle)
+
+    @property
+    def frames(self) -> int:
+        """frames added since creation / the last reset"""
+        return lib.ws_grad_frames(self.handle)
+
+    def download(self) -> np.ndarray:
+        """(N, 4) int64: the q32 sums of colour r, g, b and ln-opacity per Gaussian (syncs)."""
+        n = self.num_points()
+        q = np.empty((n, L.WS_GRAD_CHANNELS), dtype=np.int64)
+        check(lib.ws_grad_download(self.handle, n, q.ctypes.data_as(C.POINTER(C.c_int64))))
+        return q
+
+    def add(self, q32):
+        """Exact merge of another accumulator's (or rank's) downloaded (N, 4) int64 sums."""
+        q = np.ascontiguousarray(q32, dtype=np.int64)
+        if q.ndim != 2 or q.shape[1] != L.WS_GRAD_CHANNELS:
+            raise ValueError(f"Grad.add: want an (N, {L.WS_GRAD_CHANNELS}) int64 array, got {q.shape}")
+        check(lib.ws_grad_add(self.handle, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0]))
+
+
 def accumulate_contrib_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, contrib: "Contrib") -> int:
     """Every camera of `split`, set up as render_views sets its frames up, added to `contrib`; returns the frames added."""
     n = C.c_uint32()
@@ -822,6 +863,43 @@ def image_error_plane(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, kind="
         ctx.sync()
         for p in ptrs:
             ctx.free(p)
+
+
+def image_error_gradient(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, kind="sq", background_a=None, background_b=None) -> np.ndarray:
+    """The derivative of image_error_plane's value with respect to image a's pixel values (H x W x 4 float32, the fourth
+    component 0; ws_image_error_gradient) of two H x W x 4 numpy images: upload, one launch, download."""
+    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
+    for im in imgs:
+        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
+            raise ValueError("image_error_gradient: two H x W x 4 arrays of one size, uint8 / float16 / float32")
+    h, w = imgs[0].shape[:2]
+    ptrs = []
+    try:
+        views = []
+        for im, bg in zip(imgs, (background_a, background_b)):
+            ptrs.append(ctx.malloc(im.nbytes))
+            ctx.upload(ptrs[-1], im)
+            views.append(ImageView(ptrs[-1], _NP_FORMATS[im.dtype], w * im.itemsize * 4, bg).to_c())
+        ptrs.append(ctx.malloc(w * h * 16))
+        check(lib.ws_image_error_gradient(ctx.handle, C.byref(views[0]), C.byref(views[1]), w, h, ERROR_KINDS[kind], 0,
+                                          C.c_void_p(ptrs[-1]), w * 16, None))
+        return ctx.download(ptrs[-1], (h, w, 4), np.float32)
+    finally:
+        ctx.sync()
+        for p in ptrs:
+            ctx.free(p)
+
+
+def accumulate_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, grad: "Grad", ref: "PointCloud" = None,
+                              gt_dir: str = None, kind="sq", scale=1.0, opacity_scale=1.0) -> int:
+    """Every camera of `split`, set up as accumulate_error_scene sets it up: the colour and ln-opacity gradients of the frames'
+    error ("sq" or "abs") against the cloud `ref` or the PNGs of `gt_dir`, per Gaussian of `pc`, into `grad`
+    (ws_scene_accumulate_gradient).  Returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_accumulate_gradient(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+                                           None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(scale),
+                                           float(opacity_scale), grad.handle, C.byref(n)))
+    return n.value
 
 
 def accumulate_error_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, err: "Contrib", weight: "Contrib" = None,
@@ -1107,8 +1185,51 @@ class GaussianRenderer:
         with self._staged(v, staged, stream):
             check(lib.ws_renderer_accumulate_removal(self.handle, pc.handle, contrib.handle, C.byref(p), C.c_void_p(stream or 0)))
 
+    def accumulate_gradient(self, pc: PointCloud, grad: "Grad", plane, background=(0.0, 0.0, 0.0), scale=1.0, opacity_scale=1.0,
+                            base=False, stream=None, plane_pitch=None, base_ptr=None, base_pitch=None):
+        """Add to `grad`, per Gaussian, the gradients of an image loss over the prepared frame (ws_renderer_accumulate_gradient):
+        colour[ch] += sum of w * G_ch, opacity += -sum of (G . D + G_T r T_end), G = clamp(scale * plane, -1, 1).  `plane`: the
+        loss's derivative (dL/dF_r, dL/dF_g, dL/dF_b, dL/dT_end) per pixel, an H x W x 4 float32 numpy array (uploaded for the
+        call, which then waits for the launches) or a device pointer with `plane_pitch` bytes per row.  Needs enable_contrib()
+        before prepare(); render() is not needed, no target changes.  base / base_ptr / base_pitch: as accumulate_removal."""
+        p = L.ws_gradient_params()
+        for i in range(3):
+            p.background[i] = float(background[i])
+        p.scale, p.opacity_scale = float(scale), float(opacity_scale)
+        w, h = getattr(self, "_viewport", (0, 0))  # ((0, 0): not prepared -- the library says so)
+        if base_ptr is not None:
+            p.d_base, p.base_pitch_bytes = int(base_ptr), int(base_pitch if base_pitch is not None else w * 16)
+        elif base:
+            if self._rm_base_shape != (w, h):
+                self._free_removal_base()
+                self._rm_base = self.ctx.malloc(max(w * h * 16, 16))
+                self._rm_base_shape = (w, h)
+            p.d_base, p.base_pitch_bytes = self._rm_base, w * 16
+        staged = None
+        if isinstance(plane, np.ndarray):
+            a = np.ascontiguousarray(plane, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 4 or (w and (a.shape[0] != h or a.shape[1] < w)):  # (wider rows: padding)
+                raise ValueError(f"accumulate_gradient: want an H x W x 4 float32 plane of the viewport {(w, h)}, got {a.shape}")
+            p.grad_pitch_bytes = int(plane_pitch) if plane_pitch is not None else a.shape[1] * 16
+            staged = a
+        else:
+            if plane is not None and plane_pitch is None:
+                raise ValueError("accumulate_gradient: a device plane needs its row pitch")
+            p.d_grad, p.grad_pitch_bytes = (int(plane) if plane is not None else None), int(plane_pitch or 0)
+        if staged is None:
+            check(lib.ws_renderer_accumulate_gradient(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
+            return
+        d = self.ctx.malloc(max(staged.nbytes, 16))
+        try:
+            self.ctx.upload(d, staged)
+            p.d_grad = d
+            check(lib.ws_renderer_accumulate_gradient(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
+        finally:
+            self.ctx.sync(stream)
+            self.ctx.free(d)
+
     def download_removal_base(self) -> np.ndarray:
-        """H x W x 4 float32 (F_r, F_g, F_b, T_end) of what the last accumulate_removal(base=True) wrote (syncs)."""
+        """H x W x 4 float32 (F_r, F_g, F_b, T_end) of what the last accumulate_removal(base=True) or accumulate_gradient(base=True) wrote (syncs)."""
         if not self._rm_base:
             raise ValueError("download_removal_base: no accumulate_removal(base=True) since the viewport changed")
         w, h = self._rm_base_shape

@@ -55,3 +55,23 @@ def reduce_contrib(sum_q32, max_weight, dist=None, device: str = "cpu"):
     if tq.numel() and int(tq.min().item()) < 0:
         raise OverflowError("reduce_contrib: the reduced q32 sums left the int64 range")
     return tq.cpu().numpy().view(np.uint64), tm.cpu().numpy()
+
+
+def reduce_grad(q32, dist=None, device: str = "cpu"):
+    """All-reduce the per-Gaussian gradient sums of ranks that scored disjoint camera subsets (Grad.download(): (N, 4) int64)
+    over the default process group: an int64 SUM, exact, so every rank ends with the accumulator one rank would have built
+    from all cameras.  The sums wrap silently in int64, so the magnitudes travel beside them: where the ranks' |q| together reach
+    2^62 (a Gaussian's gradient magnitude 2^30 times the calls' scales) the result is not trusted and OverflowError is raised."""
+    import numpy as np
+    q = np.ascontiguousarray(q32, dtype=np.int64)
+    if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
+        return q.copy()
+    import torch
+    tq = torch.from_numpy(q.copy()).to(device)
+    # |sum| <= sum of |q|, taken in float64: its rounding is far below the factor of two left to 2^63
+    mag = torch.from_numpy(np.abs(q.astype(np.float64))).to(device)
+    dist.all_reduce(tq, op=dist.ReduceOp.SUM)
+    dist.all_reduce(mag, op=dist.ReduceOp.SUM)
+    if mag.numel() and float(mag.max().item()) >= 2.0 ** 62:
+        raise OverflowError("reduce_grad: the reduced q32 sums may have left the int64 range")
+    return tq.cpu().numpy()
