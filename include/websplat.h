@@ -909,8 +909,8 @@ int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const
  * red is above 0 in the frame -- with E == 1 everywhere, ws_renderer_accumulate_contrib's sum.
  * THE STOPS.  As "Removal effect": F ignores what lies behind a stop, so a pair's opacity term is under-reported by at most
  * r * 2^-14 * colour * |G|.
- * Out of scope: gradients with respect to position, covariance and the higher SH coefficients; an optimiser; writing a refitted
- * cloud to disk.
+ * Out of scope: gradients with respect to position, covariance and the higher SH coefficients; writing a refitted cloud to disk
+ * (the optimiser is "Refitting colour and opacity" below).
  * Errors: as ws_renderer_accumulate_removal, judged from the descriptor before a handle is looked at; in addition
  * WS_ERR_INVALID for a null d_grad, a gradient pointer or pitch that is not a multiple of 16, a pitch below 16 * width, a scale
  * or opacity_scale that is not finite and above 0.
@@ -946,6 +946,73 @@ int  ws_image_error_gradient(ws_context* ctx, const ws_image_view* a, const ws_i
                              uint32_t flags, float* d_grad, size_t grad_pitch_bytes, void* stream);
 int  ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                   const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames);
+/* ---- Refitting colour and opacity: Adam steps on the resident planes, in place (no counterpart in the reference) -----------------
+ * What "Gradients of an image loss" is for: its sums say in which direction every colour and opacity of a (pruned) cloud should
+ * move; a ws_refit moves them.  It belongs to ONE uncompressed point cloud and holds, per Gaussian, f32 masters of four
+ * parameters and the two Adam moments of each, in device memory.  The parameters are indexed like WS_GRAD_CHANNELS:
+ *   x[0..2]  the DC SH coefficients: the first [f16;3] of the 96-B SH record (the first 6 bytes of plane 2's chunk)
+ *   x[3]     the opacity: the f16 behind x, y, z in the 28-B record (plane 0), the post-sigmoid value the loaders store
+ * ws_refit_create runs a small kernel that widens those four halves to the f32 masters and sets m = v = 0; steps = 0 and the
+ * running powers p1 = beta1^steps, p2 = beta2^steps are host doubles, 1.0 at creation.  Compressed clouds are refused with
+ * WS_ERR_UNSUPPORTED: their codebooks are shared between Gaussians.
+ * GRADIENTS TO PARAMETERS.  K1 computes colour = max(0, 0.5 + C0 * dc + the view-dependent rest), C0 = 0.28209479177387814, and a
+ * ws_grad's colour sums are derivatives with respect to an offset before that clamp: dL/d dc = C0 * dL/d colour.  Its opacity
+ * sum is dL/d ln(opacity), which a constant factor on the opacity (mip-splatting's) does not change: dL/d opacity = sum / opacity.
+ * colour_unit and opacity_unit say what ONE unit of a sum is worth as dL/d colour and as dL/d ln opacity: for sums of B frames
+ * through `scale` and `opacity_scale`, the mean over the frames has colour_unit = 1 / (2^32 * scale * B) and opacity_unit =
+ * 1 / (2^32 * scale * opacity_scale * B).
+ * THE STEP, TO THE BIT.  Once per call, on the host: p1 <- p1 * (double)beta1, p2 <- p2 * (double)beta2; bc1 = (float)(1.0 - p1),
+ * bc2 = (float)(1.0 - p2); omb1 = 1.0f - beta1, omb2 = 1.0f - beta2 in f32; u_c = colour_unit * C0, u_o = opacity_unit in double.
+ * One thread per Gaussian j; for each channel k of a group whose rate is not 0, with x, m, v the stored f32 values and q the sum:
+ *   g  = (float)((double)q[j][k] * u)         u = u_c for k < 3, u_o for k = 3; int64 -> double and double -> float round to
+ *                                             nearest even
+ *   k = 3 only:  g = (x == 0) ? 0 : g / x     x the opacity master before the step
+ *   m' = (beta1 * m) + (omb1 * g)
+ *   v' = (beta2 * v) + (omb2 * (g * g))
+ *   s  = (m' / bc1) / (sqrtf(v' / bc2) + eps)
+ *   x' = x - (lr * s)                         lr = lr_colour for k < 3, lr_opacity for k = 3
+ *   k < 3:  x' below -65504 becomes -65504, above 65504 becomes 65504     k = 3:  below opacity_min -> opacity_min, above 1 -> 1
+ * every operation a separately rounded IEEE f32 operation, no contraction, division and square root correctly rounded.  x', m',
+ * v' are stored, and f16(x'), round to nearest even, into the four halves of the cloud's planes.  NO OTHER BYTE OF THE RESIDENT
+ * CLOUD CHANGES: not x, y, z, not the two bytes of padding beside the opacity, not the SH halves behind the DC triple.  A rate of
+ * 0 freezes its group: its masters, moments and stored halves are not written.  Consequences that hold to the bit: (a) a Gaussian
+ * with q = 0 and m = v = 0 keeps its masters and its stored halves, provided opacity_min is not above its opacity; (b) the result
+ * does not depend on the launch geometry.  Denormal intermediates are not pinned.
+ * ORDER.  ws_refit_step only ENQUEUES on `stream`, behind the accumulations that filled `g` on it.  Frames prepared later on that
+ * stream see the new values (K1 reads the planes at every prepare()); frames of the cloud in flight on OTHER streams, prepared
+ * or being prepared, are the caller's business -- the step does not wait for them.  ws_refit_download syncs.
+ * Errors: WS_ERR_INVALID for null params, a rate that is negative or not finite, a beta outside [0, 1), an eps that is not finite
+ * and above 0, an opacity_min outside [0, 1], a unit that is not finite and above 0, non-zero reserved words -- all judged from the
+ * descriptor before a handle is looked at; then for null handles, a `pc` other than the one the object was created for, a ws_grad
+ * of another size; ws_refit_download: a capacity below the number of points.
+ * ws_scene_refit: per epoch, the cameras of `split` in split order through the per-frame sequence of
+ * ws_scene_accumulate_gradient (the same set-up; scale = 1, the caller's opacity_scale, image b the render of `ref_pc` or the
+ * PNGs of `gt_dir`) into a ws_grad of the driver's own.  A batch ends after every views_per_step frames (0 = the whole split) and
+ * at the end of the epoch if one is partly filled; after a batch of B frames the driver enqueues ws_refit_step with colour_unit =
+ * 1 / (2^32 * B), opacity_unit = 1 / (2^32 * opacity_scale * B), computed in double (the two fields of `params` are ignored),
+ * then ws_grad_reset.  Argument checks as ws_scene_accumulate_gradient, the params' as ws_refit_step; ref_pc == pc is refused.
+ * One stream, one sync and one look at the error bits per epoch; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule, after
+ * the steps of that epoch have been taken.  *steps = the steps taken.  Known costs: the reference cloud is rendered again every
+ * epoch, and the PNGs are read again every epoch.
+ * Out of scope: position, covariance and the higher SH coefficients; learning-rate schedules; writing a cloud to disk (a refitted
+ * cloud can be kept through ws_pointcloud_download and ws_pointcloud_create). */
+typedef struct ws_refit ws_refit;               /* f32 masters and Adam moments of one uncompressed cloud, device memory */
+typedef struct ws_refit_params {
+    float lr_colour, lr_opacity;     /* finite, >= 0; 0 freezes the group: its masters, moments and stored halves are not touched */
+    float beta1, beta2, eps;         /* betas in [0, 1), eps finite and > 0 */
+    float opacity_min;               /* in [0, 1]: lower clamp of the opacity master */
+    double colour_unit, opacity_unit;/* what ONE unit of a ws_grad sum is worth as dL/d colour and as dL/d ln opacity: finite, > 0 */
+    uint32_t reserved[4];            /* zero */
+} ws_refit_params;
+int  ws_refit_create(ws_context* ctx, const ws_pointcloud* pc, ws_refit** out);
+void ws_refit_destroy(ws_refit* refit);
+uint32_t ws_refit_num_points(const ws_refit* refit);
+uint32_t ws_refit_steps(const ws_refit* refit);
+int  ws_refit_step(ws_refit* refit, ws_pointcloud* pc, const ws_grad* g, const ws_refit_params* params, void* stream);   /* enqueues only */
+int  ws_refit_download(ws_refit* refit, uint32_t capacity, float* master, float* m, float* v);   /* [capacity][4] each, any may be NULL; syncs */
+int  ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
+                    int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params, uint32_t epochs, uint32_t views_per_step,
+                    uint32_t* steps);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

@@ -638,6 +638,24 @@ int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws
 
 // ... and the colour and ln-opacity gradients of that error (websplat.h "Gradients of an image loss"): image a is the frame's
 // f32 base plane over the cloud's background, the first half of the scratch plane; the loss gradient is the second half.
+// One frame of it, shared with ws_scene_refit: ws_renderer_accumulate_gradient in its two steps, the plane made of pass 1's image.
+extern "C++" {
+static int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, ws_grad* grad, const ws_gradient_params& gp, int kind, const ErrorFrame& f) {
+    const size_t pitch = (size_t)f.w * 16;
+    float* base = static_cast<float*>(f.plane);
+    float* g = base + (size_t)f.w * f.h * 4;
+    ws_gradient_params p = gp;
+    p.d_base = base;
+    p.base_pitch_bytes = pitch;
+    p.d_grad = g;
+    p.grad_pitch_bytes = pitch;
+    int frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 1u);
+    const ws_image_view va = view_of(base, WS_FORMAT_RGBA32_FLOAT, pitch, nullptr);  // (the alpha slot holds T_end: ignored)
+    if (frc == WS_OK) frc = ws_image_error_gradient(ctx, &va, &f.vb, f.w, f.h, kind, 0, g, pitch, nullptr);
+    if (frc == WS_OK) frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 2u);
+    return frc;
+}
+}  // extern "C++"
 int ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                  const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames) {
     const std::string who("ws_scene_accumulate_gradient");
@@ -655,22 +673,56 @@ int ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const
     eval_background(pc, gp.background);
     gp.scale = scale;
     gp.opacity_scale = opacity_scale;
-    return over_error_frames(who, ctx, pc, scene, split, ref_pc, gt_dir, 32, false, frames, [&](const ErrorFrame& f) {
-        const size_t pitch = (size_t)f.w * 16;
-        float* base = static_cast<float*>(f.plane);
-        float* g = base + (size_t)f.w * f.h * 4;
-        ws_gradient_params p = gp;
-        p.d_base = base;
-        p.base_pitch_bytes = pitch;
-        p.d_grad = g;
-        p.grad_pitch_bytes = pitch;
-        // the call in its two steps: the plane is made of pass 1's image
-        int frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 1u);
-        const ws_image_view va = view_of(base, WS_FORMAT_RGBA32_FLOAT, pitch, nullptr);  // (the alpha slot holds T_end: ignored)
-        if (frc == WS_OK) frc = ws_image_error_gradient(ctx, &va, &f.vb, f.w, f.h, kind, 0, g, pitch, nullptr);
-        if (frc == WS_OK) frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 2u);
-        return frc;
-    });
+    return over_error_frames(who, ctx, pc, scene, split, ref_pc, gt_dir, 32, false, frames,
+                             [&](const ErrorFrame& f) { return gradient_frame(ctx, pc, grad, gp, kind, f); });
+}
+
+// ... and the loop those gradients are for (websplat.h "Refitting colour and opacity"): per epoch the frames of
+// ws_scene_accumulate_gradient into a ws_grad of the driver's own, an Adam step and a reset after every batch.  Everything is
+// enqueued on one stream, so the next frame's K1 reads the planes the step before it wrote; over_error_frames brings the one sync
+// and the one look at the error bits per epoch.
+int ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
+                   int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params, uint32_t epochs, uint32_t views_per_step,
+                   uint32_t* steps) {
+    const std::string who("ws_scene_refit");
+    if (steps) *steps = 0;
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
+    if (!std::isfinite(opacity_scale) || !(opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
+    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL) return fail(WS_ERR_INVALID, who + ": split must be train, test or all");
+    if (const int rc = ws_internal_refit_check_params(params, who, false)) return rc;
+    if (!ctx || !pc || !scene || !refit) return fail(WS_ERR_INVALID, who + ": null argument");
+    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, who + ": exactly one of ref_pc and gt_dir");
+    if (ref_pc == pc) return fail(WS_ERR_INVALID, who + ": ref_pc is the cloud being refitted");
+    if (ws_refit_num_points(refit) != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the refit object was created for another number of points");
+    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
+    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
+    const uint32_t batch = views_per_step ? views_per_step : n;
+    ws_grad* grad = nullptr;
+    int rc = ws_grad_create(ctx, ws_pointcloud_num_points(pc), &grad);
+    ws_gradient_params gp;
+    std::memset(&gp, 0, sizeof gp);
+    eval_background(pc, gp.background);
+    gp.scale = 1.0f;
+    gp.opacity_scale = opacity_scale;
+    uint32_t taken = 0;
+    for (uint32_t epoch = 0; epoch < epochs && rc == WS_OK; ++epoch) {
+        uint32_t seen = 0, in_batch = 0;
+        rc = over_error_frames(who, ctx, pc, scene, split, ref_pc, gt_dir, 32, false, nullptr, [&](const ErrorFrame& f) {
+            int frc = gradient_frame(ctx, pc, grad, gp, kind, f);
+            if (frc != WS_OK) return frc;
+            ++seen, ++in_batch;
+            if (in_batch < batch && seen < n) return frc;
+            ws_refit_params sp = *params;
+            sp.colour_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)in_batch);
+            sp.opacity_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)opacity_scale * (double)in_batch);
+            frc = ws_refit_step(refit, pc, grad, &sp, nullptr);
+            if (frc == WS_OK) ++taken, in_batch = 0, frc = ws_grad_reset(grad, nullptr);
+            return frc;
+        });
+    }
+    if (steps) *steps = taken;
+    if (grad) ws_grad_destroy(grad);
+    return rc;
 }
 
 int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, uint32_t num_samples,

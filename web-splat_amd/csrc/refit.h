@@ -1,0 +1,46 @@
+// refit.h -- Adam steps on the DC colour and the opacity of a resident, uncompressed cloud (refit.hip k_refit_init, k_refit_step).
+// Internal: the ABI is include/websplat.h, "Refitting colour and opacity"; DESIGN.md 3.4j.
+#pragma once
+
+#include <cstddef>
+
+#include "ws_internal.h"
+
+namespace ws {
+
+constexpr float REFIT_C0 = 0.28209479177387814f;  // SH_C0 of K1: colour = max(0, 0.5 + C0 * dc + ...)
+constexpr double REFIT_C0_F64 = 0.28209479177387814;
+constexpr float REFIT_DC_MAX = 65504.0f;          // the largest finite f16: the clamp of the DC masters
+
+// One step over every Gaussian.  The four parameters of Gaussian i, indexed like GRAD_CHANNELS: x[0..2] = the DC triple, the
+// first three halves of plane 2's chunk; x[3] = the opacity, the low half of word 3 of plane 0's chunk.
+struct RefitParams {
+    uint4* planes;                   // the cloud's PC_PLANES planes of n 16-B chunks
+    const unsigned long long* sums;  // [n][4] two's-complement q32 sums (ws_grad)
+    float4* master;                  // [n] f32 masters
+    float4* m;                       // [n] first moments
+    float4* v;                       // [n] second moments
+    uint32_t n;
+    float lr_colour, lr_opacity;     // 0 freezes the group
+    float beta1, beta2, omb1, omb2;  // omb = 1.0f - beta, in f32
+    float bc1, bc2;                  // (float)(1.0 - beta^steps), the powers kept in double on the host
+    float eps, opacity_min;
+    double u_colour, u_opacity;      // what one unit of a sum is worth: colour_unit * C0, opacity_unit
+};
+
+// TO THE BIT, one thread per Gaussian, per channel k of a group whose rate is not 0 (x, m, v the stored f32 values):
+//   g  = (float)((double)(int64_t)q[k] * u)      u = u_colour for k < 3, u_opacity for k = 3; both conversions round to nearest even
+//   k = 3:  g = (x == 0) ? 0 : g / x
+//   m' = (beta1 * m) + (omb1 * g);   v' = (beta2 * v) + (omb2 * (g * g))
+//   s  = (m' / bc1) / (sqrtf(v' / bc2) + eps);   x' = x - (lr * s)
+//   k < 3:  x' < -65504 -> -65504, x' > 65504 -> 65504        k = 3:  x' < opacity_min -> opacity_min, x' > 1 -> 1
+// every operation a separately rounded IEEE f32 operation (the file is compiled without contraction; division and square root are
+// correctly rounded).  x', m', v' are stored, and f16(x'), round to nearest even, into the four halves of the planes.  A frozen
+// group's masters, moments and halves are not written.  No other byte of the planes changes: the opacity's word keeps its upper
+// half (the loader's padding), the second DC word its upper half (the first half of SH coefficient 1).
+int launch_refit_step(const RefitParams& p, hipStream_t stream);
+
+// master[i] = the four halves widened to f32, m[i] = v[i] = 0
+int launch_refit_init(const uint4* planes, uint32_t n, float4* master, float4* m, float4* v, hipStream_t stream);
+
+}  // namespace ws

@@ -14,6 +14,7 @@
 #include "contrib.h"
 #include "metrics.h"
 #include "gradient.h"
+#include "refit.h"
 #include "removal.h"
 #include "values.h"
 #include "ws_internal.h"
@@ -2705,6 +2706,126 @@ int ws_image_error_gradient(ws_context* ctx, const ws_image_view* a, const ws_im
     p.plane_pitch = grad_pitch_bytes;
     p.gradient = 1;
     return launch_image_error(p, static_cast<hipStream_t>(stream_v));
+}
+
+}  // extern "C"
+
+// ---- refitting colour and opacity (include/websplat.h "Refitting colour and opacity"; refit.hip) ----------------
+struct ws_refit {
+    ws_context* ctx = nullptr;
+    const ws_pointcloud* pc = nullptr;   // the cloud the masters were widened from: the only one a step accepts
+    const uint4* planes = nullptr;       // (and its planes: a later cloud at the same address is another cloud)
+    uint32_t num_points = 0;
+    float4 *master = nullptr, *m = nullptr, *v = nullptr;
+    uint32_t steps = 0;
+    double p1 = 1.0, p2 = 1.0;           // beta1^steps, beta2^steps
+    hipStream_t last_stream = nullptr;
+};
+static_assert(sizeof(ws_refit_params) == 56 && offsetof(ws_refit_params, colour_unit) == 24 && offsetof(ws_refit_params, reserved) == 40,
+              "ws_refit_params layout (websplat/_lib.py mirrors it)");
+
+// Everything about a ws_refit_params that can be judged without a handle; units = false: the two unit fields are not looked at
+// (ws_scene_refit computes them per batch).
+int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& who, bool units) {
+    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
+    for (uint32_t w : p->reserved)
+        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
+    if (!std::isfinite(p->lr_colour) || !(p->lr_colour >= 0.0f)) return fail(WS_ERR_INVALID, who + ": lr_colour must be finite and not below 0");
+    if (!std::isfinite(p->lr_opacity) || !(p->lr_opacity >= 0.0f)) return fail(WS_ERR_INVALID, who + ": lr_opacity must be finite and not below 0");
+    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f)) return fail(WS_ERR_INVALID, who + ": beta1 must lie in [0, 1)");
+    if (!(p->beta2 >= 0.0f && p->beta2 < 1.0f)) return fail(WS_ERR_INVALID, who + ": beta2 must lie in [0, 1)");
+    if (!std::isfinite(p->eps) || !(p->eps > 0.0f)) return fail(WS_ERR_INVALID, who + ": eps must be finite and above 0");
+    if (!(p->opacity_min >= 0.0f && p->opacity_min <= 1.0f)) return fail(WS_ERR_INVALID, who + ": opacity_min must lie in [0, 1]");
+    if (units && (!std::isfinite(p->colour_unit) || !(p->colour_unit > 0.0))) return fail(WS_ERR_INVALID, who + ": colour_unit must be finite and above 0");
+    if (units && (!std::isfinite(p->opacity_unit) || !(p->opacity_unit > 0.0))) return fail(WS_ERR_INVALID, who + ": opacity_unit must be finite and above 0");
+    return WS_OK;
+}
+
+extern "C" {
+
+int ws_refit_create(ws_context* ctx, const ws_pointcloud* pc, ws_refit** out) {
+    if (!ctx || !pc || !out) return fail(WS_ERR_INVALID, "ws_refit_create: null argument");
+    *out = nullptr;
+    if (pc->compressed)
+        return fail(WS_ERR_UNSUPPORTED, "ws_refit_create: a compressed cloud cannot be refitted (its codebooks are shared between Gaussians)");
+    ws_refit* rf = new (std::nothrow) ws_refit();
+    if (!rf) return fail(WS_ERR_OOM, "ws_refit_create: host allocation failed");
+    rf->ctx = ctx;
+    rf->pc = pc;
+    rf->planes = pc->planes;
+    rf->num_points = pc->num_points;
+    int rc = dmalloc(&rf->master, (size_t)rf->num_points);
+    if (rc == WS_OK) rc = dmalloc(&rf->m, (size_t)rf->num_points);
+    if (rc == WS_OK) rc = dmalloc(&rf->v, (size_t)rf->num_points);
+    if (rc == WS_OK) rc = launch_refit_init(pc->planes, rf->num_points, rf->master, rf->m, rf->v, nullptr);
+    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_refit_create: device sync failed");
+    if (rc != WS_OK) {
+        ws_refit_destroy(rf);
+        return rc;
+    }
+    *out = rf;
+    return WS_OK;
+}
+
+void ws_refit_destroy(ws_refit* rf) {
+    if (!rf) return;
+    (void)hipDeviceSynchronize();
+    dfree(rf->master);
+    dfree(rf->m);
+    dfree(rf->v);
+    delete rf;
+}
+
+uint32_t ws_refit_num_points(const ws_refit* rf) { return rf ? rf->num_points : 0u; }
+uint32_t ws_refit_steps(const ws_refit* rf) { return rf ? rf->steps : 0u; }
+
+// The descriptor is judged by itself first, then the handles; the host's share of the step (the running beta powers, the bias
+// corrections, the units) is committed only when the launch went out.
+int ws_refit_step(ws_refit* rf, ws_pointcloud* pc, const ws_grad* g, const ws_refit_params* p, void* stream_v) {
+    const std::string who("ws_refit_step");
+    if (const int rc = ws_internal_refit_check_params(p, who, true)) return rc;
+    if (!rf || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (pc != rf->pc || pc->planes != rf->planes || pc->compressed || pc->num_points != rf->num_points)
+        return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
+    if (g->num_points != rf->num_points) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another number of points");
+    const double p1 = rf->p1 * (double)p->beta1, p2 = rf->p2 * (double)p->beta2;
+    RefitParams kp;
+    kp.planes = pc->planes;
+    kp.sums = g->sums;
+    kp.master = rf->master;
+    kp.m = rf->m;
+    kp.v = rf->v;
+    kp.n = rf->num_points;
+    kp.lr_colour = p->lr_colour;
+    kp.lr_opacity = p->lr_opacity;
+    kp.beta1 = p->beta1;
+    kp.beta2 = p->beta2;
+    kp.omb1 = 1.0f - p->beta1;
+    kp.omb2 = 1.0f - p->beta2;
+    kp.bc1 = (float)(1.0 - p1);
+    kp.bc2 = (float)(1.0 - p2);
+    kp.eps = p->eps;
+    kp.opacity_min = p->opacity_min;
+    kp.u_colour = p->colour_unit * REFIT_C0_F64;
+    kp.u_opacity = p->opacity_unit;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (const int rc = launch_refit_step(kp, stream)) return rc;
+    rf->p1 = p1;
+    rf->p2 = p2;
+    ++rf->steps;
+    rf->last_stream = stream;
+    return WS_OK;
+}
+
+int ws_refit_download(ws_refit* rf, uint32_t capacity, float* master, float* m, float* v) {
+    if (!rf) return fail(WS_ERR_INVALID, "ws_refit_download: null object");
+    if ((master || m || v) && capacity < rf->num_points) return fail(WS_ERR_INVALID, "ws_refit_download: capacity smaller than the number of points");
+    WS_HIP(hipStreamSynchronize(rf->last_stream));
+    const size_t bytes = (size_t)rf->num_points * sizeof(float4);
+    if (master) WS_TRY(copy_d2h(master, rf->master, bytes, rf->last_stream));
+    if (m) WS_TRY(copy_d2h(m, rf->m, bytes, rf->last_stream));
+    if (v) WS_TRY(copy_d2h(v, rf->v, bytes, rf->last_stream));
+    return WS_OK;
 }
 
 }  // extern "C"

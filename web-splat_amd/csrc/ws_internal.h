@@ -536,6 +536,10 @@ void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count);
 struct ws_grad;
 struct ws_gradient_params;
 int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream, unsigned passes);
+// what ws_refit_step judges from its descriptor alone, for ws_scene_refit, which fills in the two units itself (units = false:
+// they are not looked at) (ws_api.cpp)
+struct ws_refit_params;
+int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& who, bool units);
 
 // opaque handle definitions -------------------------------------------------------------------------
 // The depth sort of a frame (V keys + store index + footprint word):

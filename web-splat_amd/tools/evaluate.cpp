@@ -1,6 +1,7 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
 //                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]
+//                     [--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
 // another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
 // --blame N: behind that table, the N Gaussians of the scene with the largest error sum over the split (websplat.h "Attributing a
@@ -11,6 +12,9 @@
 // --gradient N: behind all that, the N Gaussians with the largest |d error / d ln opacity| over the split (websplat.h "Gradients
 // of an image loss"; the error is --blame's, sq or abs, against --ref / --gt): index, opacity gradient, the three colour
 // gradients, then how many drawn Gaussians have all four sums 0.
+// --refit EPOCHS: behind all that, Adam steps on the scene's DC colours and opacities over the TRAIN split against --ref / --gt
+// (websplat.h "Refitting colour and opacity"; a step after every B views, default: one per epoch), then the first table again,
+// of the refitted scene, under a line "after refit: EPOCHS epochs, S steps".  A compressed scene is refused.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -25,7 +29,9 @@ int main(int argc, char** argv) {
     const char *ref = nullptr, *gt = nullptr;
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
-    long blame = 0, removal = 0, gradient = 0;
+    long blame = 0, removal = 0, gradient = 0, refit = 0, views_per_step = 0;
+    double lr_colour = 0.0025, lr_opacity = 0.01;
+    bool have_refit_option = false;
     int kind = WS_ERROR_SQ;
     bool bad = argc < 3, have_error = false;
     for (int i = 3; i < argc && !bad; ++i) {
@@ -49,6 +55,21 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             gradient = std::strtol(argv[++i], &end, 10);
             if (*end || gradient <= 0) bad = true;
+        } else if (!std::strcmp(argv[i], "--refit") && i + 1 < argc) {
+            char* end = nullptr;
+            refit = std::strtol(argv[++i], &end, 10);
+            if (*end || refit <= 0) bad = true;
+        } else if (!std::strcmp(argv[i], "--views-per-step") && i + 1 < argc) {
+            char* end = nullptr;
+            views_per_step = std::strtol(argv[++i], &end, 10);
+            have_refit_option = true;
+            if (*end || views_per_step <= 0) bad = true;
+        } else if ((!std::strcmp(argv[i], "--lr-colour") || !std::strcmp(argv[i], "--lr-opacity")) && i + 1 < argc) {
+            double& lr = !std::strcmp(argv[i], "--lr-colour") ? lr_colour : lr_opacity;
+            char* end = nullptr;
+            lr = std::strtod(argv[++i], &end);
+            have_refit_option = true;
+            if (*end || !(lr >= 0.0) || !std::isfinite(lr)) bad = true;
         } else if (!std::strcmp(argv[i], "--error") && i + 1 < argc) {
             ++i;
             have_error = true;
@@ -58,13 +79,15 @@ int main(int argc, char** argv) {
             else bad = true;
         } else bad = true;
     }
-    if (have_error && blame == 0 && removal == 0 && gradient == 0) bad = true;
-    if ((removal > 0 || gradient > 0) && kind == WS_ERROR_DSSIM) bad = true;
+    if (have_error && blame == 0 && removal == 0 && gradient == 0 && refit == 0) bad = true;
+    if ((removal > 0 || gradient > 0 || refit > 0) && kind == WS_ERROR_DSSIM) bad = true;
+    if (have_refit_option && refit == 0) bad = true;
     const bool compare = ref != nullptr || gt != nullptr;  // (--removal alone needs no second image)
-    if ((blame > 0 || gradient > 0) && !compare) bad = true;
+    if ((blame > 0 || gradient > 0 || refit > 0) && !compare) bad = true;
     if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0)) {
         std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
-                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]\n", argv[0]);
+                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]] "
+                             "[--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]]\n", argv[0]);
         return 2;
     }
     ws_context* ctx = nullptr;
@@ -87,9 +110,12 @@ int main(int argc, char** argv) {
     }
     if (rc == WS_OK) ws_scene_cameras(scene, split, n, cams.data());
     if (rc == WS_OK && compare) rc = ws_metrics_create(ctx, n, &m);
-    if (rc == WS_OK && compare) rc = ws_scene_evaluate(ctx, pc, scene, split, ref_pc, gt, flags, m, &frames);
-    if (rc == WS_OK && compare) rc = ws_metrics_download(m, n, recs.data(), &count);
-    if (rc == WS_OK && compare) {
+    // the table of per-camera PSNR and SSIM and their means, of the scene as it is now
+    auto table = [&]() {
+        int trc = ws_metrics_reset(m, nullptr);
+        if (trc == WS_OK) trc = ws_scene_evaluate(ctx, pc, scene, split, ref_pc, gt, flags, m, &frames);
+        if (trc == WS_OK) trc = ws_metrics_download(m, n, recs.data(), &count);
+        if (trc != WS_OK) return trc;
         double psnr = 0.0, ssim = 0.0;
         for (uint32_t i = 0; i < count; ++i) {
             std::printf("%5u %-32s %4ux%-4u PSNR %8.4f  SSIM %.6f\n", cams[i].id, cams[i].img_name, recs[i].width, recs[i].height, recs[i].psnr,
@@ -98,7 +124,9 @@ int main(int argc, char** argv) {
             ssim += recs[i].ssim;
         }
         std::printf("mean over %u images: PSNR %.4f  SSIM %.6f\n", count, psnr / count, ssim / count);
-    }
+        return (int)WS_OK;
+    };
+    if (rc == WS_OK && compare) rc = table();
     ws_contrib *err = nullptr, *weight = nullptr;
     if (rc == WS_OK && blame > 0) {
         const uint32_t np = ws_pointcloud_num_points(pc);
@@ -189,9 +217,28 @@ int main(int argc, char** argv) {
             std::printf("gradient: %u of %u drawn Gaussians have all four sums exactly 0\n", zero_n, drawn_n);
         }
     }
+    ws_refit* fit = nullptr;
+    if (rc == WS_OK && refit > 0) {
+        ws_refit_params rp;
+        std::memset(&rp, 0, sizeof rp);
+        rp.lr_colour = (float)lr_colour;
+        rp.lr_opacity = (float)lr_opacity;
+        rp.beta1 = 0.9f;
+        rp.beta2 = 0.999f;
+        rp.eps = 1e-15f;
+        rp.opacity_min = 0.0f;
+        uint32_t steps = 0;
+        rc = ws_refit_create(ctx, pc, &fit);
+        if (rc == WS_OK) rc = ws_scene_refit(ctx, pc, scene, WS_SPLIT_TRAIN, ref_pc, gt, kind, 1.0f / 128.0f, fit, &rp, (uint32_t)refit, (uint32_t)views_per_step, &steps);
+        if (rc == WS_OK) {
+            std::printf("after refit: %ld epochs, %u steps\n", refit, steps);
+            rc = table();
+        }
+    }
     if (rc != WS_OK) {
         std::fprintf(stderr, "error %d: %s\n", rc, ws_last_error());
     }
+    if (fit) ws_refit_destroy(fit);
     if (grad) ws_grad_destroy(grad);
     if (grad_drawn) ws_contrib_destroy(grad_drawn);
     if (effect) ws_contrib_destroy(effect);

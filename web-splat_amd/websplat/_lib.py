@@ -202,6 +202,12 @@ class ws_gradient_params(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class ws_refit_params(C.Structure):
+    _fields_ = [("lr_colour", C.c_float), ("lr_opacity", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("opacity_min", C.c_float), ("colour_unit", C.c_double), ("opacity_unit", C.c_double), ("reserved", C.c_uint32 * 4)]
+
+
+assert C.sizeof(ws_refit_params) == 56
 assert C.sizeof(ws_gradient_params) == 72
 assert C.sizeof(ws_removal_params) == 64
 assert C.sizeof(ws_image_view) == 40
@@ -369,6 +375,14 @@ SIGNATURES = {
     "ws_image_error_gradient": (C.c_int, [_P, C.POINTER(ws_image_view), C.POINTER(ws_image_view), C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_uint32, _P, C.c_size_t, _P]),
     "ws_scene_accumulate_gradient": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, C.c_float, _P, _u32p]),
+    "ws_refit_create": (C.c_int, [_P, _P, _PP]),
+    "ws_refit_destroy": (None, [_P]),
+    "ws_refit_num_points": (C.c_uint32, [_P]),
+    "ws_refit_steps": (C.c_uint32, [_P]),
+    "ws_refit_step": (C.c_int, [_P, _P, _P, C.POINTER(ws_refit_params), _P]),
+    "ws_refit_download": (C.c_int, [_P, C.c_uint32, _f32p, _f32p, _f32p]),
+    "ws_scene_refit": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, _P, C.POINTER(ws_refit_params), C.c_uint32,
+                                 C.c_uint32, _u32p]),
 }
 
 

@@ -689,6 +689,62 @@ class Grad:
         check(lib.ws_grad_add(self.handle, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0]))
 
 
+def _refit_params(lr_colour=0.0025, lr_opacity=0.01, beta1=0.9, beta2=0.999, eps=1e-15, opacity_min=0.0, colour_unit=1.0,
+                  opacity_unit=1.0):
+    p = L.ws_refit_params()
+    p.lr_colour, p.lr_opacity, p.beta1, p.beta2, p.eps, p.opacity_min = lr_colour, lr_opacity, beta1, beta2, eps, opacity_min
+    p.colour_unit, p.opacity_unit = colour_unit, opacity_unit
+    return p
+
+
+class Refit:
+    """f32 masters and Adam moments of the DC colours and the opacities of one uncompressed resident cloud (websplat.h "Refitting
+    colour and opacity"): step() moves the cloud's stored halves in place along a Grad's sums."""
+
+    def __init__(self, ctx: Context, pc: "PointCloud"):
+        self.ctx = ctx
+        h = C.c_void_p()
+        check(lib.ws_refit_create(ctx.handle, pc.handle, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            lib.ws_refit_destroy(self.handle)
+            self.handle = None
+
+    def num_points(self) -> int:
+        return lib.ws_refit_num_points(self.handle)
+
+    @property
+    def steps(self) -> int:
+        """steps taken since creation"""
+        return lib.ws_refit_steps(self.handle)
+
+    def step(self, pc: "PointCloud", grad: "Grad", lr_colour=0.0025, lr_opacity=0.01, beta1=0.9, beta2=0.999, eps=1e-15, opacity_min=0.0,
+             colour_unit=None, opacity_unit=None, scale=1.0, opacity_scale=1.0, stream=None):
+        """One Adam step along grad's sums (enqueues only).  A unit left None makes the step one along the MEAN gradient of the
+        frames in `grad`, accumulated through `scale` and `opacity_scale` (taken as the float32 values the accumulation used):
+        1 / (2^32 * scale [* opacity_scale] * grad.frames)."""
+        if colour_unit is None or opacity_unit is None:
+            per = L.WS_GRAD_SUM_SCALE * float(np.float32(scale))
+            frames = grad.frames
+            if frames == 0:
+                raise ValueError("Refit.step: the accumulator holds no frame: give colour_unit and opacity_unit")
+            if colour_unit is None:
+                colour_unit = 1.0 / (per * frames)
+            if opacity_unit is None:
+                opacity_unit = 1.0 / (per * float(np.float32(opacity_scale)) * frames)
+        p = _refit_params(lr_colour, lr_opacity, beta1, beta2, eps, opacity_min, colour_unit, opacity_unit)
+        check(lib.ws_refit_step(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
+
+    def download(self) -> dict:
+        """{"master", "m", "v"}: (N, 4) float32 each -- DC r, g, b and the opacity; their first and second moments (syncs)."""
+        n = self.num_points()
+        out = {k: np.empty((n, L.WS_GRAD_CHANNELS), dtype=np.float32) for k in ("master", "m", "v")}
+        check(lib.ws_refit_download(self.handle, n, *(out[k].ctypes.data_as(C.POINTER(C.c_float)) for k in ("master", "m", "v"))))
+        return out
+
+
 def accumulate_contrib_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, contrib: "Contrib") -> int:
     """Every camera of `split`, set up as render_views sets its frames up, added to `contrib`; returns the frames added."""
     n = C.c_uint32()
@@ -899,6 +955,20 @@ def accumulate_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene, sp
     check(lib.ws_scene_accumulate_gradient(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
                                            None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(scale),
                                            float(opacity_scale), grad.handle, C.byref(n)))
+    return n.value
+
+
+def refit_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, refit: "Refit", ref: "PointCloud" = None, gt_dir: str = None,
+                kind="sq", opacity_scale=1.0 / 128, epochs=1, views_per_step=0, **adam) -> int:
+    """`epochs` passes over the cameras of `split`, set up as accumulate_gradient_scene sets them up: the gradients of the frames'
+    error against the cloud `ref` or the PNGs of `gt_dir`, and an Adam step of `refit` on `pc` after every `views_per_step` frames
+    (0 = one step per epoch) along their mean (ws_scene_refit).  **adam: Refit.step's rates, betas, eps and opacity_min.  Returns
+    the steps taken."""
+    p = _refit_params(**adam)
+    n = C.c_uint32()
+    check(lib.ws_scene_refit(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+                             None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(opacity_scale), refit.handle,
+                             C.byref(p), int(epochs), int(views_per_step), C.byref(n)))
     return n.value
 
 
