@@ -636,7 +636,8 @@ int  ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, cons
 /* Every camera of `split` (sorted by id) added to `c`, set up exactly as ws_render_views does (1600-px cap, fit_near_far,
  * walltime 100 s, max_sh_deg = pc.sh_deg): one renderer, one stream, one sync at the end, no target and no blend launch.
  * *frames = cameras added.  WS_ERR_OVERFLOW when a frame overflowed its tile-entry list (read once, after the sync): the
- * accumulator is then incomplete. */
+ * accumulator is then incomplete.  (Every ws_scene_* driver and ws_render_views walk their cameras with one function and size
+ * their frames by one rule, csrc/scene_frames.h; a camera with an empty image is WS_ERR_INVALID before the first frame.) */
 int  ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c, uint32_t* frames);
 /* ---- Attributing a pixel plane to Gaussians: weighted contribution sums (no counterpart in the reference) ---------------------
  * (Declared behind "Image metrics" below, whose types they use; this is the normative text.)
@@ -665,8 +666,8 @@ int  ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const
  * Errors: those of ws_metrics_add for the views, sizes and flags; WS_ERR_INVALID for a null plane, a plane pitch below
  * 4 * width or not a multiple of 4, a misaligned plane pointer, an unknown kind (WS_ERROR_DSSIM included: it has no kernel).
  * ws_scene_accumulate_error: every camera of `split` (sorted by id) blamed on the Gaussians of `pc`.  Exactly one of ref_pc /
- * gt_dir; cameras, frame sizes, targets, blend mode, background and PNG handling are exactly those of ws_scene_evaluate (the
- * two drivers share that set-up).  Per camera: prepare with contributions enabled and render `pc` (image a); image b is the
+ * gt_dir; cameras, frame sizes, targets, blend mode, background and PNG handling are exactly those of ws_scene_evaluate (one
+ * walk serves every scene driver).  Per camera: prepare with contributions enabled and render `pc` (image a); image b is the
  * render of `ref_pc` (by a second renderer, as in ws_scene_evaluate) or the PNG; the error plane is ws_image_error_plane's,
  * or for WS_ERROR_DSSIM the SSIM map of a private one-slot ws_metrics through scale -0.5, bias 0.5; the weighted sum is added
  * to `err` and, if `weight` is not NULL, the plain contribution sum of the same prepared frame to `weight`.  One stream, one
@@ -854,7 +855,7 @@ int  ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws
  * base_pitch_bytes that is not a multiple of 16 or a pitch below 16 * width, a reserved word that is not 0.  Everything that can
  * be judged from the descriptor alone is refused before a handle is looked at.
  * ws_scene_accumulate_removal: every camera of `split` (sorted by id), set up exactly as ws_scene_accumulate_contrib sets it up
- * (the two share that function), over the cloud's own background colour, or black when it has none; the effect is added to
+ * (the same walk over the cameras), over the cloud's own background colour, or black when it has none; the effect is added to
  * `effect` and, if `weight` is not NULL, the plain contribution sums of the same prepared frames to `weight`.  One renderer, one
  * stream, one sync at the end; *frames = cameras added; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule. */
 typedef struct ws_removal_params {
@@ -922,8 +923,8 @@ int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const
  * clamp lay outside [0, 1] or was NaN; the fourth component is 0.  So sum g * dx is the first-order change of the sum of
  * ws_image_error_plane's plane.  Image a may be the base plane itself: rgba32float, over_background = 0 (the alpha slot holds
  * T_end and is ignored).  d_grad: float4 per pixel, pointer and pitch multiples of 16, pitch >= 16 * width.
- * ws_scene_accumulate_gradient: cameras, image b and PNG handling exactly those of ws_scene_accumulate_error (they share that
- * set-up); per camera: prepare, the base image over the cloud's background (black if none), ws_image_error_gradient(base, b),
+ * ws_scene_accumulate_gradient: cameras, image b and PNG handling exactly those of ws_scene_accumulate_error (the same walk
+ * over the cameras); per camera: prepare, the base image over the cloud's background (black if none), ws_image_error_gradient(base, b),
  * accumulate.  One stream, one sync at the end; *frames = cameras added; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule. */
 typedef struct ws_grad ws_grad;                 /* four int64 sums per Gaussian, device memory, zeroed */
 #define WS_GRAD_CHANNELS 4                      /* colour r, g, b; ln-opacity */

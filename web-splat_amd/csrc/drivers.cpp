@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "scene_frames.h"
 #include "ws_internal.h"
 
 using namespace ws;
@@ -102,174 +103,13 @@ int ws_download_texture_rgba8(ws_context* ctx, const void* d_image, ws_color_for
     return WS_OK;
 }
 
-int ws_render_views(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const char* out_dir,
-                    uint32_t* rendered) {
-    if (!ctx || !pc || !scene || !out_dir) return fail(WS_ERR_INVALID, "ws_render_views: null argument");
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, "ws_render_views: split must be train or test");
-    if (rendered) *rendered = 0;
-    const std::string dir = std::string(out_dir) + "/" + (split == WS_SPLIT_TEST ? "test" : "train");
-    if (!make_dirs(dir)) return fail(WS_ERR_IO, "ws_render_views: cannot create " + dir);
-    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
-    std::vector<ws_scene_camera> cams(n);
-    ws_scene_cameras(scene, split, n, cams.data());
-    ws_renderer* r = nullptr;
-    int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), &r);
-    if (rc) return rc;
-    // bin/render.rs:154 draws into an Rgba16Float target: the fixed-function blender rounds the destination to f16 after
-    // every splat.  The target-precision blend mode reproduces that (ws_context_config::render_views_fast_blend: the throughput blend,
-    // one rounding at the store).
-    if (!ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(r, WS_BLEND_TARGET_PRECISION);
-    void* target = nullptr;
-    size_t target_bytes = 0;
-    std::vector<uint8_t> rgba;
-    const float clear[4] = {0, 0, 0, 0};
-    for (uint32_t i = 0; i < n && rc == WS_OK; ++i) {
-        uint32_t w = cams[i].width, h = cams[i].height;
-        if (w > 1600) {  // bin/render.rs:58-62
-            const float s = (float)w / 1600.0f;
-            w = 1600;
-            h = (uint32_t)((float)h / s);
-        }
-        if (w == 0 || h == 0) {
-            rc = fail(WS_ERR_INVALID, "ws_render_views: camera with an empty image");
-            break;
-        }
-        const size_t need = (size_t)w * h * 8;
-        if (need > target_bytes) {
-            if (target) ws_device_free(ctx, target);
-            target = nullptr;
-            if ((rc = ws_device_malloc(ctx, need, &target))) break;
-            target_bytes = need;
-        }
-        ws_splatting_args a;
-        offline_args(cams[i], pc, w, h, &a);
-        // Entries are emitted far -> near and truncated at the capacity, so an overflowing frame would silently lose
-        // its NEAREST splats: render, look at the frame's error bits, grow the entry list and render again if needed.
-        for (int attempt = 0; attempt < 3; ++attempt) {
-            if ((rc = ws_renderer_prepare(r, pc, &a, nullptr))) break;
-            if ((rc = ws_renderer_render(r, pc, clear, target, (size_t)w * 8, nullptr))) break;
-            uint32_t bits = 0, needed = 0;
-            if ((rc = ws_renderer_errors(r, &bits, &needed, 1))) break;
-            if (bits == 0) break;
-            if ((bits & ~1u) != 0 || attempt == 2) {
-                rc = fail(WS_ERR_OVERFLOW, "ws_render_views: the frame reported device-side errors (tile-entry overflow or a "
-                                           "look-back time-out)");
-                break;
-            }
-            ws_renderer_set_tile_entry_capacity(r, (uint64_t)needed + needed / 4 + 4096);
-        }
-        if (rc) break;
-        rgba.resize((size_t)w * h * 4);
-        if ((rc = ws_download_texture_rgba8(ctx, target, WS_FORMAT_RGBA16_FLOAT, w, h, (size_t)w * 8, rgba.data(), nullptr))) break;
-        char name[32];
-        std::snprintf(name, sizeof name, "/%05u.png", i);
-        if ((rc = ws_png_write_rgba8((dir + name).c_str(), w, h, rgba.data(), (size_t)w * 4))) break;
-        if (rendered) *rendered = i + 1;
-    }
-    if (target) ws_device_free(ctx, target);
-    ws_renderer_destroy(r);
-    return rc;
-}
-
-// Every camera of `split` into per-Gaussian accumulators, set up exactly as ws_render_views sets its frames up.  No target and
-// no blend: prepare() + per_camera's attribution launches on one stream, one sync at the end, then one look at the error bits.
-// The camera set-up of ws_scene_accumulate_contrib and ws_scene_accumulate_removal.
+// ---- the scene drivers ------------------------------------------------------------------------------------------------------
+// Seven drivers, ONE walk over the cameras of a split (SceneWalk::pass).  A driver is its argument checks, a description of the
+// frames it needs (SceneFrames) and what it does with one frame (its per-frame function); the small rules -- the frame's size
+// under the 1600-px cap, the ground-truth PNG's name and aspect, what a frame's error bits mean -- are scene_frames.h's, and how
+// far an entry list grows is frame_plan.h's.  Like everything here the walk only calls public entry points.
 extern "C++" {
 namespace {
-template <class PerCamera>
-int accumulate_over_cameras(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const std::string& who,
-                            const char* incomplete, uint32_t* frames, PerCamera&& per_camera) {
-    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
-    std::vector<ws_scene_camera> cams(n);
-    ws_scene_cameras(scene, split, n, cams.data());
-    ws_renderer* r = nullptr;
-    int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), &r);
-    if (rc) return rc;
-    rc = ws_renderer_enable_contrib(r, 1);
-    uint32_t done = 0;
-    for (uint32_t i = 0; i < n && rc == WS_OK; ++i) {
-        uint32_t w = cams[i].width, h = cams[i].height;
-        if (w > 1600) {  // bin/render.rs:58-62
-            const float s = (float)w / 1600.0f;
-            w = 1600;
-            h = (uint32_t)((float)h / s);
-        }
-        if (w == 0 || h == 0) {
-            rc = fail(WS_ERR_INVALID, who + ": camera with an empty image");
-            break;
-        }
-        ws_splatting_args a;
-        offline_args(cams[i], pc, w, h, &a);
-        if ((rc = ws_renderer_prepare(r, pc, &a, nullptr))) break;
-        if ((rc = per_camera(r))) break;
-        ++done;
-    }
-    if (rc == WS_OK) {
-        uint32_t bits = 0;
-        rc = ws_renderer_errors(r, &bits, nullptr, 1);  // (the one sync)
-        if (rc == WS_OK && bits)
-            rc = fail(WS_ERR_OVERFLOW, who + ": a frame reported device-side errors (tile-entry overflow or a look-back time-out): " + incomplete);
-    }
-    if (frames) *frames = done;
-    ws_renderer_destroy(r);
-    return rc;
-}
-}  // namespace
-}  // extern "C++"
-
-int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c,
-                                uint32_t* frames) {
-    if (!ctx || !pc || !scene || !c) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: null argument");
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: split must be train or test");
-    if (frames) *frames = 0;
-    if (ws_contrib_num_points(c) != ws_pointcloud_num_points(pc))
-        return fail(WS_ERR_INVALID, "ws_scene_accumulate_contrib: the accumulator was created for another number of points");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_contrib: the context stops its frames early (debug_cut)");
-    return accumulate_over_cameras(ctx, pc, scene, split, "ws_scene_accumulate_contrib", "the accumulator is incomplete", frames,
-                                   [&](ws_renderer* r) { return ws_renderer_accumulate_contrib(r, pc, c, nullptr); });
-}
-
-// ... and what deleting each Gaussian alone would do to them (websplat.h "Removal effect"), over the cloud's own background
-// colour, or black; `weight`: the plain contribution sums of the same prepared frames.
-int ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, int kind, float scale,
-                                ws_contrib* effect, ws_contrib* weight, uint32_t* frames) {
-    const std::string who("ws_scene_accumulate_removal");
-    if (frames) *frames = 0;
-    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
-    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST) return fail(WS_ERR_INVALID, who + ": split must be train or test");
-    if (!ctx || !pc || !scene || !effect) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (ws_contrib_num_points(effect) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
-        return fail(WS_ERR_INVALID, who + ": an accumulator was created for another number of points");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
-    ws_removal_params rp;
-    std::memset(&rp, 0, sizeof rp);
-    float pc_bg[3];
-    if (ws_pointcloud_background_color(pc, pc_bg) == 1) std::memcpy(rp.background, pc_bg, sizeof pc_bg);  // (else black)
-    rp.kind = kind;
-    rp.scale = scale;
-    return accumulate_over_cameras(ctx, pc, scene, split, who, "the accumulators are incomplete", frames, [&](ws_renderer* r) {
-        int rc = ws_renderer_accumulate_removal(r, pc, effect, &rp, nullptr);
-        if (rc == WS_OK && weight) rc = ws_renderer_accumulate_contrib(r, pc, weight, nullptr);
-        return rc;
-    });
-}
-
-// Every camera of `split` compared on the device (websplat.h "Image metrics"): `pc` against another cloud, or against
-// ground-truth PNGs.  Like everything here it only calls public entry points.
-namespace {
-
-// bin/render.rs:58-62: the frame size of ws_render_views
-bool capped_size(const ws_scene_camera& c, uint32_t* w, uint32_t* h) {
-    *w = c.width;
-    *h = c.height;
-    if (*w > 1600) {
-        const float s = (float)*w / 1600.0f;
-        *w = 1600;
-        *h = (uint32_t)((float)*h / s);
-    }
-    return *w != 0 && *h != 0;
-}
 
 ws_image_view view_of(const void* p, ws_color_format f, size_t pitch, const float* bg) {
     ws_image_view v;
@@ -282,192 +122,6 @@ ws_image_view view_of(const void* p, ws_color_format f, size_t pitch, const floa
     return v;
 }
 
-// prepare + render one frame, then look at its error bits (syncs): a plain overflow grows the entry list and draws again
-int eval_render_checked(ws_renderer* r, const ws_pointcloud* pc, const ws_splatting_args* a, void* target, size_t pitch) {
-    const float clear[4] = {0, 0, 0, 0};
-    int rc = WS_OK;
-    for (int attempt = 0; attempt < 3; ++attempt) {  // (ws_render_views' overflow retry)
-        if ((rc = ws_renderer_prepare(r, pc, a, nullptr))) return rc;
-        if ((rc = ws_renderer_render(r, pc, clear, target, pitch, nullptr))) return rc;
-        uint32_t bits = 0, needed = 0;
-        if ((rc = ws_renderer_errors(r, &bits, &needed, 1))) return rc;
-        if (bits == 0) return WS_OK;
-        if ((bits & ~1u) != 0 || attempt == 2)
-            return fail(WS_ERR_OVERFLOW, "ws_scene_evaluate: the frame reported device-side errors (tile-entry overflow or a look-back time-out)");
-        ws_renderer_set_tile_entry_capacity(r, (uint64_t)needed + needed / 4 + 4096);
-    }
-    return rc;
-}
-
-// ---- the per-camera set-up of ws_scene_evaluate, shared with ws_scene_accumulate_error ------------------------------------------
-// a renderer as ws_render_views makes it: Rgba16Float, the context's render-views blend mode
-int eval_renderer(ws_context* ctx, const ws_pointcloud* pc, ws_renderer** r) {
-    const int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), r);
-    if (rc == WS_OK && !ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(*r, WS_BLEND_TARGET_PRECISION);
-    return rc;
-}
-
-// the largest Rgba16Float frame of the cameras at ws_render_views' sizes, in pixels; 0: a camera with an empty image
-size_t eval_max_pixels(const std::vector<ws_scene_camera>& cams, bool* ok) {
-    size_t px = 0;
-    *ok = true;
-    for (const ws_scene_camera& c : cams) {
-        uint32_t w, h;
-        if (!capped_size(c, &w, &h)) *ok = false;
-        else px = std::max(px, (size_t)w * h);
-    }
-    return px;
-}
-
-// <gt_dir>/<img_name>, ".png" appended unless the name ends in it: read as RGBA8 and checked against the camera's aspect.
-// *rgba is released with ws_host_free (nothing to release on an error).
-int truth_read(const char* who, const char* gt_dir, const ws_scene_camera& c, uint32_t* w, uint32_t* h, uint8_t** rgba) {
-    std::string name(c.img_name, strnlen(c.img_name, sizeof c.img_name));
-    const size_t L = name.size();
-    const bool has_ext = L >= 4 && name[L - 4] == '.' && (name[L - 3] | 0x20) == 'p' && (name[L - 2] | 0x20) == 'n' && (name[L - 1] | 0x20) == 'g';
-    const std::string path = std::string(gt_dir) + "/" + name + (has_ext ? "" : ".png");
-    *rgba = nullptr;
-    int rc = ws_png_read_rgba8(path.c_str(), w, h, rgba);  // (the message names the file)
-    if (rc) return rc;
-    const uint64_t skew = (uint64_t)*w * c.height > (uint64_t)*h * c.width ? (uint64_t)*w * c.height - (uint64_t)*h * c.width
-                                                                            : (uint64_t)*h * c.width - (uint64_t)*w * c.height;
-    if (c.width == 0 || c.height == 0 || skew > std::max(c.width, c.height)) {
-        rc = fail(WS_ERR_INVALID, std::string(who) + ": " + path + " (" + std::to_string(*w) + " x " + std::to_string(*h) + ") does not have the aspect of its camera (" +
-                                      std::to_string(c.width) + " x " + std::to_string(c.height) + ")");
-        ws_host_free(*rgba);
-        *rgba = nullptr;
-    }
-    return rc;
-}
-
-// the frame's Rgba16Float target and the image it is compared with (other_texel bytes per pixel), grown when a frame has more
-// pixels than both hold (every earlier frame has been waited for, or the free waits)
-struct EvalBuffers {
-    void *target = nullptr, *other = nullptr;
-    size_t capacity = 0;  // pixels both hold
-};
-int eval_buffers_reserve(ws_context* ctx, EvalBuffers* eb, size_t px, size_t other_texel) {
-    if (px <= eb->capacity) return WS_OK;
-    if (eb->target) ws_device_free(ctx, eb->target);
-    if (eb->other) ws_device_free(ctx, eb->other);
-    eb->target = eb->other = nullptr;
-    eb->capacity = 0;
-    int rc = ws_device_malloc(ctx, px * 8, &eb->target);
-    if (rc == WS_OK) rc = ws_device_malloc(ctx, px * other_texel, &eb->other);
-    if (rc == WS_OK) eb->capacity = px;
-    return rc;
-}
-void eval_buffers_free(ws_context* ctx, EvalBuffers* eb) {
-    if (eb->target) ws_device_free(ctx, eb->target);
-    if (eb->other) ws_device_free(ctx, eb->other);
-    eb->target = eb->other = nullptr;
-    eb->capacity = 0;
-}
-
-// the ground-truth image of a frame into eb->other: the comparison of the frame before still reads it, so that is waited for
-int truth_upload(ws_context* ctx, EvalBuffers* eb, const uint8_t* rgba, size_t px) {
-    int rc = ws_sync(ctx, nullptr);
-    if (rc == WS_OK) rc = ws_memcpy_h2d(ctx, eb->other, rgba, px * 4, nullptr);
-    return rc;
-}
-
-int evaluate_against_cloud(ws_context* ctx, const ws_pointcloud* pc, const ws_pointcloud* ref_pc, const std::vector<ws_scene_camera>& cams,
-                           const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
-    bool sizes_ok;
-    const size_t bytes = eval_max_pixels(cams, &sizes_ok) * 8;
-    if (!sizes_ok) return fail(WS_ERR_INVALID, "ws_scene_evaluate: camera with an empty image");
-    const uint32_t base = ws_metrics_count(m);
-    ws_renderer* rs[2] = {nullptr, nullptr};
-    void* targets[2] = {nullptr, nullptr};
-    const ws_pointcloud* clouds[2] = {pc, ref_pc};
-    int rc = WS_OK;
-    for (int k = 0; k < 2 && rc == WS_OK; ++k) {
-        rc = eval_renderer(ctx, clouds[k], &rs[k]);
-        if (rc == WS_OK) rc = ws_device_malloc(ctx, bytes, &targets[k]);
-    }
-    const float clear[4] = {0, 0, 0, 0};
-    // One stream, nothing read back per frame: the error bits are looked at once, after the sync.  A pass whose frames
-    // overflowed the tile-entry list is not a measurement: grow the lists and run the whole split again (as ws_measure does).
-    for (int attempt = 0; rc == WS_OK; ++attempt) {
-        *done = 0;
-        for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
-            uint32_t w, h;
-            capped_size(cams[i], &w, &h);
-            for (int k = 0; k < 2 && rc == WS_OK; ++k) {
-                ws_splatting_args a;
-                offline_args(cams[i], clouds[k], w, h, &a);
-                rc = ws_renderer_prepare(rs[k], clouds[k], &a, nullptr);
-                if (rc == WS_OK) rc = ws_renderer_render(rs[k], clouds[k], clear, targets[k], (size_t)w * 8, nullptr);
-            }
-            if (rc != WS_OK) break;
-            const ws_image_view va = view_of(targets[0], WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
-            const ws_image_view vb = view_of(targets[1], WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
-            // (the next frame's renders are ordered behind this comparison on the stream: the two targets are reused)
-            rc = ws_metrics_add(m, &va, &vb, w, h, flags, nullptr, 0, nullptr);
-            if (rc == WS_OK) ++*done;
-        }
-        uint32_t all_bits = 0;
-        for (int k = 0; k < 2 && rc == WS_OK; ++k) {  // (the one sync)
-            uint32_t bits = 0, needed = 0;
-            rc = ws_renderer_errors(rs[k], &bits, &needed, 1);
-            all_bits |= bits;
-            if (rc == WS_OK && (bits & 1u)) ws_renderer_set_tile_entry_capacity(rs[k], (uint64_t)needed + needed / 4 + 4096);
-        }
-        if (rc != WS_OK || all_bits == 0) break;
-        ws_internal_metrics_truncate(m, base);
-        *done = 0;
-        if ((all_bits & ~1u) != 0 || attempt == 2)
-            rc = fail(WS_ERR_OVERFLOW, "ws_scene_evaluate: frames reported device-side errors (tile-entry overflow or a look-back time-out)");
-    }
-    if (rc != WS_OK) {
-        (void)ws_sync(ctx, nullptr);
-        ws_internal_metrics_truncate(m, base);
-        *done = 0;
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (rs[k]) ws_renderer_destroy(rs[k]);
-        if (targets[k]) ws_device_free(ctx, targets[k]);
-    }
-    return rc;
-}
-
-int evaluate_against_files(ws_context* ctx, const ws_pointcloud* pc, const char* gt_dir, const std::vector<ws_scene_camera>& cams,
-                           const float bg[3], uint32_t flags, ws_metrics* m, uint32_t* done) {
-    const uint32_t base = ws_metrics_count(m);
-    ws_renderer* r = nullptr;
-    int rc = eval_renderer(ctx, pc, &r);
-    if (rc) return rc;
-    EvalBuffers eb;
-    for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
-        const ws_scene_camera& c = cams[i];
-        uint32_t w = 0, h = 0;
-        uint8_t* rgba = nullptr;
-        if ((rc = truth_read("ws_scene_evaluate", gt_dir, c, &w, &h, &rgba))) break;
-        const size_t px = (size_t)w * h;
-        rc = eval_buffers_reserve(ctx, &eb, px, 4);
-        // no resampler: the camera's own field of view on the PNG's viewport (the renderer derives the focal length from both)
-        ws_splatting_args a;
-        if (rc == WS_OK) offline_args(c, pc, w, h, &a);
-        if (rc == WS_OK) rc = truth_upload(ctx, &eb, rgba, px);
-        ws_host_free(rgba);
-        if (rc == WS_OK) rc = eval_render_checked(r, pc, &a, eb.target, (size_t)w * 8);
-        if (rc != WS_OK) break;
-        const ws_image_view va = view_of(eb.target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg);
-        const ws_image_view vb = view_of(eb.other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr);  // opaque: alpha ignored
-        rc = ws_metrics_add(m, &va, &vb, w, h, flags, nullptr, 0, nullptr);
-        if (rc == WS_OK) ++*done;
-    }
-    const int src = ws_sync(ctx, nullptr);
-    if (rc == WS_OK) rc = src;
-    if (rc != WS_OK) {
-        ws_internal_metrics_truncate(m, base);
-        *done = 0;
-    }
-    eval_buffers_free(ctx, &eb);
-    ws_renderer_destroy(r);
-    return rc;
-}
-
 // the cloud's own background colour, or black: what both images of a comparison go over
 void eval_background(const ws_pointcloud* pc, float bg[3]) {
     bg[0] = bg[1] = bg[2] = 0.0f;
@@ -475,172 +129,219 @@ void eval_background(const ws_pointcloud* pc, float bg[3]) {
     if (ws_pointcloud_background_color(pc, pc_bg) == 1) std::memcpy(bg, pc_bg, sizeof pc_bg);
 }
 
-}  // namespace
-
-int ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
-                      const char* gt_dir, uint32_t flags, ws_metrics* m, uint32_t* frames) {
-    if (!ctx || !pc || !scene || !m) return fail(WS_ERR_INVALID, "ws_scene_evaluate: null argument");
-    if (frames) *frames = 0;
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL)
-        return fail(WS_ERR_INVALID, "ws_scene_evaluate: split must be train, test or all");
-    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, "ws_scene_evaluate: exactly one of ref_pc and gt_dir");
-    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_scene_evaluate: unknown flag bits");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_evaluate: the context stops its frames early (debug_cut)");
-    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
-    std::vector<ws_scene_camera> cams(n);
-    ws_scene_cameras(scene, split, n, cams.data());
-    float bg[3];
-    eval_background(pc, bg);
-    uint32_t done = 0;
-    const int rc = ref_pc ? evaluate_against_cloud(ctx, pc, ref_pc, cams, bg, flags, m, &done)
-                          : evaluate_against_files(ctx, pc, gt_dir, cams, bg, flags, m, &done);
-    if (frames) *frames = done;
+// One look at a renderer's error bits (syncs, and clears them).  A plain overflow leaves the renderer a grown entry list for
+// whatever it draws next.
+int look_and_grow(ws_renderer* r, uint32_t* bits) {
+    uint32_t needed = 0;
+    const int rc = ws_renderer_errors(r, bits, &needed, 1);
+    if (rc == WS_OK && (*bits & 1u)) ws_renderer_set_tile_entry_capacity(r, grown_entry_capacity(needed));
     return rc;
 }
 
-// The frames of ws_scene_accumulate_error and ws_scene_accumulate_gradient: every camera of `split` set up as ws_scene_evaluate
-// sets it up -- `pc` prepared with contributions on (and, render_a, drawn into an Rgba16Float target), image b the render of
-// `ref_pc` or the ground-truth PNG, a scratch plane of plane_texel bytes per pixel -- then per_frame, all on one stream; one sync
-// and one look at the error bits at the end.
-extern "C++" {
-namespace {
-struct ErrorFrame {
-    ws_renderer* r;
+// What a driver does about frames that overflowed their entry lists.  These are real differences:
+enum OverflowPolicy {
+    OVERFLOW_DRAWS_THE_FRAME_AGAIN,  // look at the bits behind every frame (a sync per frame), grow, draw that frame again
+    OVERFLOW_IS_THE_DRIVERS,         // nothing read back per frame: SceneWalk::bits after the pass, and the driver may run another
+    OVERFLOW_FAILS,                  // sums of frames that dropped entries cannot be mended: WS_ERR_OVERFLOW, "... incomplete"
+};
+
+// The frames a driver needs of every camera of `split` (sorted by id).
+struct SceneFrames {
+    const char* who;  // the entry point, for messages
+    const ws_pointcloud* pc;
+    const ws_scene* scene;
+    int split;
+    const ws_pointcloud* ref_pc;  // image b: the render of ref_pc, or the PNGs of gt_dir, or (neither) none
+    const char* gt_dir;
+    bool contrib;        // pc is prepared with contributions enabled
+    bool render_a;       // pc is drawn into the Rgba16Float target, cleared to TRANSPARENT
+    size_t plane_texel;  // bytes per pixel of a scratch plane, 0: none
+    OverflowPolicy overflow;
+    const char* incomplete;  // OVERFLOW_FAILS: what the message calls incomplete
+};
+
+// One frame, as the per-frame function gets it: everything is enqueued on the null stream, nothing has been waited for.
+struct SceneFrame {
+    uint32_t index, count;  // the camera's position in the split, and the split's size
+    ws_renderer* r;         // pc's renderer, prepared for this frame
     uint32_t w, h;
-    ws_image_view va, vb;  // pc's render over the background (render_a only), and what it is compared with
+    ws_image_view va, vb;  // pc's render over the background (render_a only), and image b
     void* plane;
 };
-template <class PerFrame>
-int over_error_frames(const std::string& who, ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split,
-                      const ws_pointcloud* ref_pc, const char* gt_dir, size_t plane_texel, bool render_a, uint32_t* frames,
-                      PerFrame&& per_frame) {
-    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
-    std::vector<ws_scene_camera> cams(n);
-    ws_scene_cameras(scene, split, n, cams.data());
+
+// The walk owns the renderers (set up as bin/render.rs:154 needs them), the target, image b and the plane.  A frame is the
+// camera's capped size (bin/render.rs:58-62), fit_near_far, the offline callers' SplattingArgs -- except with gt_dir, where it
+// is the PNG's own size under the camera's field of view (no resampler: the renderer derives the focal length from both).
+struct SceneWalk {
+    ws_context* ctx;
+    const SceneFrames d;
+    std::vector<ws_scene_camera> cams;
+    size_t max_px = 0;  // the largest frame at the cameras' own sizes
     float bg[3];
-    eval_background(pc, bg);
-    size_t cloud_px = 0;  // ref_pc: every frame's size is known up front, nothing is reallocated on the way
-    if (ref_pc) {
-        bool sizes_ok;
-        cloud_px = eval_max_pixels(cams, &sizes_ok);
-        if (!sizes_ok) return fail(WS_ERR_INVALID, who + ": camera with an empty image");
-    }
     ws_renderer *r = nullptr, *rb = nullptr;
-    EvalBuffers eb;
-    void* plane = nullptr;
-    size_t plane_px = 0;
-    int rc = eval_renderer(ctx, pc, &r);
-    if (rc == WS_OK) rc = ws_renderer_enable_contrib(r, 1);
-    if (rc == WS_OK && ref_pc) rc = eval_renderer(ctx, ref_pc, &rb);
-    const float clear[4] = {0, 0, 0, 0};
-    uint32_t done = 0;
-    for (size_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
-        const ws_scene_camera& c = cams[i];
-        uint32_t w = 0, h = 0;
-        uint8_t* rgba = nullptr;
-        if (ref_pc) capped_size(c, &w, &h);
-        else if ((rc = truth_read(who.c_str(), gt_dir, c, &w, &h, &rgba))) break;
-        const size_t px = (size_t)w * h;
-        rc = eval_buffers_reserve(ctx, &eb, ref_pc ? cloud_px : px, ref_pc ? 8 : 4);
-        if (rc == WS_OK && eb.capacity > plane_px) {
-            if (plane) ws_device_free(ctx, plane);
-            plane = nullptr;
-            plane_px = 0;
-            if ((rc = ws_device_malloc(ctx, eb.capacity * plane_texel, &plane)) == WS_OK) plane_px = eb.capacity;
-        }
-        if (rc == WS_OK && !ref_pc) rc = truth_upload(ctx, &eb, rgba, px);
-        if (rgba) ws_host_free(rgba);
-        ws_splatting_args a;
-        if (rc == WS_OK) {
-            offline_args(c, pc, w, h, &a);
-            rc = ws_renderer_prepare(r, pc, &a, nullptr);
-        }
-        if (rc == WS_OK && render_a) rc = ws_renderer_render(r, pc, clear, eb.target, (size_t)w * 8, nullptr);
-        if (rc == WS_OK && ref_pc) {
-            ws_splatting_args ab;
-            offline_args(c, ref_pc, w, h, &ab);
-            rc = ws_renderer_prepare(rb, ref_pc, &ab, nullptr);
-            if (rc == WS_OK) rc = ws_renderer_render(rb, ref_pc, clear, eb.other, (size_t)w * 8, nullptr);
-        }
-        if (rc != WS_OK) break;
-        const ErrorFrame f{r, w, h, view_of(eb.target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg),
-                           ref_pc ? view_of(eb.other, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg)
-                                  : view_of(eb.other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr),  // opaque: alpha ignored
-                           plane};
-        // (the next frame's renders and plane are ordered behind these on the stream: targets and plane are reused)
-        rc = per_frame(f);
-        if (rc == WS_OK) ++done;
-    }
-    if (rc == WS_OK) {
-        uint32_t all_bits = 0;
-        ws_renderer* both[2] = {r, rb};
-        for (int k = 0; k < 2 && rc == WS_OK; ++k) {  // (the one sync)
-            uint32_t bits = 0;
-            if (both[k]) rc = ws_renderer_errors(both[k], &bits, nullptr, 1);
-            all_bits |= bits;
-        }
-        if (rc == WS_OK && all_bits)
-            rc = fail(WS_ERR_OVERFLOW, who + ": a frame reported device-side errors (tile-entry overflow or a look-back "
-                                             "time-out): the accumulators are incomplete");
-    } else {
-        (void)ws_sync(ctx, nullptr);
-    }
-    if (frames) *frames = done;
-    if (plane) ws_device_free(ctx, plane);
-    eval_buffers_free(ctx, &eb);
-    if (rb) ws_renderer_destroy(rb);
-    if (r) ws_renderer_destroy(r);
-    return rc;
-}
-}  // namespace
-}  // extern "C++"
+    void *target = nullptr, *other = nullptr, *plane = nullptr;
+    size_t capacity = 0;  // pixels that target, image b and plane hold
+    uint32_t frames = 0;  // frames of the last pass whose per-frame function succeeded
+    uint32_t bits = 0;    // error bits the last pass left behind
 
-// Every camera of `split` blamed on the Gaussians of `pc` (websplat.h "Attributing a pixel plane to Gaussians"): the frames of
-// ws_scene_evaluate, their per-pixel error against `ref_pc` or the ground-truth PNGs, and the weighted contribution sums.
-int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
-                              const char* gt_dir, int kind, uint32_t flags, ws_contrib* err, ws_contrib* weight, uint32_t* frames) {
-    if (!ctx || !pc || !scene || !err) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: null argument");
-    if (frames) *frames = 0;
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL)
-        return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: split must be train, test or all");
-    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: exactly one of ref_pc and gt_dir");
-    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: unknown flag bits");
-    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS && kind != WS_ERROR_DSSIM)
-        return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: kind must be WS_ERROR_SQ, WS_ERROR_ABS or WS_ERROR_DSSIM");
-    if (ws_contrib_num_points(err) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
-        return fail(WS_ERR_INVALID, "ws_scene_accumulate_error: an accumulator was created for another number of points");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, "ws_scene_accumulate_error: the context stops its frames early (debug_cut)");
-    ws_metrics* ssim = nullptr;  // WS_ERROR_DSSIM: one slot, written again by every frame; only its map is used
-    int rc = kind == WS_ERROR_DSSIM ? ws_metrics_create(ctx, 1, &ssim) : WS_OK;
-    if (rc == WS_OK)
-        rc = over_error_frames("ws_scene_accumulate_error", ctx, pc, scene, split, ref_pc, gt_dir, 4, true, frames, [&](const ErrorFrame& f) {
-            ws_plane_view pv;
-            pv.d_values = static_cast<const float*>(f.plane);
-            pv.row_pitch_bytes = (size_t)f.w * 4;
-            pv.scale = 1.0f;
-            pv.bias = 0.0f;
-            int frc;
-            if (kind == WS_ERROR_DSSIM) {  // (1 - ssim) / 2 of the map
-                frc = ws_metrics_reset(ssim, nullptr);
-                if (frc == WS_OK) frc = ws_metrics_add(ssim, &f.va, &f.vb, f.w, f.h, flags, static_cast<float*>(f.plane), (size_t)f.w * 4, nullptr);
-                pv.scale = -0.5f;
-                pv.bias = 0.5f;
-            } else {
-                frc = ws_image_error_plane(ctx, &f.va, &f.vb, f.w, f.h, kind, flags, static_cast<float*>(f.plane), (size_t)f.w * 4, nullptr);
+    SceneWalk(ws_context* c, const SceneFrames& f) : ctx(c), d(f) {}
+    SceneWalk(const SceneWalk&) = delete;
+    ~SceneWalk() {
+        release();
+        if (rb) ws_renderer_destroy(rb);
+        if (r) ws_renderer_destroy(r);
+    }
+
+    // The cameras and the renderers.  A camera with an empty image is refused here, before the first frame.
+    int open() {
+        const uint32_t n = ws_scene_cameras(d.scene, d.split, 0, nullptr);
+        cams.resize(n);
+        ws_scene_cameras(d.scene, d.split, n, cams.data());
+        for (size_t i = 0; i < cams.size() && !d.gt_dir; ++i) {
+            uint32_t w, h;
+            if (!scene_frame_size(cams[i].width, cams[i].height, &w, &h)) return fail(WS_ERR_INVALID, std::string(d.who) + ": camera with an empty image");
+            max_px = std::max(max_px, (size_t)w * h);
+        }
+        eval_background(d.pc, bg);
+        int rc = renderer_for(d.pc, &r);
+        if (rc == WS_OK && d.contrib) rc = ws_renderer_enable_contrib(r, 1);
+        if (rc == WS_OK && d.ref_pc) rc = renderer_for(d.ref_pc, &rb);
+        return rc;
+    }
+
+    // bin/render.rs:154 draws into an Rgba16Float target: the fixed-function blender rounds the destination to f16 after every
+    // splat.  The target-precision blend mode reproduces that (ws_context_config::render_views_fast_blend: the throughput
+    // blend, one rounding at the store).  Only render() reads the mode.
+    int renderer_for(const ws_pointcloud* cloud, ws_renderer** out) {
+        const int rc = ws_renderer_create(ctx, WS_FORMAT_RGBA16_FLOAT, ws_pointcloud_sh_deg(cloud), ws_pointcloud_compressed(cloud), out);
+        if (rc == WS_OK && !ctx->render_views_fast_blend) (void)ws_renderer_set_blend_mode(*out, WS_BLEND_TARGET_PRECISION);
+        return rc;
+    }
+
+    void release() {
+        for (void** p : {&target, &other, &plane}) {
+            if (*p) ws_device_free(ctx, *p);
+            *p = nullptr;
+        }
+        capacity = 0;
+    }
+    // grown when a frame has more pixels than they hold (every earlier frame has been waited for, or the free waits)
+    int reserve(size_t px) {
+        if (px <= capacity) return WS_OK;
+        release();
+        int rc = d.render_a ? ws_device_malloc(ctx, px * 8, &target) : (int)WS_OK;
+        if (rc == WS_OK && (d.ref_pc || d.gt_dir)) rc = ws_device_malloc(ctx, px * (d.ref_pc ? 8 : 4), &other);
+        if (rc == WS_OK && d.plane_texel) rc = ws_device_malloc(ctx, px * d.plane_texel, &plane);
+        if (rc == WS_OK) capacity = px;
+        return rc;
+    }
+
+    // The camera's ground-truth PNG as RGBA8, refused unless it has the camera's aspect.  *rgba is released with ws_host_free
+    // (nothing to release on an error).
+    int read_truth(const ws_scene_camera& c, uint32_t* w, uint32_t* h, uint8_t** rgba) {
+        const std::string path = scene_truth_path(d.gt_dir, c);
+        int rc = ws_png_read_rgba8(path.c_str(), w, h, rgba);  // (the message names the file)
+        if (rc == WS_OK && !scene_truth_aspect_ok(*w, *h, c.width, c.height)) {
+            rc = fail(WS_ERR_INVALID, std::string(d.who) + ": " + path + " (" + std::to_string(*w) + " x " + std::to_string(*h) + ") does not have the aspect of its camera (" +
+                                          std::to_string(c.width) + " x " + std::to_string(c.height) + ")");
+            ws_host_free(*rgba);
+            *rgba = nullptr;
+        }
+        return rc;
+    }
+
+    // Every camera once, in order, all on one stream: image b, pc prepared (and drawn), the per-frame function.  The next frame's
+    // renders and plane are ordered behind the per-frame function's work on the stream: targets and plane are reused.  One sync
+    // and one look at the error bits at the end.  May be called again: the renderers keep what they learnt of the demand.
+    template <class PerFrame>
+    int pass(PerFrame&& per_frame) {
+        const float clear[4] = {0, 0, 0, 0};
+        const std::string who(d.who);
+        int rc = WS_OK;
+        frames = bits = 0;
+        for (uint32_t i = 0; i < cams.size() && rc == WS_OK; ++i) {
+            const ws_scene_camera& c = cams[i];
+            uint32_t w = 0, h = 0;
+            uint8_t* rgba = nullptr;
+            if (d.gt_dir) rc = read_truth(c, &w, &h, &rgba);
+            else scene_frame_size(c.width, c.height, &w, &h);
+            const size_t px = (size_t)w * h;
+            if (rc == WS_OK) rc = reserve(d.gt_dir ? px : max_px);
+            // the ground truth into image b: the comparison of the frame before still reads it, so that is waited for
+            if (rc == WS_OK && rgba) rc = ws_sync(ctx, nullptr);
+            if (rc == WS_OK && rgba) rc = ws_memcpy_h2d(ctx, other, rgba, px * 4, nullptr);
+            if (rgba) ws_host_free(rgba);
+            ws_splatting_args a;
+            if (rc == WS_OK) offline_args(c, d.pc, w, h, &a);
+            for (int attempt = 0; rc == WS_OK; ++attempt) {
+                rc = ws_renderer_prepare(r, d.pc, &a, nullptr);
+                if (rc == WS_OK && d.render_a) rc = ws_renderer_render(r, d.pc, clear, target, (size_t)w * 8, nullptr);
+                if (rc != WS_OK || d.overflow != OVERFLOW_DRAWS_THE_FRAME_AGAIN) break;
+                uint32_t frame_bits = 0;
+                rc = look_and_grow(r, &frame_bits);
+                const FrameVerdict v = frame_verdict(frame_bits, attempt);
+                if (rc != WS_OK || v == FRAME_DONE) break;
+                if (v == FRAME_FAILED) rc = fail(WS_ERR_OVERFLOW, who + ": the frame reported device-side errors (tile-entry overflow or a look-back time-out)");
             }
-            if (frc == WS_OK) frc = ws_renderer_accumulate_weighted(f.r, pc, err, &pv, nullptr);
-            if (frc == WS_OK && weight) frc = ws_renderer_accumulate_contrib(f.r, pc, weight, nullptr);
-            return frc;
-        });
-    if (ssim) ws_metrics_destroy(ssim);
+            if (rc == WS_OK && rb) {
+                offline_args(c, d.ref_pc, w, h, &a);
+                rc = ws_renderer_prepare(rb, d.ref_pc, &a, nullptr);
+                if (rc == WS_OK) rc = ws_renderer_render(rb, d.ref_pc, clear, other, (size_t)w * 8, nullptr);
+            }
+            if (rc != WS_OK) break;
+            const SceneFrame f{i, (uint32_t)cams.size(), r, w, h, view_of(target, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg),
+                               rb ? view_of(other, WS_FORMAT_RGBA16_FLOAT, (size_t)w * 8, bg)
+                                  : view_of(other, WS_FORMAT_RGBA8_UNORM, (size_t)w * 4, nullptr),  // opaque: alpha ignored
+                               plane};
+            rc = per_frame(f);
+            if (rc == WS_OK) ++frames;
+        }
+        for (ws_renderer* x : {r, rb}) {  // (the one sync)
+            uint32_t b = 0;
+            if (rc == WS_OK && x) rc = look_and_grow(x, &b);
+            bits |= b;
+        }
+        if (rc == WS_OK && bits && d.overflow == OVERFLOW_FAILS)
+            rc = fail(WS_ERR_OVERFLOW, who + ": a frame reported device-side errors (tile-entry overflow or a look-back time-out): " + d.incomplete);
+        if (rc != WS_OK) (void)ws_sync(ctx, nullptr);
+        return rc;
+    }
+};
+
+// a driver that walks its split once: *frames is what it enqueued, also when it fails
+template <class PerFrame>
+int walk_once(ws_context* ctx, const SceneFrames& d, uint32_t* frames, PerFrame&& per_frame) {
+    SceneWalk walk(ctx, d);
+    int rc = walk.open();
+    if (rc == WS_OK) rc = walk.pass(per_frame);
+    if (frames) *frames = walk.frames;
     return rc;
 }
 
-// ... and the colour and ln-opacity gradients of that error (websplat.h "Gradients of an image loss"): image a is the frame's
-// f32 base plane over the cloud's background, the first half of the scratch plane; the loss gradient is the second half.
-// One frame of it, shared with ws_scene_refit: ws_renderer_accumulate_gradient in its two steps, the plane made of pass 1's image.
-extern "C++" {
-static int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, ws_grad* grad, const ws_gradient_params& gp, int kind, const ErrorFrame& f) {
+// what several entry points refuse in the same words
+int refuse_unless_one_split(const std::string& who, int split) {
+    return split == WS_SPLIT_TRAIN || split == WS_SPLIT_TEST ? (int)WS_OK : fail(WS_ERR_INVALID, who + ": split must be train or test");
+}
+int refuse_unless_a_split(const std::string& who, int split) {
+    return split == WS_SPLIT_TRAIN || split == WS_SPLIT_TEST || split == WS_SPLIT_ALL ? (int)WS_OK : fail(WS_ERR_INVALID, who + ": split must be train, test or all");
+}
+int refuse_unless_one_image_b(const std::string& who, const ws_pointcloud* ref_pc, const char* gt_dir) {
+    return (ref_pc != nullptr) != (gt_dir != nullptr) ? (int)WS_OK : fail(WS_ERR_INVALID, who + ": exactly one of ref_pc and gt_dir");
+}
+int refuse_debug_cut(const std::string& who, const ws_context* ctx) {
+    return ctx->debug_cut ? fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)") : (int)WS_OK;
+}
+int refuse_kind(const std::string& who, int kind) {
+    return kind == WS_ERROR_SQ || kind == WS_ERROR_ABS ? (int)WS_OK : fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
+}
+int refuse_scale(const std::string& who, const char* name, float v) {
+    return std::isfinite(v) && v > 0.0f ? (int)WS_OK : fail(WS_ERR_INVALID, who + ": " + name + " must be finite and above 0");
+}
+
+// One frame of ws_scene_accumulate_gradient and ws_scene_refit: image a is the frame's f32 base plane over the cloud's background,
+// the first half of the scratch plane; the loss gradient is the second half.  ws_renderer_accumulate_gradient in its two steps,
+// the plane made of pass 1's image.
+int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, ws_grad* grad, const ws_gradient_params& gp, int kind, const SceneFrame& f) {
     const size_t pitch = (size_t)f.w * 16;
     float* base = static_cast<float*>(f.plane);
     float* g = base + (size_t)f.w * f.h * 4;
@@ -655,48 +356,185 @@ static int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, ws_grad* gra
     if (frc == WS_OK) frc = ws_internal_gradient_passes(f.r, pc, grad, &p, nullptr, 2u);
     return frc;
 }
+
+}  // namespace
 }  // extern "C++"
+
+// bin/render.rs:33-128: every camera of `split` drawn and written as <out_dir>/<split>/<index>.png
+int ws_render_views(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const char* out_dir,
+                    uint32_t* rendered) {
+    if (!ctx || !pc || !scene || !out_dir) return fail(WS_ERR_INVALID, "ws_render_views: null argument");
+    if (const int rc = refuse_unless_one_split("ws_render_views", split)) return rc;
+    if (rendered) *rendered = 0;
+    const std::string dir = std::string(out_dir) + "/" + (split == WS_SPLIT_TEST ? "test" : "train");
+    if (!make_dirs(dir)) return fail(WS_ERR_IO, "ws_render_views: cannot create " + dir);
+    std::vector<uint8_t> rgba;
+    return walk_once(ctx, {"ws_render_views", pc, scene, split, nullptr, nullptr, false, true, 0, OVERFLOW_DRAWS_THE_FRAME_AGAIN, nullptr}, nullptr,
+                     [&](const SceneFrame& f) {
+                         rgba.resize((size_t)f.w * f.h * 4);
+                         int rc = ws_download_texture_rgba8(ctx, f.va.d_pixels, WS_FORMAT_RGBA16_FLOAT, f.w, f.h, (size_t)f.w * 8, rgba.data(), nullptr);
+                         char name[32];
+                         std::snprintf(name, sizeof name, "/%05u.png", f.index);
+                         if (rc == WS_OK) rc = ws_png_write_rgba8((dir + name).c_str(), f.w, f.h, rgba.data(), (size_t)f.w * 4);
+                         if (rc == WS_OK && rendered) *rendered = f.index + 1;
+                         return rc;
+                     });
+}
+
+// Every camera of `split` into per-Gaussian accumulators (websplat.h "Per-Gaussian contribution"): no target and no blend,
+// prepare() and the attribution launches.
+int ws_scene_accumulate_contrib(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, ws_contrib* c,
+                                uint32_t* frames) {
+    const std::string who("ws_scene_accumulate_contrib");
+    if (!ctx || !pc || !scene || !c) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (const int rc = refuse_unless_one_split(who, split)) return rc;
+    if (frames) *frames = 0;
+    if (ws_contrib_num_points(c) != ws_pointcloud_num_points(pc))
+        return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
+    if (const int rc = refuse_debug_cut(who, ctx)) return rc;
+    return walk_once(ctx, {who.c_str(), pc, scene, split, nullptr, nullptr, true, false, 0, OVERFLOW_FAILS, "the accumulator is incomplete"}, frames,
+                     [&](const SceneFrame& f) { return ws_renderer_accumulate_contrib(f.r, pc, c, nullptr); });
+}
+
+// ... and what deleting each Gaussian alone would do to them (websplat.h "Removal effect"), over the cloud's own background
+// colour, or black; `weight`: the plain contribution sums of the same prepared frames.
+int ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, int kind, float scale,
+                                ws_contrib* effect, ws_contrib* weight, uint32_t* frames) {
+    const std::string who("ws_scene_accumulate_removal");
+    if (frames) *frames = 0;
+    if (const int rc = refuse_kind(who, kind)) return rc;
+    if (const int rc = refuse_scale(who, "scale", scale)) return rc;
+    if (const int rc = refuse_unless_one_split(who, split)) return rc;
+    if (!ctx || !pc || !scene || !effect) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (ws_contrib_num_points(effect) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
+        return fail(WS_ERR_INVALID, who + ": an accumulator was created for another number of points");
+    if (const int rc = refuse_debug_cut(who, ctx)) return rc;
+    ws_removal_params rp;
+    std::memset(&rp, 0, sizeof rp);
+    eval_background(pc, rp.background);
+    rp.kind = kind;
+    rp.scale = scale;
+    return walk_once(ctx, {who.c_str(), pc, scene, split, nullptr, nullptr, true, false, 0, OVERFLOW_FAILS, "the accumulators are incomplete"}, frames,
+                     [&](const SceneFrame& f) {
+                         int rc = ws_renderer_accumulate_removal(f.r, pc, effect, &rp, nullptr);
+                         if (rc == WS_OK && weight) rc = ws_renderer_accumulate_contrib(f.r, pc, weight, nullptr);
+                         return rc;
+                     });
+}
+
+// Every camera of `split` compared on the device (websplat.h "Image metrics"): `pc` against another cloud, or against
+// ground-truth PNGs.
+int ws_scene_evaluate(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                      const char* gt_dir, uint32_t flags, ws_metrics* m, uint32_t* frames) {
+    const std::string who("ws_scene_evaluate");
+    if (!ctx || !pc || !scene || !m) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (frames) *frames = 0;
+    if (const int rc = refuse_unless_a_split(who, split)) return rc;
+    if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
+    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, who + ": unknown flag bits");
+    if (const int rc = refuse_debug_cut(who, ctx)) return rc;
+    // Against PNGs every frame is waited for anyway (the upload of the next ground truth), so an overflowed frame is drawn again
+    // on the spot.  Against a cloud nothing is read back per frame: the bits are looked at once, after the pass, and a pass whose
+    // frames overflowed is not a measurement -- the lists have grown, the whole split runs again (as ws_measure does).
+    SceneWalk walk(ctx, {who.c_str(), pc, scene, split, ref_pc, gt_dir, false, true, 0, ref_pc ? OVERFLOW_IS_THE_DRIVERS : OVERFLOW_DRAWS_THE_FRAME_AGAIN, nullptr});
+    const uint32_t base = ws_metrics_count(m);
+    int rc = walk.open();
+    for (int attempt = 0; rc == WS_OK; ++attempt) {
+        rc = walk.pass([&](const SceneFrame& f) { return ws_metrics_add(m, &f.va, &f.vb, f.w, f.h, flags, nullptr, 0, nullptr); });
+        const FrameVerdict v = frame_verdict(walk.bits, attempt);
+        if (rc != WS_OK || v == FRAME_DONE) break;
+        ws_internal_metrics_truncate(m, base);
+        if (v == FRAME_FAILED) rc = fail(WS_ERR_OVERFLOW, who + ": frames reported device-side errors (tile-entry overflow or a look-back time-out)");
+    }
+    if (rc != WS_OK) ws_internal_metrics_truncate(m, base);  // (the metrics as they stood, and 0 frames)
+    else if (frames) *frames = walk.frames;
+    return rc;
+}
+
+// Every camera of `split` blamed on the Gaussians of `pc` (websplat.h "Attributing a pixel plane to Gaussians"): the frames of
+// ws_scene_evaluate with contributions enabled, their per-pixel error against `ref_pc` or the ground-truth PNGs in an f32 plane,
+// and the weighted contribution sums.
+int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                              const char* gt_dir, int kind, uint32_t flags, ws_contrib* err, ws_contrib* weight, uint32_t* frames) {
+    const std::string who("ws_scene_accumulate_error");
+    if (!ctx || !pc || !scene || !err) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (frames) *frames = 0;
+    if (const int rc = refuse_unless_a_split(who, split)) return rc;
+    if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
+    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, who + ": unknown flag bits");
+    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS && kind != WS_ERROR_DSSIM)
+        return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ, WS_ERROR_ABS or WS_ERROR_DSSIM");
+    if (ws_contrib_num_points(err) != ws_pointcloud_num_points(pc) || (weight && ws_contrib_num_points(weight) != ws_pointcloud_num_points(pc)))
+        return fail(WS_ERR_INVALID, who + ": an accumulator was created for another number of points");
+    if (const int rc = refuse_debug_cut(who, ctx)) return rc;
+    ws_metrics* ssim = nullptr;  // WS_ERROR_DSSIM: one slot, written again by every frame; only its map is used
+    int rc = kind == WS_ERROR_DSSIM ? ws_metrics_create(ctx, 1, &ssim) : (int)WS_OK;
+    if (rc == WS_OK)
+        rc = walk_once(ctx, {who.c_str(), pc, scene, split, ref_pc, gt_dir, true, true, 4, OVERFLOW_FAILS, "the accumulators are incomplete"}, frames,
+                       [&](const SceneFrame& f) {
+                           ws_plane_view pv;
+                           pv.d_values = static_cast<const float*>(f.plane);
+                           pv.row_pitch_bytes = (size_t)f.w * 4;
+                           pv.scale = 1.0f;
+                           pv.bias = 0.0f;
+                           int frc;
+                           if (kind == WS_ERROR_DSSIM) {  // (1 - ssim) / 2 of the map
+                               frc = ws_metrics_reset(ssim, nullptr);
+                               if (frc == WS_OK) frc = ws_metrics_add(ssim, &f.va, &f.vb, f.w, f.h, flags, static_cast<float*>(f.plane), (size_t)f.w * 4, nullptr);
+                               pv.scale = -0.5f;
+                               pv.bias = 0.5f;
+                           } else {
+                               frc = ws_image_error_plane(ctx, &f.va, &f.vb, f.w, f.h, kind, flags, static_cast<float*>(f.plane), (size_t)f.w * 4, nullptr);
+                           }
+                           if (frc == WS_OK) frc = ws_renderer_accumulate_weighted(f.r, pc, err, &pv, nullptr);
+                           if (frc == WS_OK && weight) frc = ws_renderer_accumulate_contrib(f.r, pc, weight, nullptr);
+                           return frc;
+                       });
+    if (ssim) ws_metrics_destroy(ssim);
+    return rc;
+}
+
+// ... and the colour and ln-opacity gradients of that error (websplat.h "Gradients of an image loss"): the same frames without
+// the Rgba16Float render of `pc`, a plane of two float4 per pixel (gradient_frame).
 int ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                  const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames) {
     const std::string who("ws_scene_accumulate_gradient");
     if (frames) *frames = 0;
-    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
-    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    if (!std::isfinite(opacity_scale) || !(opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL) return fail(WS_ERR_INVALID, who + ": split must be train, test or all");
+    if (const int rc = refuse_kind(who, kind)) return rc;
+    if (const int rc = refuse_scale(who, "scale", scale)) return rc;
+    if (const int rc = refuse_scale(who, "opacity_scale", opacity_scale)) return rc;
+    if (const int rc = refuse_unless_a_split(who, split)) return rc;
     if (!ctx || !pc || !scene || !grad) return fail(WS_ERR_INVALID, who + ": null argument");
-    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, who + ": exactly one of ref_pc and gt_dir");
+    if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
     if (ws_grad_num_points(grad) != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
+    if (const int rc = refuse_debug_cut(who, ctx)) return rc;
     ws_gradient_params gp;
     std::memset(&gp, 0, sizeof gp);
     eval_background(pc, gp.background);
     gp.scale = scale;
     gp.opacity_scale = opacity_scale;
-    return over_error_frames(who, ctx, pc, scene, split, ref_pc, gt_dir, 32, false, frames,
-                             [&](const ErrorFrame& f) { return gradient_frame(ctx, pc, grad, gp, kind, f); });
+    return walk_once(ctx, {who.c_str(), pc, scene, split, ref_pc, gt_dir, true, false, 32, OVERFLOW_FAILS, "the accumulators are incomplete"}, frames,
+                     [&](const SceneFrame& f) { return gradient_frame(ctx, pc, grad, gp, kind, f); });
 }
 
 // ... and the loop those gradients are for (websplat.h "Refitting colour and opacity"): per epoch the frames of
 // ws_scene_accumulate_gradient into a ws_grad of the driver's own, an Adam step and a reset after every batch.  Everything is
-// enqueued on one stream, so the next frame's K1 reads the planes the step before it wrote; over_error_frames brings the one sync
-// and the one look at the error bits per epoch.
+// enqueued on one stream, so the next frame's K1 reads the planes the step before it wrote; a walk of its own per epoch brings the
+// one sync and the one look at the error bits per epoch.
 int ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
                    int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params, uint32_t epochs, uint32_t views_per_step,
                    uint32_t* steps) {
     const std::string who("ws_scene_refit");
     if (steps) *steps = 0;
-    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
-    if (!std::isfinite(opacity_scale) || !(opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
-    if (split != WS_SPLIT_TRAIN && split != WS_SPLIT_TEST && split != WS_SPLIT_ALL) return fail(WS_ERR_INVALID, who + ": split must be train, test or all");
+    if (const int rc = refuse_kind(who, kind)) return rc;
+    if (const int rc = refuse_scale(who, "opacity_scale", opacity_scale)) return rc;
+    if (const int rc = refuse_unless_a_split(who, split)) return rc;
     if (const int rc = ws_internal_refit_check_params(params, who, false)) return rc;
     if (!ctx || !pc || !scene || !refit) return fail(WS_ERR_INVALID, who + ": null argument");
-    if ((ref_pc != nullptr) == (gt_dir != nullptr)) return fail(WS_ERR_INVALID, who + ": exactly one of ref_pc and gt_dir");
+    if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
     if (ref_pc == pc) return fail(WS_ERR_INVALID, who + ": ref_pc is the cloud being refitted");
     if (ws_refit_num_points(refit) != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the refit object was created for another number of points");
-    if (ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
-    const uint32_t n = ws_scene_cameras(scene, split, 0, nullptr);
-    const uint32_t batch = views_per_step ? views_per_step : n;
+    if (const int rc = refuse_debug_cut(who, ctx)) return rc;
     ws_grad* grad = nullptr;
     int rc = ws_grad_create(ctx, ws_pointcloud_num_points(pc), &grad);
     ws_gradient_params gp;
@@ -706,19 +544,20 @@ int ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, in
     gp.opacity_scale = opacity_scale;
     uint32_t taken = 0;
     for (uint32_t epoch = 0; epoch < epochs && rc == WS_OK; ++epoch) {
-        uint32_t seen = 0, in_batch = 0;
-        rc = over_error_frames(who, ctx, pc, scene, split, ref_pc, gt_dir, 32, false, nullptr, [&](const ErrorFrame& f) {
-            int frc = gradient_frame(ctx, pc, grad, gp, kind, f);
-            if (frc != WS_OK) return frc;
-            ++seen, ++in_batch;
-            if (in_batch < batch && seen < n) return frc;
-            ws_refit_params sp = *params;
-            sp.colour_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)in_batch);
-            sp.opacity_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)opacity_scale * (double)in_batch);
-            frc = ws_refit_step(refit, pc, grad, &sp, nullptr);
-            if (frc == WS_OK) ++taken, in_batch = 0, frc = ws_grad_reset(grad, nullptr);
-            return frc;
-        });
+        uint32_t in_batch = 0;
+        rc = walk_once(ctx, {who.c_str(), pc, scene, split, ref_pc, gt_dir, true, false, 32, OVERFLOW_FAILS, "the accumulators are incomplete"}, nullptr,
+                       [&](const SceneFrame& f) {
+                           int frc = gradient_frame(ctx, pc, grad, gp, kind, f);
+                           if (frc != WS_OK) return frc;
+                           ++in_batch;
+                           if (in_batch < (views_per_step ? views_per_step : f.count) && f.index + 1 < f.count) return frc;
+                           ws_refit_params sp = *params;
+                           sp.colour_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)in_batch);
+                           sp.opacity_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)opacity_scale * (double)in_batch);
+                           frc = ws_refit_step(refit, pc, grad, &sp, nullptr);
+                           if (frc == WS_OK) ++taken, in_batch = 0, frc = ws_grad_reset(grad, nullptr);
+                           return frc;
+                       });
     }
     if (steps) *steps = taken;
     if (grad) ws_grad_destroy(grad);
@@ -776,12 +615,12 @@ int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, 
             demand = std::max(demand, ws_internal_renderer_demand(rs[k]));
         }
         if (rc != WS_OK || all_bits == 0) break;
-        if ((all_bits & ~1u) != 0 || attempt == 2 || demand == 0) {
+        if (frame_verdict(all_bits, attempt) == FRAME_FAILED || demand == 0) {
             rc = fail(WS_ERR_OVERFLOW, "ws_measure: frames reported device-side errors (tile-entry overflow or a look-back time-out)");
             break;
         }
         for (uint32_t k = 0; k < frames_in_flight; ++k)
-            ws_renderer_set_tile_entry_capacity(rs[k], (uint64_t)demand + demand / 4 + 4096);
+            ws_renderer_set_tile_entry_capacity(rs[k], grown_entry_capacity(demand));
     }
     for (uint32_t k = 0; k < frames_in_flight; ++k) {
         if (rs[k]) ws_renderer_destroy(rs[k]);

@@ -120,6 +120,10 @@ constexpr int depth_sort_digit_bits(int forced, bool skip_top, uint32_t span_cla
     return WS_DEPTH_DIGIT_BITS_DEFAULT;
 }
 
+// The entry capacity a frame gets after one that needed `demand` entries overflowed: 1.25 x the demand and a margin.  The one rule
+// of the automatic capacity below and of every driver that grows a renderer's list and draws again (drivers.cpp).
+constexpr uint64_t grown_entry_capacity(uint32_t demand) { return (uint64_t)demand + demand / 4 + 4096; }
+
 struct FramePlan {
     // the grid of binning tiles
     uint32_t tile_w_log2, tile_h_log2;  // tile size in pixels (8 * QW, 8 * QH)
@@ -176,8 +180,7 @@ constexpr FramePlan frame_plan(const FramePlanRequest& q) {
         const double mpix = (double)q.viewport[0] * (double)q.viewport[1] / (1200.0 * 800.0);
         const uint64_t formula = (uint64_t)(4.0 * (double)q.num_points * (1.0 < mpix ? mpix : 1.0));
         want_cap = formula < (8ull << 20) ? (8ull << 20) : formula;
-        const uint64_t grown = (uint64_t)q.demand + q.demand / 4 + 4096;
-        if (q.demand && want_cap < grown) want_cap = grown;
+        if (q.demand && want_cap < grown_entry_capacity(q.demand)) want_cap = grown_entry_capacity(q.demand);
     }
     // look-back words carry 30-bit counts (lookback.h): keep D below 2^30
     const uint64_t cap_max = (1ull << 30) - 2 * EMIT_TILE;

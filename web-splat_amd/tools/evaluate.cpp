@@ -25,6 +25,24 @@
 #include "websplat.h"
 #include "websplat_env.h"  // the harness-side translation of WS_* switches (the library reads no environment)
 
+// the value of an option that takes a positive integer; false: not one
+static bool positive(const char* text, long* value) {
+    char* end = nullptr;
+    *value = std::strtol(text, &end, 10);
+    return !*end && *value > 0;
+}
+
+// the indices of the `want` largest keys among np (all of them when there are fewer), largest first, ties by index
+template <class Key>
+static std::vector<uint32_t> top_by(uint32_t np, long want, Key key) {
+    std::vector<uint32_t> order(np);
+    for (uint32_t i = 0; i < np; ++i) order[i] = i;
+    const size_t top = std::min<size_t>((size_t)want, np);
+    std::partial_sort(order.begin(), order.begin() + top, order.end(), [&](uint32_t a, uint32_t b) { return key(a) != key(b) ? key(a) > key(b) : a < b; });
+    order.resize(top);
+    return order;
+}
+
 int main(int argc, char** argv) {
     const char *ref = nullptr, *gt = nullptr;
     int split = WS_SPLIT_TEST;
@@ -43,27 +61,13 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(argv[i], "test")) split = WS_SPLIT_TEST;
             else bad = true;
         } else if (!std::strcmp(argv[i], "--quantize")) flags |= WS_METRICS_QUANTIZE_U8;
-        else if (!std::strcmp(argv[i], "--blame") && i + 1 < argc) {
-            char* end = nullptr;
-            blame = std::strtol(argv[++i], &end, 10);
-            if (*end || blame <= 0) bad = true;
-        } else if (!std::strcmp(argv[i], "--removal") && i + 1 < argc) {
-            char* end = nullptr;
-            removal = std::strtol(argv[++i], &end, 10);
-            if (*end || removal <= 0) bad = true;
-        } else if (!std::strcmp(argv[i], "--gradient") && i + 1 < argc) {
-            char* end = nullptr;
-            gradient = std::strtol(argv[++i], &end, 10);
-            if (*end || gradient <= 0) bad = true;
-        } else if (!std::strcmp(argv[i], "--refit") && i + 1 < argc) {
-            char* end = nullptr;
-            refit = std::strtol(argv[++i], &end, 10);
-            if (*end || refit <= 0) bad = true;
-        } else if (!std::strcmp(argv[i], "--views-per-step") && i + 1 < argc) {
-            char* end = nullptr;
-            views_per_step = std::strtol(argv[++i], &end, 10);
+        else if (!std::strcmp(argv[i], "--blame") && i + 1 < argc) bad = !positive(argv[++i], &blame);
+        else if (!std::strcmp(argv[i], "--removal") && i + 1 < argc) bad = !positive(argv[++i], &removal);
+        else if (!std::strcmp(argv[i], "--gradient") && i + 1 < argc) bad = !positive(argv[++i], &gradient);
+        else if (!std::strcmp(argv[i], "--refit") && i + 1 < argc) bad = !positive(argv[++i], &refit);
+        else if (!std::strcmp(argv[i], "--views-per-step") && i + 1 < argc) {
             have_refit_option = true;
-            if (*end || views_per_step <= 0) bad = true;
+            bad = !positive(argv[++i], &views_per_step);
         } else if ((!std::strcmp(argv[i], "--lr-colour") || !std::strcmp(argv[i], "--lr-opacity")) && i + 1 < argc) {
             double& lr = !std::strcmp(argv[i], "--lr-colour") ? lr_colour : lr_opacity;
             char* end = nullptr;
@@ -131,22 +135,17 @@ int main(int argc, char** argv) {
     if (rc == WS_OK && blame > 0) {
         const uint32_t np = ws_pointcloud_num_points(pc);
         std::vector<uint64_t> e(np), w(np);
-        std::vector<uint32_t> order(np);
         rc = ws_contrib_create(ctx, np, &err);
         if (rc == WS_OK) rc = ws_contrib_create(ctx, np, &weight);
         if (rc == WS_OK) rc = ws_scene_accumulate_error(ctx, pc, scene, split, ref_pc, gt, kind, flags, err, weight, &frames);
         if (rc == WS_OK) rc = ws_contrib_download(err, np, e.data(), nullptr);
         if (rc == WS_OK) rc = ws_contrib_download(weight, np, w.data(), nullptr);
         if (rc == WS_OK) {
-            for (uint32_t i = 0; i < np; ++i) order[i] = i;
-            const size_t top = std::min<size_t>((size_t)blame, np);
-            std::partial_sort(order.begin(), order.begin() + top, order.end(),
-                              [&](uint32_t a, uint32_t b) { return e[a] != e[b] ? e[a] > e[b] : a < b; });
+            const std::vector<uint32_t> order = top_by(np, blame, [&](uint32_t i) { return e[i]; });
             std::printf("blame (%s error over %u frames): %zu of %u Gaussians by error sum\n",
-                        kind == WS_ERROR_SQ ? "sq" : (kind == WS_ERROR_ABS ? "abs" : "dssim"), frames, top, np);
+                        kind == WS_ERROR_SQ ? "sq" : (kind == WS_ERROR_ABS ? "abs" : "dssim"), frames, order.size(), np);
             std::printf("%10s %16s %16s %12s\n", "index", "error sum", "weight sum", "error/weight");
-            for (size_t k = 0; k < top; ++k) {
-                const uint32_t i = order[k];
+            for (const uint32_t i : order) {
                 const double es = (double)e[i] / WS_CONTRIB_SUM_SCALE, wsum = (double)w[i] / WS_CONTRIB_SUM_SCALE;
                 std::printf("%10u %16.9f %16.6f %12.6g\n", i, es, wsum, w[i] ? es / wsum : 0.0);
             }
@@ -156,21 +155,16 @@ int main(int argc, char** argv) {
     if (rc == WS_OK && removal > 0) {
         const uint32_t np = ws_pointcloud_num_points(pc);
         std::vector<uint64_t> e(np), w(np);
-        std::vector<uint32_t> order(np);
         rc = ws_contrib_create(ctx, np, &effect);
         if (rc == WS_OK) rc = ws_contrib_create(ctx, np, &drawn);
         if (rc == WS_OK) rc = ws_scene_accumulate_removal(ctx, pc, scene, split, kind, 1.0f, effect, drawn, &frames);
         if (rc == WS_OK) rc = ws_contrib_download(effect, np, e.data(), nullptr);
         if (rc == WS_OK) rc = ws_contrib_download(drawn, np, w.data(), nullptr);
         if (rc == WS_OK) {
-            for (uint32_t i = 0; i < np; ++i) order[i] = i;
-            const size_t top = std::min<size_t>((size_t)removal, np);
-            std::partial_sort(order.begin(), order.begin() + top, order.end(),
-                              [&](uint32_t a, uint32_t b) { return e[a] != e[b] ? e[a] > e[b] : a < b; });
-            std::printf("removal (%s effect over %u frames): %zu of %u Gaussians by effect sum\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, top, np);
+            const std::vector<uint32_t> order = top_by(np, removal, [&](uint32_t i) { return e[i]; });
+            std::printf("removal (%s effect over %u frames): %zu of %u Gaussians by effect sum\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, order.size(), np);
             std::printf("%10s %16s %16s %12s\n", "index", "effect sum", "weight sum", "effect/weight");
-            for (size_t k = 0; k < top; ++k) {
-                const uint32_t i = order[k];
+            for (const uint32_t i : order) {
                 const double es = (double)e[i] / WS_CONTRIB_SUM_SCALE, wsum = (double)w[i] / WS_CONTRIB_SUM_SCALE;
                 std::printf("%10u %16.9g %16.6f %12.6g\n", i, es, wsum, w[i] ? es / wsum : 0.0);
             }
@@ -188,7 +182,6 @@ int main(int argc, char** argv) {
         const uint32_t np = ws_pointcloud_num_points(pc);
         std::vector<int64_t> q((size_t)np * WS_GRAD_CHANNELS);
         std::vector<uint64_t> w(np);
-        std::vector<uint32_t> order(np);
         rc = ws_grad_create(ctx, np, &grad);
         if (rc == WS_OK) rc = ws_contrib_create(ctx, np, &grad_drawn);
         if (rc == WS_OK) rc = ws_scene_accumulate_gradient(ctx, pc, scene, split, ref_pc, gt, kind, 1.0f, 1.0f, grad, &frames);
@@ -196,16 +189,14 @@ int main(int argc, char** argv) {
         if (rc == WS_OK) rc = ws_grad_download(grad, np, q.data());
         if (rc == WS_OK) rc = ws_contrib_download(grad_drawn, np, w.data(), nullptr);
         if (rc == WS_OK) {
-            for (uint32_t i = 0; i < np; ++i) order[i] = i;
-            const size_t top = std::min<size_t>((size_t)gradient, np);
-            auto mag = [&](uint32_t i) { return q[(size_t)i * 4 + 3] < 0 ? 0ull - (uint64_t)q[(size_t)i * 4 + 3] : (uint64_t)q[(size_t)i * 4 + 3]; };
-            std::partial_sort(order.begin(), order.begin() + top, order.end(),
-                              [&](uint32_t a, uint32_t b) { return mag(a) != mag(b) ? mag(a) > mag(b) : a < b; });
-            std::printf("gradient (%s error over %u frames): %zu of %u Gaussians by |opacity gradient|\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, top, np);
+            const std::vector<uint32_t> order = top_by(np, gradient, [&](uint32_t i) {
+                return q[(size_t)i * 4 + 3] < 0 ? 0ull - (uint64_t)q[(size_t)i * 4 + 3] : (uint64_t)q[(size_t)i * 4 + 3];
+            });
+            std::printf("gradient (%s error over %u frames): %zu of %u Gaussians by |opacity gradient|\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, order.size(), np);
             std::printf("%10s %16s %16s %16s %16s\n", "index", "d/d ln opacity", "d/d red", "d/d green", "d/d blue");
-            for (size_t k = 0; k < top; ++k) {
-                const int64_t* g = &q[(size_t)order[k] * 4];
-                std::printf("%10u %16.9g %16.9g %16.9g %16.9g\n", order[k], (double)g[3] / WS_GRAD_SUM_SCALE, (double)g[0] / WS_GRAD_SUM_SCALE,
+            for (const uint32_t i : order) {
+                const int64_t* g = &q[(size_t)i * 4];
+                std::printf("%10u %16.9g %16.9g %16.9g %16.9g\n", i, (double)g[3] / WS_GRAD_SUM_SCALE, (double)g[0] / WS_GRAD_SUM_SCALE,
                             (double)g[1] / WS_GRAD_SUM_SCALE, (double)g[2] / WS_GRAD_SUM_SCALE);
             }
             uint32_t drawn_n = 0, zero_n = 0;
