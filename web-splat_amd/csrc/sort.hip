@@ -767,7 +767,7 @@ int launch_sort_pairs(const SortScratch& sc, const SortJob& job, hipStream_t str
         return fail(WS_ERR_INVALID, "sort: the top-byte skip belongs to the four-pass depth sort");
 
     const bool big = sort_tile_size(n) == SORT_TILE;
-    // (9-bit digits, 1024-pair tiles only up to SORT_SMALL_MAX keys: the count rows' pitch is sized for that, alloc_sort_scratch)
+    // (9-bit digits, 1024-pair tiles only up to SORT_SMALL_MAX keys: the count rows' pitch is sized for that, frame_scratch.h sort_shape)
     const bool big9 = (job.kpt9 == SORT_KPT_SMALL && n <= SORT_SMALL_MAX) ? false : (job.kpt9 ? true : big);
     switch (digit_bits) {
         case 9: return run_scan<9>(big9, sc, job, npass, stream, km, names, res);

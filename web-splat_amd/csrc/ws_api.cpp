@@ -8,10 +8,12 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "contrib.h"
+#include "frame_scratch.h"
 #include "metrics.h"
 #include "gradient.h"
 #include "refit.h"
@@ -35,12 +37,17 @@ int hip_fail(hipError_t e, const char* what) {
 }
 
 
-template <typename T>
-static int dmalloc(T** p, size_t count) {
+// The runtime behind every DeviceBuf (device_buf.h).  The text of a failure is the one this library's allocations have always given.
+int device_alloc(void** p, size_t bytes) {
     *p = nullptr;
-    if (count == 0) count = 1;
-    WS_HIP(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    return WS_OK;
+    const hipError_t e = hipMalloc(p, bytes);
+    return e == hipSuccess ? WS_OK : hip_fail(e, "hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T))");
+}
+void device_free(void* p) { (void)hipFree(p); }
+// ... under the name an entry point gives its uploads ("ws_pointcloud_create: upload: out of memory"): hip_fail's "what: why"
+static int alloc_as(int rc, const char* what) {
+    if (rc) g_last_error.replace(0, g_last_error.rfind(": "), what);
+    return rc;
 }
 // Device -> host read-back ORDERED ON THE RENDERER'S OWN STREAM (then waited for): the library never touches the legacy
 // NULL stream for a frame's data.  (Besides the device-wide implicit synchronisation a NULL-stream copy brings, a
@@ -53,11 +60,16 @@ static int copy_d2h(void* dst, const void* src, size_t bytes, hipStream_t stream
     return WS_OK;
 }
 
-template <typename T>
-static void dfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
+// How the ABI destroys a handle whose buffers a launch may still read, and how a creator drops one it could not finish:
+// behind a device sync (DeviceBuf frees without one)
+struct SyncedDelete {
+    template <typename H>
+    void operator()(H* h) const {
+        if (!h) return;
+        (void)hipDeviceSynchronize();
+        delete h;
+    }
+};
 
 int KernelMarks::create() {
     if (created) return WS_OK;
@@ -105,10 +117,11 @@ struct SorterZero {
 
 struct ws_sorter {
     ws_context* ctx = nullptr;
-    SortScratch sc;
-    FatSortScratch fat;    // ws_sorter_sort_depth of a context whose depth sort is the fat-tile one-sweep (status: own allocation)
-    uint32_t* aux_alt = nullptr;
-    SorterZero* zero = nullptr;
+    DeviceBuf<uint32_t> keys_alt, vals_alt, aux_alt, tile_sums;  // ping-pong partners [max_n + 4] and the count rows
+    DeviceBuf<SorterZero> zero;
+    DeviceBuf<uint64_t> fat_status;  // a context whose depth sort is the fat-tile one-sweep: its chunk-count rows
+    SortScratch sc;        // what the launchers take: views of the buffers above
+    FatSortScratch fat;
     uint32_t epoch = 0;
     bool folded = false;              // the last ws_sorter_sort_depth folded the key range (ws_sorter_depth_range)
     hipStream_t last_stream = nullptr;
@@ -121,49 +134,42 @@ struct FrameArrays {
     // frame), nullptr: this frame's sort cannot skip
     SortResult depth;
     uint32_t* entries = nullptr;     // the tile-sorted entry values (store indices)
-    bool blend_order_valid = false;  // the frame wrote ws_renderer::blend_order (it ran k_blend_order)
+    bool blend_order_valid = false;  // the frame wrote FrameScratch::blend_order (it ran k_blend_order)
+};
+
+// The last prepared frame.  Reset as a whole wherever it stops being one: every reader asks `prepared` first.
+struct PreparedFrame {
+    bool prepared = false;
+    const ws_pointcloud* pc = nullptr;
+    bool contrib = false;            // K1 kept the source indices (ws_renderer_enable_contrib was on)
+    bool depth = false;              // K1 wrote the z plane (ws_renderer_enable_depth was on)
+    float znear = 0.0f, zfar = 0.0f; // K1Params::znear / zfar (the composite's NDC occluder)
+    FrameArrays arrays;
+    float* k1_depths = nullptr;      // the z plane the prepare() in progress writes (nullptr: depth off)
+    unsigned long long* trace_slot = nullptr;  // the frame's slot of ws_renderer::frame_trace (nullptr: not traced)
 };
 
 struct ws_renderer {
+    // ---- fixed configuration and switches ----
     ws_context* ctx = nullptr;
     ws_color_format format = WS_FORMAT_RGBA32_FLOAT;
     uint32_t sh_deg = 3;
     bool compressed = false;
-
-    // scratch, (re)created when num_points or the viewport changes (renderer.rs:200-211)
-    uint32_t cap_points = 0;
-    uint32_t vw = 0, vh = 0;
     uint64_t entry_cap_request = 0;
-    FramePlan plan{};                // of the last prepare(): the scratch is sized by it, the frame's launches are filled from it (frame_plan.h)
-    uint32_t *fpw_a = nullptr, *fpw_b = nullptr;  // footprint words (FootprintMode): store order / ping-pong of the depth sort
-    uint8_t* splats = nullptr;      // Splat[N], 20 B each (pointcloud.rs:103-108 allocates it in PointCloud;
-                                    // here it is per renderer so that renderers never share scratch)
-    uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr;
-    uint32_t* src_index = nullptr;
-    float* depths = nullptr;         // [N] view-space depth per store slot (ws_renderer_enable_depth; allocated while it is on)
-    uint64_t* k1_status = nullptr;   // epoch-tagged look-back words (never re-zeroed)
-    uint64_t* bin_status = nullptr;
-    uint32_t* bin_offsets = nullptr;
-    uint32_t* emit_start = nullptr;
-    uint32_t *ekeys_a = nullptr, *ekeys_b = nullptr, *evals_a = nullptr, *evals_b = nullptr;
-    FrameZero* zero = nullptr;       // counters + histograms + tile ranges: ONE memset per frame
-    size_t zero_bytes = 0;
-    uint2* tile_ranges = nullptr;    // inside the zero arena
-    FrameCounters* counters = nullptr;  // = &zero->counters
-    SortScratch sort_depth, sort_tiles;
-    FatSortScratch fat;              // fat-tile one-sweep depth sort (WS_DEPTH_SORT=onesweep | coop): chunk-count rows
-    uint32_t epoch = 0;
-    uint32_t* sticky = nullptr;      // two device words that survive the per-frame memset (ws_renderer_errors): [0] error bits
-                                     // of all frames since the last reset, [1] the largest entries_needed of an overflowed frame
-    uint32_t needed_seen = 0;        // host copy of [1]: the automatic entry capacity grows to it at the next prepare()
-    uint32_t* demand_mailbox = nullptr;      // TWO pinned host words the blend posts to (device-visible address: demand_mailbox_dev):
-    uint32_t* demand_mailbox_dev = nullptr;  //   ([2]: depth_span_class of the last frame whose blend has started -> the next frame's digit width)
-                                             //   [0] the demand [1] above -- prepare() reads it without a sync, so the capacity grows
-                                             //   without anyone polling; [1] the number of the last frame whose blend has started
-    uint32_t frames_enqueued = 0;            // render() calls so far (the sequence number the blend posts)
-    bool throughput_mode = false;            // this renderer runs beside others (a slot of a view batch with frames in flight):
-                                             //   its blend keeps the image order of its workgroups (see ws_renderer_render)
+    int blend_mode = WS_BLEND_FAST;  // ws_renderer_set_blend_mode
+    bool capture = false;
+    bool contrib = false;            // ws_renderer_enable_contrib: K1 keeps the source indices from the next prepare() on
+    bool depth = false;              // ws_renderer_enable_depth: K1 writes the z plane from the next prepare() on
+    bool blend_timing = false;       // ws_renderer_enable_blend_timing: render() launches the time-stamped blend
+    bool throughput_mode = false;    // this renderer runs beside others (a slot of a view batch with frames in flight):
+                                     //   its blend keeps the image order of its workgroups (see ws_renderer_render)
 
+    // ---- the scratch, (re)created when num_points, the viewport or the entry capacity changes (renderer.rs:200-211) ----
+    FrameScratch scratch;
+    uint32_t cap_points = 0, vw = 0, vh = 0;  // what it was made for
+    FramePlan plan{};                // of the last prepare(): the scratch is sized by it, the frame's launches are filled from it (frame_plan.h)
+    uint32_t epoch = 0;              // look-back epoch of the last frame (lookback.h); 0 with fresh (zeroed) status arrays
+    uint64_t scratch_generation = 0;
     // The frame's launch sequence of prepare() (memset + 21 kernels), captured once per (point cloud, scratch) and replayed:
     // only K1's arguments change from frame to frame (camera / settings uniforms, epoch).  A ring of executable graphs,
     // because updating an executable graph's kernel arguments while an earlier launch of it has not run yet would change
@@ -184,75 +190,31 @@ struct ws_renderer {
         int order_mode = 0;              // decide_blend_order() of the captured frame: a change re-captures
         int depth_bits = 0;              // != 0 while the graph is valid: the digit width its depth sort was captured with
     } fg;
-    uint64_t scratch_generation = 0;
 
-    // last prepared frame
-    bool prepared = false;
-    const ws_pointcloud* prepared_pc = nullptr;
-    FrameArrays arrays;
+    // ---- the last prepared frame ----
+    PreparedFrame frame;
+    int order_mode = 0;              // decide_blend_order() of the last prepare(): a captured graph replays only under its own
+
+    // ---- error words and progress: they outlive a failed prepare() and a new scratch (ws_renderer_errors) ----
     hipStream_t last_stream = nullptr;
+    DeviceBuf<uint32_t> sticky;      // two device words that survive the per-frame memset (ws_renderer_errors): [0] error bits
+                                     // of all frames since the last reset, [1] the largest entries_needed of an overflowed frame
+    uint32_t needed_seen = 0;        // host copy of [1]: the automatic entry capacity grows to it at the next prepare()
+    uint32_t* demand_mailbox = nullptr;      // FOUR pinned host words the blend posts to (device-visible address: demand_mailbox_dev):
+    uint32_t* demand_mailbox_dev = nullptr;  //   [0] the demand [1] above -- prepare() reads it without a sync, so the capacity grows
+                                             //   without anyone polling; [1] the number of the last frame whose blend has started;
+                                             //   [2] depth_span_class of that frame -> the next frame's digit width
+    uint32_t frames_enqueued = 0;            // render() calls so far (the sequence number the blend posts)
 
-    int blend_mode = WS_BLEND_FAST;  // ws_renderer_set_blend_mode
-    bool capture = false;
-    bool contrib = false;                // ws_renderer_enable_contrib: K1 keeps the source indices from the next prepare() on
-    bool prepared_contrib = false;       // the last prepared frame has them
-    bool depth = false;                  // ws_renderer_enable_depth: K1 writes the z plane from the next prepare() on
-    float* k1_depths = nullptr;          // the z plane the prepare() in progress writes (nullptr: depth off)
-    bool prepared_depth = false;         // the last prepared frame wrote the z plane
-    float prepared_znear = 0.0f, prepared_zfar = 0.0f;  // K1Params::znear / zfar of the last prepare (the composite's NDC occluder)
-    uint32_t* debug_consumed = nullptr;  // [tiles], capture mode only
-    uint32_t* debug_walked = nullptr;    // [tiles][17], capture mode only
-    uint4* blend_order = nullptr;        // [blend_order_blocks]: the blend's tiles, longest list first (k_blend_order)
-    int order_mode = 0;                  // decide_blend_order() of the last prepare(): a captured graph replays only under its own
-    unsigned long long* frame_trace = nullptr;  // [trace_cap][4]: {K1 start, K1 end, blend start, blend end} per frame (ws_renderer_enable_frame_trace)
-    uint32_t trace_cap = 0, trace_count = 0;
-    unsigned long long* trace_slot = nullptr;   // the slot of the frame being prepared / rendered (nullptr: not traced)
-    bool blend_timing = false;           // ws_renderer_enable_blend_timing: render() launches the time-stamped blend
-    uint32_t* debug_timing = nullptr;    // [tiles][16][BLEND_TIMING_WORDS], allocated on first use
-    uint32_t debug_timing_tiles = 0;
-    float4* removal_base = nullptr;      // [removal_base_px]: the base plane of ws_renderer_accumulate_removal / _gradient without d_base, grown on first use
-    size_t removal_base_px = 0;
+    // ---- instrumentation ----
+    DeviceBuf<unsigned long long> frame_trace;  // [frames][4]: {K1 start, K1 end, blend start, blend end} per frame (ws_renderer_enable_frame_trace)
+    uint32_t trace_count = 0;        // slots handed out so far
     bool timers = false;
     KernelMarks marks;               // per-kernel events, timers level 2
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_group[2] = {nullptr, nullptr};  // grouped prepare of a view batch: "arena cleared" / "shared K1 done"
     bool ev_prepare_valid = false, ev_render_valid = false;
 };
-
-static void free_sort_scratch(SortScratch& sc, bool own_alt) {
-    if (own_alt) {
-        dfree(sc.keys_alt);
-        dfree(sc.vals_alt);
-    }
-    dfree(sc.tile_sums);
-    dfree(sc.wide_hist);
-    sc = SortScratch();
-}
-
-// wide_bins != 0: also room for the [tiles][wide_bins] count rows of the single-pass tile-id sort (launch_tile_sort_wide;
-// FramePlan::wide_bins, which has weighed their size)
-static int alloc_sort_scratch(SortScratch& sc, uint32_t cap, bool own_alt, uint32_t wide_bins = 0, uint32_t rows = RADIX) {
-    sc.cap = cap;
-    sc.rows = rows;
-    sc.tiles = (cap + SORT_TILE - 1) / SORT_TILE;
-    if (sc.tiles == 0) sc.tiles = 1;
-    int rc;
-    if (own_alt) {
-        if ((rc = dmalloc(&sc.keys_alt, (size_t)cap + 4))) return rc;
-        if ((rc = dmalloc(&sc.vals_alt, (size_t)cap + 4))) return rc;
-    }
-    const uint32_t small_n = std::min<uint32_t>(cap, SORT_SMALL_MAX);
-    const uint32_t small_tiles = (small_n + SORT_THREADS * SORT_KPT_SMALL - 1) / (SORT_THREADS * SORT_KPT_SMALL);
-    sc.tiles_cap = std::max<uint32_t>(std::max<uint32_t>(small_tiles, sc.tiles), 1u);
-    size_t sum_words = (size_t)sc.tiles_cap * rows;
-    if (wide_bins) {
-        sc.wide_bins = wide_bins;
-        sum_words = std::max(sum_words, (size_t)sc.tiles * wide_bins);
-        if ((rc = dmalloc(&sc.wide_hist, (size_t)wide_bins))) return rc;
-    }
-    if ((rc = dmalloc(&sc.tile_sums, sum_words))) return rc;
-    return WS_OK;
-}
 
 // FrameCounters::depth_span_class of the renderer's last frame whose blend has started: the blend posts it to pinned memory,
 // read here without a sync (0: none yet, or no mailbox)
@@ -273,47 +235,14 @@ static void renderer_free_graph(ws_renderer* r) {
     r->plan.depth_digit_bits = depth_sort_digit_bits(r->ctx->depth_digit_bits, r->ctx->depth_skip_top != 0, renderer_span_class(r), 0);
 }
 
+// Lets the scratch go (no sync: the callers have waited for the device) and with it the frame that lived in it
 static void renderer_free_scratch(ws_renderer* r) {
     renderer_free_graph(r);
     ++r->scratch_generation;
-    dfree(r->splats);
-    dfree(r->keys_a);
-    dfree(r->keys_b);
-    dfree(r->vals_a);
-    dfree(r->vals_b);
-    dfree(r->fpw_a);
-    dfree(r->fpw_b);
-    dfree(r->fat.status);
-    r->fat = FatSortScratch();
-    dfree(r->src_index);
-    dfree(r->depths);
-    r->k1_depths = nullptr;
-    r->prepared_depth = false;
-    dfree(r->k1_status);
-    dfree(r->bin_status);
-    dfree(r->bin_offsets);
-    dfree(r->emit_start);
-    dfree(r->ekeys_a);
-    dfree(r->ekeys_b);
-    dfree(r->evals_a);
-    dfree(r->evals_b);
-    dfree(r->debug_consumed);
-    dfree(r->debug_walked);
-    dfree(r->debug_timing);
-    r->debug_timing_tiles = 0;
-    dfree(r->removal_base);
-    r->removal_base_px = 0;
-    dfree(r->blend_order);
-    r->arrays.blend_order_valid = false;
-    if (r->zero) (void)hipFree(r->zero);
-    r->zero = nullptr;
-    r->tile_ranges = nullptr;
-    r->counters = nullptr;
-    free_sort_scratch(r->sort_depth, false);
-    free_sort_scratch(r->sort_tiles, false);
+    r->scratch = FrameScratch();
     r->cap_points = 0;
     r->vw = r->vh = 0;
-    r->prepared = false;
+    r->frame = PreparedFrame();
 }
 
 // What the automatic entry capacity of a frame of n points at vw x vh may grow to (FramePlanRequest::demand): an overflowed
@@ -321,12 +250,12 @@ static void renderer_free_scratch(ws_renderer* r) {
 // It belongs to THIS point-cloud size and viewport: another scene or target size starts from the formula again
 // (one heavy frame must not inflate the scratch for the renderer's lifetime).
 static int renderer_refresh_demand(ws_renderer* r, uint32_t n, uint32_t vw, uint32_t vh) {
-    if (r->zero && (r->cap_points != n || r->vw != vw || r->vh != vh)) {
+    if (r->scratch.zero.get() && (r->cap_points != n || r->vw != vw || r->vh != vh)) {
         r->needed_seen = 0;
         if (r->demand_mailbox) {
             WS_HIP(hipDeviceSynchronize());
             *reinterpret_cast<volatile uint32_t*>(r->demand_mailbox) = 0u;
-            WS_HIP(hipMemset(r->sticky + 1, 0, sizeof(uint32_t)));
+            WS_HIP(hipMemset(r->sticky.get() + 1, 0, sizeof(uint32_t)));
         }
     } else if (r->demand_mailbox) {
         const uint32_t posted = *reinterpret_cast<volatile uint32_t*>(r->demand_mailbox);
@@ -335,71 +264,27 @@ static int renderer_refresh_demand(ws_renderer* r, uint32_t n, uint32_t vw, uint
     return WS_OK;
 }
 
-// The scratch of frames of n points at vw x vh laid out by `plan`; kept while those three and the entry capacity stay.
+// The scratch of frames of n points at vw x vh laid out by `plan` (frame_scratch.h); kept while those three and the entry
+// capacity stay.  Here: the syncs around a reallocation and what the new arrays start with.
 static int renderer_ensure_scratch(ws_renderer* r, uint32_t n, uint32_t vw, uint32_t vh, const FramePlan& plan) {
-    const bool keep = r->cap_points == n && r->vw == vw && r->vh == vh && r->plan.entry_cap == plan.entry_cap && r->zero;
+    const bool keep = r->cap_points == n && r->vw == vw && r->vh == vh && r->plan.entry_cap == plan.entry_cap && r->scratch.zero.get();
     r->plan = plan;
     if (keep) return WS_OK;
     WS_HIP(hipDeviceSynchronize());
     renderer_free_scratch(r);
-    int rc;
-    const size_t np = (size_t)n + 8;
-    if ((rc = dmalloc(&r->splats, np * SPLAT_STRIDE))) return rc;
-    if ((rc = dmalloc(&r->keys_a, np))) return rc;
-    if ((rc = dmalloc(&r->keys_b, np))) return rc;
-    if ((rc = dmalloc(&r->vals_a, np))) return rc;
-    if ((rc = dmalloc(&r->vals_b, np))) return rc;
-    if ((rc = dmalloc(&r->fpw_a, np))) return rc;
-    if ((rc = dmalloc(&r->fpw_b, np))) return rc;
-    if ((rc = dmalloc(&r->src_index, np))) return rc;
-    if ((rc = dmalloc(&r->bin_offsets, np))) return rc;
-    const size_t k1_words = (size_t)preprocess_blocks(n) + 1, bin_words = (size_t)bin_prefix_blocks(n) + 1;
-    if ((rc = dmalloc(&r->k1_status, k1_words))) return rc;
-    if ((rc = dmalloc(&r->bin_status, bin_words))) return rc;
-    WS_HIP(hipMemset(r->k1_status, 0, k1_words * sizeof(uint64_t)));
-    WS_HIP(hipMemset(r->bin_status, 0, bin_words * sizeof(uint64_t)));
-    const size_t ne = (size_t)plan.entry_cap + 8;
-    if ((rc = dmalloc(&r->ekeys_a, ne))) return rc;
-    if ((rc = dmalloc(&r->ekeys_b, ne))) return rc;
-    if ((rc = dmalloc(&r->evals_a, ne))) return rc;
-    if ((rc = dmalloc(&r->evals_b, ne))) return rc;
-    if ((rc = dmalloc(&r->emit_start, (size_t)plan.entry_cap / EMIT_TILE + 4))) return rc;
-    if ((rc = dmalloc(&r->blend_order, (size_t)blend_order_blocks(plan.tiles_x, plan.tiles_y) + 8))) return rc;
-    if ((rc = dmalloc(&r->debug_consumed, (size_t)plan.ntiles))) return rc;
-    if ((rc = dmalloc(&r->debug_walked, (size_t)plan.ntiles * 17))) return rc;
+    ScratchRequest q{};
+    q.plan = plan, q.num_points = n, q.vw = vw, q.vh = vh;
+    q.fat_depth_sort = r->ctx->depth_sort_mode == DS_ONESWEEP || r->ctx->depth_sort_mode == DS_COOP;
+    q.k1_blocks = preprocess_blocks(n), q.bin_blocks = bin_prefix_blocks(n);
+    q.order_blocks = blend_order_blocks(plan.tiles_x, plan.tiles_y), q.fat_status_words = fat_sort_status_words();
+    FrameScratch& sc = r->scratch;
+    WS_TRY(sc.alloc(scratch_layout(q)));
+    WS_HIP(hipMemset(sc.k1_status.get(), 0, sc.k1_status.bytes()));
+    WS_HIP(hipMemset(sc.bin_status.get(), 0, sc.bin_status.bytes()));
     // the per-frame zero arena: counters | depth histograms | tile histograms | tile ranges
-    r->zero_bytes = sizeof(FrameZero) + (size_t)plan.ntiles * sizeof(uint2);
-    WS_HIP(hipMalloc(reinterpret_cast<void**>(&r->zero), r->zero_bytes));
-    WS_HIP(hipMemset(r->zero, 0, r->zero_bytes));
-    r->counters = &r->zero->counters;
-    r->tile_ranges = reinterpret_cast<uint2*>(reinterpret_cast<char*>(r->zero) + sizeof(FrameZero));
-    if ((rc = alloc_sort_scratch(r->sort_depth, n ? n : 1, false, 0, 512))) return rc;  // (512 count rows: 9-bit digits)
-    r->sort_depth.keys_alt = r->keys_b;
-    r->sort_depth.vals_alt = r->vals_b;
-    r->sort_depth.hist = r->zero->depth_hist;
-    r->sort_depth.hist_pitch = 512;
-    if ((rc = alloc_sort_scratch(r->sort_tiles, plan.entry_cap, false, plan.wide_bins))) return rc;
-    r->sort_tiles.keys_alt = r->ekeys_b;
-    r->sort_tiles.vals_alt = r->evals_b;
-    r->sort_tiles.hist = r->zero->tile_hist;
-    if (r->ctx->depth_sort_mode == DS_ONESWEEP || r->ctx->depth_sort_mode == DS_COOP) {
-        FatSortScratch& fs = r->fat;
-        fs.cap = n ? n : 1;
-        if ((rc = dmalloc(&fs.status, fat_sort_status_words()))) return rc;
-        WS_HIP(hipMemset(fs.status, 0, fat_sort_status_words() * sizeof(uint64_t)));
-        fs.keys_alt = r->keys_b;
-        fs.vals_alt = r->vals_b;
-        fs.aux_alt = r->fpw_b;
-        fs.hist = r->zero->depth_hist;
-        fs.tickets = r->counters->sort_ticket;  // [0..3]; the tile sort uses [4..7]
-        fs.barrier = r->zero->fat_barrier;
-        fs.d_epoch = &r->counters->epoch;       // written by K1 every frame: a captured frame graph replays with it
-        fs.error = &r->counters->overflow;
-        fs.grid_request = r->ctx->dsort_fat_grid;
-    }
-    r->cap_points = n;
-    r->vw = vw;
-    r->vh = vh;
+    WS_HIP(hipMemset(sc.zero.get(), 0, sc.zero.bytes()));
+    if (sc.fat_status.get()) WS_HIP(hipMemset(sc.fat_status.get(), 0, sc.fat_status.bytes()));
+    r->cap_points = n, r->vw = vw, r->vh = vh;
     r->epoch = 0;  // fresh (zeroed) status arrays
     // The allocation-time memsets above ran on the null stream; frames run on hipStreamNonBlocking streams, which are
     // not ordered against it, and recycled memory may still hold a previous renderer's epoch-tagged words.
@@ -666,6 +551,15 @@ int ws_memcpy_d2h(ws_context* ctx, void* h_dst, const void* d_src, size_t bytes,
 }
 
 // ---- PointCloud --------------------------------------------------------------------------------------
+// what a descriptor says about how its scene wants to be drawn
+static void set_render_hints(PointCloudMeta* pc, const ws_pointcloud_desc* d) {
+    pc->has_mip = d->has_mip_splatting != 0;
+    pc->mip = d->mip_splatting != 0;
+    pc->has_kernel_size = d->has_kernel_size != 0;
+    pc->kernel_size = d->kernel_size;
+    pc->has_background = d->has_background_color != 0;
+    std::memcpy(pc->background, d->background_color, sizeof pc->background);
+}
 int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* d, ws_pointcloud** out) {
     if (!ctx || !d || !out) return fail(WS_ERR_INVALID, "ws_pointcloud_create: null argument");
     *out = nullptr;
@@ -674,7 +568,7 @@ int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* d, ws_pointc
     if (n == 0) return fail(WS_ERR_INVALID, "ws_pointcloud_create: empty point cloud");
     if (n >= (1u << 30)) return fail(WS_ERR_UNSUPPORTED, "ws_pointcloud_create: more than 2^30-1 points");
     if (!d->gaussians || !d->sh_coefs) return fail(WS_ERR_INVALID, "ws_pointcloud_create: missing buffers");
-    ws_pointcloud* pc = new (std::nothrow) ws_pointcloud();
+    std::unique_ptr<ws_pointcloud> pc(new (std::nothrow) ws_pointcloud());
     if (!pc) return fail(WS_ERR_OOM, "ws_pointcloud_create: host allocation failed");
     pc->ctx = ctx;
     pc->num_points = n;
@@ -684,24 +578,15 @@ int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* d, ws_pointc
     std::memcpy(pc->center, d->center, sizeof pc->center);
     pc->has_up = d->has_up != 0;
     std::memcpy(pc->up, d->up, sizeof pc->up);
-    pc->has_mip = d->has_mip_splatting != 0;
-    pc->mip = d->mip_splatting != 0;
-    pc->has_kernel_size = d->has_kernel_size != 0;
-    pc->kernel_size = d->kernel_size;
-    pc->has_background = d->has_background_color != 0;
-    std::memcpy(pc->background, d->background_color, sizeof pc->background);
-    int rc = WS_OK;
+    set_render_hints(pc.get(), d);
     if (!pc->compressed) {
-        if (d->gaussians_bytes != (size_t)n * 28 || d->sh_coefs_bytes != (size_t)n * 96) {
-            delete pc;
+        if (d->gaussians_bytes != (size_t)n * 28 || d->sh_coefs_bytes != (size_t)n * 96)
             return fail(WS_ERR_INVALID, "ws_pointcloud_create: expected 28 B Gaussians and 96 B SH records");
-        }
         // re-lay the loader's AoS records as eight planes of 16-B chunks (ws_internal.h)
         std::vector<uint32_t> staging;
         try {
             staging.resize((size_t)n * PC_PLANES * 4);
         } catch (...) {
-            delete pc;
             return fail(WS_ERR_OOM, "ws_pointcloud_create: host staging allocation failed");
         }
         const uint8_t* g = static_cast<const uint8_t*>(d->gaussians);
@@ -719,18 +604,15 @@ int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* d, ws_pointc
             const uint8_t* si = s + (size_t)i * 96;
             for (int q = 0; q < 6; ++q) std::memcpy(st + ((size_t)(2 + q) * n + i) * 4, si + q * 16, 16);
         }
-        pc->device_bytes = staging.size() * 4;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&pc->planes), pc->device_bytes);
-        if (e == hipSuccess) e = hipMemcpy(pc->planes, st, pc->device_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_pointcloud_create: upload");
+        WS_TRY(alloc_as(pc->planes.alloc((size_t)n * PC_PLANES), "ws_pointcloud_create: upload"));
+        const hipError_t e = hipMemcpy(pc->planes.get(), st, pc->planes.bytes(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "ws_pointcloud_create: upload");
     } else {
         const uint32_t ncoef = (d->sh_deg + 1) * (d->sh_deg + 1);
         if (d->gaussians_bytes != (size_t)n * 24 || !d->covars || !d->quantization || (d->covars_bytes % 12) != 0 ||
-            (d->sh_coefs_bytes % (3 * ncoef)) != 0) {
-            delete pc;
+            (d->sh_coefs_bytes % (3 * ncoef)) != 0)
             return fail(WS_ERR_INVALID, "ws_pointcloud_create: compressed layout mismatch (24 B splats, 12 B covars, "
                                         "3*(deg+1)^2 B SH records, quantization block)");
-        }
         // the kernel indexes covars / SH records with the per-Gaussian indices: validate them on the host,
         // where WebGPU would have clamped out-of-bounds reads
         const uint8_t* g = static_cast<const uint8_t*>(d->gaussians);
@@ -739,28 +621,20 @@ int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* d, ws_pointc
             uint32_t gi, si;
             std::memcpy(&gi, g + (size_t)i * 24 + 16, 4);
             std::memcpy(&si, g + (size_t)i * 24 + 20, 4);
-            if (gi >= n_cov || si >= n_sh) {
-                delete pc;
-                return fail(WS_ERR_INVALID, "ws_pointcloud_create: geometry_idx / sh_idx out of range");
-            }
+            if (gi >= n_cov || si >= n_sh) return fail(WS_ERR_INVALID, "ws_pointcloud_create: geometry_idx / sh_idx out of range");
         }
         pc->quant = *d->quantization;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&pc->gaussians_c), d->gaussians_bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->sh_bytes), d->sh_coefs_bytes + 16);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->covars), d->covars_bytes);
-        if (e == hipSuccess) e = hipMemcpy(pc->gaussians_c, d->gaussians, d->gaussians_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(pc->sh_bytes, d->sh_coefs, d->sh_coefs_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(pc->covars, d->covars, d->covars_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_pointcloud_create: upload (compressed)");
-        pc->device_bytes = d->gaussians_bytes + d->sh_coefs_bytes + d->covars_bytes;
-        pc->sh_bytes_size = d->sh_coefs_bytes;
-        pc->covars_size = d->covars_bytes;
+        // (the index check above has seen n_cov >= 1: no codebook is empty)
+        const char* what = "ws_pointcloud_create: upload (compressed)";
+        WS_TRY(alloc_as(pc->gaussians_c.alloc(d->gaussians_bytes), what));
+        WS_TRY(alloc_as(pc->sh_bytes.alloc(d->sh_coefs_bytes + 16), what));
+        WS_TRY(alloc_as(pc->covars.alloc(d->covars_bytes), what));
+        hipError_t e = hipMemcpy(pc->gaussians_c.get(), d->gaussians, d->gaussians_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(pc->sh_bytes.get(), d->sh_coefs, d->sh_coefs_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(pc->covars.get(), d->covars, d->covars_bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, what);
     }
-    if (rc != WS_OK) {
-        ws_pointcloud_destroy(pc);
-        return rc;
-    }
-    *out = pc;
+    *out = pc.release();
     return WS_OK;
 }
 
@@ -774,7 +648,7 @@ int ws_pointcloud_create_from_ply_rows(ws_context* ctx, const float* rows, uint3
     if (n == 0) return fail(WS_ERR_INVALID, "ws_pointcloud_create_from_ply_rows: empty point cloud");
     if (n >= (1u << 30)) return fail(WS_ERR_UNSUPPORTED, "ws_pointcloud_create_from_ply_rows: more than 2^30-1 points");
     const uint32_t row_len = 14u + 3u * (sh_deg + 1u) * (sh_deg + 1u);
-    ws_pointcloud* pc = new (std::nothrow) ws_pointcloud();
+    std::unique_ptr<ws_pointcloud> pc(new (std::nothrow) ws_pointcloud());
     if (!pc) return fail(WS_ERR_OOM, "ws_pointcloud_create_from_ply_rows: host allocation failed");
     pc->ctx = ctx;
     pc->num_points = n;
@@ -785,42 +659,29 @@ int ws_pointcloud_create_from_ply_rows(ws_context* ctx, const float* rows, uint3
     int32_t has_up = 0;
     int rc = ws_pointcloud_stats(rows, n, row_len * (uint32_t)sizeof(float), &zero, &pc->bbox, pc->center, &has_up, pc->up);
     pc->has_up = has_up != 0;
-    if (meta) {
-        pc->has_mip = meta->has_mip_splatting != 0;
-        pc->mip = meta->mip_splatting != 0;
-        pc->has_kernel_size = meta->has_kernel_size != 0;
-        pc->kernel_size = meta->kernel_size;
-        pc->has_background = meta->has_background_color != 0;
-        std::memcpy(pc->background, meta->background_color, sizeof pc->background);
-    }
+    if (meta) set_render_hints(pc.get(), meta);
     // Upload and decode run on a PRIVATE stream and are waited for with hipStreamSynchronize: no legacy-NULL-stream work
     // (it would serialise against every renderer and break replays of a captured frame graph) and no
     // device-wide synchronisation of other renderers' frames.
-    float* d_rows = nullptr;
+    if (rc) return rc;
+    DeviceBuf<float> d_rows;  // (let go at the return, behind the stream sync)
     hipStream_t ls = nullptr;
+    const char* what = "ws_pointcloud_create_from_ply_rows: upload";
+    hipError_t e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
+    if (e != hipSuccess) rc = hip_fail(e, what);
+    if (rc == WS_OK) rc = alloc_as(pc->planes.alloc((size_t)n * PC_PLANES), what);
+    if (rc == WS_OK) rc = alloc_as(d_rows.alloc((size_t)n * row_len), what);
+    if (rc == WS_OK && (e = hipMemcpyAsync(d_rows.get(), rows, d_rows.bytes(), hipMemcpyHostToDevice, ls)) != hipSuccess) rc = hip_fail(e, what);
+    if (rc == WS_OK) rc = launch_ply_decode(d_rows.get(), n, sh_deg, pc->planes.get(), ls);
     if (rc == WS_OK) {
-        pc->device_bytes = (size_t)n * PC_PLANES * 16;
-        const size_t row_bytes = (size_t)n * row_len * sizeof(float);
-        hipError_t e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->planes), pc->device_bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rows), row_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows, row_bytes, hipMemcpyHostToDevice, ls);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_pointcloud_create_from_ply_rows: upload");
-    }
-    if (rc == WS_OK) rc = launch_ply_decode(d_rows, n, sh_deg, pc->planes, ls);
-    if (rc == WS_OK) {
-        hipError_t e = hipStreamSynchronize(ls);
+        e = hipStreamSynchronize(ls);
         if (e != hipSuccess) rc = hip_fail(e, "ws_pointcloud_create_from_ply_rows: decode");
     } else if (ls) {
         (void)hipStreamSynchronize(ls);
     }
-    if (d_rows) (void)hipFree(d_rows);
     if (ls) (void)hipStreamDestroy(ls);
-    if (rc != WS_OK) {
-        ws_pointcloud_destroy(pc);
-        return rc;
-    }
-    *out = pc;
+    if (rc) return rc;
+    *out = pc.release();
     return WS_OK;
 }
 
@@ -831,7 +692,7 @@ int ws_pointcloud_download(const ws_pointcloud* pc, void* gaussians, size_t gaus
     const size_t n = pc->num_points;
     if (pc->compressed) {
         if (gaussians_bytes < n * 24) return fail(WS_ERR_INVALID, "ws_pointcloud_download: gaussians buffer too small");
-        WS_HIP(hipMemcpy(gaussians, pc->gaussians_c, n * 24, hipMemcpyDeviceToHost));
+        WS_HIP(hipMemcpy(gaussians, pc->gaussians_c.get(), n * 24, hipMemcpyDeviceToHost));
         return WS_OK;  // (the packed SH / covariance codebooks are what the caller uploaded; not re-exported)
     }
     if (gaussians_bytes < n * 28 || sh_bytes < n * 96) return fail(WS_ERR_INVALID, "ws_pointcloud_download: buffers too small");
@@ -841,7 +702,7 @@ int ws_pointcloud_download(const ws_pointcloud* pc, void* gaussians, size_t gaus
     } catch (...) {
         return fail(WS_ERR_OOM, "ws_pointcloud_download: host allocation failed");
     }
-    WS_HIP(hipMemcpy(st.data(), pc->planes, st.size() * 4, hipMemcpyDeviceToHost));
+    WS_HIP(hipMemcpy(st.data(), pc->planes.get(), st.size() * 4, hipMemcpyDeviceToHost));
     uint8_t* g = static_cast<uint8_t*>(gaussians);
     uint8_t* s = static_cast<uint8_t*>(sh_coefs);
     const ws::OmpQuietWorkers omp_quiet;  // (ws_internal.h: the region's workers sleep at once instead of spinning 200 ms)
@@ -854,14 +715,7 @@ int ws_pointcloud_download(const ws_pointcloud* pc, void* gaussians, size_t gaus
     return WS_OK;
 }
 
-void ws_pointcloud_destroy(ws_pointcloud* pc) {
-    if (!pc) return;
-    dfree(pc->planes);
-    dfree(pc->gaussians_c);
-    dfree(pc->sh_bytes);
-    dfree(pc->covars);
-    delete pc;
-}
+void ws_pointcloud_destroy(ws_pointcloud* pc) { delete pc; }
 
 uint32_t ws_pointcloud_num_points(const ws_pointcloud* pc) { return pc ? pc->num_points : 0; }
 uint32_t ws_pointcloud_sh_deg(const ws_pointcloud* pc) { return pc ? pc->sh_deg : 0; }
@@ -917,8 +771,7 @@ int ws_renderer_create(ws_context* ctx, ws_color_format format, uint32_t sh_deg,
             return fail(WS_ERR_HIP, "ws_renderer_create: hipEventCreate failed");
         }
     }
-    if (hipMalloc(reinterpret_cast<void**>(&r->sticky), 2 * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(r->sticky, 0, 2 * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    if (r->sticky.alloc(2) != WS_OK || hipMemset(r->sticky.get(), 0, r->sticky.bytes()) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         ws_renderer_destroy(r);
         return fail(WS_ERR_HIP, "ws_renderer_create: error word allocation failed");
     }
@@ -940,9 +793,7 @@ int ws_renderer_create(ws_context* ctx, ws_color_format format, uint32_t sh_deg,
 void ws_renderer_destroy(ws_renderer* r) {
     if (!r) return;
     (void)hipDeviceSynchronize();
-    renderer_free_scratch(r);
-    dfree(r->sticky);
-    if (r->frame_trace) (void)hipFree(r->frame_trace);
+    renderer_free_graph(r);
     if (r->demand_mailbox) (void)hipHostFree(r->demand_mailbox);
     for (auto& e : r->ev)
         if (e) (void)hipEventDestroy(e);
@@ -981,55 +832,55 @@ int ws_renderer_enable_capture(ws_renderer* r, int enable) {
     // Whether a frame bins coarse (64-px lists) is latched at prepare() from the capture state, and the capture blend's
     // per-tile read-backs are sized by that frame's lists: a frame prepared under the other state must not be drawn or
     // read back under this one -- the caller prepares again.
-    if (r->capture != (enable != 0)) r->prepared = false;
+    if (r->capture != (enable != 0)) r->frame = PreparedFrame();
     r->capture = enable != 0;
     return WS_OK;
 }
 
 int ws_renderer_download_blend_order(ws_renderer* r, uint32_t capacity_blocks, uint32_t* order4, uint32_t* num_blocks) {
     if (!r || !num_blocks) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_order: null argument");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_blend_order: no prepared frame");
-    const uint32_t nb = r->arrays.blend_order_valid ? blend_order_blocks(r->plan.tiles_x, r->plan.tiles_y) : 0u;
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_download_blend_order: no prepared frame");
+    const uint32_t nb = r->frame.arrays.blend_order_valid ? blend_order_blocks(r->plan.tiles_x, r->plan.tiles_y) : 0u;
     *num_blocks = nb;
     if (!order4 || nb == 0) return WS_OK;
     if (capacity_blocks < nb) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_order: capacity smaller than the block count");
     WS_HIP(hipStreamSynchronize(r->last_stream));
-    return copy_d2h(order4, r->blend_order, (size_t)nb * sizeof(uint4), r->last_stream);
+    return copy_d2h(order4, r->scratch.blend_order.get(), (size_t)nb * sizeof(uint4), r->last_stream);
 }
 
 // Analysis of frames in flight (round 6): rocprofv3's kernel trace serialises the queues, so what really runs beside what is
 // measured on the device -- K1 and the blend of the next `frames` frames of this renderer leave {min start, max end} of their
 // workgroups on the 100-MHz device clock (one 64-bit atomic per workgroup at each end; off: a null pointer, one scalar branch).
+static uint32_t trace_capacity(const ws_renderer* r) { return (uint32_t)(r->frame_trace.count() / 4); }  // frames
+
 int ws_renderer_enable_frame_trace(ws_renderer* r, uint32_t frames) {
     if (!r) return fail(WS_ERR_INVALID, "ws_renderer_enable_frame_trace: null renderer");
-    if (r->last_stream || r->prepared) WS_HIP(hipStreamSynchronize(r->last_stream));
-    if (r->frame_trace) {
-        (void)hipFree(r->frame_trace);
-        r->frame_trace = nullptr;
-    }
-    r->trace_cap = r->trace_count = 0;
-    r->trace_slot = nullptr;
+    if (r->last_stream || r->frame.prepared) WS_HIP(hipStreamSynchronize(r->last_stream));
+    r->frame_trace.reset();
+    r->trace_count = 0;
+    r->frame.trace_slot = nullptr;
     if (frames == 0) return WS_OK;
     std::vector<unsigned long long> init((size_t)frames * 4);
     for (uint32_t i = 0; i < frames; ++i) {
         init[4 * i + 0] = init[4 * i + 2] = ~0ull;
         init[4 * i + 1] = init[4 * i + 3] = 0ull;
     }
-    WS_HIP(hipMalloc(reinterpret_cast<void**>(&r->frame_trace), init.size() * sizeof(unsigned long long)));
-    WS_HIP(hipMemcpyAsync(r->frame_trace, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, r->last_stream));
+    DeviceBuf<unsigned long long> trace;
+    WS_TRY(trace.alloc(init.size()));
+    WS_HIP(hipMemcpyAsync(trace.get(), init.data(), trace.bytes(), hipMemcpyHostToDevice, r->last_stream));
     WS_HIP(hipStreamSynchronize(r->last_stream));
-    r->trace_cap = frames;
+    r->frame_trace = std::move(trace);  // (from here on prepare() hands its slots out)
     return WS_OK;
 }
 
 int ws_renderer_download_frame_trace(ws_renderer* r, uint32_t capacity, uint64_t* stamps, uint32_t* count) {
     if (!r || !count) return fail(WS_ERR_INVALID, "ws_renderer_download_frame_trace: null argument");
-    *count = r->trace_count < r->trace_cap ? r->trace_count : r->trace_cap;
+    *count = std::min(r->trace_count, trace_capacity(r));
     if (!stamps) return WS_OK;
     if (capacity < *count) return fail(WS_ERR_INVALID, "ws_renderer_download_frame_trace: capacity smaller than the traced frames");
     if (*count == 0) return WS_OK;
     // (on the renderer's own stream, like every read-back of this library: never the legacy NULL stream)
-    return copy_d2h(stamps, r->frame_trace, (size_t)*count * 4 * sizeof(unsigned long long), r->last_stream);
+    return copy_d2h(stamps, r->frame_trace.get(), (size_t)*count * 4 * sizeof(unsigned long long), r->last_stream);
 }
 
 int ws_renderer_enable_blend_timing(ws_renderer* r, int enable) {
@@ -1043,11 +894,11 @@ int ws_renderer_download_blend_timing(ws_renderer* r, uint32_t tile_capacity, ui
     const uint32_t nt = r->plan.ntiles;
     if (num_tiles) *num_tiles = nt;
     if (!times) return WS_OK;
-    if (!r->prepared || !r->blend_timing || !r->debug_timing || r->debug_timing_tiles != nt)
+    if (!r->frame.prepared || !r->blend_timing || !r->scratch.debug_timing.get())
         return fail(WS_ERR_STATE, "ws_renderer_download_blend_timing: needs ws_renderer_enable_blend_timing and a rendered frame");
     if (tile_capacity < nt) return fail(WS_ERR_INVALID, "ws_renderer_download_blend_timing: capacity smaller than the tile count");
     WS_HIP(hipStreamSynchronize(r->last_stream));
-    return copy_d2h(times, r->debug_timing, (size_t)nt * 16 * BLEND_TIMING_WORDS * sizeof(uint32_t), r->last_stream);
+    return copy_d2h(times, r->scratch.debug_timing.get(), r->scratch.debug_timing.bytes(), r->last_stream);
 }
 
 int ws_renderer_set_tile_entry_capacity(ws_renderer* r, uint64_t entries) {
@@ -1087,8 +938,8 @@ static int decide_blend_order(ws_renderer* r, hipStream_t stream) {
 
 // the renderer holds a prepared frame of pc, enqueued on stream
 static int frame_prepared(ws_renderer* r, const ws_pointcloud* pc, hipStream_t stream) {
-    r->prepared = true;
-    r->prepared_pc = pc;
+    r->frame.prepared = true;
+    r->frame.pc = pc;
     r->last_stream = stream;
     return WS_OK;
 }
@@ -1097,15 +948,18 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
                          int phase = FRAME_ALL) {
     int rc;
     const FramePlan& plan = r->plan;
+    const FrameScratch& sc = r->scratch;
+    FrameCounters* const counters = sc.counters();
+    uint2* const tile_ranges = sc.tile_ranges();
     KernelMarks* km = r->marks.active ? &r->marks : nullptr;
     if (phase != FRAME_REST) {
         // GPURSSorter::record_reset_indirect_buffer (gpu_rs.rs:720-727): keys_size = 0, dispatch = 0 -- here ONE
         // memset clears the counters, every ticket, both sorts' digit histograms and the tile ranges
-        WS_HIP(hipMemsetAsync(r->zero, 0, r->zero_bytes, stream));
+        WS_HIP(hipMemsetAsync(sc.zero.get(), 0, sc.zero.bytes(), stream));
         if (phase == FRAME_CLEAR) return WS_OK;
         if (km) km->begin(stream, true);
         if (r->timers) WS_HIP(hipEventRecord(r->ev[0], stream));
-        if ((rc = launch_preprocess(kp, kb, pc->compressed, plan.footprint_mode, stream, r->k1_depths))) return rc;
+        if ((rc = launch_preprocess(kp, kb, pc->compressed, plan.footprint_mode, stream, r->frame.k1_depths))) return rc;
         km_mark(km, pc->compressed ? "k_preprocess<compressed>" : "k_preprocess");
         if (r->timers) WS_HIP(hipEventRecord(r->ev[1], stream));
         if (km) {  // calibration interval between two kernels: the dispatch latency of a dependent launch
@@ -1119,15 +973,15 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
     // depth sort: V (key, store index) pairs, values start as iota (preprocess.wgsl:274), the splat's footprint word
     // (packed tile rectangle, or tile count) rides along as a companion value.  Default: the generic 4 x 8-bit sorter
     // (GPURSSorter's shape); WS_DEPTH_SORT=onesweep | coop: the fat-tile one-sweep (measured variants).
-    const bool fat_sort = (r->ctx->depth_sort_mode == DS_ONESWEEP || r->ctx->depth_sort_mode == DS_COOP) && r->fat.status &&
-                          fat_sort_grid(pc->num_points, r->ctx->num_cus, r->fat.grid_request) != 0u;
+    const bool fat_sort = (r->ctx->depth_sort_mode == DS_ONESWEEP || r->ctx->depth_sort_mode == DS_COOP) && sc.fat_status.get() &&
+                          fat_sort_grid(pc->num_points, r->ctx->num_cus, r->ctx->dsort_fat_grid) != 0u;
     if (fat_sort) {
         // fat-tile one-sweep (sort.hip k_dsort_fat): four 8-bit passes A -> B -> A -> B -> A, everything ends where it started
-        if ((rc = launch_depth_sort_fat(r->fat, r->keys_a, r->vals_a, r->fpw_a, &r->counters->num_visible, pc->num_points, true,
+        if ((rc = launch_depth_sort_fat(sc.fat_sort(r->ctx->dsort_fat_grid), sc.keys_a.get(), sc.vals_a.get(), sc.fpw_a.get(), &counters->num_visible, pc->num_points, true,
                                         // (the single-launch form needs all its workgroups resident at once: never beside other
                                         // frames' kernels -- a slot of a view batch falls back to the one-sweep form)
                                         r->ctx->depth_sort_mode == DS_COOP && !r->throughput_mode, r->epoch, r->ctx->num_cus, stream,
-                                        km, &r->arrays.depth)))
+                                        km, &r->frame.arrays.depth)))
             return rc;
     } else {
         // Four 8-bit passes over the 32-bit keys (gpu_rs.rs:865-884), of which the last one leaves at once on frames whose keys
@@ -1136,44 +990,45 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
         // clip z, which is below znear for the nearest splats.)
         SortJob job;
         job.kind = SORT_DEPTH;
-        job.keys = r->keys_a, job.vals = r->vals_a, job.d_count = &r->counters->num_visible, job.n = pc->num_points;
+        job.keys = sc.keys_a.get(), job.vals = sc.vals_a.get(), job.d_count = &counters->num_visible, job.n = pc->num_points;
         job.implicit_iota = true;
-        job.aux = r->fpw_a, job.aux_alt = r->fpw_b;
-        job.skip_top = r->ctx->depth_skip_top ? r->counters : nullptr;
+        job.aux = sc.fpw_a.get(), job.aux_alt = sc.fpw_b.get();
+        job.skip_top = r->ctx->depth_skip_top ? counters : nullptr;
         job.kpt9 = r->ctx->depth_tile_kpt ? r->ctx->depth_tile_kpt : 8;
         job.digit_bits = plan.depth_digit_bits;  // (8 | 9, per frame: frame_plan.h depth_sort_digit_bits)
-        if ((rc = launch_sort_pairs(r->sort_depth, job, stream, km, &r->arrays.depth))) return rc;
+        if ((rc = launch_sort_pairs(sc.sort_depth(), job, stream, km, &r->frame.arrays.depth))) return rc;
     }
     if (r->timers) WS_HIP(hipEventRecord(r->ev[2], stream));
     if (cut == 2) return frame_prepared(r, pc, stream);  // analysis only (WS_DEBUG_CUT): the image is NOT produced
 
     // tile binning
     BinBuffers bb;
-    bb.sorted_idx = r->arrays.depth.vals;
-    bb.fp_sorted = r->arrays.depth.aux;
-    bb.sorted_idx_alt = r->arrays.depth.vals_skipped;
-    bb.fp_sorted_alt = r->arrays.depth.aux_skipped;
+    bb.sorted_idx = r->frame.arrays.depth.vals;
+    bb.fp_sorted = r->frame.arrays.depth.aux;
+    bb.sorted_idx_alt = r->frame.arrays.depth.vals_skipped;
+    bb.fp_sorted_alt = r->frame.arrays.depth.aux_skipped;
     bb.footprint_mode = plan.footprint_mode;
-    bb.splats = r->splats;
+    bb.splats = sc.splats.get();
     bb.vw = kp.cam.viewport[0];
     bb.vh = kp.cam.viewport[1];
     bb.tile_w_log2 = plan.tile_w_log2;
     bb.tile_h_log2 = plan.tile_h_log2;
-    bb.offsets = r->bin_offsets;
-    bb.emit_start = r->emit_start;
-    bb.block_status = r->bin_status;
-    bb.entry_keys = r->ekeys_a;
-    bb.entry_vals = r->evals_a;
+    bb.offsets = sc.bin_offsets.get();
+    bb.emit_start = sc.emit_start.get();
+    bb.block_status = sc.bin_status.get();
+    bb.entry_keys = sc.ekeys_a.get();
+    bb.entry_vals = sc.evals_a.get();
     bb.entry_cap = plan.entry_cap;
-    bb.tile_ranges = r->tile_ranges;
-    bb.counters = r->counters;
+    bb.tile_ranges = tile_ranges;
+    bb.counters = counters;
     bb.max_points = pc->num_points;
     bb.tiles_x = plan.tiles_x;
     bb.tiles_y = plan.tiles_y;
     // the tile-id sort's shape (frame_plan.h): k_bin_emit writes the counts of its first pass -- or of its only pass, as
     // [sort tile][bin] rows of wide_bins words -- and the sort below reads them with the same digit width and key width
-    bb.tile_hist = plan.fused_hist ? r->sort_tiles.tile_sums : nullptr;
-    bb.tile_hist_pitch = plan.wide_sort() ? plan.wide_bins : r->sort_tiles.tiles_cap;
+    const SortScratch sort_tiles = sc.sort_tiles();
+    bb.tile_hist = plan.fused_hist ? sort_tiles.tile_sums : nullptr;
+    bb.tile_hist_pitch = plan.wide_sort() ? plan.wide_bins : sort_tiles.tiles_cap;
     bb.tile_hist_mask = plan.tile_hist_mask;
     bb.tile_hist_wide = plan.wide_sort() ? 1 : 0;
     bb.key16 = plan.key16 ? 1 : 0;
@@ -1184,26 +1039,26 @@ static int enqueue_frame(ws_renderer* r, const ws_pointcloud* pc, const K1Params
     if (cut == 3) return frame_prepared(r, pc, stream);
     SortResult tiles;
     if (plan.wide_sort()) {
-        if ((rc = launch_tile_sort_wide(r->sort_tiles, r->ekeys_a, r->evals_a, &r->counters->num_entries, plan.entry_cap,
-                                        plan.wide_bits(), stream, km, r->tile_ranges, plan.ntiles, &tiles)))
+        if ((rc = launch_tile_sort_wide(sort_tiles, sc.ekeys_a.get(), sc.evals_a.get(), &counters->num_entries, plan.entry_cap,
+                                        plan.wide_bits(), stream, km, tile_ranges, plan.ntiles, &tiles)))
             return rc;
     } else {
         SortJob job;
         job.kind = SORT_TILE_IDS;
-        job.keys = r->ekeys_a, job.vals = r->evals_a, job.d_count = &r->counters->num_entries, job.n = plan.entry_cap;
+        job.keys = sc.ekeys_a.get(), job.vals = sc.evals_a.get(), job.d_count = &counters->num_entries, job.n = plan.entry_cap;
         job.end_bit = plan.tile_bits, job.digit_bits = plan.digit_bits;
         job.first_tile_hist_ready = plan.fused_hist, job.key16 = plan.key16;
-        job.ranges = r->tile_ranges, job.nranges = plan.ntiles;
-        if ((rc = launch_sort_pairs(r->sort_tiles, job, stream, km, &tiles))) return rc;
+        job.ranges = tile_ranges, job.nranges = plan.ntiles;
+        if ((rc = launch_sort_pairs(sort_tiles, job, stream, km, &tiles))) return rc;
     }
-    r->arrays.entries = tiles.vals;  // the last pass wrote the per-tile ranges instead of the sorted tile ids
+    r->frame.arrays.entries = tiles.vals;  // the last pass wrote the per-tile ranges instead of the sorted tile ids
     // the compositing workgroups in longest-list-first order, where the plan says so (the order mode itself is decided once
     // per prepare(), OUTSIDE any captured region: decide_blend_order)
-    r->arrays.blend_order_valid = false;
+    r->frame.arrays.blend_order_valid = false;
     if (plan.blend_order) {
-        if ((rc = launch_blend_order(r->tile_ranges, r->counters, plan.tiles_x, plan.tiles_y, r->blend_order, plan.blend_order, stream))) return rc;
+        if ((rc = launch_blend_order(tile_ranges, counters, plan.tiles_x, plan.tiles_y, sc.blend_order.get(), plan.blend_order, stream))) return rc;
         km_mark(km, "k_blend_order");
-        r->arrays.blend_order_valid = true;
+        r->frame.arrays.blend_order_valid = true;
     }
     if (r->timers) {
         WS_HIP(hipEventRecord(r->ev[3], stream));
@@ -1228,7 +1083,7 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
         return fail(WS_ERR_INVALID, "ws_renderer_prepare: max_sh_deg exceeds the renderer's SH layout degree");
     if (pc->compressed && pc->sh_deg > r->sh_deg)
         return fail(WS_ERR_INVALID, "ws_renderer_prepare: compressed point cloud has a higher SH degree than the renderer was created for");
-    r->prepared = false;
+    r->frame = PreparedFrame();
     int rc;
     // an automatic capacity follows the demand of this scene's and viewport's overflowed frames
     if (r->entry_cap_request == 0 && (rc = renderer_refresh_demand(r, pc->num_points, args->viewport[0], args->viewport[1]))) return rc;
@@ -1245,10 +1100,10 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     q.graph_depth_bits = r->fg.depth_bits;
     if ((rc = renderer_ensure_scratch(r, pc->num_points, args->viewport[0], args->viewport[1], frame_plan(q)))) return rc;
     const FramePlan& plan = r->plan;
-    // the z plane: 4 B per splat, allocated with the scratch (and freed with it) while depth is on
-    if (r->depth && !r->depths && (rc = dmalloc(&r->depths, (size_t)pc->num_points + 8))) return rc;
-    r->k1_depths = r->depth ? r->depths : nullptr;
-    r->prepared_depth = false;
+    FrameScratch& sc = r->scratch;
+    // the z plane: 4 B per splat, allocated while depth is on and freed with the scratch
+    if (r->depth && !sc.depths.get() && (rc = sc.depths.alloc(sc.layout.depths))) return rc;
+    r->frame.k1_depths = r->depth ? sc.depths.get() : nullptr;
 
     K1Params kp;
     std::memset(&kp, 0, sizeof kp);
@@ -1266,8 +1121,8 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     kp.bin_request = plan.bin_request;
     kp.znear = -kp.cam.proj[3 * 4 + 2] / kp.cam.proj[2 * 4 + 2];
     kp.zfar = -kp.cam.proj[3 * 4 + 2] / (kp.cam.proj[2 * 4 + 2] - 1.0f);
-    r->prepared_znear = kp.znear;
-    r->prepared_zfar = kp.zfar;
+    r->frame.znear = kp.znear;
+    r->frame.zfar = kp.zfar;
     // fade-in (preprocess.wgsl:196-203): dd = 5 |centre - xyz| / extend <= 10 because the centroid lies inside the
     // bbox and extend >= its radius; beyond walltime 11 s smoothstep(walltime - dd) is exactly 1 for every Gaussian.
     // (the clip box only removes Gaussians, so the bound holds for user boxes too)
@@ -1275,27 +1130,27 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
                     !args->has_clipping_box) ? 1u : 0u;
 
     K1Buffers kb;
-    kb.planes = pc->planes;
-    kb.gaussians_c = pc->gaussians_c;
-    kb.sh_bytes = pc->sh_bytes;
-    kb.covars = pc->covars;
-    kb.splats = r->splats;
-    kb.keys = r->keys_a;
-    kb.footprints = r->fpw_a;
-    kb.src_index = (r->capture || r->contrib) ? r->src_index : nullptr;
-    r->prepared_contrib = r->contrib;
-    kb.block_status = r->k1_status;
-    kb.counters = r->counters;
-    // (the next `trace_cap` frames of a traced renderer: one slot of four stamps per frame, each used once)
-    r->trace_slot = (r->frame_trace && r->trace_count < r->trace_cap) ? r->frame_trace + (size_t)r->trace_count * 4 : nullptr;
-    if (r->trace_slot) ++r->trace_count;
-    kb.trace = r->trace_slot;
+    kb.planes = pc->planes.get();
+    kb.gaussians_c = pc->gaussians_c.get();
+    kb.sh_bytes = pc->sh_bytes.get();
+    kb.covars = pc->covars.get();
+    kb.splats = sc.splats.get();
+    kb.keys = sc.keys_a.get();
+    kb.footprints = sc.fpw_a.get();
+    kb.src_index = (r->capture || r->contrib) ? sc.src_index.get() : nullptr;
+    r->frame.contrib = r->contrib;
+    kb.block_status = sc.k1_status.get();
+    kb.counters = sc.counters();
+    // (the next frames of a traced renderer, as many as it has slots: one slot of four stamps per frame, each used once)
+    r->frame.trace_slot = r->trace_count < trace_capacity(r) ? r->frame_trace.get() + (size_t)r->trace_count * 4 : nullptr;
+    if (r->frame.trace_slot) ++r->trace_count;
+    kb.trace = r->frame.trace_slot;
 
     // look-back epoch of this frame (lookback.h); on wrap-around the status arrays are re-zeroed
     if (++r->epoch == 0) {
-        WS_HIP(hipMemsetAsync(r->k1_status, 0, ((size_t)preprocess_blocks(pc->num_points) + 1) * sizeof(uint64_t), stream));
-        WS_HIP(hipMemsetAsync(r->bin_status, 0, ((size_t)bin_prefix_blocks(pc->num_points) + 1) * sizeof(uint64_t), stream));
-        if (r->fat.status) WS_HIP(hipMemsetAsync(r->fat.status, 0, fat_sort_status_words() * sizeof(uint64_t), stream));
+        WS_HIP(hipMemsetAsync(sc.k1_status.get(), 0, sc.k1_status.bytes(), stream));
+        WS_HIP(hipMemsetAsync(sc.bin_status.get(), 0, sc.bin_status.bytes(), stream));
+        if (sc.fat_status.get()) WS_HIP(hipMemsetAsync(sc.fat_status.get(), 0, sc.fat_status.bytes(), stream));
         r->epoch = 1;
     }
     kp.epoch = r->epoch;
@@ -1317,7 +1172,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
                            !r->contrib && cut_mode == 0;
     if (!use_graph) {
         rc = enqueue_frame(r, pc, kp, kb, stream);
-        if (rc == WS_OK) r->prepared_depth = r->k1_depths != nullptr;
+        if (rc == WS_OK) r->frame.depth = r->frame.k1_depths != nullptr;
         return rc;
     }
     ws_renderer::FrameGraph& g = r->fg;
@@ -1329,7 +1184,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         const hipError_t ce = hipStreamEndCapture(stream, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);
-            r->prepared = false;
+            r->frame = PreparedFrame();
             return rc;
         }
         if (ce != hipSuccess || !graph) return hip_fail(ce, "ws_renderer_prepare: stream capture");
@@ -1339,7 +1194,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         WS_HIP(hipGraphGetNodes(graph, nullptr, &nn));
         std::vector<hipGraphNode_t> nodes(nn);
         WS_HIP(hipGraphGetNodes(graph, nodes.data(), &nn));
-        const void* k1_func = preprocess_kernel_func(pc->compressed, r->plan.footprint_mode, r->k1_depths != nullptr);
+        const void* k1_func = preprocess_kernel_func(pc->compressed, r->plan.footprint_mode, r->frame.k1_depths != nullptr);
         for (size_t i = 0; i < nn && !g.k1_node; ++i) {
             hipGraphNodeType ty;
             if (hipGraphNodeGetType(nodes[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
@@ -1360,7 +1215,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
         }
         g.pc = pc;
         g.generation = r->scratch_generation;
-        g.arrays = r->arrays;  // (with: did the captured frame run k_blend_order?)
+        g.arrays = r->frame.arrays;  // (with: did the captured frame run k_blend_order?)
         g.order_mode = r->order_mode;
         g.depth_bits = r->plan.depth_digit_bits;
         g.valid = true;
@@ -1368,7 +1223,7 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     const int slot = (int)(g.next++ % ws_renderer::GRAPH_RING);
     if (g.used[slot]) WS_HIP(hipEventSynchronize(g.done[slot]));  // an earlier launch of this executable graph must have run
     // (the DEPTH form of K1 takes the z plane as a third argument; toggling depth re-captures: ws_renderer_enable_depth)
-    float* k1_depths = r->k1_depths;
+    float* k1_depths = r->frame.k1_depths;
     void* k1_args[3] = {const_cast<K1Params*>(&kp), const_cast<K1Buffers*>(&kb), &k1_depths};
     hipKernelNodeParams np = g.k1_params;
     np.kernelParams = k1_args;
@@ -1377,8 +1232,8 @@ int ws_renderer_prepare(ws_renderer* r, const ws_pointcloud* pc, const ws_splatt
     WS_HIP(hipGraphLaunch(g.exec[slot], stream));
     WS_HIP(hipEventRecord(g.done[slot], stream));
     g.used[slot] = true;
-    r->arrays = g.arrays;  // what THIS graph's frames write, whatever a launch-by-launch frame left behind
-    r->prepared_depth = r->k1_depths != nullptr;
+    r->frame.arrays = g.arrays;  // what THIS graph's frames write, whatever a launch-by-launch frame left behind
+    r->frame.depth = r->frame.k1_depths != nullptr;
     return frame_prepared(r, pc, stream);
 }
 
@@ -1461,7 +1316,7 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
                         size_t row_pitch_bytes, void* stream_v, const BlendAuxPlanes* planes,
                         const BlendComposite* comp = nullptr) {
     if (!r || !pc || !d_rgba_out) return fail(WS_ERR_INVALID, "ws_renderer_render: null argument");
-    if (!r->prepared || r->prepared_pc != pc)
+    if (!r->frame.prepared || r->frame.pc != pc)
         return fail(WS_ERR_STATE, "ws_renderer_render: prepare() was not called for this point cloud");
     const size_t texel = r->format == WS_FORMAT_RGBA8_UNORM ? 4 : (r->format == WS_FORMAT_RGBA16_FLOAT ? 8 : 16);
     if (row_pitch_bytes < texel * r->vw || (row_pitch_bytes % texel) != 0 ||
@@ -1472,12 +1327,12 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
     fr.target_precision = r->blend_mode == WS_BLEND_TARGET_PRECISION, fr.exact_mode = r->blend_mode == WS_BLEND_FAST_EXACT_CUT;
     fr.variant = r->ctx->blend_variant, fr.capture = r->capture, fr.timing = r->blend_timing;
     fr.split_wanted = r->plan.split_wanted;
-    fr.order_valid = r->arrays.blend_order_valid, fr.qw = r->ctx->tile_qw, fr.qh = r->ctx->tile_qh;
+    fr.order_valid = r->frame.arrays.blend_order_valid, fr.qw = r->ctx->tile_qw, fr.qh = r->ctx->tile_qh;
     const BlendFrameChoice form = blend_frame_choice(fr);
     BlendParams bp;
-    bp.splats = r->splats;
-    bp.entry_vals = r->arrays.entries;
-    bp.tile_ranges = r->tile_ranges;
+    bp.splats = r->scratch.splats.get();
+    bp.entry_vals = r->frame.arrays.entries;
+    bp.tile_ranges = r->scratch.tile_ranges();
     bp.width = r->vw;
     bp.height = r->vh;
     bp.tiles_x = r->plan.tiles_x;
@@ -1501,30 +1356,28 @@ static int render_frame(ws_renderer* r, const ws_pointcloud* pc, const float bac
         bp.tiles_y = (r->vh + 15u) / 16u;
         bp.range_row_shift = 1;
     }
-    bp.counters = r->counters;
-    bp.sticky = r->sticky;
+    bp.counters = r->scratch.counters();
+    bp.sticky = r->sticky.get();
     bp.demand_mailbox = r->demand_mailbox_dev;
     bp.progress_mailbox = r->demand_mailbox_dev ? r->demand_mailbox_dev + 1 : nullptr;
     bp.frame_seq = r->frames_enqueued + 1u;  // (counted below, once the launch is certain)
-    bp.order = form.ordered ? r->blend_order : nullptr;
-    bp.debug_consumed = r->capture ? r->debug_consumed : nullptr;
-    bp.debug_walked = r->capture ? r->debug_walked : nullptr;
+    bp.order = form.ordered ? r->scratch.blend_order.get() : nullptr;
+    bp.debug_consumed = r->capture ? r->scratch.debug_consumed.get() : nullptr;
+    bp.debug_walked = r->capture ? r->scratch.debug_walked.get() : nullptr;
     bp.debug_timing = nullptr;
-    bp.trace = r->trace_slot ? r->trace_slot + 2 : nullptr;
+    bp.trace = r->frame.trace_slot ? r->frame.trace_slot + 2 : nullptr;
     if (r->blend_timing && !r->capture) {
-        const uint32_t nt = r->plan.ntiles;
-        if (r->debug_timing_tiles != nt) {
+        DeviceBuf<uint32_t>& timing = r->scratch.debug_timing;  // (allocated on first use, freed with the scratch)
+        if (!timing.get()) {
             WS_HIP(hipStreamSynchronize(stream));
-            dfree(r->debug_timing);
-            WS_TRY(dmalloc(&r->debug_timing, (size_t)nt * 16 * BLEND_TIMING_WORDS));
-            r->debug_timing_tiles = nt;
+            WS_TRY(timing.alloc(r->scratch.layout.debug_timing));
         }
-        WS_HIP(hipMemsetAsync(r->debug_timing, 0, (size_t)nt * 16 * BLEND_TIMING_WORDS * sizeof(uint32_t), stream));
-        bp.debug_timing = r->debug_timing;
+        WS_HIP(hipMemsetAsync(timing.get(), 0, timing.bytes(), stream));
+        bp.debug_timing = timing.get();
     }
     if (bp.debug_consumed) {
-        WS_HIP(hipMemsetAsync(r->debug_consumed, 0, (size_t)r->plan.ntiles * sizeof(uint32_t), stream));
-        WS_HIP(hipMemsetAsync(r->debug_walked, 0, (size_t)r->plan.ntiles * 17 * sizeof(uint32_t), stream));
+        WS_HIP(hipMemsetAsync(r->scratch.debug_consumed.get(), 0, r->scratch.debug_consumed.bytes(), stream));
+        WS_HIP(hipMemsetAsync(r->scratch.debug_walked.get(), 0, r->scratch.debug_walked.bytes(), stream));
     }
     KernelMarks* km = r->marks.active ? &r->marks : nullptr;
     if (km) km->begin(stream, false);
@@ -1579,7 +1432,7 @@ static int aux_planes_of(ws_renderer* r, const ws_pointcloud* pc, const ws_aux_t
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need WS_BLEND_FAST");
     if (!production_launch(r))
         return fail(WS_ERR_UNSUPPORTED, "ws_renderer_render_aux: auxiliary planes need the production blend (no capture / timing / variants)");
-    if (r->prepared && r->prepared_pc == pc && (aux->depth || aux->median_depth) && !r->prepared_depth)
+    if (r->frame.prepared && r->frame.pc == pc && (aux->depth || aux->median_depth) && !r->frame.depth)
         return fail(WS_ERR_STATE, "ws_renderer_render_aux: depth planes need ws_renderer_enable_depth before prepare()");
     bp->depth = aux->depth;
     bp->depth_pitch = aux->depth_pitch;
@@ -1587,7 +1440,7 @@ static int aux_planes_of(ws_renderer* r, const ws_pointcloud* pc, const ws_aux_t
     bp->median_pitch = aux->median_depth_pitch;
     bp->alpha = aux->alpha;
     bp->alpha_pitch = aux->alpha_pitch;
-    bp->z = r->prepared_depth ? r->depths : nullptr;
+    bp->z = r->frame.depth ? r->scratch.depths.get() : nullptr;
     return WS_OK;
 }
 
@@ -1628,14 +1481,14 @@ int ws_renderer_render_composite(ws_renderer* r, const ws_pointcloud* pc, const 
         const int rc = aux_planes_of(r, pc, aux, &bp);
         if (rc) return rc;
     }
-    if (comp->occluder && r->prepared && r->prepared_pc == pc && !r->prepared_depth)
+    if (comp->occluder && r->frame.prepared && r->frame.pc == pc && !r->frame.depth)
         return fail(WS_ERR_STATE, "ws_renderer_render_composite: an occluder needs ws_renderer_enable_depth before prepare()");
-    bp.z = r->prepared_depth ? r->depths : nullptr;
+    bp.z = r->frame.depth ? r->scratch.depths.get() : nullptr;
     BlendComposite c;
     c.occluder = comp->occluder;
     c.occluder_pitch = comp->occluder_pitch;
-    c.znear = r->prepared_znear;
-    c.zfar = r->prepared_zfar;
+    c.znear = r->frame.znear;
+    c.zfar = r->frame.zfar;
     c.occ_ndc = comp->occluder_kind == WS_OCCLUDER_NDC_DEPTH ? 1 : 0;
     c.load = comp->load ? 1 : 0;
     return render_frame(r, pc, background, d_rgba, row_pitch_bytes, stream, &bp, &c);
@@ -1643,8 +1496,8 @@ int ws_renderer_render_composite(ws_renderer* r, const ws_pointcloud* pc, const 
 
 int ws_renderer_download_depths(ws_renderer* r, uint32_t capacity, float* z, uint32_t* num_visible) {
     if (!r) return fail(WS_ERR_INVALID, "ws_renderer_download_depths: null renderer");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_depths: no prepared frame");
-    if (!r->prepared_depth) return fail(WS_ERR_STATE, "ws_renderer_download_depths: depth was off at prepare()");
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_download_depths: no prepared frame");
+    if (!r->frame.depth) return fail(WS_ERR_STATE, "ws_renderer_download_depths: depth was off at prepare()");
     ws_frame_stats st;
     int rc = ws_renderer_frame_stats(r, &st);
     if (rc) return rc;
@@ -1652,15 +1505,15 @@ int ws_renderer_download_depths(ws_renderer* r, uint32_t capacity, float* z, uin
     const uint32_t v = st.num_visible;
     if (z && capacity < v) return fail(WS_ERR_INVALID, "ws_renderer_download_depths: capacity smaller than the visible count");
     if (!z || v == 0) return WS_OK;
-    return copy_d2h(z, r->depths, (size_t)v * sizeof(float), r->last_stream);
+    return copy_d2h(z, r->scratch.depths.get(), (size_t)v * sizeof(float), r->last_stream);
 }
 
 int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out) {
     if (!r || !out) return fail(WS_ERR_INVALID, "ws_renderer_frame_stats: null argument");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_frame_stats: no prepared frame");
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_frame_stats: no prepared frame");
     WS_HIP(hipStreamSynchronize(r->last_stream));
     FrameCounters fc;
-    WS_TRY(copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream));
+    WS_TRY(copy_d2h(&fc, r->scratch.counters(), offsetof(FrameCounters, tile_sums), r->last_stream));
     out->num_visible = fc.num_visible;
     out->num_tile_entries = fc.num_entries;
     out->tile_entries_capacity = r->plan.entry_cap;
@@ -1673,7 +1526,7 @@ int ws_renderer_frame_stats(ws_renderer* r, ws_frame_stats* out) {
 static int frame_list_counts(ws_renderer* r, uint32_t* shift, uint32_t* lists_x, uint32_t* lists_y) {
     WS_HIP(hipStreamSynchronize(r->last_stream));
     FrameCounters fc;
-    WS_TRY(copy_d2h(&fc, r->counters, offsetof(FrameCounters, tile_sums), r->last_stream));
+    WS_TRY(copy_d2h(&fc, r->scratch.counters(), offsetof(FrameCounters, tile_sums), r->last_stream));
     const uint32_t s = fc.bin_shift;
     *shift = s;
     *lists_x = (r->plan.tiles_x + s) >> s;
@@ -1683,7 +1536,7 @@ static int frame_list_counts(ws_renderer* r, uint32_t* shift, uint32_t* lists_x,
 
 int ws_renderer_binning_tile(ws_renderer* r, uint32_t* width, uint32_t* height) {
     if (!r || !width || !height) return fail(WS_ERR_INVALID, "ws_renderer_binning_tile: null argument");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_binning_tile: no prepared frame");
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_binning_tile: no prepared frame");
     uint32_t s, lx, ly;
     WS_TRY(frame_list_counts(r, &s, &lx, &ly));
     *width = (QUAD * r->ctx->tile_qw) << s;
@@ -1694,11 +1547,11 @@ int ws_renderer_binning_tile(ws_renderer* r, uint32_t* width, uint32_t* height) 
 // Which depth-sorted arrays hold the prepared frame's order: where the sort's last pass left them, or -- decided on the device,
 // read back here only when the frame could skip -- where pass 2 did (*skipped).
 static int frame_depth_order(ws_renderer* r, const uint32_t** keys, const uint32_t** vals, bool* skipped) {
-    const SortResult& d = r->arrays.depth;
+    const SortResult& d = r->frame.arrays.depth;
     uint32_t skip = 0;
     if (d.vals_skipped) {
         WS_HIP(hipStreamSynchronize(r->last_stream));
-        WS_TRY(copy_d2h(&skip, &r->counters->depth_skip_top, sizeof skip, r->last_stream));
+        WS_TRY(copy_d2h(&skip, &r->scratch.counters()->depth_skip_top, sizeof skip, r->last_stream));
     }
     *keys = skip ? d.keys_skipped : d.keys;
     *vals = skip ? d.vals_skipped : d.vals;
@@ -1708,7 +1561,7 @@ static int frame_depth_order(ws_renderer* r, const uint32_t** keys, const uint32
 
 int ws_renderer_depth_sort_passes(ws_renderer* r, uint32_t* passes) {
     if (!r || !passes) return fail(WS_ERR_INVALID, "ws_renderer_depth_sort_passes: null argument");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_depth_sort_passes: no prepared frame");
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_depth_sort_passes: no prepared frame");
     const uint32_t *keys, *vals;
     bool skipped;
     WS_TRY(frame_depth_order(r, &keys, &vals, &skipped));
@@ -1718,7 +1571,7 @@ int ws_renderer_depth_sort_passes(ws_renderer* r, uint32_t* passes) {
 
 int ws_renderer_depth_sort_digit_bits(ws_renderer* r, uint32_t* digit_bits) {
     if (!r || !digit_bits) return fail(WS_ERR_INVALID, "ws_renderer_depth_sort_digit_bits: null argument");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_depth_sort_digit_bits: no prepared frame");
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_depth_sort_digit_bits: no prepared frame");
     *digit_bits = (uint32_t)r->plan.depth_digit_bits;
     return WS_OK;
 }
@@ -1727,17 +1580,17 @@ int ws_renderer_errors(ws_renderer* r, uint32_t* bits, uint32_t* entries_needed,
     if (!r || !bits) return fail(WS_ERR_INVALID, "ws_renderer_errors: null argument");
     *bits = 0;
     if (entries_needed) *entries_needed = 0;
-    if (!r->sticky) return WS_OK;  // (never: allocated with the renderer)
+    if (!r->sticky.get()) return WS_OK;  // (never: allocated with the renderer)
     // The sticky word outlives failed prepare() calls and scratch reallocations (both clear `prepared`): bits that earlier
     // frames left must not disappear behind them.  Only the per-frame counter needs a prepared frame.
     WS_HIP(hipStreamSynchronize(r->last_stream));
     uint32_t both[2] = {0u, 0u};
-    WS_TRY(copy_d2h(both, r->sticky, sizeof(both), r->last_stream));
+    WS_TRY(copy_d2h(both, r->sticky.get(), sizeof(both), r->last_stream));
     *bits = both[0];
     if (both[1] > r->needed_seen) r->needed_seen = both[1];  // an overflowed frame's demand: the next prepare() allocates it
-    if (entries_needed && r->prepared && r->counters) WS_TRY(copy_d2h(entries_needed, &r->counters->entries_needed, sizeof(uint32_t), r->last_stream));
+    if (entries_needed && r->frame.prepared && r->scratch.counters()) WS_TRY(copy_d2h(entries_needed, &r->scratch.counters()->entries_needed, sizeof(uint32_t), r->last_stream));
     if (reset && *bits) {
-        WS_HIP(hipMemsetAsync(r->sticky, 0, sizeof(uint32_t), r->last_stream));
+        WS_HIP(hipMemsetAsync(r->sticky.get(), 0, sizeof(uint32_t), r->last_stream));
         WS_HIP(hipStreamSynchronize(r->last_stream));
     }
     return WS_OK;
@@ -1785,7 +1638,7 @@ int ws_renderer_kernel_times(ws_renderer* r, uint32_t capacity, ws_kernel_time* 
 int ws_renderer_download_tile_stats(ws_renderer* r, uint32_t capacity, uint32_t* list_len, uint32_t* consumed,
                                     uint32_t* num_tiles) {
     if (!r) return fail(WS_ERR_INVALID, "ws_renderer_download_tile_stats: null renderer");
-    if (!r->prepared) return fail(WS_ERR_STATE, "ws_renderer_download_tile_stats: no prepared frame");
+    if (!r->frame.prepared) return fail(WS_ERR_STATE, "ws_renderer_download_tile_stats: no prepared frame");
     uint32_t bs, lx, ly;
     WS_TRY(frame_list_counts(r, &bs, &lx, &ly));
     const uint32_t nt = lx * ly;  // one entry per LIST (= per binning tile; capture keeps them at the blend tile)
@@ -1797,21 +1650,21 @@ int ws_renderer_download_tile_stats(ws_renderer* r, uint32_t capacity, uint32_t*
     WS_HIP(hipStreamSynchronize(r->last_stream));
     if (list_len) {
         std::vector<uint2> rg(nt);
-        WS_TRY(copy_d2h(rg.data(), r->tile_ranges, (size_t)nt * sizeof(uint2), r->last_stream));
+        WS_TRY(copy_d2h(rg.data(), r->scratch.tile_ranges(), (size_t)nt * sizeof(uint2), r->last_stream));
         for (uint32_t i = 0; i < nt; ++i) list_len[i] = rg[i].y ? rg[i].y - (0xFFFFFFFFu - rg[i].x) : 0u;
     }
-    if (consumed) WS_TRY(copy_d2h(consumed, r->debug_consumed, (size_t)nt * 4, r->last_stream));
+    if (consumed) WS_TRY(copy_d2h(consumed, r->scratch.debug_consumed.get(), (size_t)nt * 4, r->last_stream));
     return WS_OK;
 }
 
 int ws_renderer_download_wave_stats(ws_renderer* r, uint32_t tile_capacity, uint32_t* walked) {
     if (!r || !walked) return fail(WS_ERR_INVALID, "ws_renderer_download_wave_stats: null argument");
-    if (!r->prepared || !r->capture)
+    if (!r->frame.prepared || !r->capture)
         return fail(WS_ERR_STATE, "ws_renderer_download_wave_stats: needs ws_renderer_enable_capture and a rendered frame");
     const uint32_t nt = r->plan.ntiles;
     if (tile_capacity < nt) return fail(WS_ERR_INVALID, "ws_renderer_download_wave_stats: capacity smaller than the tile count");
     WS_HIP(hipStreamSynchronize(r->last_stream));
-    WS_TRY(copy_d2h(walked, r->debug_walked, (size_t)nt * 17 * sizeof(uint32_t), r->last_stream));
+    WS_TRY(copy_d2h(walked, r->scratch.debug_walked.get(), r->scratch.debug_walked.bytes(), r->last_stream));
     return WS_OK;
 }
 
@@ -1830,14 +1683,14 @@ int ws_renderer_download_tile_lists(ws_renderer* r, uint32_t tile_capacity, uint
         return fail(WS_ERR_INVALID, "ws_renderer_download_tile_lists: entry capacity too small");
     if (begin || end) {
         std::vector<uint2> rg(nt);
-        WS_TRY(copy_d2h(rg.data(), r->tile_ranges, (size_t)nt * sizeof(uint2), r->last_stream));
+        WS_TRY(copy_d2h(rg.data(), r->scratch.tile_ranges(), (size_t)nt * sizeof(uint2), r->last_stream));
         for (uint32_t i = 0; i < nt; ++i) {
             if (begin) begin[i] = rg[i].y ? 0xFFFFFFFFu - rg[i].x : 0u;
             if (end) end[i] = rg[i].y;
         }
     }
     if (entries && st.num_tile_entries)
-        WS_TRY(copy_d2h(entries, r->arrays.entries, (size_t)st.num_tile_entries * 4, r->last_stream));
+        WS_TRY(copy_d2h(entries, r->frame.arrays.entries, (size_t)st.num_tile_entries * 4, r->last_stream));
     return WS_OK;
 }
 
@@ -1851,7 +1704,7 @@ int ws_renderer_download_frame(ws_renderer* r, uint32_t capacity, void* splats, 
     const uint32_t v = st.num_visible;
     if ((splats || keys || src_index || sorted) && capacity < v)
         return fail(WS_ERR_INVALID, "ws_renderer_download_frame: capacity smaller than the visible count");
-    if (src_index && !r->capture && !r->prepared_contrib)
+    if (src_index && !r->capture && !r->frame.contrib)
         return fail(WS_ERR_STATE, "ws_renderer_download_frame: src_index needs ws_renderer_enable_capture before prepare");
     if (v == 0) return WS_OK;
     const uint32_t *sorted_keys, *sorted_idx;
@@ -1859,14 +1712,14 @@ int ws_renderer_download_frame(ws_renderer* r, uint32_t capacity, void* splats, 
     WS_TRY(frame_depth_order(r, &sorted_keys, &sorted_idx, &skipped));
     if (splats) {  // the caller gets the reference's 20-B records whatever stride the device keeps them at
         if (SPLAT_STRIDE == 20u) {
-            WS_TRY(copy_d2h(splats, r->splats, (size_t)v * 20, r->last_stream));
+            WS_TRY(copy_d2h(splats, r->scratch.splats.get(), (size_t)v * 20, r->last_stream));
         } else {
             std::vector<uint8_t> padded((size_t)v * SPLAT_STRIDE);
-            WS_TRY(copy_d2h(padded.data(), r->splats, padded.size(), r->last_stream));
+            WS_TRY(copy_d2h(padded.data(), r->scratch.splats.get(), padded.size(), r->last_stream));
             for (size_t i = 0; i < (size_t)v; ++i) std::memcpy(static_cast<uint8_t*>(splats) + i * 20, padded.data() + i * SPLAT_STRIDE, 20);
         }
     }
-    if (src_index) WS_TRY(copy_d2h(src_index, r->src_index, (size_t)v * 4, r->last_stream));
+    if (src_index) WS_TRY(copy_d2h(src_index, r->scratch.src_index.get(), (size_t)v * 4, r->last_stream));
     if (sorted) WS_TRY(copy_d2h(sorted, sorted_idx, (size_t)v * 4, r->last_stream));
     if (keys) {
         // the sort permutes the keys in place; un-permute them with the sorted indices so that the caller
@@ -1885,57 +1738,39 @@ int ws_sorter_create(ws_context* ctx, uint32_t max_n, ws_sorter** out) {
     if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_sorter_create: null argument");
     *out = nullptr;
     if (max_n == 0 || max_n >= (1u << 30)) return fail(WS_ERR_INVALID, "ws_sorter_create: max_n out of range");
-    ws_sorter* s = new (std::nothrow) ws_sorter();
+    std::unique_ptr<ws_sorter, SyncedDelete> s(new (std::nothrow) ws_sorter());
     if (!s) return fail(WS_ERR_OOM, "ws_sorter_create: host allocation failed");
     s->ctx = ctx;
-    int rc = alloc_sort_scratch(s->sc, max_n, true, 0, 512);
-    s->sc.hist_pitch = 512;
-    if (rc == WS_OK) rc = dmalloc(&s->zero, 1);
-    if (rc == WS_OK) rc = dmalloc(&s->aux_alt, (size_t)max_n + 4);
-    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_sorter_create: device sync failed");
-    if (rc == WS_OK) {
-        s->sc.hist = s->zero->hist;
-        if (ctx->depth_sort_mode == DS_ONESWEEP || ctx->depth_sort_mode == DS_COOP) {
-            FatSortScratch& fs = s->fat;
-            fs.cap = max_n;
-            rc = dmalloc(&fs.status, fat_sort_status_words());
-            if (rc == WS_OK && (hipMemset(fs.status, 0, fat_sort_status_words() * sizeof(uint64_t)) != hipSuccess ||
-                                hipDeviceSynchronize() != hipSuccess))
-                rc = fail(WS_ERR_HIP, "ws_sorter_create: look-back word initialisation failed");
-            fs.keys_alt = s->sc.keys_alt;
-            fs.vals_alt = s->sc.vals_alt;
-            fs.aux_alt = s->aux_alt;
-            fs.hist = s->zero->hist;
-            fs.tickets = s->zero->tickets;
-            fs.barrier = s->zero->fat_barrier;
-            fs.error = &s->zero->error;
-            fs.grid_request = ctx->dsort_fat_grid;
-        }
+    const SortShape shape = sort_shape(max_n, 0, 512);  // (512 count rows: 9-bit digits)
+    WS_TRY(s->keys_alt.alloc((size_t)max_n + 4));
+    WS_TRY(s->vals_alt.alloc((size_t)max_n + 4));
+    WS_TRY(s->tile_sums.alloc(shape.sum_words));
+    WS_TRY(s->zero.alloc(1));
+    WS_TRY(s->aux_alt.alloc((size_t)max_n + 4));
+    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_sorter_create: device sync failed");
+    SorterZero* const zero = s->zero.get();
+    s->sc = sort_view(shape, s->keys_alt.get(), s->vals_alt.get(), zero->hist, 512, s->tile_sums.get(), nullptr);
+    if (ctx->depth_sort_mode == DS_ONESWEEP || ctx->depth_sort_mode == DS_COOP) {
+        WS_TRY(s->fat_status.alloc(fat_sort_status_words()));
+        if (hipMemset(s->fat_status.get(), 0, s->fat_status.bytes()) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+            return fail(WS_ERR_HIP, "ws_sorter_create: look-back word initialisation failed");
+        FatSortScratch& fs = s->fat;
+        fs.cap = max_n, fs.status = s->fat_status.get(), fs.grid_request = ctx->dsort_fat_grid;
+        fs.keys_alt = s->keys_alt.get(), fs.vals_alt = s->vals_alt.get(), fs.aux_alt = s->aux_alt.get();
+        fs.hist = zero->hist, fs.tickets = zero->tickets, fs.barrier = zero->fat_barrier, fs.error = &zero->error;
     }
-    if (rc != WS_OK) {
-        ws_sorter_destroy(s);
-        return rc;
-    }
-    *out = s;
+    *out = s.release();
     return WS_OK;
 }
 
-void ws_sorter_destroy(ws_sorter* s) {
-    if (!s) return;
-    (void)hipDeviceSynchronize();
-    dfree(s->zero);
-    dfree(s->aux_alt);
-    dfree(s->fat.status);
-    free_sort_scratch(s->sc, true);
-    delete s;
-}
+void ws_sorter_destroy(ws_sorter* s) { SyncedDelete()(s); }
 
 int ws_sorter_sort(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, const uint32_t* d_count, uint32_t n,
                    void* stream_v) {
     if (!s || !d_keys || !d_payload) return fail(WS_ERR_INVALID, "ws_sorter_sort: null argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     s->folded = false;  // (the memset below clears what a ws_sorter_sort_depth decided)
-    WS_HIP(hipMemsetAsync(s->zero, 0, sizeof(SorterZero), stream));
+    WS_HIP(hipMemsetAsync(s->zero.get(), 0, sizeof(SorterZero), stream));
     SortJob job;
     job.keys = d_keys, job.vals = d_payload, job.d_count = d_count, job.n = n;
     SortResult res;
@@ -1958,16 +1793,16 @@ int ws_sorter_sort_depth(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, ui
         return fail(WS_ERR_INVALID, "ws_sorter_sort_depth: keys must be 16-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (++s->epoch == 0) {  // epoch-tagged count rows of the fat-tile form: re-zeroed on wrap-around
-        if (s->fat.status) WS_HIP(hipMemsetAsync(s->fat.status, 0, fat_sort_status_words() * sizeof(uint64_t), stream));
+        if (s->fat_status.get()) WS_HIP(hipMemsetAsync(s->fat_status.get(), 0, s->fat_status.bytes(), stream));
         s->epoch = 1;
     }
     s->folded = false;
     s->last_stream = stream;
-    WS_HIP(hipMemsetAsync(s->zero, 0, sizeof(SorterZero), stream));
+    WS_HIP(hipMemsetAsync(s->zero.get(), 0, sizeof(SorterZero), stream));
     const bool fat = n != 0 && s->fat.status && fat_sort_grid(n, s->ctx->num_cus, s->fat.grid_request) != 0u;
     // the frame's form (ws_renderer_prepare): the first histogram kernel reports the key range, the column scan behind it decides
     // the base of passes 1..3 and whether the fourth pass runs (depth_range_decide)
-    FrameCounters* skip_top = (s->ctx->depth_skip_top && !fat) ? &s->zero->counters : nullptr;
+    FrameCounters* skip_top = (s->ctx->depth_skip_top && !fat) ? &s->zero.get()->counters : nullptr;
     s->folded = skip_top != nullptr;
     if (n == 0) return WS_OK;
     SortResult res;
@@ -1978,7 +1813,7 @@ int ws_sorter_sort_depth(ws_sorter* s, uint32_t* d_keys, uint32_t* d_payload, ui
     job.kind = SORT_DEPTH;
     job.keys = d_keys, job.vals = d_payload, job.d_count = d_count, job.n = n;
     job.digit_bits = depth_sort_digit_bits(s->ctx->depth_digit_bits, false, 0u, 0);  // (no previous frame, no graph: forced, or the default)
-    job.aux = d_aux, job.aux_alt = d_aux ? s->aux_alt : nullptr;
+    job.aux = d_aux, job.aux_alt = d_aux ? s->aux_alt.get() : nullptr;
     job.skip_top = skip_top;
     job.kpt9 = s->ctx->depth_tile_kpt ? s->ctx->depth_tile_kpt : 8;
     WS_TRY(launch_sort_pairs(s->sc, job, stream, nullptr, &res));
@@ -2000,7 +1835,7 @@ int ws_sorter_depth_range(ws_sorter* s, uint32_t* base, uint32_t* skip, uint32_t
     static_assert(offsetof(FrameCounters, depth_key_base) == offsetof(FrameCounters, depth_skip_top) + 4 &&
                       offsetof(FrameCounters, depth_span_class) == offsetof(FrameCounters, depth_skip_top) + 8,
                   "FrameCounters layout");
-    WS_TRY(copy_d2h(w, &s->zero->counters.depth_skip_top, sizeof w, s->last_stream));
+    WS_TRY(copy_d2h(w, &s->zero.get()->counters.depth_skip_top, sizeof w, s->last_stream));
     *skip = w[0];
     *base = w[1];
     *span_class = w[2];
@@ -2018,29 +1853,22 @@ int ws_sort_selftest(ws_context* ctx, int* passed) {
         expect[i] = (float)i;
         payload[i] = i;
     }
-    ws_sorter* s = nullptr;
-    int rc = ws_sorter_create(ctx, n, &s);
-    if (rc) return rc;
-    uint32_t *dk = nullptr, *dv = nullptr;
-    rc = dmalloc(&dk, n);
-    if (rc == WS_OK) rc = dmalloc(&dv, n);
-    if (rc == WS_OK) {
-        hipError_t e = hipMemcpy(dk, scrambled.data(), n * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dv, payload.data(), n * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_sort_selftest: upload");
-    }
-    if (rc == WS_OK) rc = ws_sorter_sort(s, dk, dv, nullptr, n, nullptr);
+    ws_sorter* sorter = nullptr;
+    WS_TRY(ws_sorter_create(ctx, n, &sorter));
+    DeviceBuf<uint32_t> dk, dv;  // (declared first: let go after the sorter's destroyer has waited for the device)
+    const std::unique_ptr<ws_sorter, SyncedDelete> s(sorter);
+    WS_TRY(dk.alloc(n));
+    WS_TRY(dv.alloc(n));
+    hipError_t e = hipMemcpy(dk.get(), scrambled.data(), n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dv.get(), payload.data(), n * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "ws_sort_selftest: upload");
+    WS_TRY(ws_sorter_sort(s.get(), dk.get(), dv.get(), nullptr, n, nullptr));
     std::vector<float> got(n);
-    if (rc == WS_OK) {
-        hipError_t e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(got.data(), dk, n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_sort_selftest: download");
-    }
-    if (rc == WS_OK) *passed = std::memcmp(got.data(), expect.data(), n * 4) == 0 ? 1 : 0;
-    dfree(dk);
-    dfree(dv);
-    ws_sorter_destroy(s);
-    return rc;
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(got.data(), dk.get(), n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "ws_sort_selftest: download");
+    *passed = std::memcmp(got.data(), expect.data(), n * 4) == 0 ? 1 : 0;
+    return WS_OK;
 }
 
 }  // extern "C"
@@ -2049,8 +1877,8 @@ int ws_sort_selftest(ws_context* ctx, int* passed) {
 struct ws_contrib {
     ws_context* ctx = nullptr;
     uint32_t num_points = 0;
-    unsigned long long* sum_q32 = nullptr;  // [num_points]
-    uint32_t* max_bits = nullptr;           // [num_points] bits of the largest weight (non-negative floats order as their bits)
+    DeviceBuf<unsigned long long> sum_q32;  // [num_points]
+    DeviceBuf<uint32_t> max_bits;           // [num_points] bits of the largest weight (non-negative floats order as their bits)
     uint32_t frames = 0;
     hipStream_t last_stream = nullptr;
 };
@@ -2061,35 +1889,25 @@ int ws_contrib_create(ws_context* ctx, uint32_t num_points, ws_contrib** out) {
     if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_contrib_create: null argument");
     *out = nullptr;
     if (num_points == 0) return fail(WS_ERR_INVALID, "ws_contrib_create: no points");
-    ws_contrib* c = new (std::nothrow) ws_contrib();
+    std::unique_ptr<ws_contrib, SyncedDelete> c(new (std::nothrow) ws_contrib());
     if (!c) return fail(WS_ERR_OOM, "ws_contrib_create: host allocation failed");
     c->ctx = ctx;
     c->num_points = num_points;
-    int rc = dmalloc(&c->sum_q32, num_points);
-    if (rc == WS_OK) rc = dmalloc(&c->max_bits, num_points);
-    if (rc == WS_OK) rc = ws_contrib_reset(c, nullptr);
-    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_contrib_create: device sync failed");
-    if (rc != WS_OK) {
-        ws_contrib_destroy(c);
-        return rc;
-    }
-    *out = c;
+    WS_TRY(c->sum_q32.alloc(num_points));
+    WS_TRY(c->max_bits.alloc(num_points));
+    WS_TRY(ws_contrib_reset(c.get(), nullptr));
+    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_contrib_create: device sync failed");
+    *out = c.release();
     return WS_OK;
 }
 
-void ws_contrib_destroy(ws_contrib* c) {
-    if (!c) return;
-    (void)hipDeviceSynchronize();
-    dfree(c->sum_q32);
-    dfree(c->max_bits);
-    delete c;
-}
+void ws_contrib_destroy(ws_contrib* c) { SyncedDelete()(c); }
 
 int ws_contrib_reset(ws_contrib* c, void* stream_v) {
     if (!c) return fail(WS_ERR_INVALID, "ws_contrib_reset: null accumulator");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    WS_HIP(hipMemsetAsync(c->sum_q32, 0, (size_t)c->num_points * sizeof(unsigned long long), stream));
-    WS_HIP(hipMemsetAsync(c->max_bits, 0, (size_t)c->num_points * sizeof(uint32_t), stream));
+    WS_HIP(hipMemsetAsync(c->sum_q32.get(), 0, c->sum_q32.bytes(), stream));
+    WS_HIP(hipMemsetAsync(c->max_bits.get(), 0, c->max_bits.bytes(), stream));
     c->frames = 0;
     c->last_stream = stream;
     return WS_OK;
@@ -2103,25 +1921,25 @@ int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
     // Only K1's src_index pointer changes (a kernel argument the frame graph's update rewrites anyway); the binning tile and
     // the blend's form stay what they are, unlike capture.  Off: the frame at hand no longer answers accumulate_contrib.
     r->contrib = enable != 0;
-    if (!r->contrib) r->prepared_contrib = false;
+    if (!r->contrib) r->frame.contrib = false;
     return WS_OK;
 }
 
 // What a launch over the prepared frame's weights (k_contrib, k_values, k_removal_base, k_removal) reads of the renderer
 static FrameLists frame_lists(const ws_renderer* r) {
     FrameLists f;
-    f.splats = r->splats;
-    f.entry_vals = r->arrays.entries;
-    f.tile_ranges = r->tile_ranges;
-    f.src_index = r->src_index;
+    f.splats = r->scratch.splats.get();
+    f.entry_vals = r->frame.arrays.entries;
+    f.tile_ranges = r->scratch.tile_ranges();
+    f.src_index = r->scratch.src_index.get();
     f.width = r->vw;
     f.height = r->vh;
     f.tiles_x = r->plan.tiles_x;
     f.tiles_y = r->plan.tiles_y;
     f.qw = r->ctx->tile_qw;
     f.qh = r->ctx->tile_qh;
-    f.counters = r->counters;
-    f.sticky = r->sticky;
+    f.counters = r->scratch.counters();
+    f.sticky = r->sticky.get();
     f.demand_mailbox = r->demand_mailbox_dev;
     return f;
 }
@@ -2131,8 +1949,8 @@ static int check_weights_frame(const ws_renderer* r, const ws_pointcloud* pc, co
                                const char* points_text) {
     if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
     if (!points_match) return fail(WS_ERR_INVALID, who + ": " + points_text);
-    if (!r->prepared || r->prepared_pc != pc) return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
-    if (!r->prepared_contrib) return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
+    if (!r->frame.prepared || r->frame.pc != pc) return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
+    if (!r->frame.contrib) return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
     return WS_OK;
 }
 
@@ -2152,8 +1970,8 @@ static int check_plane_view(const ws_renderer* r, const std::string& who, const 
 
 // The accumulator as the kernels' argument: the plain sums (plane == nullptr) or the weighted ones
 static Accum accum_arg(const ws_contrib* c, const ws_plane_view* plane) {
-    if (!plane) return {c->sum_q32, c->max_bits, nullptr, 0, 1.0f, 0.0f};
-    return {c->sum_q32, c->max_bits, plane->d_values, plane->row_pitch_bytes, plane->scale, plane->bias};
+    if (!plane) return {c->sum_q32.get(), c->max_bits.get(), nullptr, 0, 1.0f, 0.0f};
+    return {c->sum_q32.get(), c->max_bits.get(), plane->d_values, plane->row_pitch_bytes, plane->scale, plane->bias};
 }
 
 // The bracket of a launch over the prepared frame: the timers' begin before it; behind it, with its status, the mark and the
@@ -2250,16 +2068,11 @@ static int base_plane(ws_renderer* r, float* d_base, size_t pitch, float4** base
         *base_pitch = pitch;
         return WS_OK;
     }
-    const size_t px = (size_t)r->vw * r->vh;
-    if (px > r->removal_base_px) {
-        // (an earlier call's launches may still read the plane, on any stream: as the frame scratch, it is replaced behind a device sync)
+    if (!r->scratch.removal_base.get()) {  // (one viewport per scratch: the plane is freed with it)
         WS_HIP(hipDeviceSynchronize());
-        dfree(r->removal_base);
-        r->removal_base_px = 0;
-        WS_TRY(dmalloc(&r->removal_base, px));
-        r->removal_base_px = px;
+        WS_TRY(r->scratch.removal_base.alloc(r->scratch.layout.removal_base));
     }
-    *base = r->removal_base;
+    *base = r->scratch.removal_base.get();
     *base_pitch = (size_t)r->vw * 16;
     return WS_OK;
 }
@@ -2303,8 +2116,8 @@ int ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, flo
         return fail(WS_ERR_INVALID, "ws_contrib_download: capacity smaller than the number of points");
     WS_HIP(hipStreamSynchronize(c->last_stream));
     int rc = WS_OK;
-    if (sum_q32) rc = copy_d2h(sum_q32, c->sum_q32, (size_t)c->num_points * sizeof(uint64_t), c->last_stream);
-    if (rc == WS_OK && max_weight) rc = copy_d2h(max_weight, c->max_bits, (size_t)c->num_points * sizeof(float), c->last_stream);
+    if (sum_q32) rc = copy_d2h(sum_q32, c->sum_q32.get(), c->sum_q32.bytes(), c->last_stream);
+    if (rc == WS_OK && max_weight) rc = copy_d2h(max_weight, c->max_bits.get(), c->max_bits.bytes(), c->last_stream);
     return rc;
 }
 
@@ -2313,20 +2126,18 @@ int ws_contrib_add(ws_contrib* c, const uint64_t* sum_q32, const float* max_weig
     if (n < c->num_points) return fail(WS_ERR_INVALID, "ws_contrib_add: fewer values than the accumulator has points");
     if (!sum_q32 && !max_weight) return WS_OK;
     const size_t np = c->num_points;
-    unsigned long long* d_sum = nullptr;
-    uint32_t* d_max = nullptr;
+    DeviceBuf<unsigned long long> d_sum;  // (both let go at the return, behind the stream sync)
+    DeviceBuf<uint32_t> d_max;
     hipStream_t stream = c->last_stream;
     int rc = WS_OK;
-    if (sum_q32) rc = dmalloc(&d_sum, np);
-    if (rc == WS_OK && max_weight) rc = dmalloc(&d_max, np);
+    if (sum_q32) rc = d_sum.alloc(np);
+    if (rc == WS_OK && max_weight) rc = d_max.alloc(np);
     hipError_t e = hipSuccess;
-    if (rc == WS_OK && sum_q32) e = hipMemcpyAsync(d_sum, sum_q32, np * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
-    if (rc == WS_OK && e == hipSuccess && max_weight) e = hipMemcpyAsync(d_max, max_weight, np * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (rc == WS_OK && sum_q32) e = hipMemcpyAsync(d_sum.get(), sum_q32, np * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
+    if (rc == WS_OK && e == hipSuccess && max_weight) e = hipMemcpyAsync(d_max.get(), max_weight, np * sizeof(float), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) rc = hip_fail(e, "ws_contrib_add: upload");
-    if (rc == WS_OK) rc = launch_contrib_merge(c->sum_q32, c->max_bits, d_sum, d_max, c->num_points, stream);
+    if (rc == WS_OK) rc = launch_contrib_merge(c->sum_q32.get(), c->max_bits.get(), d_sum.get(), d_max.get(), c->num_points, stream);
     if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_contrib_add: stream sync failed");
-    dfree(d_sum);
-    dfree(d_max);
     return rc;
 }
 
@@ -2337,50 +2148,44 @@ int ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, const
     for (uint32_t i = 0; i < n; ++i)
         if (indices[i] >= src->num_points || (i && indices[i] <= indices[i - 1]))
             return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: indices must be strictly ascending and below the number of points");
-    ws_pointcloud* pc = new (std::nothrow) ws_pointcloud(*src);  // bbox, centre, up, metadata, sh_deg, quantisation: verbatim
+    std::unique_ptr<ws_pointcloud> pc(new (std::nothrow) ws_pointcloud());
     if (!pc) return fail(WS_ERR_OOM, "ws_pointcloud_create_subset: host allocation failed");
+    static_cast<PointCloudMeta&>(*pc) = *src;  // bbox, centre, up, metadata, sh_deg, quantisation: verbatim
     pc->ctx = ctx;
     pc->num_points = n;
-    pc->planes = nullptr;
-    pc->gaussians_c = pc->sh_bytes = pc->covars = nullptr;
     // upload, gather and the codebook copies run on a private stream and are waited for (as ws_pointcloud_create_from_ply_rows)
-    uint32_t* d_idx = nullptr;
+    DeviceBuf<uint32_t> d_idx;  // (let go at the return, behind the stream sync)
     hipStream_t ls = nullptr;
-    int rc = dmalloc(&d_idx, n);
+    const char* what = "ws_pointcloud_create_subset: allocation / copy";
+    int rc = d_idx.alloc(n);
     hipError_t e = hipSuccess;
     if (rc == WS_OK) e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
-    if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(d_idx, indices, (size_t)n * 4, hipMemcpyHostToDevice, ls);
+    if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(d_idx.get(), indices, (size_t)n * 4, hipMemcpyHostToDevice, ls);
     if (rc == WS_OK && e == hipSuccess) {
         if (!src->compressed) {
-            pc->device_bytes = (size_t)n * PC_PLANES * 16;
-            e = hipMalloc(reinterpret_cast<void**>(&pc->planes), pc->device_bytes);
-            if (e == hipSuccess)
-                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->planes), reinterpret_cast<uint32_t*>(pc->planes), d_idx,
+            rc = alloc_as(pc->planes.alloc((size_t)n * PC_PLANES), what);
+            if (rc == WS_OK)
+                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->planes.get()), reinterpret_cast<uint32_t*>(pc->planes.get()), d_idx.get(),
                                       src->num_points, n, PC_PLANES, 4, ls);
         } else {
-            pc->device_bytes = (size_t)n * 24 + src->sh_bytes_size + src->covars_size;
-            e = hipMalloc(reinterpret_cast<void**>(&pc->gaussians_c), (size_t)n * 24);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->sh_bytes), src->sh_bytes_size + 16);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&pc->covars), src->covars_size ? src->covars_size : 1);
-            if (e == hipSuccess) e = hipMemcpyAsync(pc->sh_bytes, src->sh_bytes, src->sh_bytes_size + 16, hipMemcpyDeviceToDevice, ls);
-            if (e == hipSuccess && src->covars_size) e = hipMemcpyAsync(pc->covars, src->covars, src->covars_size, hipMemcpyDeviceToDevice, ls);
-            if (e == hipSuccess)
-                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->gaussians_c), reinterpret_cast<uint32_t*>(pc->gaussians_c), d_idx,
+            rc = alloc_as(pc->gaussians_c.alloc((size_t)n * 24), what);
+            if (rc == WS_OK) rc = alloc_as(pc->sh_bytes.alloc(src->sh_bytes.count()), what);
+            if (rc == WS_OK) rc = alloc_as(pc->covars.alloc(src->covars.count()), what);
+            if (rc == WS_OK) e = hipMemcpyAsync(pc->sh_bytes.get(), src->sh_bytes.get(), src->sh_bytes.bytes(), hipMemcpyDeviceToDevice, ls);
+            if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(pc->covars.get(), src->covars.get(), src->covars.bytes(), hipMemcpyDeviceToDevice, ls);
+            if (rc == WS_OK && e == hipSuccess)
+                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->gaussians_c.get()), reinterpret_cast<uint32_t*>(pc->gaussians_c.get()), d_idx.get(),
                                       src->num_points, n, 1, 6, ls);
         }
     }
-    if (e != hipSuccess && rc == WS_OK) rc = hip_fail(e, "ws_pointcloud_create_subset: allocation / copy");
+    if (e != hipSuccess && rc == WS_OK) rc = hip_fail(e, what);
     if (ls) {
         const hipError_t se = hipStreamSynchronize(ls);
         if (se != hipSuccess && rc == WS_OK) rc = hip_fail(se, "ws_pointcloud_create_subset: gather");
         (void)hipStreamDestroy(ls);
     }
-    dfree(d_idx);
-    if (rc != WS_OK) {
-        ws_pointcloud_destroy(pc);
-        return rc;
-    }
-    *out = pc;
+    if (rc) return rc;
+    *out = pc.release();
     return WS_OK;
 }
 
@@ -2391,9 +2196,8 @@ struct ws_metrics {
     ws_context* ctx = nullptr;
     uint32_t max_images = 0;
     uint32_t count = 0;                  // records added (host counter)
-    MetricsRecord* records = nullptr;    // [max_images]
-    MetricsPartial* slab = nullptr;      // one partial record per workgroup of the add in flight; shared by the adds of one stream
-    uint32_t slab_tiles = 0;
+    DeviceBuf<MetricsRecord> records;    // [max_images]
+    DeviceBuf<MetricsPartial> slab;      // one partial record per workgroup of the add in flight; shared by the adds of one stream
     hipStream_t last_stream = nullptr;
 };
 
@@ -2434,7 +2238,7 @@ int ws_metrics_create(ws_context* ctx, uint32_t max_images, ws_metrics** out) {
     if (!m) return fail(WS_ERR_OOM, "ws_metrics_create: host allocation failed");
     m->ctx = ctx;
     m->max_images = max_images;
-    const int rc = dmalloc(&m->records, max_images);
+    const int rc = m->records.alloc(max_images);
     if (rc != WS_OK) {
         delete m;
         return rc;
@@ -2443,13 +2247,7 @@ int ws_metrics_create(ws_context* ctx, uint32_t max_images, ws_metrics** out) {
     return WS_OK;
 }
 
-void ws_metrics_destroy(ws_metrics* m) {
-    if (!m) return;
-    (void)hipDeviceSynchronize();
-    dfree(m->records);
-    dfree(m->slab);
-    delete m;
-}
+void ws_metrics_destroy(ws_metrics* m) { SyncedDelete()(m); }
 
 int ws_metrics_reset(ws_metrics* m, void* stream_v) {
     if (!m) return fail(WS_ERR_INVALID, "ws_metrics_reset: null accumulator");
@@ -2476,19 +2274,15 @@ int ws_metrics_add(ws_metrics* m, const ws_image_view* a, const ws_image_view* b
     if (m->count >= m->max_images) return fail(WS_ERR_OVERFLOW, "ws_metrics_add: the accumulator is full");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const uint32_t tiles = metrics_num_tiles(width, height);
-    if (tiles > m->slab_tiles) {  // (hipFree waits for the adds that still use the old slab)
-        dfree(m->slab);
-        m->slab_tiles = 0;
-        if ((rc = dmalloc(&m->slab, tiles))) return rc;
-        m->slab_tiles = tiles;
-    }
+    // (alloc frees the old slab first, and hipFree waits for the adds that still use it)
+    if (tiles > m->slab.count() && (rc = m->slab.alloc(tiles))) return rc;
     p.width = width;
     p.height = height;
     p.flags = flags;
     p.map = d_ssim_map;
     p.map_pitch = map_pitch_bytes;
-    p.slab = m->slab;
-    if ((rc = launch_image_metrics(p, m->records + m->count, stream))) return rc;
+    p.slab = m->slab.get();
+    if ((rc = launch_image_metrics(p, m->records.get() + m->count, stream))) return rc;
     ++m->count;
     m->last_stream = stream;
     return WS_OK;
@@ -2531,7 +2325,7 @@ int ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out,
         return fail(WS_ERR_OOM, "ws_metrics_download: host allocation failed");
     }
     WS_HIP(hipStreamSynchronize(m->last_stream));
-    const int rc = copy_d2h(recs.data(), m->records, (size_t)m->count * sizeof(MetricsRecord), m->last_stream);
+    const int rc = copy_d2h(recs.data(), m->records.get(), (size_t)m->count * sizeof(MetricsRecord), m->last_stream);
     if (rc) return rc;
     for (uint32_t i = 0; i < m->count; ++i) {
         const MetricsRecord& r = recs[i];
@@ -2555,7 +2349,7 @@ int ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out,
 struct ws_grad {
     ws_context* ctx = nullptr;
     uint32_t num_points = 0;
-    unsigned long long* sums = nullptr;  // [num_points][WS_GRAD_CHANNELS] two's-complement q32 sums
+    DeviceBuf<unsigned long long> sums;  // [num_points][WS_GRAD_CHANNELS] two's-complement q32 sums
     uint32_t frames = 0;
     hipStream_t last_stream = nullptr;
 };
@@ -2567,32 +2361,23 @@ int ws_grad_create(ws_context* ctx, uint32_t num_points, ws_grad** out) {
     if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_grad_create: null argument");
     *out = nullptr;
     if (num_points == 0) return fail(WS_ERR_INVALID, "ws_grad_create: no points");
-    ws_grad* g = new (std::nothrow) ws_grad();
+    std::unique_ptr<ws_grad, SyncedDelete> g(new (std::nothrow) ws_grad());
     if (!g) return fail(WS_ERR_OOM, "ws_grad_create: host allocation failed");
     g->ctx = ctx;
     g->num_points = num_points;
-    int rc = dmalloc(&g->sums, (size_t)num_points * GRAD_CHANNELS);
-    if (rc == WS_OK) rc = ws_grad_reset(g, nullptr);
-    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_grad_create: device sync failed");
-    if (rc != WS_OK) {
-        ws_grad_destroy(g);
-        return rc;
-    }
-    *out = g;
+    WS_TRY(g->sums.alloc((size_t)num_points * GRAD_CHANNELS));
+    WS_TRY(ws_grad_reset(g.get(), nullptr));
+    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_grad_create: device sync failed");
+    *out = g.release();
     return WS_OK;
 }
 
-void ws_grad_destroy(ws_grad* g) {
-    if (!g) return;
-    (void)hipDeviceSynchronize();
-    dfree(g->sums);
-    delete g;
-}
+void ws_grad_destroy(ws_grad* g) { SyncedDelete()(g); }
 
 int ws_grad_reset(ws_grad* g, void* stream_v) {
     if (!g) return fail(WS_ERR_INVALID, "ws_grad_reset: null accumulator");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    WS_HIP(hipMemsetAsync(g->sums, 0, (size_t)g->num_points * GRAD_CHANNELS * sizeof(unsigned long long), stream));
+    WS_HIP(hipMemsetAsync(g->sums.get(), 0, g->sums.bytes(), stream));
     g->frames = 0;
     g->last_stream = stream;
     return WS_OK;
@@ -2606,24 +2391,23 @@ int ws_grad_download(ws_grad* g, uint32_t capacity, int64_t* q32) {
     if (q32 && capacity < g->num_points) return fail(WS_ERR_INVALID, "ws_grad_download: capacity smaller than the number of points");
     WS_HIP(hipStreamSynchronize(g->last_stream));
     if (!q32) return WS_OK;
-    return copy_d2h(q32, g->sums, (size_t)g->num_points * GRAD_CHANNELS * sizeof(int64_t), g->last_stream);
+    return copy_d2h(q32, g->sums.get(), g->sums.bytes(), g->last_stream);
 }
 
 int ws_grad_add(ws_grad* g, const int64_t* q32, uint32_t n) {
     if (!g) return fail(WS_ERR_INVALID, "ws_grad_add: null accumulator");
     if (n < g->num_points) return fail(WS_ERR_INVALID, "ws_grad_add: fewer values than the accumulator has points");
     if (!q32) return WS_OK;
-    const size_t words = (size_t)g->num_points * GRAD_CHANNELS;
-    unsigned long long* d_other = nullptr;
+    const size_t words = g->sums.count();
+    DeviceBuf<unsigned long long> d_other;  // (let go at the return, behind the stream sync)
     hipStream_t stream = g->last_stream;
-    int rc = dmalloc(&d_other, words);
+    int rc = d_other.alloc(words);
     if (rc == WS_OK) {
-        const hipError_t e = hipMemcpyAsync(d_other, q32, words * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+        const hipError_t e = hipMemcpyAsync(d_other.get(), q32, words * sizeof(int64_t), hipMemcpyHostToDevice, stream);
         if (e != hipSuccess) rc = hip_fail(e, "ws_grad_add: upload");
     }
-    if (rc == WS_OK) rc = launch_grad_merge(g->sums, d_other, words, stream);
+    if (rc == WS_OK) rc = launch_grad_merge(g->sums.get(), d_other.get(), words, stream);
     if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_grad_add: stream sync failed");
-    dfree(d_other);
     return rc;
 }
 
@@ -2670,7 +2454,7 @@ int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad
     gp.grad_pitch = p->grad_pitch_bytes;
     gp.scale = p->scale;
     gp.opacity_scale = p->opacity_scale;
-    gp.sums = g->sums;
+    gp.sums = g->sums.get();
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     KernelMarks* km = launch_begin(r, stream);
     int rc = (passes & 1u) ? launch_removal_base(rp, stream) : WS_OK;
@@ -2716,7 +2500,7 @@ struct ws_refit {
     const ws_pointcloud* pc = nullptr;   // the cloud the masters were widened from: the only one a step accepts
     const uint4* planes = nullptr;       // (and its planes: a later cloud at the same address is another cloud)
     uint32_t num_points = 0;
-    float4 *master = nullptr, *m = nullptr, *v = nullptr;
+    DeviceBuf<float4> master, m, v;      // [num_points] each
     uint32_t steps = 0;
     double p1 = 1.0, p2 = 1.0;           // beta1^steps, beta2^steps
     hipStream_t last_stream = nullptr;
@@ -2748,33 +2532,22 @@ int ws_refit_create(ws_context* ctx, const ws_pointcloud* pc, ws_refit** out) {
     *out = nullptr;
     if (pc->compressed)
         return fail(WS_ERR_UNSUPPORTED, "ws_refit_create: a compressed cloud cannot be refitted (its codebooks are shared between Gaussians)");
-    ws_refit* rf = new (std::nothrow) ws_refit();
+    std::unique_ptr<ws_refit, SyncedDelete> rf(new (std::nothrow) ws_refit());
     if (!rf) return fail(WS_ERR_OOM, "ws_refit_create: host allocation failed");
     rf->ctx = ctx;
     rf->pc = pc;
-    rf->planes = pc->planes;
+    rf->planes = pc->planes.get();
     rf->num_points = pc->num_points;
-    int rc = dmalloc(&rf->master, (size_t)rf->num_points);
-    if (rc == WS_OK) rc = dmalloc(&rf->m, (size_t)rf->num_points);
-    if (rc == WS_OK) rc = dmalloc(&rf->v, (size_t)rf->num_points);
-    if (rc == WS_OK) rc = launch_refit_init(pc->planes, rf->num_points, rf->master, rf->m, rf->v, nullptr);
-    if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_refit_create: device sync failed");
-    if (rc != WS_OK) {
-        ws_refit_destroy(rf);
-        return rc;
-    }
-    *out = rf;
+    WS_TRY(rf->master.alloc(rf->num_points));
+    WS_TRY(rf->m.alloc(rf->num_points));
+    WS_TRY(rf->v.alloc(rf->num_points));
+    WS_TRY(launch_refit_init(rf->planes, rf->num_points, rf->master.get(), rf->m.get(), rf->v.get(), nullptr));
+    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_refit_create: device sync failed");
+    *out = rf.release();
     return WS_OK;
 }
 
-void ws_refit_destroy(ws_refit* rf) {
-    if (!rf) return;
-    (void)hipDeviceSynchronize();
-    dfree(rf->master);
-    dfree(rf->m);
-    dfree(rf->v);
-    delete rf;
-}
+void ws_refit_destroy(ws_refit* rf) { SyncedDelete()(rf); }
 
 uint32_t ws_refit_num_points(const ws_refit* rf) { return rf ? rf->num_points : 0u; }
 uint32_t ws_refit_steps(const ws_refit* rf) { return rf ? rf->steps : 0u; }
@@ -2785,16 +2558,16 @@ int ws_refit_step(ws_refit* rf, ws_pointcloud* pc, const ws_grad* g, const ws_re
     const std::string who("ws_refit_step");
     if (const int rc = ws_internal_refit_check_params(p, who, true)) return rc;
     if (!rf || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (pc != rf->pc || pc->planes != rf->planes || pc->compressed || pc->num_points != rf->num_points)
+    if (pc != rf->pc || pc->planes.get() != rf->planes || pc->compressed || pc->num_points != rf->num_points)
         return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
     if (g->num_points != rf->num_points) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another number of points");
     const double p1 = rf->p1 * (double)p->beta1, p2 = rf->p2 * (double)p->beta2;
     RefitParams kp;
-    kp.planes = pc->planes;
-    kp.sums = g->sums;
-    kp.master = rf->master;
-    kp.m = rf->m;
-    kp.v = rf->v;
+    kp.planes = pc->planes.get();
+    kp.sums = g->sums.get();
+    kp.master = rf->master.get();
+    kp.m = rf->m.get();
+    kp.v = rf->v.get();
     kp.n = rf->num_points;
     kp.lr_colour = p->lr_colour;
     kp.lr_opacity = p->lr_opacity;
@@ -2821,10 +2594,9 @@ int ws_refit_download(ws_refit* rf, uint32_t capacity, float* master, float* m, 
     if (!rf) return fail(WS_ERR_INVALID, "ws_refit_download: null object");
     if ((master || m || v) && capacity < rf->num_points) return fail(WS_ERR_INVALID, "ws_refit_download: capacity smaller than the number of points");
     WS_HIP(hipStreamSynchronize(rf->last_stream));
-    const size_t bytes = (size_t)rf->num_points * sizeof(float4);
-    if (master) WS_TRY(copy_d2h(master, rf->master, bytes, rf->last_stream));
-    if (m) WS_TRY(copy_d2h(m, rf->m, bytes, rf->last_stream));
-    if (v) WS_TRY(copy_d2h(v, rf->v, bytes, rf->last_stream));
+    if (master) WS_TRY(copy_d2h(master, rf->master.get(), rf->master.bytes(), rf->last_stream));
+    if (m) WS_TRY(copy_d2h(m, rf->m.get(), rf->m.bytes(), rf->last_stream));
+    if (v) WS_TRY(copy_d2h(v, rf->v.get(), rf->v.bytes(), rf->last_stream));
     return WS_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "blend_form.h"
+#include "device_buf.h"
 #include "frame_plan.h"
 #include "websplat.h"
 
@@ -273,6 +274,8 @@ inline void km_mark(KernelMarks* km, const char* what) {
 
 // ---- sort (tile sizes and digit widths: frame_plan.h) -------------------------------------------
 
+// What a sort launch works in: a view, owning nothing -- of a renderer's FrameScratch or of a ws_sorter's buffers (sized by
+// frame_scratch.h sort_shape)
 struct SortScratch {
     uint32_t* keys_alt = nullptr;     // ping-pong partner of the caller's key buffer   [cap]
     uint32_t* vals_alt = nullptr;     // ping-pong partner of the caller's value buffer [cap]
@@ -347,12 +350,12 @@ int launch_tile_sort_wide(const SortScratch& sc, const uint32_t* keys16, const u
 // *res: the caller's arrays, nothing skipped.
 constexpr uint32_t FAT_MAX_GRID = 256;
 constexpr uint32_t FAT_CHUNK_MAX = 1024u * 8u;
-struct FatSortScratch {
+struct FatSortScratch {  // (a view, as SortScratch)
     uint32_t* keys_alt = nullptr;   // [cap] ping-pong partners
     uint32_t* vals_alt = nullptr;
     uint32_t* aux_alt = nullptr;
     uint32_t* hist = nullptr;       // [4][256] digit totals, zero on entry
-    uint64_t* status = nullptr;     // [4][FAT_MAX_GRID][256] epoch-tagged chunk counts (zeroed once)
+    uint64_t* status = nullptr;     // [4][FAT_MAX_GRID][256] epoch-tagged chunk counts (zeroed when allocated and when the epoch wraps)
     uint32_t* tickets = nullptr;    // [4] chunk dispensers, zero on entry
     uint32_t* barrier = nullptr;    // 9 x 16 words, zero on entry (coop)
     const uint32_t* d_epoch = nullptr;  // != nullptr: the epoch is read from device memory (a captured frame graph replays)
@@ -589,7 +592,8 @@ struct ws_context {
     std::atomic<uint32_t> same_stream_run{0};
 };
 
-struct ws_pointcloud {
+// What a point cloud is, without its device memory: ws_pointcloud_create_subset copies this part and allocates its own buffers
+struct PointCloudMeta {
     ws_context* ctx = nullptr;
     uint32_t num_points = 0;
     uint32_t sh_deg = 0;
@@ -604,11 +608,10 @@ struct ws_pointcloud {
     bool has_background = false;
     float background[3] = {0, 0, 0};
     ws_gaussian_quantization quant{};
-    // device memory
-    uint4* planes = nullptr;         // uncompressed
-    uint8_t* gaussians_c = nullptr;  // compressed
-    uint8_t* sh_bytes = nullptr;
-    uint8_t* covars = nullptr;
-    size_t sh_bytes_size = 0, covars_size = 0;  // compressed: bytes of the two codebooks (ws_pointcloud_create_subset copies them whole)
-    size_t device_bytes = 0;
+};
+struct ws_pointcloud : PointCloudMeta {
+    ws::DeviceBuf<uint4> planes;          // uncompressed
+    ws::DeviceBuf<uint8_t> gaussians_c;   // compressed: 24-B records
+    ws::DeviceBuf<uint8_t> sh_bytes;      //   the packed SH codebook and 16 B of padding
+    ws::DeviceBuf<uint8_t> covars;        //   the covariance codebook
 };
