@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import lib, check
+from .devmem import DeviceArray, ViewportPlanes, staged
 
 FORMATS = {
     "rgba8unorm": (L.WS_FORMAT_RGBA8_UNORM, np.uint8, 4),
@@ -262,9 +263,10 @@ class Context:
     def free(self, ptr: int):
         check(lib.ws_device_free(self.handle, C.c_void_p(ptr)))
 
-    def upload(self, ptr: int, arr: np.ndarray):
+    def upload(self, ptr: int, arr: np.ndarray, stream=None):
         arr = np.ascontiguousarray(arr)
-        check(lib.ws_memcpy_h2d(self.handle, C.c_void_p(ptr), arr.ctypes.data_as(C.c_void_p), arr.nbytes, None))
+        check(lib.ws_memcpy_h2d(self.handle, C.c_void_p(ptr), arr.ctypes.data_as(C.c_void_p), arr.nbytes,
+                                C.c_void_p(stream or 0)))
 
     def download(self, ptr: int, shape, dtype) -> np.ndarray:
         out = np.empty(shape, dtype=dtype)
@@ -786,23 +788,22 @@ class Metrics:
         check(lib.ws_metrics_create(ctx.handle, int(max_images), C.byref(h)))
         self.handle = h
         self.max_images = int(max_images)
-        self._maps = []  # (device plane, width, height) of the adds that asked for the SSIM map, in add order
+        self._maps = []  # DeviceArray (H x W float32) of the adds that asked for the SSIM map, in add order
 
-    def _free_maps(self):
-        for ptr, _, _ in self._maps:
-            self.ctx.free(ptr)
-        self._maps = []
+    def _drop_maps(self):
+        while self._maps:
+            self._maps.pop().free()
 
     def close(self):
         if self.handle:
             lib.ws_metrics_destroy(self.handle)  # (waits for the device)
             self.handle = None
-            self._free_maps()
+            self._drop_maps()
 
     def reset(self, stream=None):
         check(lib.ws_metrics_reset(self.handle, C.c_void_p(stream or 0)))
         self.ctx.sync(stream)
-        self._free_maps()
+        self._drop_maps()
 
     @property
     def count(self) -> int:
@@ -813,19 +814,17 @@ class Metrics:
         """Enqueue the comparison of views a and b (ImageView, or (ptr, format, pitch, background-or-None) tuples).  ssim_map:
         also keep the W x H map, returned by maps()."""
         va, vb = _as_view(a).to_c(), _as_view(b).to_c()
-        d_map, pitch = None, 0
-        if ssim_map:
-            d_map, pitch = self.ctx.malloc(int(width) * int(height) * 4), int(width) * 4
+        m = DeviceArray(self.ctx, (height, width), np.float32) if ssim_map else None
         try:
             check(lib.ws_metrics_add(self.handle, C.byref(va), C.byref(vb), int(width), int(height),
-                                     L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, C.c_void_p(d_map or 0), pitch,
-                                     C.c_void_p(stream or 0)))
+                                     L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, C.c_void_p(m.ptr if m else 0),
+                                     m.pitch if m else 0, C.c_void_p(stream or 0)))
         except Exception:
-            if d_map:
-                self.ctx.free(d_map)
+            if m:
+                m.free()
             raise
-        if d_map:
-            self._maps.append((d_map, int(width), int(height)))
+        if m:
+            self._maps.append(m)
 
     def download(self):
         """One dict per image pair, in add order: mse, psnr, ssim, sse_u8, width, height, flags (syncs)."""
@@ -837,36 +836,48 @@ class Metrics:
 
     def maps(self):
         """The SSIM maps (H x W float32) of the adds that asked for one, in add order (call after download(), which syncs)."""
-        return [self.ctx.download(ptr, (h, w), np.float32) for ptr, w, h in self._maps]
+        return [m.download() for m in self._maps]
 
 
 _NP_FORMATS = {np.dtype(np.uint8): "rgba8unorm", np.dtype(np.float16): "rgba16float", np.dtype(np.float32): "rgba32float"}
+
+
+def _upload_pair(ctx: Context, who: str, img_a, img_b, background_a, background_b):
+    """(the two images as DeviceArrays, their ImageViews, w, h) of `who`'s two H x W x 4 numpy images; the caller frees the
+    arrays once the device is done with them."""
+    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
+    for im in imgs:
+        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
+            raise ValueError(f"{who}: two H x W x 4 arrays of one size, uint8 / float16 / float32")
+    arrays = []
+    try:
+        for im in imgs:
+            arrays.append(DeviceArray.from_host(ctx, im))
+    except Exception:
+        for a in arrays:
+            a.free()
+        raise
+    views = [ImageView(a.ptr, _NP_FORMATS[a.dtype], a.pitch, bg) for a, bg in zip(arrays, (background_a, background_b))]
+    h, w = imgs[0].shape[:2]
+    return arrays, views, w, h
 
 
 def image_metrics(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, background_a=None, background_b=None, quantize_u8=False,
                   ssim_map=False):
     """PSNR / SSIM of two H x W x 4 numpy images (uint8, float16 or float32, each its own format): upload, add, download.
     Returns the record's dict, or (dict, H x W float32 map) with ssim_map."""
-    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
-    for im in imgs:
-        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
-            raise ValueError("image_metrics: two H x W x 4 arrays of one size, uint8 / float16 / float32")
-    h, w = imgs[0].shape[:2]
-    ptrs = []
-    m = Metrics(ctx, 1)
+    arrays, views, w, h = _upload_pair(ctx, "image_metrics", img_a, img_b, background_a, background_b)
+    m = None
     try:
-        views = []
-        for im, bg in zip(imgs, (background_a, background_b)):
-            ptrs.append(ctx.malloc(im.nbytes))
-            ctx.upload(ptrs[-1], im)
-            views.append(ImageView(ptrs[-1], _NP_FORMATS[im.dtype], w * im.itemsize * 4, bg))
+        m = Metrics(ctx, 1)
         m.add(views[0], views[1], w, h, quantize_u8=quantize_u8, ssim_map=ssim_map)
         rec = m.download()[0]
         return (rec, m.maps()[0]) if ssim_map else rec
     finally:
-        m.close()
-        for p in ptrs:
-            ctx.free(p)
+        if m:
+            m.close()
+        for a in arrays:
+            a.free()
 
 
 def read_png(path: str) -> np.ndarray:
@@ -899,51 +910,35 @@ def image_error_plane(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, kind="
     """The per-pixel error plane (H x W float32) of two H x W x 4 numpy images (uint8, float16 or float32, each its own format):
     the mean over the colour channels of d * d ("sq") or |d| ("abs") on the pixel values of image_metrics
     (ws_image_error_plane): upload, one launch, download."""
-    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
-    for im in imgs:
-        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
-            raise ValueError("image_error_plane: two H x W x 4 arrays of one size, uint8 / float16 / float32")
-    h, w = imgs[0].shape[:2]
-    ptrs = []
+    arrays, views, w, h = _upload_pair(ctx, "image_error_plane", img_a, img_b, background_a, background_b)
     try:
-        views = []
-        for im, bg in zip(imgs, (background_a, background_b)):
-            ptrs.append(ctx.malloc(im.nbytes))
-            ctx.upload(ptrs[-1], im)
-            views.append(ImageView(ptrs[-1], _NP_FORMATS[im.dtype], w * im.itemsize * 4, bg).to_c())
-        ptrs.append(ctx.malloc(w * h * 4))
-        check(lib.ws_image_error_plane(ctx.handle, C.byref(views[0]), C.byref(views[1]), w, h, ERROR_KINDS[kind],
-                                       L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, C.c_void_p(ptrs[-1]), w * 4, None))
-        return ctx.download(ptrs[-1], (h, w), np.float32)
+        va, vb = views[0].to_c(), views[1].to_c()
+        out = DeviceArray(ctx, (h, w), np.float32)
+        arrays.append(out)
+        check(lib.ws_image_error_plane(ctx.handle, C.byref(va), C.byref(vb), w, h, ERROR_KINDS[kind],
+                                       L.WS_METRICS_QUANTIZE_U8 if quantize_u8 else 0, C.c_void_p(out.ptr), out.pitch, None))
+        return out.download()
     finally:
         ctx.sync()
-        for p in ptrs:
-            ctx.free(p)
+        for a in arrays:
+            a.free()
 
 
 def image_error_gradient(ctx: Context, img_a: np.ndarray, img_b: np.ndarray, kind="sq", background_a=None, background_b=None) -> np.ndarray:
     """The derivative of image_error_plane's value with respect to image a's pixel values (H x W x 4 float32, the fourth
     component 0; ws_image_error_gradient) of two H x W x 4 numpy images: upload, one launch, download."""
-    imgs = [np.ascontiguousarray(im) for im in (img_a, img_b)]
-    for im in imgs:
-        if im.ndim != 3 or im.shape[2] != 4 or im.dtype not in _NP_FORMATS or im.shape != imgs[0].shape:
-            raise ValueError("image_error_gradient: two H x W x 4 arrays of one size, uint8 / float16 / float32")
-    h, w = imgs[0].shape[:2]
-    ptrs = []
+    arrays, views, w, h = _upload_pair(ctx, "image_error_gradient", img_a, img_b, background_a, background_b)
     try:
-        views = []
-        for im, bg in zip(imgs, (background_a, background_b)):
-            ptrs.append(ctx.malloc(im.nbytes))
-            ctx.upload(ptrs[-1], im)
-            views.append(ImageView(ptrs[-1], _NP_FORMATS[im.dtype], w * im.itemsize * 4, bg).to_c())
-        ptrs.append(ctx.malloc(w * h * 16))
-        check(lib.ws_image_error_gradient(ctx.handle, C.byref(views[0]), C.byref(views[1]), w, h, ERROR_KINDS[kind], 0,
-                                          C.c_void_p(ptrs[-1]), w * 16, None))
-        return ctx.download(ptrs[-1], (h, w, 4), np.float32)
+        va, vb = views[0].to_c(), views[1].to_c()
+        out = DeviceArray(ctx, (h, w, 4), np.float32)
+        arrays.append(out)
+        check(lib.ws_image_error_gradient(ctx.handle, C.byref(va), C.byref(vb), w, h, ERROR_KINDS[kind], 0,
+                                          C.c_void_p(out.ptr), out.pitch, None))
+        return out.download()
     finally:
         ctx.sync()
-        for p in ptrs:
-            ctx.free(p)
+        for a in arrays:
+            a.free()
 
 
 def accumulate_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, grad: "Grad", ref: "PointCloud" = None,
@@ -1001,36 +996,39 @@ class GaussianRenderer:
     read-back helpers (num_visible_points, frame_stats, stage_times, download_*)."""
 
     def __init__(self, ctx: Context, color_format: str = "rgba32float", sh_deg: int = 3, compressed: bool = False):
-        self.ctx = ctx
-        self.color_format_name = color_format
-        fmt, self.np_dtype, self.texel_bytes = FORMATS[color_format]
         h = C.c_void_p()
-        check(lib.ws_renderer_create(ctx.handle, fmt, int(sh_deg), int(compressed), C.byref(h)))
-        self.handle = h
-        self._own_target = None
-        self._own_target_shape = None
-        self._aux = {}            # plane name -> renderer-owned device buffer (H x W f32) of render_aux
-        self._aux_shape = None
-        self._aux_last = ()       # the planes the last render_aux wrote
-        self._occluder = None     # renderer-owned device copy (H x W f32) of render_composite's numpy occluder
-        self._occluder_shape = None
-        self._val = {}            # plane index 0..3 / "winner" -> renderer-owned device buffer (H x W, 4 B) of render_values
-        self._val_shape = None
-        self._val_last = (0, False)  # (channels, winner) the last render_values wrote
-        self._rm_base = None      # renderer-owned device buffer (H x W float4) of accumulate_removal(base=True)
-        self._rm_base_shape = None
+        check(lib.ws_renderer_create(ctx.handle, FORMATS[color_format][0], int(sh_deg), int(compressed), C.byref(h)))
+        self._set_state(ctx, h, color_format, owns_handle=True)
+
+    @classmethod
+    def _view(cls, ctx: Context, handle, color_format: str):
+        """A renderer object on a handle somebody else owns (ViewBatch.renderer): close() frees its planes, not the handle."""
+        r = cls.__new__(cls)
+        r._set_state(ctx, handle, color_format, owns_handle=False)
+        return r
+
+    def _set_state(self, ctx, handle, color_format, owns_handle):
+        self.ctx = ctx
+        self.handle = handle
+        self._owns_handle = owns_handle
+        self.color_format_name = color_format
+        _, self.np_dtype, self.texel_bytes = FORMATS[color_format]
+        self._viewport = (0, 0)   # of the last prepare(); (0, 0): not prepared -- the library says so
+        # renderer-owned planes, one set per group: each is let go when ITS next use sees another viewport
+        self._target = ViewportPlanes(ctx)    # "target": H x W x 4 of the colour format
+        self._aux = ViewportPlanes(ctx)       # plane name -> H x W f32 of render_aux / render_composite
+        self._aux_last = ()                   # the planes the last render_aux wrote
+        self._val = ViewportPlanes(ctx)       # 0..3 -> H x W f32, "winner" -> H x W u32 of render_values
+        self._val_last = (0, False)           # (channels, winner) the last render_values wrote
+        self._base = ViewportPlanes(ctx)      # "base": H x W float4 of accumulate_removal / _gradient(base=True)
+        self._occluder = ViewportPlanes(ctx)  # "occluder": H x W f32 copy of render_composite's numpy occluder
 
     def close(self):
-        self._free_aux()
-        self._free_values()
-        self._free_removal_base()
-        self._free_occluder()
-        if self._own_target:
-            self.ctx.free(self._own_target)
-            self._own_target = None
-        if self.handle:
+        for planes in (self._aux, self._val, self._base, self._occluder, self._target):
+            planes.free()
+        if self.handle and self._owns_handle:
             lib.ws_renderer_destroy(self.handle)
-            self.handle = None
+        self.handle = None
 
     def color_format(self):
         return self.color_format_name
@@ -1148,19 +1146,18 @@ class GaussianRenderer:
 
     def render(self, pc: PointCloud, target_ptr: int = None, pitch: int = None, background=(0.0, 0.0, 0.0, 0.0),
                stream=None):
-        w, h = self._viewport
         if target_ptr is None:
-            if self._own_target_shape != (w, h):
-                if self._own_target:
-                    self.ctx.free(self._own_target)
-                self._own_target = self.ctx.malloc(w * h * self.texel_bytes)
-                self._own_target_shape = (w, h)
-            target_ptr = self._own_target
+            target_ptr = self._own_target().ptr
         if pitch is None:
-            pitch = w * self.texel_bytes
+            pitch = self._viewport[0] * self.texel_bytes
         bg = (C.c_float * 4)(*[float(x) for x in background])
         check(lib.ws_renderer_render(self.handle, pc.handle, bg, C.c_void_p(target_ptr), pitch, C.c_void_p(stream or 0)))
         return target_ptr
+
+    def _own_target(self) -> DeviceArray:
+        """The renderer-owned target (H x W x 4 of the colour format) of the prepared viewport."""
+        self._target.fit(*self._viewport)
+        return self._target.plane("target", self.np_dtype, 4)
 
     def enable_depth(self, on=True):
         """K1 also writes each visible splat's view-space depth (4 B per splat) from the next prepare() on: what the depth and
@@ -1176,25 +1173,9 @@ class GaussianRenderer:
         """Add the prepared frame's per-Gaussian weights to `contrib` (enqueues; render() is not needed)."""
         check(lib.ws_renderer_accumulate_contrib(self.handle, pc.handle, contrib.handle, C.c_void_p(stream or 0)))
 
-    @contextlib.contextmanager
-    def _staged(self, v, array, stream):
-        """For the calls of the body, v.d_values points at a device copy of `array`; behind them: wait for `stream`, free the
-        copy.  array None: v is left as it is, nothing is uploaded or waited for."""
-        if array is None:
-            yield
-            return
-        d = self.ctx.malloc(max(array.nbytes, 4))
-        try:
-            self.ctx.upload(d, array)
-            v.d_values = d
-            yield
-        finally:
-            self.ctx.sync(stream)
-            self.ctx.free(d)
-
     def _plane_view(self, who, what, plane, pitch, scale, bias, view):
         """(ws_plane_view, array to stage | None) of an H x W float32 numpy plane of the viewport `view` -- its d_values is
-        _staged()'s to set -- or of a device pointer with its row `pitch` in bytes."""
+        the caller's to set from staged() -- or of a device pointer with its row `pitch` in bytes."""
         v = L.ws_plane_view()
         v.scale, v.bias = float(scale), float(bias)
         if not isinstance(plane, np.ndarray):
@@ -1212,16 +1193,22 @@ class GaussianRenderer:
         """Add the prepared frame's per-Gaussian weights times E(p) = clamp(scale * plane[p] + bias, 0, 1) to `contrib`
         (ws_renderer_accumulate_weighted).  `plane`: an H x W float32 numpy array of the viewport's shape (uploaded for the
         call, which then waits for the launch), or a device pointer with its row `pitch` in bytes (enqueues only)."""
-        view = getattr(self, "_viewport", None)  # (None: not prepared -- the library says so)
-        v, staged = self._plane_view("accumulate_weighted", "plane", plane, pitch, scale, bias, view)
-        with self._staged(v, staged, stream):
+        v, host = self._plane_view("accumulate_weighted", "plane", plane, pitch, scale, bias, self._viewport)
+        with staged(self.ctx, host, stream) as d:
+            if d is not None:
+                v.d_values = d
             check(lib.ws_renderer_accumulate_weighted(self.handle, pc.handle, contrib.handle, C.byref(v), C.c_void_p(stream or 0)))
 
-    def _free_removal_base(self):
-        if self._rm_base:
-            self.ctx.free(self._rm_base)
-        self._rm_base = None
-        self._rm_base_shape = None
+    def _set_base(self, p, base, base_ptr, base_pitch):
+        """d_base / base_pitch_bytes of a ws_removal_params or ws_gradient_params: the caller's device plane, the
+        renderer-owned H x W float4 plane of the prepared viewport (base=True), or none."""
+        w, h = self._viewport
+        if base_ptr is not None:
+            p.d_base, p.base_pitch_bytes = int(base_ptr), int(base_pitch if base_pitch is not None else w * 16)
+        elif base:
+            self._base.fit(w, h)
+            own = self._base.plane("base", np.float32, 4)
+            p.d_base, p.base_pitch_bytes = own.ptr, own.pitch
 
     def accumulate_removal(self, pc: PointCloud, contrib: "Contrib", background=(0.0, 0.0, 0.0), kind="sq", scale=1.0, weight=None,
                            weight_scale=1.0, weight_bias=0.0, base=False, stream=None, weight_pitch=None, base_ptr=None,
@@ -1239,20 +1226,15 @@ class GaussianRenderer:
             p.background[i] = float(background[i])
         p.kind = ERROR_KINDS[kind] if isinstance(kind, str) else int(kind)
         p.scale = float(scale)
-        w, h = getattr(self, "_viewport", (0, 0))  # ((0, 0): not prepared -- the library says so)
-        if base_ptr is not None:
-            p.d_base, p.base_pitch_bytes = int(base_ptr), int(base_pitch if base_pitch is not None else w * 16)
-        elif base:
-            if self._rm_base_shape != (w, h):
-                self._free_removal_base()
-                self._rm_base = self.ctx.malloc(max(w * h * 16, 16))
-                self._rm_base_shape = (w, h)
-            p.d_base, p.base_pitch_bytes = self._rm_base, w * 16
-        v, staged = None, None
+        self._set_base(p, base, base_ptr, base_pitch)
+        v, host = None, None
         if weight is not None:
-            v, staged = self._plane_view("accumulate_removal", "weight plane", weight, weight_pitch, weight_scale, weight_bias, (w, h))
+            v, host = self._plane_view("accumulate_removal", "weight plane", weight, weight_pitch, weight_scale, weight_bias,
+                                       self._viewport)
             p.weight = C.pointer(v)
-        with self._staged(v, staged, stream):
+        with staged(self.ctx, host, stream) as d:
+            if d is not None:
+                v.d_values = d
             check(lib.ws_renderer_accumulate_removal(self.handle, pc.handle, contrib.handle, C.byref(p), C.c_void_p(stream or 0)))
 
     def accumulate_gradient(self, pc: PointCloud, grad: "Grad", plane, background=(0.0, 0.0, 0.0), scale=1.0, opacity_scale=1.0,
@@ -1266,52 +1248,31 @@ class GaussianRenderer:
         for i in range(3):
             p.background[i] = float(background[i])
         p.scale, p.opacity_scale = float(scale), float(opacity_scale)
-        w, h = getattr(self, "_viewport", (0, 0))  # ((0, 0): not prepared -- the library says so)
-        if base_ptr is not None:
-            p.d_base, p.base_pitch_bytes = int(base_ptr), int(base_pitch if base_pitch is not None else w * 16)
-        elif base:
-            if self._rm_base_shape != (w, h):
-                self._free_removal_base()
-                self._rm_base = self.ctx.malloc(max(w * h * 16, 16))
-                self._rm_base_shape = (w, h)
-            p.d_base, p.base_pitch_bytes = self._rm_base, w * 16
-        staged = None
+        w, h = self._viewport
+        self._set_base(p, base, base_ptr, base_pitch)
+        host = None
         if isinstance(plane, np.ndarray):
             a = np.ascontiguousarray(plane, dtype=np.float32)
             if a.ndim != 3 or a.shape[2] != 4 or (w and (a.shape[0] != h or a.shape[1] < w)):  # (wider rows: padding)
                 raise ValueError(f"accumulate_gradient: want an H x W x 4 float32 plane of the viewport {(w, h)}, got {a.shape}")
             p.grad_pitch_bytes = int(plane_pitch) if plane_pitch is not None else a.shape[1] * 16
-            staged = a
+            host = a
         else:
             if plane is not None and plane_pitch is None:
                 raise ValueError("accumulate_gradient: a device plane needs its row pitch")
             p.d_grad, p.grad_pitch_bytes = (int(plane) if plane is not None else None), int(plane_pitch or 0)
-        if staged is None:
+        with staged(self.ctx, host, stream, min_bytes=16) as d:
+            if d is not None:
+                p.d_grad = d
             check(lib.ws_renderer_accumulate_gradient(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
-            return
-        d = self.ctx.malloc(max(staged.nbytes, 16))
-        try:
-            self.ctx.upload(d, staged)
-            p.d_grad = d
-            check(lib.ws_renderer_accumulate_gradient(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
-        finally:
-            self.ctx.sync(stream)
-            self.ctx.free(d)
 
     def download_removal_base(self) -> np.ndarray:
         """H x W x 4 float32 (F_r, F_g, F_b, T_end) of what the last accumulate_removal(base=True) or accumulate_gradient(base=True) wrote (syncs)."""
-        if not self._rm_base:
+        base = self._base.get("base")
+        if base is None:
             raise ValueError("download_removal_base: no accumulate_removal(base=True) since the viewport changed")
-        w, h = self._rm_base_shape
         self.ctx.sync()
-        return self.ctx.download(self._rm_base, (h, w, 4), np.float32)
-
-    def _free_values(self):
-        for ptr in self._val.values():
-            self.ctx.free(ptr)
-        self._val = {}
-        self._val_shape = None
-        self._val_last = (0, False)
+        return base.download()
 
     def render_values(self, pc: PointCloud, values=None, winner=False, stream=None, stride=None, channels=None):
         """Draw per-Gaussian values through the prepared frame's weights (ws_renderer_render_values): per pixel and channel the sum
@@ -1321,11 +1282,10 @@ class GaussianRenderer:
         `values`: an (N,) or (N, C) float32 numpy array, C <= 4, over the cloud's Gaussians (uploaded for the call, which then
         waits for the launch); or a device pointer with `stride` bytes per Gaussian and `channels` (enqueues only); or None with
         winner=True.  The planes go to renderer-owned H x W buffers: download_values() reads them back."""
-        w, h = getattr(self, "_viewport", (0, 0))  # ((0, 0): not prepared -- the library says so)
-        if self._val_shape != (w, h):
-            self._free_values()
-            self._val_shape = (w, h)
-        v, staged = None, None
+        if self._val.viewport != self._viewport:
+            self._val_last = (0, False)  # (the planes it names are let go)
+        self._val.fit(*self._viewport)
+        v, host = None, None
         if isinstance(values, np.ndarray):
             a = np.ascontiguousarray(values, dtype=np.float32)
             if a.ndim == 1:
@@ -1334,7 +1294,7 @@ class GaussianRenderer:
                 raise ValueError(f"render_values: want (N,) or (N, C <= 4) float32 values, got {values.shape}")
             v = L.ws_values_view()
             v.stride_bytes, v.num_points, v.channels = a.shape[1] * 4, a.shape[0], a.shape[1]
-            staged = a
+            host = a
         elif values is not None:
             if stride is None or channels is None:
                 raise ValueError("render_values: device values need their stride in bytes and their number of channels")
@@ -1342,71 +1302,53 @@ class GaussianRenderer:
             v.d_values, v.stride_bytes, v.num_points, v.channels = int(values), int(stride), pc.num_points(), int(channels)
         nch = int(v.channels) if v is not None else 0
         t = L.ws_value_targets()
-        for key in list(range(min(nch, 4))) + (["winner"] if winner else []):
-            if key not in self._val:
-                self._val[key] = self.ctx.malloc(max(w * h * 4, 4))
         for c in range(min(nch, 4)):
-            t.plane[c], t.pitch[c] = self._val[c], w * 4
+            own = self._val.plane(c, np.float32)
+            t.plane[c], t.pitch[c] = own.ptr, own.pitch
         if winner:
-            t.winner, t.winner_pitch = self._val["winner"], w * 4
+            own = self._val.plane("winner", np.uint32)
+            t.winner, t.winner_pitch = own.ptr, own.pitch
         vref = C.byref(v) if v is not None else None
-        with self._staged(v, staged, stream):
+        with staged(self.ctx, host, stream) as d:
+            if d is not None:
+                v.d_values = d
             check(lib.ws_renderer_render_values(self.handle, pc.handle, vref, C.byref(t), C.c_void_p(stream or 0)))
         self._val_last = (nch, bool(winner))
 
     def download_values(self) -> dict:
         """{"values": H x W x C float32, "winner": H x W uint32} of what the last render_values() wrote (syncs); a key is
         absent when the call did not ask for it."""
-        w, h = self._val_shape or (0, 0)
         nch, winner = self._val_last
         self.ctx.sync()
         out = {}
         if nch:
-            out["values"] = np.stack([self.ctx.download(self._val[c], (h, w), np.float32) for c in range(nch)], axis=-1)
+            out["values"] = np.stack([self._val.get(c).download() for c in range(nch)], axis=-1)
         if winner:
-            out["winner"] = self.ctx.download(self._val["winner"], (h, w), np.uint32)
+            out["winner"] = self._val.get("winner").download()
         return out
 
-    def _free_aux(self):
-        for ptr in self._aux.values():
-            self.ctx.free(ptr)
-        self._aux = {}
-        self._aux_shape = None
+    def _aux_targets(self, depth, median_depth, alpha):
+        """(ws_aux_targets, names) of the asked-for planes among the renderer-owned H x W f32 ones of the prepared viewport."""
+        self._aux.fit(*self._viewport)
+        want = tuple(name for name, on in (("depth", depth), ("median_depth", median_depth), ("alpha", alpha)) if on)
+        t = L.ws_aux_targets()
+        for name in want:
+            own = self._aux.plane(name, np.float32)
+            setattr(t, name, C.c_void_p(own.ptr))
+            setattr(t, name + "_pitch", own.pitch)
+        return t, want
 
     def render_aux(self, pc: PointCloud, depth=True, median_depth=False, alpha=False, background=(0.0, 0.0, 0.0, 0.0),
                    stream=None):
         """render() into the renderer-owned target plus the asked-for auxiliary planes (websplat.h ws_renderer_render_aux) into
         renderer-owned H x W float32 buffers; download_aux() reads them back."""
-        w, h = self._viewport
-        if self._own_target_shape != (w, h):
-            if self._own_target:
-                self.ctx.free(self._own_target)
-            self._own_target = self.ctx.malloc(w * h * self.texel_bytes)
-            self._own_target_shape = (w, h)
-        if self._aux_shape != (w, h):
-            self._free_aux()
-            self._aux_shape = (w, h)
-        want = [name for name, on in (("depth", depth), ("median_depth", median_depth), ("alpha", alpha)) if on]
-        t = L.ws_aux_targets()
-        for name in want:
-            if name not in self._aux:
-                self._aux[name] = self.ctx.malloc(w * h * 4)
-            setattr(t, name, C.c_void_p(self._aux[name]))
-            setattr(t, name + "_pitch", w * 4)
+        target = self._own_target()
+        t, want = self._aux_targets(depth, median_depth, alpha)
         bg = (C.c_float * 4)(*[float(x) for x in background])
-        check(lib.ws_renderer_render_aux(self.handle, pc.handle, bg, C.c_void_p(self._own_target), w * self.texel_bytes,
-                                         C.byref(t), C.c_void_p(stream or 0)))
-        self._aux_last = tuple(want)
-        return self._own_target
-
-    def _target_for_viewport(self) -> int:
-        w, h = self._viewport
-        if self._own_target_shape != (w, h):
-            if self._own_target:
-                self.ctx.free(self._own_target)
-            self._own_target = self.ctx.malloc(w * h * self.texel_bytes)
-            self._own_target_shape = (w, h)
-        return self._own_target
+        check(lib.ws_renderer_render_aux(self.handle, pc.handle, bg, C.c_void_p(target.ptr), target.pitch, C.byref(t),
+                                         C.c_void_p(stream or 0)))
+        self._aux_last = want
+        return target.ptr
 
     def upload_target(self, image: np.ndarray, stream=None):
         """Copy a host image into the renderer-owned target (prepared viewport; H x W x 4 of the target's dtype: float32,
@@ -1416,10 +1358,9 @@ class GaussianRenderer:
         img = np.ascontiguousarray(image)
         if img.shape != (h, w, 4) or img.dtype != self.np_dtype:
             raise ValueError(f"upload_target: want a ({h}, {w}, 4) {np.dtype(self.np_dtype).name} image, got {img.shape} {img.dtype}")
-        ptr = self._target_for_viewport()
-        check(lib.ws_memcpy_h2d(self.ctx.handle, C.c_void_p(ptr), img.ctypes.data_as(C.c_void_p), img.nbytes,
-                                C.c_void_p(stream or 0)))
-        return ptr
+        target = self._own_target()
+        target.upload(img, stream)
+        return target.ptr
 
     def render_composite(self, pc: PointCloud, target_ptr: int = None, pitch: int = None, load=True, occluder=None,
                          occluder_kind="view_z", occluder_pitch: int = None, depth=False, median_depth=False, alpha=False,
@@ -1436,7 +1377,7 @@ class GaussianRenderer:
         depth / median_depth / alpha: the planes of render_aux(), over the unoccluded splats (download_aux())."""
         w, h = self._viewport
         if target_ptr is None:
-            target_ptr = self._target_for_viewport()
+            target_ptr = self._own_target().ptr
         if pitch is None:
             pitch = w * self.texel_bytes
         desc = L.ws_composite_desc()
@@ -1447,43 +1388,23 @@ class GaussianRenderer:
                 occ = np.ascontiguousarray(occluder, dtype=np.float32)
                 if occ.shape != (h, w):
                     raise ValueError(f"render_composite: want an ({h}, {w}) occluder, got {occ.shape}")
-                if getattr(self, "_occluder_shape", None) != (w, h):
-                    self._free_occluder()
-                    self._occluder = self.ctx.malloc(w * h * 4)
-                    self._occluder_shape = (w, h)
-                # (on the frame's stream: a frame still in flight there reads the previous plane)
-                check(lib.ws_memcpy_h2d(self.ctx.handle, C.c_void_p(self._occluder), occ.ctypes.data_as(C.c_void_p), occ.nbytes,
-                                        C.c_void_p(stream or 0)))
-                desc.occluder, desc.occluder_pitch = self._occluder, w * 4
+                self._occluder.fit(w, h)
+                own = self._occluder.plane("occluder", np.float32)
+                own.upload(occ, stream)  # (on the frame's stream: a frame still in flight there reads the previous plane)
+                desc.occluder, desc.occluder_pitch = own.ptr, own.pitch
             else:
                 desc.occluder, desc.occluder_pitch = int(occluder), int(occluder_pitch if occluder_pitch is not None else w * 4)
-        if self._aux_shape != (w, h):
-            self._free_aux()
-            self._aux_shape = (w, h)
-        want = [name for name, on in (("depth", depth), ("median_depth", median_depth), ("alpha", alpha)) if on]
-        t = L.ws_aux_targets()
-        for name in want:
-            if name not in self._aux:
-                self._aux[name] = self.ctx.malloc(w * h * 4)
-            setattr(t, name, C.c_void_p(self._aux[name]))
-            setattr(t, name + "_pitch", w * 4)
+        t, want = self._aux_targets(depth, median_depth, alpha)
         bg = (C.c_float * 4)(*[float(x) for x in background])
         check(lib.ws_renderer_render_composite(self.handle, pc.handle, bg, C.c_void_p(target_ptr), pitch, C.byref(t),
                                                C.byref(desc), C.c_void_p(stream or 0)))
-        self._aux_last = tuple(want)
+        self._aux_last = want
         return target_ptr
-
-    def _free_occluder(self):
-        if getattr(self, "_occluder", None):
-            self.ctx.free(self._occluder)
-        self._occluder = None
-        self._occluder_shape = None
 
     def download_aux(self) -> dict:
         """{plane name: H x W float32} of the planes the last render_aux() wrote (syncs)."""
-        w, h = self._aux_shape or (0, 0)
         self.ctx.sync()
-        return {name: self.ctx.download(self._aux[name], (h, w), np.float32) for name in self._aux_last}
+        return {name: self._aux.get(name).download() for name in self._aux_last}
 
     def download_depths(self) -> np.ndarray:
         """The prepared frame's view-space depth per visible splat, store order (needs enable_depth before prepare; syncs)."""
@@ -1496,31 +1417,29 @@ class GaussianRenderer:
 
     def download_target_rgba8(self) -> np.ndarray:
         """bin/render.rs:187-246 download_texture of the renderer-owned target: H x W x 4 uint8 (truncating)."""
-        w, h = self._own_target_shape
+        target = self._target.get("target")
+        h, w = target.shape[:2]
         out = np.empty((h, w, 4), dtype=np.uint8)
-        check(lib.ws_download_texture_rgba8(self.ctx.handle, C.c_void_p(self._own_target), FORMATS[self.color_format_name][0],
-                                            w, h, w * self.texel_bytes, out.ctypes.data_as(C.c_void_p), None))
+        check(lib.ws_download_texture_rgba8(self.ctx.handle, C.c_void_p(target.ptr), FORMATS[self.color_format_name][0],
+                                            w, h, target.pitch, out.ctypes.data_as(C.c_void_p), None))
         return out
 
     def display(self, background=(0.0, 0.0, 0.0, 1.0), surface="rgba8unorm") -> np.ndarray:
         """Display::render (renderer.rs:548-582) of the renderer-owned target into an 8-bit surface: H x W x 4."""
-        w, h = self._own_target_shape
-        dst = self.ctx.malloc(w * h * 4)
-        try:
+        target = self._target.get("target")
+        h, w = target.shape[:2]
+        with DeviceArray(self.ctx, (h, w, 4), np.uint8) as dst:
             bg = (C.c_float * 4)(*[float(x) for x in background])
             sf = {"rgba8unorm": L.WS_SURFACE_RGBA8_UNORM, "bgra8unorm": L.WS_SURFACE_BGRA8_UNORM}[surface]
-            check(lib.ws_display_composite(self.ctx.handle, C.c_void_p(self._own_target), FORMATS[self.color_format_name][0],
-                                           w * self.texel_bytes, w, h, bg, sf, C.c_void_p(dst), w * 4, None))
+            check(lib.ws_display_composite(self.ctx.handle, C.c_void_p(target.ptr), FORMATS[self.color_format_name][0],
+                                           target.pitch, w, h, bg, sf, C.c_void_p(dst.ptr), dst.pitch, None))
             self.ctx.sync()
-            return self.ctx.download(dst, (h, w, 4), np.uint8)
-        finally:
-            self.ctx.free(dst)
+            return dst.download()
 
     def download_target(self) -> np.ndarray:
         """download_texture (bin/render.rs:187-246) for the renderer-owned target: H x W x 4."""
-        w, h = self._own_target_shape
         self.ctx.sync()
-        return self.ctx.download(self._own_target, (h, w, 4), self.np_dtype)
+        return self._target.get("target").download()
 
     def num_visible_points(self) -> int:
         v = C.c_uint32()
@@ -1607,16 +1526,9 @@ class ViewBatch:
         return int(lib.ws_view_batch_host_waits(self.handle))
 
     def renderer(self, slot: int) -> "GaussianRenderer":
-        """A non-owning view of slot's renderer (frame_stats, timers)."""
-        r = GaussianRenderer.__new__(GaussianRenderer)
-        r.ctx = self.ctx
-        r.color_format_name = self.color_format_name
-        _, r.np_dtype, r.texel_bytes = FORMATS[self.color_format_name]
-        r.handle = C.c_void_p(lib.ws_view_batch_renderer(self.handle, int(slot)))
-        r._own_target = None
-        r._own_target_shape = None
-        r.close = lambda: None
-        return r
+        """A non-owning view of slot's renderer (frame_stats, timers): its close() leaves the slot's renderer alone."""
+        return GaussianRenderer._view(self.ctx, C.c_void_p(lib.ws_view_batch_renderer(self.handle, int(slot))),
+                                      self.color_format_name)
 
 
 class GPURSSorter:
@@ -1654,31 +1566,14 @@ class GPURSSorter:
         """Convenience for tests: upload, sort, download. `count` exercises the device-side count path; `depth`
         selects the depth-sort specialisation, `aux` its companion values (returned as a third array)."""
         n = keys.shape[0]
-        dk = self.ctx.malloc(max(n, 1) * 4)
-        dv = self.ctx.malloc(max(n, 1) * 4)
-        da = self.ctx.malloc(max(n, 1) * 4) if aux is not None else None
-        dc = None
-        try:
-            self.ctx.upload(dk, keys.astype(np.uint32))
-            self.ctx.upload(dv, payload.astype(np.uint32))
-            if aux is not None:
-                self.ctx.upload(da, aux.astype(np.uint32))
-            if count is not None:
-                dc = self.ctx.malloc(4)
-                self.ctx.upload(dc, np.array([count], dtype=np.uint32))
+        with contextlib.ExitStack() as held:
+            def dev(a):
+                return None if a is None else held.enter_context(DeviceArray.from_host(self.ctx, np.asarray(a).astype(np.uint32)))
+
+            dk, dv, da, dc = dev(keys), dev(payload), dev(aux), dev(None if count is None else [count])
             if depth:
-                self.sort_depth(dk, dv, n, da, dc)
+                self.sort_depth(dk.ptr, dv.ptr, n, da and da.ptr, dc and dc.ptr)
             else:
-                self.sort(dk, dv, n, dc)
+                self.sort(dk.ptr, dv.ptr, n, dc and dc.ptr)
             self.ctx.sync()
-            out = (self.ctx.download(dk, (n,), np.uint32), self.ctx.download(dv, (n,), np.uint32))
-            if aux is not None:
-                out = out + (self.ctx.download(da, (n,), np.uint32),)
-            return out
-        finally:
-            self.ctx.free(dk)
-            self.ctx.free(dv)
-            if da:
-                self.ctx.free(da)
-            if dc:
-                self.ctx.free(dc)
+            return tuple(d.download() for d in (dk, dv, da) if d is not None)
