@@ -448,7 +448,8 @@ int ws_renderer_enable_capture(ws_renderer* r, int enable);
 /* Capacity of the (tile, splat) entry list; 0 = automatic: max(8 M, 4 per Gaussian per Mpixel), twice what the BASELINE
  * scenes need.  A frame that needs more sets error bit 0 and leaves its demand in a word that survives the per-frame reset;
  * once ws_renderer_errors (or ws_view_batch_errors) has read it, the next prepare() with the automatic capacity allocates
- * 1.25 x that demand.  Takes effect at the next prepare. */
+ * 1.25 x that demand.  An overflowed frame keeps the first `capacity` entries in draw order (far to near; within a splat rows
+ * top to bottom, columns left to right): its tile lists are those of exactly these entries.  Takes effect at the next prepare. */
 int ws_renderer_set_tile_entry_capacity(ws_renderer* r, uint64_t entries);
 /* parity read-back of the prepared frame (the reference's test tooling reads buffers back the same way,
  * gpu_rs.rs:900-941 download_buffer): splats = V x 20 B in store order, keys/src_index = V u32 in store
