@@ -304,6 +304,10 @@ int ws_pointcloud_load_npz(ws_context* ctx, const char* path, ws_pointcloud** ou
 int ws_pointcloud_load(ws_context* ctx, const char* path, ws_pointcloud** out);
 
 /* ---- PointCloud: pointcloud.rs:99-222, 336-349 ------------------------------------------------ */
+/* Positions are taken as they are: a Gaussian with a NaN coordinate fails no cull comparison, as in the reference, and yields a
+ * visible slot (NaN axes and centre, a NaN depth key of either sign) that reaches no tile and leaves every other splat and the
+ * image as they would be without it; +-inf coordinates are culled by the clip box.  bbox and center are the caller's too (the
+ * fade-in is computed from them as declared, wherever the centre lies). */
 int ws_pointcloud_create(ws_context* ctx, const ws_pointcloud_desc* desc, ws_pointcloud** out);
 /* PlyReader::read (io/ply.rs:50-100, 164-196) + GenericGaussianPointCloud::new (io/mod.rs:63-105) + PointCloud::new
  * with the per-vertex conversion on the GPU: `rows` = n raw vertex rows of the INRIA layout (14 + 3*(sh_deg+1)^2 f32

@@ -136,6 +136,9 @@ def _tans(viewport):
     return 0.5, h / (2.0 * w)          # (w / 2) / fx and (h / 2) / fy with fx = fy = w
 
 
+tans, base_blobs = _tans, _base_blobs      # (used by tests/k1_edges.py as well)
+
+
 def _positions(base_xyz, m, variant, viewport):
     """Survivors: base_xyz (in [-1, 1]^3) shrunk into [-0.9, 0.9]^3 and, in y, into 0.9 x the 1.2 w cull bound at the nearest
     depth (0.85 at 640 x 480, 0.011 at 8256 x 80).  Culled: the same, then moved past ONE threshold, the cause going round
@@ -312,7 +315,7 @@ def _first(cond):
     return int(np.nonzero(cond)[0][0])
 
 
-def compare_frame(got, want, mode="bitwise", key_ulp=2, tally=None):
+def compare_frame(got, want, mode="bitwise", key_ulp=2, tally=None, nan_keys=False):
     """Every difference between two frames (dicts of num_visible, splats [V, 20] u8, keys, src_index, sorted and optionally z),
     as a list of messages; empty = equal.
 
@@ -322,6 +325,9 @@ def compare_frame(got, want, mode="bitwise", key_ulp=2, tally=None):
                     permutation along which got's OWN keys do not decrease, ties in store order (keys that may differ by a unit
                     may legitimately order differently); z, where both frames carry one, is positive and within want["z_tol"]
                     (per slot; the oracle has no z plane: the caller puts numpy's there, tests/test_gpu_aux.py::_numpy_z).
+    nan_keys (oracle mode, K1's keys = the bits of an f32): a key that is a NaN in BOTH frames counts as equal, whatever its
+                    sign and payload (neither IEEE 754 nor WGSL fixes those for the result of an operation); the slots that
+                    hold a NaN key must be the same.  tests/k1_edges.py: the depth of a Gaussian with a NaN position.
     tally: a dict that receives halves / halves_inexact / keys / keys_inexact / key_max of this pair (oracle mode), for the
     pooled 2 % caps the caller applies over many frames."""
     diffs = []
@@ -371,6 +377,13 @@ def compare_frame(got, want, mode="bitwise", key_ulp=2, tally=None):
         diffs.append(f"f16 field off by more than 1 ulp from slot {s}: {dict(zip(FIELDS, d.max(axis=0).tolist()))} "
                      f"({int((d > 1).any(axis=1).sum())} slots)")
     kd = np.abs(gk - ok)
+    if nan_keys:
+        knan_g, knan_o = (gk & 0x7FFFFFFF) > 0x7F800000, (ok & 0x7FFFFFFF) > 0x7F800000
+        if not np.array_equal(knan_g, knan_o):
+            diffs.append(f"NaN keys in different slots, from slot {_first(knan_g != knan_o)}")
+        if tally is not None:
+            tally["nan_keys_of_other_bits"] = tally.get("nan_keys_of_other_bits", 0) + int(((gk != ok) & knan_g & knan_o).sum())
+        kd[knan_g & knan_o] = 0
     if v and kd.max() > key_ulp:
         diffs.append(f"keys differ by {int(kd.max())} > {key_ulp} from slot {_first(kd > key_ulp)} ({int((kd > key_ulp).sum())} slots)")
     if not np.array_equal(np.sort(gso), np.arange(v, dtype=gso.dtype)):

@@ -1123,11 +1123,29 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     kp.zfar = -kp.cam.proj[3 * 4 + 2] / (kp.cam.proj[2 * 4 + 2] - 1.0f);
     r->frame.znear = kp.znear;
     r->frame.zfar = kp.zfar;
-    // fade-in (preprocess.wgsl:196-203): dd = 5 |centre - xyz| / extend <= 10 because the centroid lies inside the
-    // bbox and extend >= its radius; beyond walltime 11 s smoothstep(walltime - dd) is exactly 1 for every Gaussian.
-    // (the clip box only removes Gaussians, so the bound holds for user boxes too)
-    kp.fade_done = (kp.rs.walltime >= 11.0f && kp.rs.scene_extend > 0.0f && std::isfinite(kp.rs.scene_extend) &&
-                    !args->has_clipping_box) ? 1u : 0u;
+    // fade-in (preprocess.wgsl:196-203): once walltime is past (largest possible dd) + 1, smoothstep(walltime - dd) is exactly
+    // 1 for every Gaussian and the kernel skips the computation.  One rule, dd = 5 |centre - xyz| / extend bounded two ways:
+    //   * every Gaussian that reaches k1_math lies inside the bbox (the default clip box IS the bbox; a user box may admit
+    //     Gaussians outside it, so the shortcut is off with one), and extend >= the bbox radius;
+    //   * the centre is the CALLER's (ws_pointcloud_create copies it unchecked).  Inside the bbox, |centre - xyz| <= 2 radius,
+    //     dd <= 10, and walltime >= 11 suffices (every cloud a loader produces).  Anywhere else the triangle inequality gives
+    //     dd <= 5 (|centre - bbox midpoint| + radius) / extend, and walltime has to pass that bound (with a margin far above
+    //     the kernel's f32 rounding of dd) plus 1 as well.
+    bool fade_done = kp.rs.walltime >= 11.0f && kp.rs.scene_extend > 0.0f && std::isfinite(kp.rs.scene_extend) &&
+                     !args->has_clipping_box;
+    bool centre_inside = true;
+    for (int i = 0; i < 3; ++i)
+        centre_inside = centre_inside && pc->center[i] >= pc->bbox.min[i] && pc->center[i] <= pc->bbox.max[i];
+    if (fade_done && !centre_inside) {  // (a NaN centre lands here too, and fails the comparison below)
+        double d2 = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            const double mid = 0.5 * ((double)pc->bbox.min[i] + (double)pc->bbox.max[i]);
+            d2 += ((double)pc->center[i] - mid) * ((double)pc->center[i] - mid);
+        }
+        const double dd_max = 5.0 * (std::sqrt(d2) + (double)ws_aabb_radius(&pc->bbox)) / (double)kp.rs.scene_extend;
+        fade_done = (double)kp.rs.walltime >= dd_max * 1.0001 + 1.0;
+    }
+    kp.fade_done = fade_done ? 1u : 0u;
 
     K1Buffers kb;
     kb.planes = pc->planes.get();
