@@ -585,7 +585,8 @@ int ws_scene_nearest_camera(const ws_scene* s, const float pos[3], int split, ui
 
 /* ---- offline front-ends: bin/render.rs, bin/measure.rs, renderer.rs:417-583 Display ------------------- */
 /* bin/render.rs:187-246 download_texture: device image (format of the renderer) -> host RGBA8, each channel
- * clamp(v, 0, 1) * 255 TRUNCATED (`as u8`); unorm8 images are copied. out = width*height*4 bytes. Syncs. */
+ * clamp(v, 0, 1) * 255 TRUNCATED (`as u8`); a NaN channel stores 0 (Rust's saturating cast), +-inf clamp to 0 / 255; unorm8
+ * images are copied. out = width*height*4 bytes. Syncs. */
 int ws_download_texture_rgba8(ws_context* ctx, const void* d_image, ws_color_format format, uint32_t width,
                               uint32_t height, size_t row_pitch_bytes, uint8_t* out, void* stream);
 /* `image` crate save (bin/render.rs:127): RGBA8 PNG */
@@ -1050,7 +1051,10 @@ uint32_t ws_view_batch_host_waits(const ws_view_batch* b);
 
 /* Display::render (renderer.rs:548-582) + display.wgsl:37-55: the splat image (premultiplied RGBA, renderer
  * format) composited with PREMULTIPLIED_ALPHA_BLENDING over a surface cleared to `background`, written as 8-bit
- * unorm in the surface's channel order (lib.rs:184-243 picks the surface format and strips the sRGB suffix). */
+ * unorm in the surface's channel order (lib.rs:184-243 picks the surface format and strips the sRGB suffix).
+ * Per channel: out = c + background * (1 - a) in f32 (the multiply-add may be fused), clamped to [0, 1], * 255, rounded half
+ * to even.  A NaN result (a NaN texel, inf - inf, 0 * inf) stores 0; +-inf clamp to 0 / 255.  Rows beyond `width` texels (the
+ * pitch's padding) are neither read into a pixel nor written. */
 typedef enum ws_surface_format { WS_SURFACE_RGBA8_UNORM = 0, WS_SURFACE_BGRA8_UNORM = 1 } ws_surface_format;
 int ws_display_composite(ws_context* ctx, const void* d_src, ws_color_format src_format, size_t src_pitch_bytes,
                          uint32_t width, uint32_t height, const float background[4], ws_surface_format dst_format,

@@ -152,16 +152,25 @@ def scene_nearest(scene, p, split=None):
     return None if best is None else best[1]
 
 
+def _clamp01(v):
+    """clamp(v, 0, 1) with NaN -> 0: Rust's saturating `as u8` of a NaN, the unorm store of a NaN (WebGPU leaves it to the
+    implementation; the library stores 0 -- include/websplat.h)"""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(v), F(0.0), np.clip(v, F(0.0), F(1.0))).astype(F)
+
+
 def download_texture_u8(img):
-    v = np.clip(img.astype(F), F(0.0), F(1.0)) * F(255.0)
+    v = _clamp01(img.astype(F)) * F(255.0)
     return v.astype(np.uint8)  # truncation, `as u8`
 
 
 def display_composite(img, background, bgra=False):
+    """f32, every operation rounded by itself: k = 1 - a; t = background * k; out = src + t; clamp, * 255, round half to even"""
     src = img.astype(F)
-    k = F(1.0) - src[..., 3:4]
-    out = src + np.array(background, dtype=F) * k
-    q = np.rint(np.clip(out, F(0.0), F(1.0)) * F(255.0)).astype(np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        k = F(1.0) - src[..., 3:4]
+        out = src + np.array(background, dtype=F) * k
+    q = np.rint(_clamp01(out) * F(255.0)).astype(np.uint8)
     return q[..., [2, 1, 0, 3]] if bgra else q
 
 

@@ -5,12 +5,14 @@ Stated tolerance: positions, the SH record and the padding are BYTE-EXACT.  Opac
 depend on exp(): the reference calls libm's expf, whose last bit is implementation-defined (glibc's differs from the
 correctly rounded value for 0.06 % of arguments); the kernel rounds an f64 exp once.  After the f16 rounding those
 seven halves may differ by ONE f16 ulp (off-diagonal covariance elements that cancel to almost nothing: by 4e-7 of the
-row's largest element), in at most 0.2 % of the values."""
+row's largest element), in at most 0.2 % of the values.  Against the restatement with the kernel's own exp the same halves are
+pinned exactly, here and on edge inputs, by tests/test_gpu_ply_edges.py."""
 import os
 
 import numpy as np
 import pytest
 
+import ply_rows as pr
 import scenes
 from websplat import synth
 
@@ -38,13 +40,8 @@ def _compare(g, s, g0, s0, n):
 
 @pytest.mark.parametrize("sh_deg", [3, 2, 1, 0])
 def test_ply_rows_decode_on_gpu_vs_oracle(ws, ctx, oracle, sh_deg):
-    n = 50_001
-    rows = synth.scene_c1(n=n, seed=70 + sh_deg, sh_deg=sh_deg)
-    rng = np.random.default_rng(5)
-    tail = 14 + 3 * (sh_deg + 1) ** 2 - 8
-    rows[:200, tail] = rng.uniform(-30, 30, 200)           # opacity logits far out on both sigmoid branches
-    rows[200:400, tail + 1:tail + 4] = rng.uniform(-14, 3, (200, 3))   # log-scales from 1e-6 to 20
-    rows[400:410, tail + 4:tail + 8] *= 1e-3               # tiny (still normalisable) quaternions
+    n = pr.BULK_N
+    rows = pr.bulk_rows(sh_deg)    # (tests/test_gpu_ply_edges.py holds the same rows to the f64-exp restatement, exactly)
     pc = ws.PointCloud.from_ply_rows(ctx, rows, sh_deg, kernel_size=0.125, mip_splatting=False)
     try:
         g, s = pc.download()
