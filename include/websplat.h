@@ -916,8 +916,8 @@ int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const
  * red is above 0 in the frame -- with E == 1 everywhere, ws_renderer_accumulate_contrib's sum.
  * THE STOPS.  As "Removal effect": F ignores what lies behind a stop, so a pair's opacity term is under-reported by at most
  * r * 2^-14 * colour * |G|.
- * Out of scope: gradients with respect to position, covariance and the higher SH coefficients; writing a refitted cloud to disk
- * (the optimiser is "Refitting colour and opacity" below).
+ * Out of scope: gradients with respect to position, covariance and the higher SH coefficients (the optimiser is "Refitting colour
+ * and opacity" below, the writer "Saving a point cloud").
  * Errors: as ws_renderer_accumulate_removal, judged from the descriptor before a handle is looked at; in addition
  * WS_ERR_INVALID for a null d_grad, a gradient pointer or pitch that is not a multiple of 16, a pitch below 16 * width, a scale
  * or opacity_scale that is not finite and above 0.
@@ -1001,8 +1001,8 @@ int  ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, cons
  * One stream, one sync and one look at the error bits per epoch; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule, after
  * the steps of that epoch have been taken.  *steps = the steps taken.  Known costs: the reference cloud is rendered again every
  * epoch, and the PNGs are read again every epoch.
- * Out of scope: position, covariance and the higher SH coefficients; learning-rate schedules; writing a cloud to disk (a refitted
- * cloud can be kept through ws_pointcloud_download and ws_pointcloud_create). */
+ * Out of scope: position, covariance and the higher SH coefficients; learning-rate schedules.  A refitted cloud is kept
+ * with ws_pointcloud_save_ply ("Saving a point cloud" below). */
 typedef struct ws_refit ws_refit;               /* f32 masters and Adam moments of one uncompressed cloud, device memory */
 typedef struct ws_refit_params {
     float lr_colour, lr_opacity;     /* finite, >= 0; 0 freezes the group: its masters, moments and stored halves are not touched */
@@ -1020,6 +1020,68 @@ int  ws_refit_download(ws_refit* refit, uint32_t capacity, float* master, float*
 int  ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
                     int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params, uint32_t epochs, uint32_t views_per_step,
                     uint32_t* steps);
+/* ---- Saving a point cloud: the resident planes back to an INRIA 3DGS .ply (no counterpart in the reference) -------------------------
+ * The last step of prune -> refit -> evaluate: a resident, uncompressed cloud written as the file this library, the reference
+ * viewer and every other 3DGS tool read.  The resident scene holds the covariance (six f16 halves) and the opacity after the
+ * sigmoid; the file stores three log-scales, a quaternion and an opacity logit: saving inverts the load kernel, one thread per
+ * Gaussian (k_ply_encode, ply_encode.hip), with a host twin of the same operations (ws_ply_rows_encode, no GPU needed).
+ * THE ROW, TO THE BIT: 14 + 3 (sh_deg + 1)^2 f32 in the file's order, x y z | nx ny nz | f_dc[3] | f_rest[3][C-1] | opacity |
+ * scale[3] | rot[4], with C = (sh_deg + 1)^2.
+ *   x y z     the f32 bits as they are.                  nx ny nz   +0.
+ *   f_dc, f_rest   the f16 halves widened to f32 (exact; a NaN half gives a NaN), transposed back from the resident
+ *             coefficient-major [16][3] to the file's channel-major [3][C-1].  Coefficients above the cloud's degree are not written.
+ *   opacity   with o the half widened to f64: (float)log(o / (1 - o)) for 0 < o < 1; -20 for o <= 0 (-0 included) and +20 for
+ *             o >= 1 -- finite, and sigmoid(-+20) rounds to the halves 0 and 1 under both decoders; a NaN half gives NaN.  THE ONE
+ *             LOSSY CASE: a half above 1 is written as 1.
+ *   scale, rot   the six halves c00 c01 c02 c11 c12 c22 widened to f64; a cyclic Jacobi eigen-solve in f64: pairs in the order
+ *             (0,1), (0,2), (1,2), at most 16 sweeps, ended when the three off-diagonal entries are exactly 0.  A rotation is
+ *             skipped when its off-diagonal entry is 0; the entry is set to 0 without a rotation when 100 times its magnitude, added
+ *             to the magnitude of either diagonal entry, changes neither; otherwise t = a_pq / h when 100 |a_pq| added to |h| does
+ *             not change |h| (h = a_qq - a_pp), else t = sign(theta) / (|theta| + sqrt(1 + theta^2)), theta = 0.5 h / a_pq; c =
+ *             1 / sqrt(1 + t^2), s = t c, tau = s / (1 + c); a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, and every other pair (x, y)
+ *             the rotation touches becomes (x - s (y + x tau), y + s (x - y tau)).  Only + - x / sqrt: host and device agree to the bit.
+ *             THE ORDER: eigenvalue k is entry k of the diagonal the sweeps end with, eigenvector k column k of the accumulated
+ *             rotations; nothing is sorted.  A product of plane rotations is a proper rotation (det = +1), and a covariance that is
+ *             diagonal already keeps R = I and comes back exactly (sorting would turn it by 90 degrees, which f32 quaternion
+ *             components cannot express exactly).  The quaternion
+ *             is taken from R by the largest pivot among trace, R00, R11, R22 (Shepperd; the first of equals), normalised in f64,
+ *             negated as a whole when its scalar part is negative (a scalar part of -0 is written +0), and each component rounded once
+ *             to f32: rot_0 >= 0 is the scalar part.  scale_k = (float)(0.5 * log(l_k)) for l_k > 0; l_k <= 0 gives -20, whose exp
+ *             squared is 0 in f16.
+ *             A covariance with a half that is not finite gets the identity quaternion (1, 0, 0, 0) and its scales from the
+ *             diagonal by the same rule, a diagonal half of +inf taken as 65504 and one that is NaN or -inf as 0: finite and
+ *             deterministic; nothing traps or loops on it.
+ * The two log() calls are the only operations that are not IEEE operations: everything else is identical between kernel and host
+ * twin, and the four log columns are within one f32 ulp of each other.
+ * WHAT COMES BACK.  Loading what was saved gives the positions, the SH halves and the opacity halves (o > 1 -> 1; NaN as a class)
+ * bit for bit.  An f16-rounded covariance is often INDEFINITE, which the file cannot express: a negative eigenvalue is written as
+ * a zero extent, and every element of the reloaded covariance C' obeys |C' - C| <= sum |l_neg| + ulp16(max(|C|, |C'|)): the
+ * clamp moves an element by at most sum |l_neg|, the re-rounding and the f32 decode by under one f16 ulp.  Where
+ * l_min > 2^-10 l_max the six halves come back identical but for about one row in 10^4.  A cloud saved twice is stable; a cloud
+ * loaded and saved is not byte-equal to its source (only the covariance is resident, not the file's scales and quaternion).
+ * ws_pointcloud_encode_ply_rows: the rows of `pc` into host memory, num_points x row length f32 (rows_bytes at least that).  The
+ * kernel and the copy run on a private stream and are waited for; the rows are staged in ONE device buffer of that size, released
+ * at the return.  Work on other streams that writes the cloud (ws_refit_step) must have been waited for.
+ * ws_pointcloud_encode_ply_rows_device: the same kernel into DEVICE memory of the caller's, only ENQUEUED on `stream` -- for rows
+ * that stay on the device, and what scripts/ply_encode_cost.py times.  ws_pointcloud_decode_ply_rows_device is its inverse: k_ply_decode
+ * of num_points device rows of the cloud's degree INTO the cloud's planes, enqueued on `stream`; bbox, centre and the comments'
+ * values stay as they are (the caller's business, as for ws_pointcloud_create).  Same refusals; rows_bytes is checked, the pointer is trusted.
+ * ws_pointcloud_save_ply: the rows, then ws_ply_write with the cloud's mip / kernel_size / background_color.  `path` is opened
+ * only after the rows exist.
+ * ws_ply_write (host only): `ply`, `format binary_little_endian 1.0`, the comments `mip=true|false`, `kernel_size=%.9g`,
+ * `background_color=%.9g,%.9g,%.9g` exactly when `meta` (may be NULL; its other fields are ignored) has them -- nine digits give
+ * every f32 back --, `element vertex N`, the property list above as `property float NAME`, `end_header`, the rows.  n == 0 writes a
+ * valid empty file.  On an I/O error the partial file is removed: WS_ERR_IO.
+ * Errors: WS_ERR_UNSUPPORTED for a compressed cloud (its codebooks are shared between Gaussians) and sh_deg > 3; WS_ERR_INVALID for
+ * null arguments and a rows_bytes that is too small.
+ * Out of scope: .npz / compressed output; big-endian or ASCII output; keeping the source file's scales and quaternion; expressing
+ * an indefinite covariance exactly. */
+int ws_ply_rows_encode(const void* gaussians /* 28 B x n */, const void* sh /* 96 B x n */, uint32_t n, uint32_t sh_deg, float* rows_out);
+int ws_pointcloud_encode_ply_rows(const ws_pointcloud* pc, float* rows, size_t rows_bytes);   /* syncs */
+int ws_pointcloud_save_ply(const ws_pointcloud* pc, const char* path);                        /* syncs */
+int ws_pointcloud_encode_ply_rows_device(const ws_pointcloud* pc, float* d_rows, size_t rows_bytes, void* stream);        /* enqueues only */
+int ws_pointcloud_decode_ply_rows_device(ws_pointcloud* pc, const float* d_rows, size_t rows_bytes, void* stream);        /* enqueues only */
+int ws_ply_write(const char* path, const float* rows, uint32_t n, uint32_t sh_deg, const ws_pointcloud_desc* meta);
 /* ---- view batches (BASELINE configs 4 / 5: many independent views of one resident scene) ----------------
  * The reference renders one view at a time on one queue (lib.rs:422-431, bin/measure.rs:98-146).  A view batch keeps
  * `frames_in_flight` frames going at once: frame i of the batch's life runs on renderer + HIP stream i mod

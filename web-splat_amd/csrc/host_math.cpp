@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "ply_encode.h"
 #include "ws_internal.h"
 
 namespace ws {
@@ -419,6 +420,46 @@ int ws_ply_rows_convert(const float* rows, uint32_t n, uint32_t sh_deg, void* ga
                 const uint16_t h = host_f32_to_f16(sh[c][j]);
                 std::memcpy(s + (c * 3 + j) * 2, &h, 2);
             }
+    }
+    return WS_OK;
+}
+
+// The inverse of ws_ply_rows_convert: ply_encode.h's definition, one row per record, the operations of k_ply_encode in its order.
+int ws_ply_rows_encode(const void* gaussians, const void* sh, uint32_t n, uint32_t sh_deg, float* rows_out) {
+    if ((!gaussians || !sh || !rows_out) && n) return fail(WS_ERR_INVALID, "ws_ply_rows_encode: null argument");
+    if (sh_deg > 3) return fail(WS_ERR_UNSUPPORTED, "ws_ply_rows_encode: sh_deg > 3");
+    const uint32_t num_coefs = (sh_deg + 1) * (sh_deg + 1);
+    const size_t row_len = 14 + 3 * static_cast<size_t>(num_coefs);
+    const uint8_t* gin = static_cast<const uint8_t*>(gaussians);
+    const uint8_t* sin = static_cast<const uint8_t*>(sh);
+    const auto term_value = [](const PlyLogTerm& t, double scale) { return t.take_log ? static_cast<float>(scale * std::log(t.arg)) : static_cast<float>(t.constant); };
+    const ws::OmpQuietWorkers omp_quiet;  // (ws_internal.h: the region's workers sleep at once instead of spinning 200 ms)
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < static_cast<int64_t>(n); ++i) {
+        const uint8_t* g = gin + static_cast<size_t>(i) * 28;
+        const uint8_t* s = sin + static_cast<size_t>(i) * 96;
+        float* r = rows_out + static_cast<size_t>(i) * row_len;
+        float* tail = r + (row_len - 8);
+        std::memcpy(r, g, 12);
+        r[3] = r[4] = r[5] = 0.0f;
+        for (uint32_t e = 0; e < 48; ++e) {
+            const uint32_t c = e / 3, j = e % 3;
+            uint16_t hbits;
+            std::memcpy(&hbits, s + 2 * e, 2);
+            if (c < num_coefs) r[ply_sh_column(c, j, num_coefs)] = ply_half_to_f32(hbits);
+        }
+        uint16_t op, cov[6];
+        std::memcpy(&op, g + 12, 2);
+        std::memcpy(cov, g + 16, 12);
+        tail[0] = term_value(ply_encode_opacity(op), 1.0);
+        const PlyEncodedCov ec = ply_encode_cov(cov[0], cov[1], cov[2], cov[3], cov[4], cov[5]);
+        tail[1] = term_value(ply_encode_extent(ec.l0), 0.5);
+        tail[2] = term_value(ply_encode_extent(ec.l1), 0.5);
+        tail[3] = term_value(ply_encode_extent(ec.l2), 0.5);
+        tail[4] = ec.q0;
+        tail[5] = ec.q1;
+        tail[6] = ec.q2;
+        tail[7] = ec.q3;
     }
     return WS_OK;
 }

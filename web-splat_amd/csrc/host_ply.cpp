@@ -284,6 +284,55 @@ static int load_ply_impl(ws_context* ctx, const char* path, ws_pointcloud** out)
     return ws_pointcloud_create_from_ply_rows(ctx, rows.data(), h.num_vertices, sh_deg, &meta, out);
 }
 
+// The writer: the header ply_read_rows accepts (binary little endian, the INRIA property list in file order), the optional comments
+// in the form ply_header_meta parses (%.9g: nine significant digits give every f32 back), then the rows.
+static int ply_write_impl(const char* path, const float* rows, uint32_t n, uint32_t sh_deg, const ws_pointcloud_desc* meta) {
+    const uint32_t ncoef = (sh_deg + 1) * (sh_deg + 1);
+    const uint32_t row_len = 14 + 3 * ncoef;
+    std::string head = "ply\nformat binary_little_endian 1.0\n";
+    char buf[160];
+    if (meta && meta->has_mip_splatting) head += meta->mip_splatting ? "comment mip=true\n" : "comment mip=false\n";
+    if (meta && meta->has_kernel_size) {
+        std::snprintf(buf, sizeof buf, "comment kernel_size=%.9g\n", (double)meta->kernel_size);
+        head += buf;
+    }
+    if (meta && meta->has_background_color) {
+        std::snprintf(buf, sizeof buf, "comment background_color=%.9g,%.9g,%.9g\n", (double)meta->background_color[0],
+                      (double)meta->background_color[1], (double)meta->background_color[2]);
+        head += buf;
+    }
+    head += "element vertex " + std::to_string(n) + "\n";
+    for (const char* p : {"x", "y", "z", "nx", "ny", "nz"}) head += std::string("property float ") + p + "\n";
+    for (uint32_t i = 0; i < 3; ++i) head += "property float f_dc_" + std::to_string(i) + "\n";
+    for (uint32_t i = 0; i < 3 * (ncoef - 1); ++i) head += "property float f_rest_" + std::to_string(i) + "\n";
+    head += "property float opacity\n";
+    for (uint32_t i = 0; i < 3; ++i) head += "property float scale_" + std::to_string(i) + "\n";
+    for (uint32_t i = 0; i < 4; ++i) head += "property float rot_" + std::to_string(i) + "\n";
+    head += "end_header\n";
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(WS_ERR_IO, std::string("ws_ply_write: cannot open ") + path);
+    const size_t count = (size_t)n * row_len;
+    bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
+    if (ok && count) ok = std::fwrite(rows, sizeof(float), count, f) == count;  // (the host is little-endian, as ply_read_rows assumes)
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) {
+        std::remove(path);  // no partial file stays behind
+        return fail(WS_ERR_IO, std::string("ws_ply_write: write failed: ") + path);
+    }
+    return WS_OK;
+}
+
+extern "C" int ws_ply_write(const char* path, const float* rows, uint32_t n, uint32_t sh_deg, const ws_pointcloud_desc* meta) {
+    if (!path || (!rows && n)) return fail(WS_ERR_INVALID, "ws_ply_write: null argument");
+    if (sh_deg > 3) return fail(WS_ERR_UNSUPPORTED, "ws_ply_write: sh_deg > 3");
+    if (n >= (1u << 30)) return fail(WS_ERR_UNSUPPORTED, "ws_ply_write: more than 2^30-1 vertices");
+    try {
+        return ply_write_impl(path, rows, n, sh_deg, meta);
+    } catch (const std::bad_alloc&) {
+        return fail(WS_ERR_OOM, "ws_ply_write: host allocation failed");
+    }
+}
+
 extern "C" int ws_pointcloud_load_ply(ws_context* ctx, const char* path, ws_pointcloud** out) {
     if (!ctx || !path || !out) return fail(WS_ERR_INVALID, "ws_pointcloud_load_ply: null argument");
     *out = nullptr;

@@ -16,6 +16,7 @@
 #include "frame_scratch.h"
 #include "metrics.h"
 #include "gradient.h"
+#include "ply_encode.h"
 #include "refit.h"
 #include "removal.h"
 #include "values.h"
@@ -713,6 +714,76 @@ int ws_pointcloud_download(const ws_pointcloud* pc, void* gaussians, size_t gaus
         for (int q = 0; q < 6; ++q) std::memcpy(s + (size_t)i * 96 + q * 16, st.data() + ((size_t)(2 + q) * n + i) * 4, 16);
     }
     return WS_OK;
+}
+
+// Saving (websplat.h "Saving a point cloud"): k_ply_encode writes the rows into one DeviceBuf, which is copied to the host and
+// let go at the return.  Kernel and copy run on a private stream and are waited for, as ws_pointcloud_create_from_ply_rows does.
+static int ply_rows_device_check(const ws_pointcloud* pc, const void* d_rows, size_t rows_bytes, const char* who, size_t* need) {
+    if (!pc) return fail(WS_ERR_INVALID, std::string(who) + ": null argument");
+    if (pc->compressed)
+        return fail(WS_ERR_UNSUPPORTED, std::string(who) + ": a compressed cloud has no PLY rows (its codebooks are shared between Gaussians)");
+    const uint32_t row_len = 14u + 3u * (pc->sh_deg + 1u) * (pc->sh_deg + 1u);
+    *need = (size_t)pc->num_points * row_len * sizeof(float);
+    if (!d_rows && *need) return fail(WS_ERR_INVALID, std::string(who) + ": null argument");
+    if (rows_bytes < *need) return fail(WS_ERR_INVALID, std::string(who) + ": rows buffer too small");
+    return WS_OK;
+}
+
+int ws_pointcloud_encode_ply_rows_device(const ws_pointcloud* pc, float* d_rows, size_t rows_bytes, void* stream) {
+    size_t need = 0;
+    WS_TRY(ply_rows_device_check(pc, d_rows, rows_bytes, "ws_pointcloud_encode_ply_rows_device", &need));
+    return launch_ply_encode(pc->planes.get(), pc->num_points, pc->sh_deg, d_rows, static_cast<hipStream_t>(stream));
+}
+
+int ws_pointcloud_decode_ply_rows_device(ws_pointcloud* pc, const float* d_rows, size_t rows_bytes, void* stream) {
+    size_t need = 0;
+    WS_TRY(ply_rows_device_check(pc, d_rows, rows_bytes, "ws_pointcloud_decode_ply_rows_device", &need));
+    return launch_ply_decode(d_rows, pc->num_points, pc->sh_deg, pc->planes.get(), static_cast<hipStream_t>(stream));
+}
+
+int ws_pointcloud_encode_ply_rows(const ws_pointcloud* pc, float* rows, size_t rows_bytes) {
+    size_t need = 0;
+    WS_TRY(ply_rows_device_check(pc, rows, rows_bytes, "ws_pointcloud_encode_ply_rows", &need));
+    const uint32_t n = pc->num_points;
+    if (n == 0) return WS_OK;
+    DeviceBuf<float> d_rows;  // (let go at the return, behind the stream sync)
+    hipStream_t ls = nullptr;
+    const char* what = "ws_pointcloud_encode_ply_rows: encode";
+    int rc = WS_OK;
+    hipError_t e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
+    if (e != hipSuccess) rc = hip_fail(e, what);
+    if (rc == WS_OK) rc = alloc_as(d_rows.alloc(need / sizeof(float)), what);
+    if (rc == WS_OK) rc = launch_ply_encode(pc->planes.get(), n, pc->sh_deg, d_rows.get(), ls);
+    if (rc == WS_OK && (e = hipMemcpyAsync(rows, d_rows.get(), need, hipMemcpyDeviceToHost, ls)) != hipSuccess) rc = hip_fail(e, what);
+    if (ls) {
+        e = hipStreamSynchronize(ls);
+        if (rc == WS_OK && e != hipSuccess) rc = hip_fail(e, what);
+        (void)hipStreamDestroy(ls);
+    }
+    return rc;
+}
+
+int ws_pointcloud_save_ply(const ws_pointcloud* pc, const char* path) {
+    if (!pc || !path) return fail(WS_ERR_INVALID, "ws_pointcloud_save_ply: null argument");
+    if (pc->compressed)
+        return fail(WS_ERR_UNSUPPORTED, "ws_pointcloud_save_ply: a compressed cloud cannot be saved as a PLY (its codebooks are shared between Gaussians)");
+    const uint32_t row_len = 14u + 3u * (pc->sh_deg + 1u) * (pc->sh_deg + 1u);
+    std::vector<float> rows;
+    try {
+        rows.resize((size_t)pc->num_points * row_len);
+    } catch (...) {
+        return fail(WS_ERR_OOM, "ws_pointcloud_save_ply: host allocation failed");
+    }
+    WS_TRY(ws_pointcloud_encode_ply_rows(pc, rows.data(), rows.size() * sizeof(float)));
+    ws_pointcloud_desc meta;  // the file is opened only now, with the rows in hand
+    std::memset(&meta, 0, sizeof meta);
+    meta.has_mip_splatting = pc->has_mip;
+    meta.mip_splatting = pc->mip;
+    meta.has_kernel_size = pc->has_kernel_size;
+    meta.kernel_size = pc->kernel_size;
+    meta.has_background_color = pc->has_background;
+    std::memcpy(meta.background_color, pc->background, sizeof meta.background_color);
+    return ws_ply_write(path, rows.data(), pc->num_points, pc->sh_deg, &meta);
 }
 
 void ws_pointcloud_destroy(ws_pointcloud* pc) { delete pc; }

@@ -1,7 +1,7 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
 //                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]
-//                     [--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]]
+//                     [--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]] [--save OUT.ply]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
 // another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
 // --blame N: behind that table, the N Gaussians of the scene with the largest error sum over the split (websplat.h "Attributing a
@@ -15,6 +15,9 @@
 // --refit EPOCHS: behind all that, Adam steps on the scene's DC colours and opacities over the TRAIN split against --ref / --gt
 // (websplat.h "Refitting colour and opacity"; a step after every B views, default: one per epoch), then the first table again,
 // of the refitted scene, under a line "after refit: EPOCHS epochs, S steps".  A compressed scene is refused.
+// --save OUT.ply: at the end, the scene as it then stands -- after --refit, the refitted one -- as an INRIA 3DGS .ply (websplat.h
+// "Saving a point cloud"), and one line "saved OUT.ply: N Gaussians, B bytes".  It needs no second image either.  A compressed
+// scene is refused with the library's message.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -44,7 +47,7 @@ static std::vector<uint32_t> top_by(uint32_t np, long want, Key key) {
 }
 
 int main(int argc, char** argv) {
-    const char *ref = nullptr, *gt = nullptr;
+    const char *ref = nullptr, *gt = nullptr, *save = nullptr;
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
     long blame = 0, removal = 0, gradient = 0, refit = 0, views_per_step = 0;
@@ -55,6 +58,7 @@ int main(int argc, char** argv) {
     for (int i = 3; i < argc && !bad; ++i) {
         if (!std::strcmp(argv[i], "--ref") && i + 1 < argc) ref = argv[++i];
         else if (!std::strcmp(argv[i], "--gt") && i + 1 < argc) gt = argv[++i];
+        else if (!std::strcmp(argv[i], "--save") && i + 1 < argc) save = argv[++i];
         else if (!std::strcmp(argv[i], "--split") && i + 1 < argc) {
             ++i;
             if (!std::strcmp(argv[i], "train")) split = WS_SPLIT_TRAIN;
@@ -88,10 +92,10 @@ int main(int argc, char** argv) {
     if (have_refit_option && refit == 0) bad = true;
     const bool compare = ref != nullptr || gt != nullptr;  // (--removal alone needs no second image)
     if ((blame > 0 || gradient > 0 || refit > 0) && !compare) bad = true;
-    if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0)) {
+    if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0 && !save)) {
         std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
                              "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]] "
-                             "[--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]]\n", argv[0]);
+                             "[--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]] [--save OUT.ply]\n", argv[0]);
         return 2;
     }
     ws_context* ctx = nullptr;
@@ -224,6 +228,17 @@ int main(int argc, char** argv) {
         if (rc == WS_OK) {
             std::printf("after refit: %ld epochs, %u steps\n", refit, steps);
             rc = table();
+        }
+    }
+    if (rc == WS_OK && save) {
+        rc = ws_pointcloud_save_ply(pc, save);
+        if (rc == WS_OK) {
+            long bytes = -1;
+            if (FILE* f = std::fopen(save, "rb")) {
+                if (std::fseek(f, 0, SEEK_END) == 0) bytes = std::ftell(f);
+                std::fclose(f);
+            }
+            std::printf("saved %s: %u Gaussians, %ld bytes\n", save, ws_pointcloud_num_points(pc), bytes);
         }
     }
     if (rc != WS_OK) {

@@ -333,6 +333,43 @@ def read_ply(path: str) -> GenericGaussianPointCloud:
         lib.ws_ply_free(pp)
 
 
+def _hints_desc(kernel_size=None, mip_splatting=None, background_color=None):
+    """a ws_pointcloud_desc that carries only the three optional header values"""
+    d = L.ws_pointcloud_desc()
+    d.has_mip_splatting = int(mip_splatting is not None)
+    d.mip_splatting = int(bool(mip_splatting))
+    d.has_kernel_size = int(kernel_size is not None)
+    d.kernel_size = float(kernel_size or 0.0)
+    d.has_background_color = int(background_color is not None)
+    if background_color is not None:
+        d.background_color[:] = [float(x) for x in background_color]
+    return d
+
+
+def write_ply_rows(path: str, rows: np.ndarray, sh_deg: int, **meta):
+    """Raw INRIA vertex rows (N x (14 + 3 (sh_deg + 1)^2) float32) as a binary little-endian .ply through the library's host-side
+    writer (ws_ply_write, no GPU); meta: kernel_size, mip_splatting, background_color, each written as a comment when given."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    want = 14 + 3 * (int(sh_deg) + 1) ** 2
+    if rows.ndim != 2 or rows.shape[1] != want:
+        raise ValueError(f"write_ply_rows: sh_deg {sh_deg} needs rows of {want} floats, got shape {rows.shape}")
+    d = _hints_desc(**meta)
+    check(lib.ws_ply_write(str(path).encode(), rows.ctypes.data_as(C.c_void_p), rows.shape[0], int(sh_deg), C.byref(d)))
+
+
+def encode_ply_rows(gaussians: np.ndarray, sh_coefs: np.ndarray, sh_deg: int) -> np.ndarray:
+    """The loader's blobs (N x 28, N x 96 uint8) back to INRIA vertex rows on the host (ws_ply_rows_encode, the twin of the
+    kernel behind PointCloud.to_ply_rows)."""
+    g = np.ascontiguousarray(gaussians, dtype=np.uint8).reshape(-1, 28)
+    s = np.ascontiguousarray(sh_coefs, dtype=np.uint8).reshape(-1, 96)
+    if g.shape[0] != s.shape[0]:
+        raise ValueError("encode_ply_rows: gaussians and sh_coefs differ in length")
+    rows = np.empty((g.shape[0], 14 + 3 * (int(sh_deg) + 1) ** 2), dtype=np.float32)
+    check(lib.ws_ply_rows_encode(g.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), g.shape[0], int(sh_deg),
+                                 rows.ctypes.data_as(C.c_void_p)))
+    return rows
+
+
 def read_npz(path: str) -> GenericGaussianPointCloud:
     """io/npz.rs:59-225 NpzReader::read + io/mod.rs:107-150 new_compressed, through the library's native reader."""
     pp = C.POINTER(L.ws_npz_cloud)()
@@ -506,14 +543,7 @@ class PointCloud:
         want = 14 + 3 * (int(sh_deg) + 1) ** 2
         if rows.ndim != 2 or rows.shape[1] != want:
             raise ValueError(f"from_ply_rows: sh_deg {sh_deg} needs rows of {want} floats, got shape {rows.shape}")
-        d = L.ws_pointcloud_desc()
-        d.has_mip_splatting = int(mip_splatting is not None)
-        d.mip_splatting = int(bool(mip_splatting))
-        d.has_kernel_size = int(kernel_size is not None)
-        d.kernel_size = float(kernel_size or 0.0)
-        d.has_background_color = int(background_color is not None)
-        if background_color is not None:
-            d.background_color[:] = [float(x) for x in background_color]
+        d = _hints_desc(kernel_size, mip_splatting, background_color)
         h = C.c_void_p()
         check(lib.ws_pointcloud_create_from_ply_rows(ctx.handle, rows.ctypes.data_as(C.c_void_p), rows.shape[0], int(sh_deg),
                                                      C.byref(d), C.byref(h)))
@@ -531,6 +561,25 @@ class PointCloud:
         s = np.empty((n, 96), dtype=np.uint8)
         check(lib.ws_pointcloud_download(self.handle, g.ctypes.data_as(C.c_void_p), g.nbytes, s.ctypes.data_as(C.c_void_p), s.nbytes))
         return g, s
+
+    def to_ply_rows(self) -> np.ndarray:
+        """(N, 14 + 3 (sh_deg + 1)^2) float32: the resident cloud as INRIA vertex rows, encoded on the device (websplat.h "Saving a
+        point cloud"); the inverse of from_ply_rows."""
+        rows = np.empty((self.num_points(), 14 + 3 * (self.sh_deg() + 1) ** 2), dtype=np.float32)
+        check(lib.ws_pointcloud_encode_ply_rows(self.handle, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+        return rows
+
+    def encode_ply_rows_device(self, d_rows: int, nbytes: int, stream=None):
+        """to_ply_rows into device memory of the caller's; only enqueues on `stream` (ws_pointcloud_encode_ply_rows_device)"""
+        check(lib.ws_pointcloud_encode_ply_rows_device(self.handle, C.c_void_p(d_rows), int(nbytes), C.c_void_p(stream or 0)))
+
+    def decode_ply_rows_device(self, d_rows: int, nbytes: int, stream=None):
+        """num_points device rows of this cloud's degree decoded INTO its planes; only enqueues on `stream`"""
+        check(lib.ws_pointcloud_decode_ply_rows_device(self.handle, C.c_void_p(d_rows), int(nbytes), C.c_void_p(stream or 0)))
+
+    def save_ply(self, path: str):
+        """the resident cloud as an INRIA 3DGS .ply with its mip / kernel_size / background_color comments (ws_pointcloud_save_ply)"""
+        check(lib.ws_pointcloud_save_ply(self.handle, str(path).encode()))
 
     @staticmethod
     def load_ply(ctx: Context, path: str):
