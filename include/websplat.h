@@ -916,8 +916,8 @@ int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const
  * red is above 0 in the frame -- with E == 1 everywhere, ws_renderer_accumulate_contrib's sum.
  * THE STOPS.  As "Removal effect": F ignores what lies behind a stop, so a pair's opacity term is under-reported by at most
  * r * 2^-14 * colour * |G|.
- * Out of scope: gradients with respect to position, covariance and the higher SH coefficients (the optimiser is "Refitting colour
- * and opacity" below, the writer "Saving a point cloud").
+ * Out of scope: gradients with respect to position and covariance (the higher SH coefficients are "SH gradients" below, the
+ * optimiser "Refitting colour and opacity", the writer "Saving a point cloud").
  * Errors: as ws_renderer_accumulate_removal, judged from the descriptor before a handle is looked at; in addition
  * WS_ERR_INVALID for a null d_grad, a gradient pointer or pitch that is not a multiple of 16, a pitch below 16 * width, a scale
  * or opacity_scale that is not finite and above 0.
@@ -953,6 +953,60 @@ int  ws_image_error_gradient(ws_context* ctx, const ws_image_view* a, const ws_i
                              uint32_t flags, float* d_grad, size_t grad_pitch_bytes, void* stream);
 int  ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                   const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames);
+/* ---- SH gradients: dL/d(sh[k][ch]) per Gaussian and coefficient, and dL/d(ln opacity) (no counterpart in the reference) -----------
+ * K1's colour is max(0, 0.5 + sum_k basis_k(dir) * sh[k][ch]) with dir the unit vector from the camera to the Gaussian, so
+ *   dL/d sh[k][ch] = basis_k(dir) * dL/d colour[ch]
+ * and dir depends on the frame: the product has to be taken per frame, before frames are summed -- a ws_grad summed over frames
+ * cannot give it.  A ws_shgrad holds 3 * ncoef + 1 int64 sums per Gaussian, ncoef = (sh_deg + 1)^2: sh[j][k][ch] and opacity[j],
+ * in device memory, zeroed at creation and by ws_shgrad_reset, and a per-frame scratch of four int64 per Gaussian laid out as a
+ * ws_grad.  DEVICE LAYOUT: one plane per element, [3 * ncoef + 1][num_points] (element 3 k + ch, the opacity's last), so that a
+ * wave's accesses are contiguous in the Gaussian index; ws_shgrad_download transposes to q_sh[capacity][ncoef][3] and
+ * q_opacity[capacity] (either may be NULL; syncs), ws_shgrad_add takes the same two arrays (either may be NULL) and is the exact
+ * merge of another accumulator's or rank's sums.
+ * ws_renderer_accumulate_sh_gradient: preconditions, descriptor and descriptor checks exactly those of
+ * ws_renderer_accumulate_gradient; in addition WS_ERR_INVALID for a ws_shgrad of another size or one whose sh_deg is not the
+ * cloud's, WS_ERR_UNSUPPORTED for a compressed cloud.  It enqueues three launches: k_removal_base, unchanged; k_gradient,
+ * unchanged, into the accumulator's scratch; k_sh_spread, one thread per Gaussian j, no atomics (a Gaussian belongs to one thread;
+ * frames are ordered by the stream):
+ *   q_r, q_g, q_b, q_o = the four scratch sums of j.  All four 0 (culled or unseen, the common case): nothing else of j is read
+ *   or written.  Otherwise the scratch row is zeroed again (the next frame starts clean without a memset) and
+ *     opacity[j] += q_o;   sh[j][0][ch] += q_ch     the plain colour sum: the factor C0 stays in the refit step, as it is there
+ *     sh[j][k][ch] += llrint((double)q_ch * (double)basis_k)    1 <= k < (min(max_sh_deg of the prepared frame, sh_deg) + 1)^2
+ *   int64 -> double, the product and double -> int64 each round to nearest even; a q_ch of 0 and a basis that is not finite add
+ *   nothing; coefficients above the frame's degree are not touched.
+ * THE DIRECTION, TO THE BIT.  x, y, z the three f32 of plane 0, cam = view_inv[12..14] of the prepared frame's ws_camera_uniform,
+ * d = xyz - cam, dl = sqrtf((dx * dx + dy * dy) + dz * dz), dir = d / dl, every operation a separately rounded IEEE f32 operation.
+ * That is K1's default arithmetic, NOT the fast rsq path a library built with WS_K1_STRICT=0 takes.  dl == 0 and a non-finite
+ * position give no finite basis: such a Gaussian gets its opacity and DC sums only.
+ * THE BASIS.  bas[1..15] by the expressions of K1's SH evaluation (preprocess.wgsl:124-154) in its order, with (x, y, z) = dir:
+ *   -C1 y, C1 z, C1 x | C2_0 xy, C2_1 yz, C2_2 (2 zz - xx - yy), C2_3 xz, C2_4 (xx - yy) | C3_0 y (3 xx - yy), C3_1 xy z,
+ *   C3_2 y (4 zz - xx - yy), C3_3 z (2 zz - 3 xx - 3 yy), C3_4 x (4 zz - xx - yy), C3_5 z (xx - yy), C3_6 x (xx - 3 yy)
+ * each product and difference evaluated left to right in f32.  K1 SUBTRACTS the term of coefficient 3: its effective basis is
+ * -bas[3].  Every basis is bounded by 1 on unit directions, so no sum overflows that a ws_grad's would not.
+ * THE CLAMP at 0 is honoured already: k_gradient counts no pair whose staged c_ch is 0.
+ * Bit for bit: (a) q_sh[:, 0, :] and q_opacity equal the ws_grad of ws_renderer_accumulate_gradient with the same arguments;
+ * (b) two frames added equal the sum of the two single-frame downloads; (c) g and -g negate every sum; (d) the result does not
+ * depend on the launch geometry.
+ * ws_sh_spread_rows (host only, no device needed): the per-Gaussian code of k_sh_spread from the same text, over n rows --
+ * q4[n][4] one frame's ws_grad-layout sums, xyz[n][3], cam[3]; ADDS to q_sh[n][ncoef][3] and q_opacity[n] (either may be NULL)
+ * with active_deg in the place of the prepared frame's max_sh_deg.
+ * ws_scene_accumulate_sh_gradient: ws_scene_accumulate_gradient's walk over the cameras with this per-frame call.
+ * The optimiser is ws_refit_step_sh ("Refitting colour and opacity" below).  Out of scope: gradients with respect to position
+ * and covariance; compressed clouds; a float or compacted accumulator. */
+typedef struct ws_shgrad ws_shgrad;             /* 3 (sh_deg + 1)^2 + 1 int64 sums per Gaussian, device memory, zeroed */
+int  ws_shgrad_create(ws_context* ctx, uint32_t num_points, uint32_t sh_deg, ws_shgrad** out);
+void ws_shgrad_destroy(ws_shgrad* g);
+int  ws_shgrad_reset(ws_shgrad* g, void* stream);
+uint32_t ws_shgrad_num_points(const ws_shgrad* g);
+uint32_t ws_shgrad_sh_deg(const ws_shgrad* g);
+uint32_t ws_shgrad_frames(const ws_shgrad* g);
+int  ws_shgrad_download(ws_shgrad* g, uint32_t capacity, int64_t* q_sh /* [capacity][ncoef][3] */, int64_t* q_opacity /* [capacity] */);   /* syncs */
+int  ws_shgrad_add(ws_shgrad* g, const int64_t* q_sh, const int64_t* q_opacity, uint32_t n);   /* exact merge of another rank's */
+int  ws_renderer_accumulate_sh_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream); /* enqueues; counts as a frame of g */
+int  ws_sh_spread_rows(const int64_t* q4, const float* xyz, const float* cam, uint32_t n, uint32_t sh_deg, uint32_t active_deg,
+                       int64_t* q_sh, int64_t* q_opacity);
+int  ws_scene_accumulate_sh_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                                     const char* gt_dir, int kind, float scale, float opacity_scale, ws_shgrad* grad, uint32_t* frames);
 /* ---- Refitting colour and opacity: Adam steps on the resident planes, in place (no counterpart in the reference) -----------------
  * What "Gradients of an image loss" is for: its sums say in which direction every colour and opacity of a (pruned) cloud should
  * move; a ws_refit moves them.  It belongs to ONE uncompressed point cloud and holds, per Gaussian, f32 masters of four
@@ -1001,7 +1055,24 @@ int  ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, cons
  * One stream, one sync and one look at the error bits per epoch; WS_ERR_OVERFLOW under ws_scene_accumulate_contrib's rule, after
  * the steps of that epoch have been taken.  *steps = the steps taken.  Known costs: the reference cloud is rendered again every
  * epoch, and the PNGs are read again every epoch.
- * Out of scope: position, covariance and the higher SH coefficients; learning-rate schedules.  A refitted cloud is kept
+ * THE REST COEFFICIENTS (the sums of "SH gradients").  ws_refit_enable_sh allocates f32 masters and two moments for the
+ * 3 * (ncoef - 1) rest elements of the cloud, one plane per element, and enqueues a small kernel that widens the stored halves and
+ * sets m = v = 0.  WS_ERR_INVALID once ws_refit_steps() > 0 (the bias-correction powers are shared); a second call is a no-op;
+ * sh_deg = 0 enables nothing and succeeds.  ws_refit_step_sh enqueues ONE kernel, one thread per (Gaussian, 16-B piece of the SH
+ * record):
+ *   DC and opacity: THE STEP above, word for word, fed with q_sh[:, 0, :] and q_opacity of the ws_shgrad.
+ *   a rest element e = 3 * coef + ch, coef >= 1: the same step with g = (float)((double)q_sh[j][coef][ch] * colour_unit) -- no C0:
+ *   the basis is in the sum already --, lr = lr_sh, the clamp at +-65504, and f16(x') stored to half e of the SH record.
+ * steps, p1 and p2 are the object's own, shared with ws_refit_step: the two calls may be mixed.  A frozen group keeps the bits it
+ * read and its masters and moments are not written; so do the halves past 3 * ncoef of the record.  No byte of the cloud changes
+ * outside the opacity half and the first 3 * ncoef SH halves.  With lr_sh = 0 a ws_refit_step_sh leaves the same masters, moments
+ * and cloud bytes as ws_refit_step with a ws_grad holding the same four sums.  ws_refit_download_sh: [capacity][ncoef - 1][3] f32
+ * each, any may be NULL; syncs.  Errors: the descriptor's as ws_refit_step's plus an lr_sh that is negative or not finite, judged
+ * before a handle is looked at; then WS_ERR_INVALID for null handles, a `pc` other than the object's, a step or download before
+ * ws_refit_enable_sh, a ws_shgrad of another size or degree.
+ * ws_scene_refit_sh: ws_scene_refit with ws_renderer_accumulate_sh_gradient as the per-frame call, a ws_shgrad of the driver's
+ * own and ws_refit_step_sh; it calls ws_refit_enable_sh itself if it has not been called.  Units as in ws_scene_refit.
+ * Out of scope: position and covariance; learning-rate schedules; raising a cloud's SH degree.  A refitted cloud is kept
  * with ws_pointcloud_save_ply ("Saving a point cloud" below). */
 typedef struct ws_refit ws_refit;               /* f32 masters and Adam moments of one uncompressed cloud, device memory */
 typedef struct ws_refit_params {
@@ -1020,6 +1091,17 @@ int  ws_refit_download(ws_refit* refit, uint32_t capacity, float* master, float*
 int  ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
                     int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params, uint32_t epochs, uint32_t views_per_step,
                     uint32_t* steps);
+typedef struct ws_refit_sh_params {
+    ws_refit_params base;            /* as ws_refit_step; colour_unit is also what one unit of a rest sum is worth */
+    float lr_sh;                     /* finite, >= 0; 0 freezes the rest coefficients */
+    uint32_t reserved[3];            /* zero */
+} ws_refit_sh_params;
+int  ws_refit_enable_sh(ws_refit* refit, const ws_pointcloud* pc, void* stream);   /* enqueues only */
+int  ws_refit_step_sh(ws_refit* refit, ws_pointcloud* pc, const ws_shgrad* g, const ws_refit_sh_params* params, void* stream);   /* enqueues only */
+int  ws_refit_download_sh(ws_refit* refit, uint32_t capacity, float* master, float* m, float* v);   /* [capacity][ncoef - 1][3] each, any may be NULL; syncs */
+int  ws_scene_refit_sh(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
+                       int kind, float opacity_scale, ws_refit* refit, const ws_refit_sh_params* params, uint32_t epochs, uint32_t views_per_step,
+                       uint32_t* steps);
 /* ---- Saving a point cloud: the resident planes back to an INRIA 3DGS .ply (no counterpart in the reference) -------------------------
  * The last step of prune -> refit -> evaluate: a resident, uncompressed cloud written as the file this library, the reference
  * viewer and every other 3DGS tool read.  The resident scene holds the covariance (six f16 halves) and the opacity after the

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "ply_encode.h"
+#include "sh_gradient.h"
 #include "ws_internal.h"
 
 namespace ws {
@@ -460,6 +461,30 @@ int ws_ply_rows_encode(const void* gaussians, const void* sh, uint32_t n, uint32
         tail[5] = ec.q1;
         tail[6] = ec.q2;
         tail[7] = ec.q3;
+    }
+    return WS_OK;
+}
+
+// The host twin of k_sh_spread: sh_gradient.h's definition, one row per Gaussian, the kernel's operations in its order.  The
+// sums here are per Gaussian ([n][ncoef][3] and [n]), not per plane.
+int ws_sh_spread_rows(const int64_t* q4, const float* xyz, const float* cam, uint32_t n, uint32_t sh_deg, uint32_t active_deg,
+                      int64_t* q_sh, int64_t* q_opacity) {
+    if ((!q4 || !xyz || !cam) && n) return fail(WS_ERR_INVALID, "ws_sh_spread_rows: null argument");
+    if (sh_deg > 3) return fail(WS_ERR_UNSUPPORTED, "ws_sh_spread_rows: sh_deg > 3");
+    const uint32_t ncoef = (sh_deg + 1) * (sh_deg + 1), nact = sh_active_coefs(active_deg, sh_deg);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t* q = q4 + i * 4;
+        if ((q[0] | q[1] | q[2] | q[3]) == 0) continue;
+        if (q_opacity) q_opacity[i] = static_cast<int64_t>(static_cast<uint64_t>(q_opacity[i]) + static_cast<uint64_t>(q[3]));
+        if (!q_sh) continue;
+        uint64_t* s = reinterpret_cast<uint64_t*>(q_sh) + i * 3 * ncoef;  // (two's-complement addition, as the device's)
+        for (uint32_t ch = 0; ch < 3; ++ch) s[ch] += static_cast<uint64_t>(q[ch]);
+        if (nact <= 1u) continue;
+        float dir[3], bas[SH_MAX_COEFS];
+        sh_spread_dir(xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2], cam, dir);
+        sh_spread_basis(dir[0], dir[1], dir[2], bas);
+        for (uint32_t k = 1; k < nact; ++k)
+            for (uint32_t ch = 0; ch < 3; ++ch) s[3 * k + ch] += static_cast<uint64_t>(sh_spread_term(q[ch], bas[k]));
     }
     return WS_OK;
 }

@@ -43,4 +43,33 @@ int launch_refit_step(const RefitParams& p, hipStream_t stream);
 // master[i] = the four halves widened to f32, m[i] = v[i] = 0
 int launch_refit_init(const uint4* planes, uint32_t n, float4* master, float4* m, float4* v, hipStream_t stream);
 
+// ---- the rest coefficients (include/websplat.h "SH gradients", ws_refit_step_sh) ----
+// Element e = 3 coef + ch of the 96-B SH record is half e % 8 of plane 2 + e / 8.  The planes a cloud of ncoef coefficients needs:
+// 1, 2, 4, 6 at degrees 0 .. 3; the last one ends in 5, 4, 5, 0 halves of padding that no step writes.
+inline uint32_t refit_sh_planes(uint32_t ncoef) { return (3u * ncoef + 7u) / 8u; }
+
+// One step over every Gaussian from a ws_shgrad's sums.  base.sums is not read: the DC triple takes elements 0 .. 2 of sh_sums, the
+// opacity element 3 ncoef.
+struct RefitShParams {
+    RefitParams base;
+    const unsigned long long* sh_sums;  // [3 ncoef + 1][n] two's-complement q32 sums, one plane per element (sh_gradient.h)
+    float* sh_master;                   // [3 (ncoef - 1)][n] f32 masters of the rest elements, plane e - 3 for element e;
+    float* sh_m;                        //   nullptr with ncoef == 1
+    float* sh_v;
+    uint32_t ncoef;
+    float lr_sh;                        // 0 freezes the rest group
+    double u_sh;                        // colour_unit: no C0 here, the basis is in the sum already
+};
+
+// TO THE BIT.  k_refit_step_sh, one thread per (Gaussian, SH plane), grid (ceil(n / 256), refit_sh_planes(ncoef)), or one row of
+// blocks when lr_sh == 0.  The thread of plane 2 takes channels 0 .. 3 exactly as launch_refit_step does.  A rest element e of a
+// group whose rate is not 0 takes the same step with g = (float)((double)(int64_t)q[e] * u_sh), lr = lr_sh and the clamp +-65504;
+// x', m', v' go to plane e - 3 of the three arrays, f16(x') to its half.  Each thread loads its 16-B chunk once and, if it stepped
+// any of its halves, stores it once as a whole: the halves it did not step (a frozen group's; the first half of coefficient 1
+// beside a moving DC; the padding) go back with the bits they were read with.  No 2-byte store, no scratch.
+int launch_refit_step_sh(const RefitShParams& p, hipStream_t stream);
+
+// master[e - 3][i] = half e of Gaussian i widened to f32, m = v = 0, for 3 <= e < 3 ncoef
+int launch_refit_init_sh(const uint4* planes, uint32_t n, uint32_t ncoef, float* master, float* m, float* v, hipStream_t stream);
+
 }  // namespace ws

@@ -18,6 +18,7 @@
 #include "gradient.h"
 #include "ply_encode.h"
 #include "refit.h"
+#include "sh_gradient.h"
 #include "removal.h"
 #include "values.h"
 #include "ws_internal.h"
@@ -145,6 +146,8 @@ struct PreparedFrame {
     bool contrib = false;            // K1 kept the source indices (ws_renderer_enable_contrib was on)
     bool depth = false;              // K1 wrote the z plane (ws_renderer_enable_depth was on)
     float znear = 0.0f, zfar = 0.0f; // K1Params::znear / zfar (the composite's NDC occluder)
+    float cam_pos[3] = {0.0f, 0.0f, 0.0f};  // view_inv[12..14] of K1's camera uniform: where K1 takes the SH direction from
+    uint32_t max_sh_deg = 0;         // of K1's settings uniform (both read by ws_renderer_accumulate_sh_gradient)
     FrameArrays arrays;
     float* k1_depths = nullptr;      // the z plane the prepare() in progress writes (nullptr: depth off)
     unsigned long long* trace_slot = nullptr;  // the frame's slot of ws_renderer::frame_trace (nullptr: not traced)
@@ -1194,6 +1197,8 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     kp.zfar = -kp.cam.proj[3 * 4 + 2] / (kp.cam.proj[2 * 4 + 2] - 1.0f);
     r->frame.znear = kp.znear;
     r->frame.zfar = kp.zfar;
+    for (int i = 0; i < 3; ++i) r->frame.cam_pos[i] = kp.cam.view_inv[12 + i];
+    r->frame.max_sh_deg = kp.rs.max_sh_deg;
     // fade-in (preprocess.wgsl:196-203): once walltime is past (largest possible dd) + 1, smoothstep(walltime - dd) is exactly
     // 1 for every Gaussian and the kernel skips the computation.  One rule, dd = 5 |centre - xyz| / extend bounded two ways:
     //   * every Gaussian that reaches k1_math lies inside the bbox (the default clip box IS the bbox; a user box may admit
@@ -2444,6 +2449,18 @@ struct ws_grad {
 };
 static_assert(WS_GRAD_CHANNELS == GRAD_CHANNELS, "the ABI's channel count is the kernel's");
 
+// ---- SH gradients (include/websplat.h "SH gradients"; sh_gradient.hip) ----
+struct ws_shgrad {
+    ws_context* ctx = nullptr;
+    uint32_t num_points = 0;
+    uint32_t sh_deg = 0, ncoef = 1;
+    DeviceBuf<unsigned long long> sums;     // [3 ncoef + 1][num_points]: one plane per element, the opacity's last
+    DeviceBuf<unsigned long long> scratch;  // [num_points][WS_GRAD_CHANNELS]: one frame's sums, zero between the calls
+    uint32_t frames = 0;
+    hipStream_t last_stream = nullptr;
+    size_t elements() const { return (size_t)3 * ncoef + 1; }
+};
+
 extern "C" {
 
 int ws_grad_create(ws_context* ctx, uint32_t num_points, ws_grad** out) {
@@ -2506,10 +2523,27 @@ int ws_renderer_accumulate_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_
     return ws_internal_gradient_passes(r, pc, g, p, stream, 3u);
 }
 
+// ... and the same two launches into the accumulator's scratch, then k_sh_spread
+int ws_renderer_accumulate_sh_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream) {
+    return ws_internal_sh_gradient_passes(r, pc, g, p, stream, 3u);
+}
+
 }  // extern "C"
 
+// One sequence for both accumulators: exactly one of g and sh is looked at (sh when `spread`)
+static int gradient_passes(const std::string& who, ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, ws_shgrad* sh, bool spread,
+                           const ws_gradient_params* p, void* stream_v, unsigned passes);
+
 int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    const std::string who("ws_renderer_accumulate_gradient");
+    return gradient_passes("ws_renderer_accumulate_gradient", r, pc, g, nullptr, false, p, stream_v, passes);
+}
+
+int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
+    return gradient_passes("ws_renderer_accumulate_sh_gradient", r, pc, nullptr, g, true, p, stream_v, passes);
+}
+
+static int gradient_passes(const std::string& who, ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, ws_shgrad* sh, bool spread,
+                           const ws_gradient_params* p, void* stream_v, unsigned passes) {
     if (!p) return fail(WS_ERR_INVALID, who + ": null params");
     if (p->reserved0 != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
     for (uint32_t w : p->reserved)
@@ -2523,9 +2557,12 @@ int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad
         return fail(WS_ERR_INVALID, who + ": d_grad: pointer and grad_pitch_bytes must be multiples of 16");
     if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
         return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
-    if (!r || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
-    const int state = check_weights_frame(r, pc, who, g->num_points == pc->num_points, "the accumulator was created for another number of points");
+    if (!r || !pc || (spread ? !sh : !g)) return fail(WS_ERR_INVALID, who + ": null argument");
+    const uint32_t acc_points = spread ? sh->num_points : g->num_points;
+    const int state = check_weights_frame(r, pc, who, acc_points == pc->num_points, "the accumulator was created for another number of points");
     if (state) return state;
+    if (spread && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no SH gradients (its codebooks are shared between Gaussians)");
+    if (spread && sh->sh_deg != pc->sh_deg) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another SH degree");
     if (p->grad_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_grad: grad_pitch_bytes below 16 x the viewport's width");
     if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
     RemovalParams rp;
@@ -2543,15 +2580,110 @@ int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad
     gp.grad_pitch = p->grad_pitch_bytes;
     gp.scale = p->scale;
     gp.opacity_scale = p->opacity_scale;
-    gp.sums = g->sums.get();
+    gp.sums = spread ? sh->scratch.get() : g->sums.get();
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     KernelMarks* km = launch_begin(r, stream);
     int rc = (passes & 1u) ? launch_removal_base(rp, stream) : WS_OK;
     if (rc == WS_OK && (passes & 2u)) rc = launch_gradient(gp, stream);
-    rc = launch_done(rc, r, nullptr, stream, km, passes == 1u ? "k_removal_base" : passes == 2u ? "k_gradient" : "k_removal_base+k_gradient");
-    if (rc == WS_OK && (passes & 2u)) ++g->frames, g->last_stream = stream;
+    if (rc == WS_OK && (passes & 2u) && spread) {
+        ShSpreadParams sp;
+        sp.planes = pc->planes.get();
+        sp.scratch = sh->scratch.get();
+        sp.sums = sh->sums.get();
+        sp.n = sh->num_points;
+        sp.ncoef = sh->ncoef;
+        sp.nact = sh_active_coefs(r->frame.max_sh_deg, sh->sh_deg);
+        for (int i = 0; i < 3; ++i) sp.cam[i] = r->frame.cam_pos[i];
+        rc = launch_sh_spread(sp, stream);
+    }
+    const char* const marks[2][3] = {{"k_removal_base", "k_gradient", "k_removal_base+k_gradient"},
+                                     {"k_removal_base", "k_gradient+k_sh_spread", "k_removal_base+k_gradient+k_sh_spread"}};
+    rc = launch_done(rc, r, nullptr, stream, km, marks[spread ? 1 : 0][passes == 1u ? 0 : passes == 2u ? 1 : 2]);
+    if (rc == WS_OK && (passes & 2u)) {
+        if (spread) ++sh->frames, sh->last_stream = stream;
+        else ++g->frames, g->last_stream = stream;
+    }
     return rc;
 }
+
+extern "C" {
+
+int ws_shgrad_create(ws_context* ctx, uint32_t num_points, uint32_t sh_deg, ws_shgrad** out) {
+    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_shgrad_create: null argument");
+    *out = nullptr;
+    if (num_points == 0) return fail(WS_ERR_INVALID, "ws_shgrad_create: no points");
+    if (sh_deg > 3) return fail(WS_ERR_UNSUPPORTED, "ws_shgrad_create: sh_deg > 3");
+    std::unique_ptr<ws_shgrad, SyncedDelete> g(new (std::nothrow) ws_shgrad());
+    if (!g) return fail(WS_ERR_OOM, "ws_shgrad_create: host allocation failed");
+    g->ctx = ctx;
+    g->num_points = num_points;
+    g->sh_deg = sh_deg;
+    g->ncoef = (sh_deg + 1) * (sh_deg + 1);
+    WS_TRY(g->sums.alloc(g->elements() * num_points));
+    WS_TRY(g->scratch.alloc((size_t)num_points * GRAD_CHANNELS));
+    WS_HIP(hipMemsetAsync(g->scratch.get(), 0, g->scratch.bytes(), nullptr));
+    WS_TRY(ws_shgrad_reset(g.get(), nullptr));
+    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_shgrad_create: device sync failed");
+    *out = g.release();
+    return WS_OK;
+}
+
+void ws_shgrad_destroy(ws_shgrad* g) { SyncedDelete()(g); }
+
+// (the scratch is zero between the calls by k_sh_spread's own doing; a reset leaves it alone)
+int ws_shgrad_reset(ws_shgrad* g, void* stream_v) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_shgrad_reset: null accumulator");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    WS_HIP(hipMemsetAsync(g->sums.get(), 0, g->sums.bytes(), stream));
+    g->frames = 0;
+    g->last_stream = stream;
+    return WS_OK;
+}
+
+uint32_t ws_shgrad_num_points(const ws_shgrad* g) { return g ? g->num_points : 0u; }
+uint32_t ws_shgrad_sh_deg(const ws_shgrad* g) { return g ? g->sh_deg : 0u; }
+uint32_t ws_shgrad_frames(const ws_shgrad* g) { return g ? g->frames : 0u; }
+
+// The device keeps one plane per element; the caller's rows are per Gaussian: the transposes are the host's.
+int ws_shgrad_download(ws_shgrad* g, uint32_t capacity, int64_t* q_sh, int64_t* q_opacity) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_shgrad_download: null accumulator");
+    if ((q_sh || q_opacity) && capacity < g->num_points) return fail(WS_ERR_INVALID, "ws_shgrad_download: capacity smaller than the number of points");
+    WS_HIP(hipStreamSynchronize(g->last_stream));
+    const size_t n = g->num_points, el = (size_t)3 * g->ncoef;
+    if (q_opacity) WS_TRY(copy_d2h(q_opacity, g->sums.get() + el * n, n * sizeof(int64_t), g->last_stream));
+    if (!q_sh) return WS_OK;
+    std::unique_ptr<int64_t[]> st(new (std::nothrow) int64_t[el * n]);
+    if (!st) return fail(WS_ERR_OOM, "ws_shgrad_download: host allocation failed");
+    WS_TRY(copy_d2h(st.get(), g->sums.get(), el * n * sizeof(int64_t), g->last_stream));
+    for (size_t e = 0; e < el; ++e)
+        for (size_t i = 0; i < n; ++i) q_sh[i * el + e] = st[e * n + i];
+    return WS_OK;
+}
+
+int ws_shgrad_add(ws_shgrad* g, const int64_t* q_sh, const int64_t* q_opacity, uint32_t n_rows) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_shgrad_add: null accumulator");
+    if (n_rows < g->num_points) return fail(WS_ERR_INVALID, "ws_shgrad_add: fewer values than the accumulator has points");
+    if (!q_sh && !q_opacity) return WS_OK;
+    const size_t n = g->num_points, el = (size_t)3 * g->ncoef, words = g->sums.count();
+    std::unique_ptr<int64_t[]> st(new (std::nothrow) int64_t[words]());  // (zeros where a pointer is NULL)
+    if (!st) return fail(WS_ERR_OOM, "ws_shgrad_add: host allocation failed");
+    if (q_sh)
+        for (size_t e = 0; e < el; ++e)
+            for (size_t i = 0; i < n; ++i) st[e * n + i] = q_sh[i * el + e];
+    if (q_opacity) std::memcpy(st.get() + el * n, q_opacity, n * sizeof(int64_t));
+    DeviceBuf<unsigned long long> d_other;  // (let go at the return, behind the stream sync)
+    hipStream_t stream = g->last_stream;
+    int rc = d_other.alloc(words);
+    if (rc == WS_OK) {
+        const hipError_t e = hipMemcpyAsync(d_other.get(), st.get(), words * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) rc = hip_fail(e, "ws_shgrad_add: upload");
+    }
+    if (rc == WS_OK) rc = launch_grad_merge(g->sums.get(), d_other.get(), words, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_shgrad_add: stream sync failed");
+    return rc;
+}
+
+}  // extern "C"
 
 extern "C" {
 
@@ -2593,7 +2725,13 @@ struct ws_refit {
     uint32_t steps = 0;
     double p1 = 1.0, p2 = 1.0;           // beta1^steps, beta2^steps
     hipStream_t last_stream = nullptr;
+    // ws_refit_enable_sh: the rest coefficients, one plane per element ([3 (ncoef - 1)][num_points]); empty at degree 0
+    uint32_t ncoef = 1;                  // (sh_deg + 1)^2 of the cloud
+    bool sh_enabled = false;
+    DeviceBuf<float> sh_master, sh_m, sh_v;
 };
+static_assert(sizeof(ws_refit_sh_params) == 72 && offsetof(ws_refit_sh_params, lr_sh) == 56 && offsetof(ws_refit_sh_params, reserved) == 60,
+              "ws_refit_sh_params layout (websplat/_lib.py mirrors it)");
 static_assert(sizeof(ws_refit_params) == 56 && offsetof(ws_refit_params, colour_unit) == 24 && offsetof(ws_refit_params, reserved) == 40,
               "ws_refit_params layout (websplat/_lib.py mirrors it)");
 
@@ -2614,6 +2752,40 @@ int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& 
     return WS_OK;
 }
 
+int ws_internal_refit_check_sh_params(const ws_refit_sh_params* p, const std::string& who, bool units) {
+    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
+    if (const int rc = ws_internal_refit_check_params(&p->base, who, units)) return rc;
+    for (uint32_t w : p->reserved)
+        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
+    if (!std::isfinite(p->lr_sh) || !(p->lr_sh >= 0.0f)) return fail(WS_ERR_INVALID, who + ": lr_sh must be finite and not below 0");
+    return WS_OK;
+}
+
+// The host's share of a step, common to ws_refit_step and ws_refit_step_sh: p1, p2 are the powers AFTER this step (committed by
+// the caller only when the launch went out); `sums` is the caller's.
+static RefitParams refit_kernel_params(const ws_refit* rf, ws_pointcloud* pc, const ws_refit_params* p, double p1, double p2) {
+    RefitParams kp;
+    kp.planes = pc->planes.get();
+    kp.sums = nullptr;
+    kp.master = rf->master.get();
+    kp.m = rf->m.get();
+    kp.v = rf->v.get();
+    kp.n = rf->num_points;
+    kp.lr_colour = p->lr_colour;
+    kp.lr_opacity = p->lr_opacity;
+    kp.beta1 = p->beta1;
+    kp.beta2 = p->beta2;
+    kp.omb1 = 1.0f - p->beta1;
+    kp.omb2 = 1.0f - p->beta2;
+    kp.bc1 = (float)(1.0 - p1);
+    kp.bc2 = (float)(1.0 - p2);
+    kp.eps = p->eps;
+    kp.opacity_min = p->opacity_min;
+    kp.u_colour = p->colour_unit * REFIT_C0_F64;
+    kp.u_opacity = p->opacity_unit;
+    return kp;
+}
+
 extern "C" {
 
 int ws_refit_create(ws_context* ctx, const ws_pointcloud* pc, ws_refit** out) {
@@ -2627,6 +2799,7 @@ int ws_refit_create(ws_context* ctx, const ws_pointcloud* pc, ws_refit** out) {
     rf->pc = pc;
     rf->planes = pc->planes.get();
     rf->num_points = pc->num_points;
+    rf->ncoef = (pc->sh_deg + 1) * (pc->sh_deg + 1);
     WS_TRY(rf->master.alloc(rf->num_points));
     WS_TRY(rf->m.alloc(rf->num_points));
     WS_TRY(rf->v.alloc(rf->num_points));
@@ -2651,31 +2824,87 @@ int ws_refit_step(ws_refit* rf, ws_pointcloud* pc, const ws_grad* g, const ws_re
         return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
     if (g->num_points != rf->num_points) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another number of points");
     const double p1 = rf->p1 * (double)p->beta1, p2 = rf->p2 * (double)p->beta2;
-    RefitParams kp;
-    kp.planes = pc->planes.get();
+    RefitParams kp = refit_kernel_params(rf, pc, p, p1, p2);
     kp.sums = g->sums.get();
-    kp.master = rf->master.get();
-    kp.m = rf->m.get();
-    kp.v = rf->v.get();
-    kp.n = rf->num_points;
-    kp.lr_colour = p->lr_colour;
-    kp.lr_opacity = p->lr_opacity;
-    kp.beta1 = p->beta1;
-    kp.beta2 = p->beta2;
-    kp.omb1 = 1.0f - p->beta1;
-    kp.omb2 = 1.0f - p->beta2;
-    kp.bc1 = (float)(1.0 - p1);
-    kp.bc2 = (float)(1.0 - p2);
-    kp.eps = p->eps;
-    kp.opacity_min = p->opacity_min;
-    kp.u_colour = p->colour_unit * REFIT_C0_F64;
-    kp.u_opacity = p->opacity_unit;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (const int rc = launch_refit_step(kp, stream)) return rc;
     rf->p1 = p1;
     rf->p2 = p2;
     ++rf->steps;
     rf->last_stream = stream;
+    return WS_OK;
+}
+
+// The rest coefficients join: masters and moments of their own, widened from the stored halves.  Refused once a step has been
+// taken: the bias-correction powers are the object's, shared by every element.
+int ws_refit_enable_sh(ws_refit* rf, const ws_pointcloud* pc, void* stream_v) {
+    const std::string who("ws_refit_enable_sh");
+    if (!rf || !pc) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (pc != rf->pc || pc->planes.get() != rf->planes || pc->compressed || pc->num_points != rf->num_points)
+        return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
+    if (rf->sh_enabled) return WS_OK;
+    if (rf->steps > 0) return fail(WS_ERR_INVALID, who + ": steps have been taken already (the bias-correction powers are shared)");
+    const size_t count = (size_t)3 * (rf->ncoef - 1) * rf->num_points;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (count) {
+        DeviceBuf<float> master, m, v;
+        WS_TRY(master.alloc(count));
+        WS_TRY(m.alloc(count));
+        WS_TRY(v.alloc(count));
+        WS_TRY(launch_refit_init_sh(rf->planes, rf->num_points, rf->ncoef, master.get(), m.get(), v.get(), stream));
+        rf->sh_master = std::move(master);
+        rf->sh_m = std::move(m);
+        rf->sh_v = std::move(v);
+        rf->last_stream = stream;
+    }
+    rf->sh_enabled = true;
+    return WS_OK;
+}
+
+int ws_refit_step_sh(ws_refit* rf, ws_pointcloud* pc, const ws_shgrad* g, const ws_refit_sh_params* p, void* stream_v) {
+    const std::string who("ws_refit_step_sh");
+    if (const int rc = ws_internal_refit_check_sh_params(p, who, true)) return rc;
+    if (!rf || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (pc != rf->pc || pc->planes.get() != rf->planes || pc->compressed || pc->num_points != rf->num_points)
+        return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
+    if (!rf->sh_enabled) return fail(WS_ERR_INVALID, who + ": ws_refit_enable_sh was not called");
+    if (g->num_points != rf->num_points) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another number of points");
+    if (g->ncoef != rf->ncoef) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another SH degree");
+    const double p1 = rf->p1 * (double)p->base.beta1, p2 = rf->p2 * (double)p->base.beta2;
+    RefitShParams kp;
+    kp.base = refit_kernel_params(rf, pc, &p->base, p1, p2);
+    kp.sh_sums = g->sums.get();
+    kp.sh_master = rf->sh_master.get();
+    kp.sh_m = rf->sh_m.get();
+    kp.sh_v = rf->sh_v.get();
+    kp.ncoef = rf->ncoef;
+    kp.lr_sh = rf->ncoef > 1 ? p->lr_sh : 0.0f;
+    kp.u_sh = p->base.colour_unit;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (const int rc = launch_refit_step_sh(kp, stream)) return rc;
+    rf->p1 = p1;
+    rf->p2 = p2;
+    ++rf->steps;
+    rf->last_stream = stream;
+    return WS_OK;
+}
+
+int ws_refit_download_sh(ws_refit* rf, uint32_t capacity, float* master, float* m, float* v) {
+    if (!rf) return fail(WS_ERR_INVALID, "ws_refit_download_sh: null object");
+    if (!rf->sh_enabled) return fail(WS_ERR_INVALID, "ws_refit_download_sh: ws_refit_enable_sh was not called");
+    if ((master || m || v) && capacity < rf->num_points) return fail(WS_ERR_INVALID, "ws_refit_download_sh: capacity smaller than the number of points");
+    WS_HIP(hipStreamSynchronize(rf->last_stream));
+    const size_t n = rf->num_points, el = (size_t)3 * (rf->ncoef - 1);
+    if (el == 0 || (!master && !m && !v)) return WS_OK;
+    std::unique_ptr<float[]> st(new (std::nothrow) float[el * n]);
+    if (!st) return fail(WS_ERR_OOM, "ws_refit_download_sh: host allocation failed");
+    const std::pair<float*, const float*> jobs[3] = {{master, rf->sh_master.get()}, {m, rf->sh_m.get()}, {v, rf->sh_v.get()}};
+    for (const auto& job : jobs) {
+        if (!job.first) continue;
+        WS_TRY(copy_d2h(st.get(), job.second, el * n * sizeof(float), rf->last_stream));
+        for (size_t e = 0; e < el; ++e)
+            for (size_t i = 0; i < n; ++i) job.first[i * el + e] = st[e * n + i];
+    }
     return WS_OK;
 }
 

@@ -543,6 +543,12 @@ int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad
 // they are not looked at) (ws_api.cpp)
 struct ws_refit_params;
 int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& who, bool units);
+// the same two for "SH gradients": ws_renderer_accumulate_sh_gradient in two steps (passes = 2: k_gradient + k_sh_spread), and what
+// ws_refit_step_sh judges from its descriptor alone, for ws_scene_accumulate_sh_gradient and ws_scene_refit_sh (ws_api.cpp)
+struct ws_shgrad;
+struct ws_refit_sh_params;
+int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream, unsigned passes);
+int ws_internal_refit_check_sh_params(const ws_refit_sh_params* p, const std::string& who, bool units);
 
 // opaque handle definitions -------------------------------------------------------------------------
 // The depth sort of a frame (V keys + store index + footprint word):

@@ -1,7 +1,8 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
 //                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]
-//                     [--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]] [--save OUT.ply]
+//                     [--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs] [--refit-sh [--lr-sh Z]]]
+//                     [--save OUT.ply]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
 // another point cloud (a pruned one against its parent); --gt against <dir>/<img_name>[.png], rendered at each PNG's size.
 // --blame N: behind that table, the N Gaussians of the scene with the largest error sum over the split (websplat.h "Attributing a
@@ -15,6 +16,8 @@
 // --refit EPOCHS: behind all that, Adam steps on the scene's DC colours and opacities over the TRAIN split against --ref / --gt
 // (websplat.h "Refitting colour and opacity"; a step after every B views, default: one per epoch), then the first table again,
 // of the refitted scene, under a line "after refit: EPOCHS epochs, S steps".  A compressed scene is refused.
+// --refit-sh: the refit also moves the higher SH coefficients (websplat.h "SH gradients"), at the rate --lr-sh (default:
+// lr_colour / 20, the 3DGS convention); the line then ends ", SH degree D".
 // --save OUT.ply: at the end, the scene as it then stands -- after --refit, the refitted one -- as an INRIA 3DGS .ply (websplat.h
 // "Saving a point cloud"), and one line "saved OUT.ply: N Gaussians, B bytes".  It needs no second image either.  A compressed
 // scene is refused with the library's message.
@@ -51,8 +54,8 @@ int main(int argc, char** argv) {
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
     long blame = 0, removal = 0, gradient = 0, refit = 0, views_per_step = 0;
-    double lr_colour = 0.0025, lr_opacity = 0.01;
-    bool have_refit_option = false;
+    double lr_colour = 0.0025, lr_opacity = 0.01, lr_sh = -1.0;  // (lr_sh < 0: lr_colour / 20)
+    bool have_refit_option = false, refit_sh = false;
     int kind = WS_ERROR_SQ;
     bool bad = argc < 3, have_error = false;
     for (int i = 3; i < argc && !bad; ++i) {
@@ -72,8 +75,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--views-per-step") && i + 1 < argc) {
             have_refit_option = true;
             bad = !positive(argv[++i], &views_per_step);
-        } else if ((!std::strcmp(argv[i], "--lr-colour") || !std::strcmp(argv[i], "--lr-opacity")) && i + 1 < argc) {
-            double& lr = !std::strcmp(argv[i], "--lr-colour") ? lr_colour : lr_opacity;
+        } else if (!std::strcmp(argv[i], "--refit-sh")) {
+            have_refit_option = refit_sh = true;
+        } else if ((!std::strcmp(argv[i], "--lr-colour") || !std::strcmp(argv[i], "--lr-opacity") || !std::strcmp(argv[i], "--lr-sh")) && i + 1 < argc) {
+            double& lr = !std::strcmp(argv[i], "--lr-colour") ? lr_colour : !std::strcmp(argv[i], "--lr-opacity") ? lr_opacity : lr_sh;
             char* end = nullptr;
             lr = std::strtod(argv[++i], &end);
             have_refit_option = true;
@@ -90,12 +95,13 @@ int main(int argc, char** argv) {
     if (have_error && blame == 0 && removal == 0 && gradient == 0 && refit == 0) bad = true;
     if ((removal > 0 || gradient > 0 || refit > 0) && kind == WS_ERROR_DSSIM) bad = true;
     if (have_refit_option && refit == 0) bad = true;
+    if (lr_sh >= 0.0 && !refit_sh) bad = true;
     const bool compare = ref != nullptr || gt != nullptr;  // (--removal alone needs no second image)
     if ((blame > 0 || gradient > 0 || refit > 0) && !compare) bad = true;
     if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0 && !save)) {
         std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
                              "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]] "
-                             "[--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs]] [--save OUT.ply]\n", argv[0]);
+                             "[--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs] [--refit-sh [--lr-sh Z]]] [--save OUT.ply]\n", argv[0]);
         return 2;
     }
     ws_context* ctx = nullptr;
@@ -214,19 +220,24 @@ int main(int argc, char** argv) {
     }
     ws_refit* fit = nullptr;
     if (rc == WS_OK && refit > 0) {
-        ws_refit_params rp;
-        std::memset(&rp, 0, sizeof rp);
+        ws_refit_sh_params sp;
+        std::memset(&sp, 0, sizeof sp);
+        ws_refit_params& rp = sp.base;
         rp.lr_colour = (float)lr_colour;
         rp.lr_opacity = (float)lr_opacity;
         rp.beta1 = 0.9f;
         rp.beta2 = 0.999f;
         rp.eps = 1e-15f;
         rp.opacity_min = 0.0f;
+        sp.lr_sh = lr_sh >= 0.0 ? (float)lr_sh : rp.lr_colour / 20.0f;
         uint32_t steps = 0;
         rc = ws_refit_create(ctx, pc, &fit);
-        if (rc == WS_OK) rc = ws_scene_refit(ctx, pc, scene, WS_SPLIT_TRAIN, ref_pc, gt, kind, 1.0f / 128.0f, fit, &rp, (uint32_t)refit, (uint32_t)views_per_step, &steps);
+        if (rc == WS_OK)
+            rc = refit_sh ? ws_scene_refit_sh(ctx, pc, scene, WS_SPLIT_TRAIN, ref_pc, gt, kind, 1.0f / 128.0f, fit, &sp, (uint32_t)refit, (uint32_t)views_per_step, &steps)
+                          : ws_scene_refit(ctx, pc, scene, WS_SPLIT_TRAIN, ref_pc, gt, kind, 1.0f / 128.0f, fit, &rp, (uint32_t)refit, (uint32_t)views_per_step, &steps);
         if (rc == WS_OK) {
-            std::printf("after refit: %ld epochs, %u steps\n", refit, steps);
+            if (refit_sh) std::printf("after refit: %ld epochs, %u steps, SH degree %u\n", refit, steps, ws_pointcloud_sh_deg(pc));
+            else std::printf("after refit: %ld epochs, %u steps\n", refit, steps);
             rc = table();
         }
     }

@@ -207,7 +207,12 @@ class ws_refit_params(C.Structure):
                 ("opacity_min", C.c_float), ("colour_unit", C.c_double), ("opacity_unit", C.c_double), ("reserved", C.c_uint32 * 4)]
 
 
+class ws_refit_sh_params(C.Structure):
+    _fields_ = [("base", ws_refit_params), ("lr_sh", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 assert C.sizeof(ws_refit_params) == 56
+assert C.sizeof(ws_refit_sh_params) == 72
 assert C.sizeof(ws_gradient_params) == 72
 assert C.sizeof(ws_removal_params) == 64
 assert C.sizeof(ws_image_view) == 40
@@ -389,6 +394,23 @@ SIGNATURES = {
     "ws_refit_download": (C.c_int, [_P, C.c_uint32, _f32p, _f32p, _f32p]),
     "ws_scene_refit": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, _P, C.POINTER(ws_refit_params), C.c_uint32,
                                  C.c_uint32, _u32p]),
+    "ws_shgrad_create": (C.c_int, [_P, C.c_uint32, C.c_uint32, _PP]),
+    "ws_shgrad_destroy": (None, [_P]),
+    "ws_shgrad_reset": (C.c_int, [_P, _P]),
+    "ws_shgrad_num_points": (C.c_uint32, [_P]),
+    "ws_shgrad_sh_deg": (C.c_uint32, [_P]),
+    "ws_shgrad_frames": (C.c_uint32, [_P]),
+    "ws_shgrad_download": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ws_shgrad_add": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_uint32]),
+    "ws_renderer_accumulate_sh_gradient": (C.c_int, [_P, _P, _P, C.POINTER(ws_gradient_params), _P]),
+    "ws_sh_spread_rows": (C.c_int, [C.POINTER(C.c_int64), _f32p, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64)]),
+    "ws_scene_accumulate_sh_gradient": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, C.c_float, _P, _u32p]),
+    "ws_refit_enable_sh": (C.c_int, [_P, _P, _P]),
+    "ws_refit_step_sh": (C.c_int, [_P, _P, _P, C.POINTER(ws_refit_sh_params), _P]),
+    "ws_refit_download_sh": (C.c_int, [_P, C.c_uint32, _f32p, _f32p, _f32p]),
+    "ws_scene_refit_sh": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, _P, C.POINTER(ws_refit_sh_params), C.c_uint32,
+                                    C.c_uint32, _u32p]),
 }
 
 

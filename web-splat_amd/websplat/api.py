@@ -740,6 +740,83 @@ class Grad:
         check(lib.ws_grad_add(self.handle, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0]))
 
 
+_i64p = C.POINTER(C.c_int64)
+
+
+class ShGrad:
+    """Per-Gaussian, per-coefficient gradient accumulators over frames (websplat.h "SH gradients"): for every Gaussian of a
+    cloud of num_points and degree sh_deg, 3 (sh_deg + 1)^2 signed q32 sums dL/d(sh[k][ch]) -- coefficient 0 holds the plain
+    colour sums of a Grad -- and dL/d(ln opacity)."""
+
+    def __init__(self, ctx: Context, num_points: int, sh_deg: int):
+        self.ctx = ctx
+        h = C.c_void_p()
+        check(lib.ws_shgrad_create(ctx.handle, int(num_points), int(sh_deg), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            lib.ws_shgrad_destroy(self.handle)
+            self.handle = None
+
+    def reset(self, stream=None):
+        check(lib.ws_shgrad_reset(self.handle, C.c_void_p(stream or 0)))
+
+    def num_points(self) -> int:
+        return lib.ws_shgrad_num_points(self.handle)
+
+    @property
+    def sh_deg(self) -> int:
+        return lib.ws_shgrad_sh_deg(self.handle)
+
+    @property
+    def frames(self) -> int:
+        """frames added since creation / the last reset"""
+        return lib.ws_shgrad_frames(self.handle)
+
+    def download(self) -> dict:
+        """{"sh": (N, ncoef, 3) int64, "opacity": (N,) int64}: the q32 sums per Gaussian (syncs)."""
+        n, ncoef = self.num_points(), (self.sh_deg + 1) ** 2
+        out = {"sh": np.empty((n, ncoef, 3), dtype=np.int64), "opacity": np.empty(n, dtype=np.int64)}
+        check(lib.ws_shgrad_download(self.handle, n, out["sh"].ctypes.data_as(_i64p), out["opacity"].ctypes.data_as(_i64p)))
+        return out
+
+    def add(self, sh=None, opacity=None):
+        """Exact merge of another accumulator's (or rank's) downloaded sums; either array may be left out."""
+        ncoef = (self.sh_deg + 1) ** 2
+        rows = []
+        if sh is not None:
+            sh = np.ascontiguousarray(sh, dtype=np.int64)
+            if sh.ndim != 3 or sh.shape[1:] != (ncoef, 3):
+                raise ValueError(f"ShGrad.add: want an (N, {ncoef}, 3) int64 array, got {sh.shape}")
+            rows.append(sh.shape[0])
+        if opacity is not None:
+            opacity = np.ascontiguousarray(opacity, dtype=np.int64)
+            if opacity.ndim != 1:
+                raise ValueError(f"ShGrad.add: want an (N,) int64 array of opacity sums, got {opacity.shape}")
+            rows.append(opacity.shape[0])
+        if not rows:
+            return
+        check(lib.ws_shgrad_add(self.handle, sh.ctypes.data_as(_i64p) if sh is not None else None,
+                                opacity.ctypes.data_as(_i64p) if opacity is not None else None, min(rows)))
+
+
+def sh_spread_rows(q4, xyz, cam, sh_deg: int, active_deg: int) -> dict:
+    """The host twin of the SH spread (ws_sh_spread_rows, no GPU needed): one frame's (N, 4) int64 Grad-layout sums, the (N, 3)
+    float32 positions and the camera position (view_inv[12:15]) -> {"sh": (N, ncoef, 3) int64, "opacity": (N,) int64}."""
+    q4 = np.ascontiguousarray(q4, dtype=np.int64)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    cam = np.ascontiguousarray(cam, dtype=np.float32)
+    if q4.ndim != 2 or q4.shape[1] != 4 or xyz.shape != (q4.shape[0], 3) or cam.shape != (3,):
+        raise ValueError("sh_spread_rows: want (N, 4) sums, (N, 3) positions and a camera position of 3")
+    n, ncoef = q4.shape[0], (int(sh_deg) + 1) ** 2
+    out = {"sh": np.zeros((n, ncoef, 3), dtype=np.int64), "opacity": np.zeros(n, dtype=np.int64)}
+    fp = C.POINTER(C.c_float)
+    check(lib.ws_sh_spread_rows(q4.ctypes.data_as(_i64p), xyz.ctypes.data_as(fp), cam.ctypes.data_as(fp), n, int(sh_deg), int(active_deg),
+                                out["sh"].ctypes.data_as(_i64p), out["opacity"].ctypes.data_as(_i64p)))
+    return out
+
+
 def _refit_params(lr_colour=0.0025, lr_opacity=0.01, beta1=0.9, beta2=0.999, eps=1e-15, opacity_min=0.0, colour_unit=1.0,
                   opacity_unit=1.0):
     p = L.ws_refit_params()
@@ -757,6 +834,7 @@ class Refit:
         h = C.c_void_p()
         check(lib.ws_refit_create(ctx.handle, pc.handle, C.byref(h)))
         self.handle = h
+        self._ncoef = (pc.sh_deg() + 1) ** 2
 
     def close(self):
         if self.handle:
@@ -776,17 +854,45 @@ class Refit:
         """One Adam step along grad's sums (enqueues only).  A unit left None makes the step one along the MEAN gradient of the
         frames in `grad`, accumulated through `scale` and `opacity_scale` (taken as the float32 values the accumulation used):
         1 / (2^32 * scale [* opacity_scale] * grad.frames)."""
+        colour_unit, opacity_unit = self._units("Refit.step", grad, colour_unit, opacity_unit, scale, opacity_scale)
+        p = _refit_params(lr_colour, lr_opacity, beta1, beta2, eps, opacity_min, colour_unit, opacity_unit)
+        check(lib.ws_refit_step(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def _units(who, grad, colour_unit, opacity_unit, scale, opacity_scale):
         if colour_unit is None or opacity_unit is None:
             per = L.WS_GRAD_SUM_SCALE * float(np.float32(scale))
             frames = grad.frames
             if frames == 0:
-                raise ValueError("Refit.step: the accumulator holds no frame: give colour_unit and opacity_unit")
+                raise ValueError(f"{who}: the accumulator holds no frame: give colour_unit and opacity_unit")
             if colour_unit is None:
                 colour_unit = 1.0 / (per * frames)
             if opacity_unit is None:
                 opacity_unit = 1.0 / (per * float(np.float32(opacity_scale)) * frames)
-        p = _refit_params(lr_colour, lr_opacity, beta1, beta2, eps, opacity_min, colour_unit, opacity_unit)
-        check(lib.ws_refit_step(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
+        return colour_unit, opacity_unit
+
+    def enable_sh(self, pc: "PointCloud", stream=None):
+        """The rest SH coefficients of `pc` join the step: masters and moments of their own (ws_refit_enable_sh; enqueues
+        only).  Before the first step; a second call is a no-op."""
+        check(lib.ws_refit_enable_sh(self.handle, pc.handle, C.c_void_p(stream or 0)))
+
+    def step_sh(self, pc: "PointCloud", shgrad: "ShGrad", lr_sh=None, lr_colour=0.0025, lr_opacity=0.01, beta1=0.9, beta2=0.999,
+                eps=1e-15, opacity_min=0.0, colour_unit=None, opacity_unit=None, scale=1.0, opacity_scale=1.0, stream=None):
+        """One Adam step along an ShGrad's sums (ws_refit_step_sh; enqueues only): the DC triple and the opacity as step() moves
+        them, the rest coefficients at the rate lr_sh (None: lr_colour / 20, the 3DGS convention; 0 freezes them).  Units as
+        step()."""
+        colour_unit, opacity_unit = self._units("Refit.step_sh", shgrad, colour_unit, opacity_unit, scale, opacity_scale)
+        p = L.ws_refit_sh_params()
+        p.base = _refit_params(lr_colour, lr_opacity, beta1, beta2, eps, opacity_min, colour_unit, opacity_unit)
+        p.lr_sh = p.base.lr_colour / 20.0 if lr_sh is None else lr_sh   # (of the float32 rate, as refit_scene takes it)
+        check(lib.ws_refit_step_sh(self.handle, pc.handle, shgrad.handle, C.byref(p), C.c_void_p(stream or 0)))
+
+    def download_sh(self) -> dict:
+        """{"master", "m", "v"}: (N, ncoef - 1, 3) float32 each -- the rest coefficients and their moments (syncs)."""
+        n, rest = self.num_points(), self._ncoef - 1
+        out = {k: np.empty((n, rest, 3), dtype=np.float32) for k in ("master", "m", "v")}
+        check(lib.ws_refit_download_sh(self.handle, n, *(out[k].ctypes.data_as(C.POINTER(C.c_float)) for k in ("master", "m", "v"))))
+        return out
 
     def download(self) -> dict:
         """{"master", "m", "v"}: (N, 4) float32 each -- DC r, g, b and the opacity; their first and second moments (syncs)."""
@@ -1002,17 +1108,38 @@ def accumulate_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene, sp
     return n.value
 
 
+def accumulate_sh_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, shgrad: "ShGrad", ref: "PointCloud" = None,
+                                 gt_dir: str = None, kind="sq", scale=1.0, opacity_scale=1.0) -> int:
+    """accumulate_gradient_scene's frames into an ShGrad: per Gaussian the gradients with respect to every SH coefficient and
+    the ln-opacity (ws_scene_accumulate_sh_gradient).  Returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_accumulate_sh_gradient(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+                                              None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(scale),
+                                              float(opacity_scale), shgrad.handle, C.byref(n)))
+    return n.value
+
+
 def refit_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, refit: "Refit", ref: "PointCloud" = None, gt_dir: str = None,
-                kind="sq", opacity_scale=1.0 / 128, epochs=1, views_per_step=0, **adam) -> int:
+                kind="sq", opacity_scale=1.0 / 128, epochs=1, views_per_step=0, sh=False, lr_sh=None, **adam) -> int:
     """`epochs` passes over the cameras of `split`, set up as accumulate_gradient_scene sets them up: the gradients of the frames'
     error against the cloud `ref` or the PNGs of `gt_dir`, and an Adam step of `refit` on `pc` after every `views_per_step` frames
-    (0 = one step per epoch) along their mean (ws_scene_refit).  **adam: Refit.step's rates, betas, eps and opacity_min.  Returns
-    the steps taken."""
+    (0 = one step per epoch) along their mean (ws_scene_refit).  **adam: Refit.step's rates, betas, eps and opacity_min.
+    sh=True: the rest SH coefficients move too, at the rate lr_sh (None: lr_colour / 20) -- ws_scene_refit_sh, which enables them
+    on `refit` if that has not been done.  Returns the steps taken."""
     p = _refit_params(**adam)
     n = C.c_uint32()
-    check(lib.ws_scene_refit(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
-                             None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(opacity_scale), refit.handle,
-                             C.byref(p), int(epochs), int(views_per_step), C.byref(n)))
+    tail = (int(epochs), int(views_per_step), C.byref(n))
+    head = (ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+            None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(opacity_scale), refit.handle)
+    if sh:
+        sp = L.ws_refit_sh_params()
+        sp.base = p
+        sp.lr_sh = p.lr_colour / 20.0 if lr_sh is None else lr_sh
+        check(lib.ws_scene_refit_sh(*head, C.byref(sp), *tail))
+    else:
+        if lr_sh is not None:
+            raise ValueError("refit_scene: lr_sh needs sh=True")
+        check(lib.ws_scene_refit(*head, C.byref(p), *tail))
     return n.value
 
 
@@ -1293,6 +1420,19 @@ class GaussianRenderer:
         loss's derivative (dL/dF_r, dL/dF_g, dL/dF_b, dL/dT_end) per pixel, an H x W x 4 float32 numpy array (uploaded for the
         call, which then waits for the launches) or a device pointer with `plane_pitch` bytes per row.  Needs enable_contrib()
         before prepare(); render() is not needed, no target changes.  base / base_ptr / base_pitch: as accumulate_removal."""
+        self._accumulate_gradient(lib.ws_renderer_accumulate_gradient, pc, grad, plane, background, scale, opacity_scale, base, stream,
+                                  plane_pitch, base_ptr, base_pitch)
+
+    def accumulate_sh_gradient(self, pc: PointCloud, shgrad: "ShGrad", plane, background=(0.0, 0.0, 0.0), scale=1.0, opacity_scale=1.0,
+                               base=False, stream=None, plane_pitch=None, base_ptr=None, base_pitch=None):
+        """accumulate_gradient into an ShGrad (ws_renderer_accumulate_sh_gradient): the same two launches into the accumulator's
+        scratch, then per Gaussian the colour sums times the SH basis of this frame's view direction, added to every coefficient
+        up to the prepared frame's degree.  Arguments as accumulate_gradient."""
+        self._accumulate_gradient(lib.ws_renderer_accumulate_sh_gradient, pc, shgrad, plane, background, scale, opacity_scale, base,
+                                  stream, plane_pitch, base_ptr, base_pitch)
+
+    def _accumulate_gradient(self, call, pc, grad, plane, background, scale, opacity_scale, base, stream, plane_pitch, base_ptr,
+                             base_pitch):
         p = L.ws_gradient_params()
         for i in range(3):
             p.background[i] = float(background[i])
@@ -1313,7 +1453,7 @@ class GaussianRenderer:
         with staged(self.ctx, host, stream, min_bytes=16) as d:
             if d is not None:
                 p.d_grad = d
-            check(lib.ws_renderer_accumulate_gradient(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
+            check(call(self.handle, pc.handle, grad.handle, C.byref(p), C.c_void_p(stream or 0)))
 
     def download_removal_base(self) -> np.ndarray:
         """H x W x 4 float32 (F_r, F_g, F_b, T_end) of what the last accumulate_removal(base=True) or accumulate_gradient(base=True) wrote (syncs)."""

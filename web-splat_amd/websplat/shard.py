@@ -75,3 +75,10 @@ def reduce_grad(q32, dist=None, device: str = "cpu"):
     if mag.numel() and float(mag.max().item()) >= 2.0 ** 62:
         raise OverflowError("reduce_grad: the reduced q32 sums may have left the int64 range")
     return tq.cpu().numpy()
+
+
+def reduce_shgrad(sums, dist=None, device: str = "cpu"):
+    """All-reduce the SH gradient sums of ranks that scored disjoint camera subsets (ShGrad.download(): {"sh": (N, ncoef, 3)
+    int64, "opacity": (N,) int64}) over the default process group: reduce_grad on each array, under its overflow rule.  Every
+    rank ends with what ShGrad.add needs to hold the accumulator one rank would have built from all cameras."""
+    return {"sh": reduce_grad(sums["sh"], dist, device), "opacity": reduce_grad(sums["opacity"], dist, device)}
