@@ -1,0 +1,46 @@
+// gaussian_sums.h -- the store under the per-Gaussian accumulators of the ABI (ws_contrib, ws_grad, ws_shgrad): a device array
+// of 64-bit sums, so many words per Gaussian, with the frames added and the stream of the last launch, and the three things every
+// accumulator does with it.  Host only; the functions are defined in api_attrib.cpp beside the handles' entry points.  They take
+// the handle as the ABI got it and the entry point's name: "<who>: null accumulator" is the first refusal of each.
+#pragma once
+
+#include <functional>
+
+#include "ws_internal.h"
+
+namespace ws {
+
+struct __attribute__((visibility("hidden"))) GaussianSums {  // (between the ABI's units: not among the library's dynamic symbols)
+    ws_context* ctx = nullptr;
+    uint32_t num_points = 0;
+    DeviceBuf<unsigned long long> sums;  // words per point x num_points; which of the two is the outer index is the handle's
+    uint32_t frames = 0;
+    hipStream_t last_stream = nullptr;
+    // what a handle with a plane of its own merges: (the device copy of the uploaded words or nullptr, the last stream) -> status
+    using Merge = std::function<int(const unsigned long long*, hipStream_t)>;
+
+    void launched(hipStream_t stream) { ++frames, last_stream = stream; }  // a launch on `stream` added a frame
+    static int reset(GaussianSums* s, const char* who, hipStream_t stream);  // zeros and no frames; `stream` becomes the last stream
+    // Refuses a capacity below num_points when the caller gave an array to fill (`wanted`: dst, or another where the handle has
+    // more), waits for the last stream -- also with nothing to fill -- and copies every word to dst (nullptr: none).  Never on the
+    // legacy NULL stream: see copy_d2h (api_state.h).
+    static int download_words(GaussianSums* s, const char* who, uint32_t capacity, bool wanted, void* dst);
+    // Refuses n below num_points; with neither host_words nor `merge` it then returns without touching the device.  Else
+    // host_words go to a temporary device buffer, `merge` (default: k_grad_merge over every word, sums += host_words) launches
+    // on the last stream, and the stream is waited for whatever came of it.
+    static int merge_words(GaussianSums* s, const char* who, uint32_t n, const void* host_words, const Merge& merge = nullptr);
+};
+
+}  // namespace ws
+
+// ---- per-Gaussian contributions (include/websplat.h; contrib.hip) ----------------------------------------
+struct ws_contrib : ws::GaussianSums {   // sums: [num_points] q32
+    ws::DeviceBuf<uint32_t> max_bits;    // [num_points] bits of the largest weight (non-negative floats order as their bits)
+};
+// ---- gradients of an image loss (include/websplat.h "Gradients of an image loss"; gradient.hip) ----------------
+struct ws_grad : ws::GaussianSums {};    // sums: [num_points][WS_GRAD_CHANNELS] two's-complement q32 sums
+// ---- SH gradients (include/websplat.h "SH gradients"; sh_gradient.hip) ----
+struct ws_shgrad : ws::GaussianSums {    // sums: [3 ncoef + 1][num_points]: one plane per element, the opacity's last
+    uint32_t sh_deg = 0, ncoef = 1;
+    ws::DeviceBuf<unsigned long long> scratch;  // [num_points][WS_GRAD_CHANNELS]: one frame's sums, zero between the calls
+};

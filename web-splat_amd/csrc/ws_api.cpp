@@ -1,4 +1,5 @@
-// ws_api.cpp -- the C ABI (include/websplat.h): handles, device memory, frame orchestration.
+// ws_api.cpp -- the C ABI (include/websplat.h): handles, device memory, frame orchestration.  The passes that only read a
+// prepared frame, and the objects they fill, are in api_attrib.cpp, api_metrics.cpp and api_refit.cpp (shared state: api_state.h).
 //
 // Mirrors the reference's object model: WGPUContext (lib.rs:57-125) -> ws_context,
 // PointCloud (pointcloud.rs:72-222) -> ws_pointcloud, GaussianRenderer (renderer.rs:17-283) -> ws_renderer,
@@ -12,16 +13,9 @@
 #include <new>
 #include <vector>
 
+#include "api_state.h"
 #include "contrib.h"
-#include "frame_scratch.h"
-#include "metrics.h"
-#include "gradient.h"
 #include "ply_encode.h"
-#include "refit.h"
-#include "sh_gradient.h"
-#include "removal.h"
-#include "values.h"
-#include "ws_internal.h"
 
 namespace ws {
 
@@ -38,7 +32,6 @@ int hip_fail(hipError_t e, const char* what) {
     return e == hipErrorOutOfMemory ? WS_ERR_OOM : WS_ERR_HIP;
 }
 
-
 // The runtime behind every DeviceBuf (device_buf.h).  The text of a failure is the one this library's allocations have always given.
 int device_alloc(void** p, size_t bytes) {
     *p = nullptr;
@@ -51,27 +44,6 @@ static int alloc_as(int rc, const char* what) {
     if (rc) g_last_error.replace(0, g_last_error.rfind(": "), what);
     return rc;
 }
-// Device -> host read-back ORDERED ON THE RENDERER'S OWN STREAM (then waited for): the library never touches the legacy
-// NULL stream for a frame's data.  (Besides the device-wide implicit synchronisation a NULL-stream copy brings, a
-// hipMemcpy on the NULL stream between two launches of a captured frame graph made the next launch of an already
-// used executable graph fault on ROCm 7.2 -- found by scripts/sweep.py, which reads frame_stats() between frames.)
-static int copy_d2h(void* dst, const void* src, size_t bytes, hipStream_t stream) {
-    if (bytes == 0) return WS_OK;
-    WS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-    WS_HIP(hipStreamSynchronize(stream));
-    return WS_OK;
-}
-
-// How the ABI destroys a handle whose buffers a launch may still read, and how a creator drops one it could not finish:
-// behind a device sync (DeviceBuf frees without one)
-struct SyncedDelete {
-    template <typename H>
-    void operator()(H* h) const {
-        if (!h) return;
-        (void)hipDeviceSynchronize();
-        delete h;
-    }
-};
 
 int KernelMarks::create() {
     if (created) return WS_OK;
@@ -127,97 +99,6 @@ struct ws_sorter {
     uint32_t epoch = 0;
     bool folded = false;              // the last ws_sorter_sort_depth folded the key range (ws_sorter_depth_range)
     hipStream_t last_stream = nullptr;
-};
-
-// Where the prepared frame's arrays are: one value, so that the frame graph's capture and replay cannot forget a member.
-struct FrameArrays {
-    // the depth sort's result: vals = the draw-ordered store indices, aux = their footprint words; the *_skipped members are
-    // where they are when the sort's last pass had nothing to do (FrameCounters::depth_skip_top, decided on the device per
-    // frame), nullptr: this frame's sort cannot skip
-    SortResult depth;
-    uint32_t* entries = nullptr;     // the tile-sorted entry values (store indices)
-    bool blend_order_valid = false;  // the frame wrote FrameScratch::blend_order (it ran k_blend_order)
-};
-
-// The last prepared frame.  Reset as a whole wherever it stops being one: every reader asks `prepared` first.
-struct PreparedFrame {
-    bool prepared = false;
-    const ws_pointcloud* pc = nullptr;
-    bool contrib = false;            // K1 kept the source indices (ws_renderer_enable_contrib was on)
-    bool depth = false;              // K1 wrote the z plane (ws_renderer_enable_depth was on)
-    float znear = 0.0f, zfar = 0.0f; // K1Params::znear / zfar (the composite's NDC occluder)
-    float cam_pos[3] = {0.0f, 0.0f, 0.0f};  // view_inv[12..14] of K1's camera uniform: where K1 takes the SH direction from
-    uint32_t max_sh_deg = 0;         // of K1's settings uniform (both read by ws_renderer_accumulate_sh_gradient)
-    FrameArrays arrays;
-    float* k1_depths = nullptr;      // the z plane the prepare() in progress writes (nullptr: depth off)
-    unsigned long long* trace_slot = nullptr;  // the frame's slot of ws_renderer::frame_trace (nullptr: not traced)
-};
-
-struct ws_renderer {
-    // ---- fixed configuration and switches ----
-    ws_context* ctx = nullptr;
-    ws_color_format format = WS_FORMAT_RGBA32_FLOAT;
-    uint32_t sh_deg = 3;
-    bool compressed = false;
-    uint64_t entry_cap_request = 0;
-    int blend_mode = WS_BLEND_FAST;  // ws_renderer_set_blend_mode
-    bool capture = false;
-    bool contrib = false;            // ws_renderer_enable_contrib: K1 keeps the source indices from the next prepare() on
-    bool depth = false;              // ws_renderer_enable_depth: K1 writes the z plane from the next prepare() on
-    bool blend_timing = false;       // ws_renderer_enable_blend_timing: render() launches the time-stamped blend
-    bool throughput_mode = false;    // this renderer runs beside others (a slot of a view batch with frames in flight):
-                                     //   its blend keeps the image order of its workgroups (see ws_renderer_render)
-
-    // ---- the scratch, (re)created when num_points, the viewport or the entry capacity changes (renderer.rs:200-211) ----
-    FrameScratch scratch;
-    uint32_t cap_points = 0, vw = 0, vh = 0;  // what it was made for
-    FramePlan plan{};                // of the last prepare(): the scratch is sized by it, the frame's launches are filled from it (frame_plan.h)
-    uint32_t epoch = 0;              // look-back epoch of the last frame (lookback.h); 0 with fresh (zeroed) status arrays
-    uint64_t scratch_generation = 0;
-    // The frame's launch sequence of prepare() (memset + 21 kernels), captured once per (point cloud, scratch) and replayed:
-    // only K1's arguments change from frame to frame (camera / settings uniforms, epoch).  A ring of executable graphs,
-    // because updating an executable graph's kernel arguments while an earlier launch of it has not run yet would change
-    // that earlier frame: slot i is reused only after the event recorded behind its last launch has completed.
-    static constexpr int GRAPH_RING = 4;
-    struct FrameGraph {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec[GRAPH_RING] = {};
-        hipEvent_t done[GRAPH_RING] = {};
-        bool used[GRAPH_RING] = {};
-        hipGraphNode_t k1_node = nullptr;
-        hipKernelNodeParams k1_params{};
-        const ws_pointcloud* pc = nullptr;
-        uint64_t generation = 0;   // scratch generation the graph was captured for
-        uint32_t next = 0;
-        bool valid = false;
-        FrameArrays arrays;              // of the captured frame
-        int order_mode = 0;              // decide_blend_order() of the captured frame: a change re-captures
-        int depth_bits = 0;              // != 0 while the graph is valid: the digit width its depth sort was captured with
-    } fg;
-
-    // ---- the last prepared frame ----
-    PreparedFrame frame;
-    int order_mode = 0;              // decide_blend_order() of the last prepare(): a captured graph replays only under its own
-
-    // ---- error words and progress: they outlive a failed prepare() and a new scratch (ws_renderer_errors) ----
-    hipStream_t last_stream = nullptr;
-    DeviceBuf<uint32_t> sticky;      // two device words that survive the per-frame memset (ws_renderer_errors): [0] error bits
-                                     // of all frames since the last reset, [1] the largest entries_needed of an overflowed frame
-    uint32_t needed_seen = 0;        // host copy of [1]: the automatic entry capacity grows to it at the next prepare()
-    uint32_t* demand_mailbox = nullptr;      // FOUR pinned host words the blend posts to (device-visible address: demand_mailbox_dev):
-    uint32_t* demand_mailbox_dev = nullptr;  //   [0] the demand [1] above -- prepare() reads it without a sync, so the capacity grows
-                                             //   without anyone polling; [1] the number of the last frame whose blend has started;
-                                             //   [2] depth_span_class of that frame -> the next frame's digit width
-    uint32_t frames_enqueued = 0;            // render() calls so far (the sequence number the blend posts)
-
-    // ---- instrumentation ----
-    DeviceBuf<unsigned long long> frame_trace;  // [frames][4]: {K1 start, K1 end, blend start, blend end} per frame (ws_renderer_enable_frame_trace)
-    uint32_t trace_count = 0;        // slots handed out so far
-    bool timers = false;
-    KernelMarks marks;               // per-kernel events, timers level 2
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_group[2] = {nullptr, nullptr};  // grouped prepare of a view batch: "arena cleared" / "shared K1 done"
-    bool ev_prepare_valid = false, ev_render_valid = false;
 };
 
 // FrameCounters::depth_span_class of the renderer's last frame whose blend has started: the blend posts it to pinned memory,
@@ -787,6 +668,54 @@ int ws_pointcloud_save_ply(const ws_pointcloud* pc, const char* path) {
     meta.has_background_color = pc->has_background;
     std::memcpy(meta.background_color, pc->background, sizeof meta.background_color);
     return ws_ply_write(path, rows.data(), pc->num_points, pc->sh_deg, &meta);
+}
+
+int ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, const uint32_t* indices, uint32_t n, ws_pointcloud** out) {
+    if (!ctx || !src || !indices || !out) return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: null argument");
+    *out = nullptr;
+    if (n == 0) return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: empty subset");
+    for (uint32_t i = 0; i < n; ++i)
+        if (indices[i] >= src->num_points || (i && indices[i] <= indices[i - 1]))
+            return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: indices must be strictly ascending and below the number of points");
+    std::unique_ptr<ws_pointcloud> pc(new (std::nothrow) ws_pointcloud());
+    if (!pc) return fail(WS_ERR_OOM, "ws_pointcloud_create_subset: host allocation failed");
+    static_cast<PointCloudMeta&>(*pc) = *src;  // bbox, centre, up, metadata, sh_deg, quantisation: verbatim
+    pc->ctx = ctx;
+    pc->num_points = n;
+    // upload, gather and the codebook copies run on a private stream and are waited for (as ws_pointcloud_create_from_ply_rows)
+    DeviceBuf<uint32_t> d_idx;  // (let go at the return, behind the stream sync)
+    hipStream_t ls = nullptr;
+    const char* what = "ws_pointcloud_create_subset: allocation / copy";
+    int rc = d_idx.alloc(n);
+    hipError_t e = hipSuccess;
+    if (rc == WS_OK) e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
+    if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(d_idx.get(), indices, (size_t)n * 4, hipMemcpyHostToDevice, ls);
+    if (rc == WS_OK && e == hipSuccess) {
+        if (!src->compressed) {
+            rc = alloc_as(pc->planes.alloc((size_t)n * PC_PLANES), what);
+            if (rc == WS_OK)
+                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->planes.get()), reinterpret_cast<uint32_t*>(pc->planes.get()), d_idx.get(),
+                                      src->num_points, n, PC_PLANES, 4, ls);
+        } else {
+            rc = alloc_as(pc->gaussians_c.alloc((size_t)n * 24), what);
+            if (rc == WS_OK) rc = alloc_as(pc->sh_bytes.alloc(src->sh_bytes.count()), what);
+            if (rc == WS_OK) rc = alloc_as(pc->covars.alloc(src->covars.count()), what);
+            if (rc == WS_OK) e = hipMemcpyAsync(pc->sh_bytes.get(), src->sh_bytes.get(), src->sh_bytes.bytes(), hipMemcpyDeviceToDevice, ls);
+            if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(pc->covars.get(), src->covars.get(), src->covars.bytes(), hipMemcpyDeviceToDevice, ls);
+            if (rc == WS_OK && e == hipSuccess)
+                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->gaussians_c.get()), reinterpret_cast<uint32_t*>(pc->gaussians_c.get()), d_idx.get(),
+                                      src->num_points, n, 1, 6, ls);
+        }
+    }
+    if (e != hipSuccess && rc == WS_OK) rc = hip_fail(e, what);
+    if (ls) {
+        const hipError_t se = hipStreamSynchronize(ls);
+        if (se != hipSuccess && rc == WS_OK) rc = hip_fail(se, "ws_pointcloud_create_subset: gather");
+        (void)hipStreamDestroy(ls);
+    }
+    if (rc) return rc;
+    *out = pc.release();
+    return WS_OK;
 }
 
 void ws_pointcloud_destroy(ws_pointcloud* pc) { delete pc; }
@@ -1962,959 +1891,6 @@ int ws_sort_selftest(ws_context* ctx, int* passed) {
     if (e == hipSuccess) e = hipMemcpy(got.data(), dk.get(), n * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "ws_sort_selftest: download");
     *passed = std::memcmp(got.data(), expect.data(), n * 4) == 0 ? 1 : 0;
-    return WS_OK;
-}
-
-}  // extern "C"
-
-// ---- per-Gaussian contributions (include/websplat.h; contrib.hip) ----------------------------------------
-struct ws_contrib {
-    ws_context* ctx = nullptr;
-    uint32_t num_points = 0;
-    DeviceBuf<unsigned long long> sum_q32;  // [num_points]
-    DeviceBuf<uint32_t> max_bits;           // [num_points] bits of the largest weight (non-negative floats order as their bits)
-    uint32_t frames = 0;
-    hipStream_t last_stream = nullptr;
-};
-
-extern "C" {
-
-int ws_contrib_create(ws_context* ctx, uint32_t num_points, ws_contrib** out) {
-    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_contrib_create: null argument");
-    *out = nullptr;
-    if (num_points == 0) return fail(WS_ERR_INVALID, "ws_contrib_create: no points");
-    std::unique_ptr<ws_contrib, SyncedDelete> c(new (std::nothrow) ws_contrib());
-    if (!c) return fail(WS_ERR_OOM, "ws_contrib_create: host allocation failed");
-    c->ctx = ctx;
-    c->num_points = num_points;
-    WS_TRY(c->sum_q32.alloc(num_points));
-    WS_TRY(c->max_bits.alloc(num_points));
-    WS_TRY(ws_contrib_reset(c.get(), nullptr));
-    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_contrib_create: device sync failed");
-    *out = c.release();
-    return WS_OK;
-}
-
-void ws_contrib_destroy(ws_contrib* c) { SyncedDelete()(c); }
-
-int ws_contrib_reset(ws_contrib* c, void* stream_v) {
-    if (!c) return fail(WS_ERR_INVALID, "ws_contrib_reset: null accumulator");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    WS_HIP(hipMemsetAsync(c->sum_q32.get(), 0, c->sum_q32.bytes(), stream));
-    WS_HIP(hipMemsetAsync(c->max_bits.get(), 0, c->max_bits.bytes(), stream));
-    c->frames = 0;
-    c->last_stream = stream;
-    return WS_OK;
-}
-
-uint32_t ws_contrib_num_points(const ws_contrib* c) { return c ? c->num_points : 0u; }
-uint32_t ws_contrib_frames(const ws_contrib* c) { return c ? c->frames : 0u; }
-
-int ws_renderer_enable_contrib(ws_renderer* r, int enable) {
-    if (!r) return fail(WS_ERR_INVALID, "ws_renderer_enable_contrib: null renderer");
-    // Only K1's src_index pointer changes (a kernel argument the frame graph's update rewrites anyway); the binning tile and
-    // the blend's form stay what they are, unlike capture.  Off: the frame at hand no longer answers accumulate_contrib.
-    r->contrib = enable != 0;
-    if (!r->contrib) r->frame.contrib = false;
-    return WS_OK;
-}
-
-// What a launch over the prepared frame's weights (k_contrib, k_values, k_removal_base, k_removal) reads of the renderer
-static FrameLists frame_lists(const ws_renderer* r) {
-    FrameLists f;
-    f.splats = r->scratch.splats.get();
-    f.entry_vals = r->frame.arrays.entries;
-    f.tile_ranges = r->scratch.tile_ranges();
-    f.src_index = r->scratch.src_index.get();
-    f.width = r->vw;
-    f.height = r->vh;
-    f.tiles_x = r->plan.tiles_x;
-    f.tiles_y = r->plan.tiles_y;
-    f.qw = r->ctx->tile_qw;
-    f.qh = r->ctx->tile_qh;
-    f.counters = r->scratch.counters();
-    f.sticky = r->sticky.get();
-    f.demand_mailbox = r->demand_mailbox_dev;
-    return f;
-}
-
-// ... and whether the renderer holds such a frame for `pc`.  points_match: the caller's own per-Gaussian array fits the cloud.
-static int check_weights_frame(const ws_renderer* r, const ws_pointcloud* pc, const std::string& who, bool points_match,
-                               const char* points_text) {
-    if (r->ctx->debug_cut) return fail(WS_ERR_UNSUPPORTED, who + ": the context stops its frames early (debug_cut)");
-    if (!points_match) return fail(WS_ERR_INVALID, who + ": " + points_text);
-    if (!r->frame.prepared || r->frame.pc != pc) return fail(WS_ERR_STATE, who + ": prepare() was not called for this point cloud");
-    if (!r->frame.contrib) return fail(WS_ERR_STATE, who + ": needs ws_renderer_enable_contrib before prepare()");
-    return WS_OK;
-}
-
-// A caller's plane of 4-B values (`what`: "plane" | "winner"; nullptr: nothing to judge).  r == nullptr: by itself, pointer and
-// pitch; else against r's prepared frame, the pitch.  who: the text's prefix.
-static int check_plane(const ws_renderer* r, const std::string& who, const char* what, const void* ptr, size_t pitch) {
-    if (ptr && !r && (pitch % 4 != 0 || reinterpret_cast<uintptr_t>(ptr) % 4 != 0))
-        return fail(WS_ERR_INVALID, who + ": " + what + " pointer and row pitch must be multiples of 4");
-    if (ptr && r && pitch < (size_t)r->vw * 4) return fail(WS_ERR_INVALID, who + ": " + what + " row pitch below 4 x the viewport's width");
-    return WS_OK;
-}
-static int check_plane_view(const ws_renderer* r, const std::string& who, const ws_plane_view* v) {
-    if (!v) return WS_OK;
-    if (!r && (!std::isfinite(v->scale) || !std::isfinite(v->bias))) return fail(WS_ERR_INVALID, who + ": scale and bias must be finite");
-    return check_plane(r, who, "plane", v->d_values, v->row_pitch_bytes);
-}
-
-// The accumulator as the kernels' argument: the plain sums (plane == nullptr) or the weighted ones
-static Accum accum_arg(const ws_contrib* c, const ws_plane_view* plane) {
-    if (!plane) return {c->sum_q32.get(), c->max_bits.get(), nullptr, 0, 1.0f, 0.0f};
-    return {c->sum_q32.get(), c->max_bits.get(), plane->d_values, plane->row_pitch_bytes, plane->scale, plane->bias};
-}
-
-// The bracket of a launch over the prepared frame: the timers' begin before it; behind it, with its status, the mark and the
-// streams to wait for.  c: the accumulator the launch added a frame to, or nullptr
-static KernelMarks* launch_begin(ws_renderer* r, hipStream_t stream) {
-    KernelMarks* km = r->marks.active ? &r->marks : nullptr;
-    if (km) km->begin(stream, false);
-    return km;
-}
-static int launch_done(int rc, ws_renderer* r, ws_contrib* c, hipStream_t stream, KernelMarks* km, const char* mark) {
-    if (rc) return rc;
-    km_mark(km, mark);
-    if (c) ++c->frames, c->last_stream = stream;
-    r->last_stream = stream;
-    return WS_OK;
-}
-
-// One attribution launch over the prepared frame: the plain sums (plane == nullptr) or the weighted ones
-static int accumulate_frame(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v,
-                            const char* who_c) {
-    const std::string who(who_c);
-    int rc = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
-    if (rc == WS_OK) rc = check_plane_view(r, who, plane);
-    if (rc) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    const ContribParams cp{frame_lists(r), accum_arg(c, plane)};
-    KernelMarks* km = launch_begin(r, stream);
-    return launch_done(launch_contrib(cp, stream), r, c, stream, km, plane ? "k_contrib_weighted" : "k_contrib");
-}
-
-int ws_renderer_accumulate_contrib(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, void* stream_v) {
-    if (!r || !pc || !c) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_contrib: null argument");
-    return accumulate_frame(r, pc, c, nullptr, stream_v, "ws_renderer_accumulate_contrib");
-}
-
-int ws_renderer_accumulate_weighted(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_plane_view* plane, void* stream_v) {
-    if (!r || !pc || !c || !plane || !plane->d_values) return fail(WS_ERR_INVALID, "ws_renderer_accumulate_weighted: null argument");
-    if (const int rc = check_plane_view(nullptr, "ws_renderer_accumulate_weighted", plane)) return rc;
-    return accumulate_frame(r, pc, c, plane, stream_v, "ws_renderer_accumulate_weighted");
-}
-
-// The forward operator of the attribution pass: the caller's per-Gaussian values through the prepared frame's weights, to planes.
-// The descriptors are judged by themselves first, then the handles, then the descriptors against the frame; only then a launch.
-int ws_renderer_render_values(ws_renderer* r, const ws_pointcloud* pc, const ws_values_view* values, const ws_value_targets* out,
-                              void* stream_v) {
-    const std::string who("ws_renderer_render_values");
-    if (!out) return fail(WS_ERR_INVALID, who + ": null targets");
-    for (uint32_t w : out->reserved)
-        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    const uint32_t channels = values ? values->channels : 0u;
-    if (values) {
-        if (!values->d_values) return fail(WS_ERR_INVALID, who + ": null d_values");
-        if (channels == 0 || channels > 4) return fail(WS_ERR_INVALID, who + ": channels must be 1..4");
-        if (values->stride_bytes < (size_t)4 * channels || values->stride_bytes % 4 != 0)
-            return fail(WS_ERR_INVALID, who + ": values stride below 4 x channels or not a multiple of 4");
-        if (reinterpret_cast<uintptr_t>(values->d_values) % 4 != 0) return fail(WS_ERR_INVALID, who + ": values pointer not 4-B aligned");
-    }
-    bool any = out->winner != nullptr;
-    for (uint32_t c = 0; c < 4; ++c) {
-        if (!out->plane[c]) continue;
-        if (c >= channels) return fail(WS_ERR_INVALID, who + ": a plane at or above the number of channels");
-        if (const int rc = check_plane(nullptr, who, "plane", out->plane[c], out->pitch[c])) return rc;
-        any = true;
-    }
-    if (const int rc = check_plane(nullptr, who, "winner", out->winner, out->winner_pitch)) return rc;
-    if (!any) return fail(WS_ERR_INVALID, who + ": no output plane");
-    if (!r || !pc) return fail(WS_ERR_INVALID, who + ": null argument");
-    const int state = check_weights_frame(r, pc, who, !values || values->num_points == pc->num_points, "the values were laid out for another number of points");
-    if (state) return state;
-    for (uint32_t c = 0; c < 4; ++c)
-        if (const int rc = check_plane(r, who, "plane", out->plane[c], out->pitch[c])) return rc;
-    if (const int rc = check_plane(r, who, "winner", out->winner, out->winner_pitch)) return rc;
-    ValuesParams vp;
-    vp.frame = frame_lists(r);
-    vp.values = values ? values->d_values : nullptr;
-    vp.stride = values ? values->stride_bytes : 0;
-    vp.channels = channels;
-    for (uint32_t c = 0; c < 4; ++c) {
-        vp.plane[c] = out->plane[c];
-        vp.pitch[c] = out->pitch[c];
-    }
-    vp.winner = out->winner;
-    vp.winner_pitch = out->winner_pitch;
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    KernelMarks* km = launch_begin(r, stream);
-    return launch_done(launch_values(vp, stream), r, nullptr, stream, km, "k_values");
-}
-
-// The base plane (F, T_end) of ws_renderer_accumulate_removal and ws_renderer_accumulate_gradient: the caller's, or the
-// renderer's scratch, grown on demand
-static int base_plane(ws_renderer* r, float* d_base, size_t pitch, float4** base, size_t* base_pitch) {
-    if (d_base) {
-        *base = reinterpret_cast<float4*>(d_base);
-        *base_pitch = pitch;
-        return WS_OK;
-    }
-    if (!r->scratch.removal_base.get()) {  // (one viewport per scratch: the plane is freed with it)
-        WS_HIP(hipDeviceSynchronize());
-        WS_TRY(r->scratch.removal_base.alloc(r->scratch.layout.removal_base));
-    }
-    *base = r->scratch.removal_base.get();
-    *base_pitch = (size_t)r->vw * 16;
-    return WS_OK;
-}
-
-// What deleting each Gaussian alone would do to the prepared frame (websplat.h "Removal effect"; removal.h).  The descriptor is
-// judged by itself first, then the handles, then the descriptor against the frame; only then the two launches.
-int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_contrib* c, const ws_removal_params* p, void* stream_v) {
-    const std::string who("ws_renderer_accumulate_removal");
-    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
-    for (uint32_t w : p->reserved)
-        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    if (p->kind == WS_ERROR_DSSIM) return fail(WS_ERR_INVALID, who + ": kind WS_ERROR_DSSIM has no removal effect (sq or abs)");
-    if (p->kind != WS_ERROR_SQ && p->kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": unknown kind");
-    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    for (float b : p->background)
-        if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
-    if (p->weight && !p->weight->d_values) return fail(WS_ERR_INVALID, who + ": weight: null d_values");
-    if (const int rc = check_plane_view(nullptr, who + ": weight", p->weight)) return rc;
-    if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
-        return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
-    if (!r || !pc || !c) return fail(WS_ERR_INVALID, who + ": null argument");
-    const int state = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
-    if (state) return state;
-    if (const int rc = check_plane_view(r, who + ": weight", p->weight)) return rc;
-    if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
-    RemovalParams rp;
-    rp.frame = frame_lists(r);
-    if (const int rc = base_plane(r, p->d_base, p->base_pitch_bytes, &rp.base, &rp.base_pitch)) return rc;
-    for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
-    rp.scale = p->scale;
-    rp.kind = p->kind;
-    rp.acc = accum_arg(c, p->weight);
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    KernelMarks* km = launch_begin(r, stream);
-    return launch_done(launch_removal(rp, stream), r, c, stream, km, "k_removal_base+k_removal");
-}
-
-int ws_contrib_download(ws_contrib* c, uint32_t capacity, uint64_t* sum_q32, float* max_weight) {
-    if (!c) return fail(WS_ERR_INVALID, "ws_contrib_download: null accumulator");
-    if ((sum_q32 || max_weight) && capacity < c->num_points)
-        return fail(WS_ERR_INVALID, "ws_contrib_download: capacity smaller than the number of points");
-    WS_HIP(hipStreamSynchronize(c->last_stream));
-    int rc = WS_OK;
-    if (sum_q32) rc = copy_d2h(sum_q32, c->sum_q32.get(), c->sum_q32.bytes(), c->last_stream);
-    if (rc == WS_OK && max_weight) rc = copy_d2h(max_weight, c->max_bits.get(), c->max_bits.bytes(), c->last_stream);
-    return rc;
-}
-
-int ws_contrib_add(ws_contrib* c, const uint64_t* sum_q32, const float* max_weight, uint32_t n) {
-    if (!c) return fail(WS_ERR_INVALID, "ws_contrib_add: null accumulator");
-    if (n < c->num_points) return fail(WS_ERR_INVALID, "ws_contrib_add: fewer values than the accumulator has points");
-    if (!sum_q32 && !max_weight) return WS_OK;
-    const size_t np = c->num_points;
-    DeviceBuf<unsigned long long> d_sum;  // (both let go at the return, behind the stream sync)
-    DeviceBuf<uint32_t> d_max;
-    hipStream_t stream = c->last_stream;
-    int rc = WS_OK;
-    if (sum_q32) rc = d_sum.alloc(np);
-    if (rc == WS_OK && max_weight) rc = d_max.alloc(np);
-    hipError_t e = hipSuccess;
-    if (rc == WS_OK && sum_q32) e = hipMemcpyAsync(d_sum.get(), sum_q32, np * sizeof(uint64_t), hipMemcpyHostToDevice, stream);
-    if (rc == WS_OK && e == hipSuccess && max_weight) e = hipMemcpyAsync(d_max.get(), max_weight, np * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) rc = hip_fail(e, "ws_contrib_add: upload");
-    if (rc == WS_OK) rc = launch_contrib_merge(c->sum_q32.get(), c->max_bits.get(), d_sum.get(), d_max.get(), c->num_points, stream);
-    if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_contrib_add: stream sync failed");
-    return rc;
-}
-
-int ws_pointcloud_create_subset(ws_context* ctx, const ws_pointcloud* src, const uint32_t* indices, uint32_t n, ws_pointcloud** out) {
-    if (!ctx || !src || !indices || !out) return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: null argument");
-    *out = nullptr;
-    if (n == 0) return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: empty subset");
-    for (uint32_t i = 0; i < n; ++i)
-        if (indices[i] >= src->num_points || (i && indices[i] <= indices[i - 1]))
-            return fail(WS_ERR_INVALID, "ws_pointcloud_create_subset: indices must be strictly ascending and below the number of points");
-    std::unique_ptr<ws_pointcloud> pc(new (std::nothrow) ws_pointcloud());
-    if (!pc) return fail(WS_ERR_OOM, "ws_pointcloud_create_subset: host allocation failed");
-    static_cast<PointCloudMeta&>(*pc) = *src;  // bbox, centre, up, metadata, sh_deg, quantisation: verbatim
-    pc->ctx = ctx;
-    pc->num_points = n;
-    // upload, gather and the codebook copies run on a private stream and are waited for (as ws_pointcloud_create_from_ply_rows)
-    DeviceBuf<uint32_t> d_idx;  // (let go at the return, behind the stream sync)
-    hipStream_t ls = nullptr;
-    const char* what = "ws_pointcloud_create_subset: allocation / copy";
-    int rc = d_idx.alloc(n);
-    hipError_t e = hipSuccess;
-    if (rc == WS_OK) e = hipStreamCreateWithFlags(&ls, hipStreamNonBlocking);
-    if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(d_idx.get(), indices, (size_t)n * 4, hipMemcpyHostToDevice, ls);
-    if (rc == WS_OK && e == hipSuccess) {
-        if (!src->compressed) {
-            rc = alloc_as(pc->planes.alloc((size_t)n * PC_PLANES), what);
-            if (rc == WS_OK)
-                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->planes.get()), reinterpret_cast<uint32_t*>(pc->planes.get()), d_idx.get(),
-                                      src->num_points, n, PC_PLANES, 4, ls);
-        } else {
-            rc = alloc_as(pc->gaussians_c.alloc((size_t)n * 24), what);
-            if (rc == WS_OK) rc = alloc_as(pc->sh_bytes.alloc(src->sh_bytes.count()), what);
-            if (rc == WS_OK) rc = alloc_as(pc->covars.alloc(src->covars.count()), what);
-            if (rc == WS_OK) e = hipMemcpyAsync(pc->sh_bytes.get(), src->sh_bytes.get(), src->sh_bytes.bytes(), hipMemcpyDeviceToDevice, ls);
-            if (rc == WS_OK && e == hipSuccess) e = hipMemcpyAsync(pc->covars.get(), src->covars.get(), src->covars.bytes(), hipMemcpyDeviceToDevice, ls);
-            if (rc == WS_OK && e == hipSuccess)
-                rc = launch_pc_gather(reinterpret_cast<const uint32_t*>(src->gaussians_c.get()), reinterpret_cast<uint32_t*>(pc->gaussians_c.get()), d_idx.get(),
-                                      src->num_points, n, 1, 6, ls);
-        }
-    }
-    if (e != hipSuccess && rc == WS_OK) rc = hip_fail(e, what);
-    if (ls) {
-        const hipError_t se = hipStreamSynchronize(ls);
-        if (se != hipSuccess && rc == WS_OK) rc = hip_fail(se, "ws_pointcloud_create_subset: gather");
-        (void)hipStreamDestroy(ls);
-    }
-    if (rc) return rc;
-    *out = pc.release();
-    return WS_OK;
-}
-
-}  // extern "C"
-
-// ---- image metrics (include/websplat.h "Image metrics"; metrics.hip) ----------------------------------------
-struct ws_metrics {
-    ws_context* ctx = nullptr;
-    uint32_t max_images = 0;
-    uint32_t count = 0;                  // records added (host counter)
-    DeviceBuf<MetricsRecord> records;    // [max_images]
-    DeviceBuf<MetricsPartial> slab;      // one partial record per workgroup of the add in flight; shared by the adds of one stream
-    hipStream_t last_stream = nullptr;
-};
-
-void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count) {
-    if (m && count < m->count) m->count = count;
-}
-
-namespace {
-int metrics_view(const ws_image_view* v, uint32_t width, const char* which, MetricsView* out, const char* fn = "ws_metrics_add") {
-    const std::string who = std::string(fn) + ": image " + which;
-    if (!v->d_pixels) return fail(WS_ERR_INVALID, who + ": null pixels");
-    size_t texel;
-    switch (v->format) {
-        case WS_FORMAT_RGBA8_UNORM: texel = 4; break;
-        case WS_FORMAT_RGBA16_FLOAT: texel = 8; break;
-        case WS_FORMAT_RGBA32_FLOAT: texel = 16; break;
-        default: return fail(WS_ERR_INVALID, who + ": unknown colour format");
-    }
-    if (v->row_pitch_bytes < texel * width) return fail(WS_ERR_INVALID, who + ": row pitch below the row");
-    if (v->row_pitch_bytes % texel != 0 || reinterpret_cast<uintptr_t>(v->d_pixels) % texel != 0)
-        return fail(WS_ERR_INVALID, who + ": pointer and row pitch must be multiples of the texel size");
-    out->pixels = v->d_pixels;
-    out->pitch = v->row_pitch_bytes;
-    out->format = (int)v->format;
-    out->over_bg = v->over_background != 0;
-    for (int i = 0; i < 3; ++i) out->bg[i] = v->background[i];
-    return WS_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int ws_metrics_create(ws_context* ctx, uint32_t max_images, ws_metrics** out) {
-    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_metrics_create: null argument");
-    *out = nullptr;
-    if (max_images == 0) return fail(WS_ERR_INVALID, "ws_metrics_create: no images");
-    ws_metrics* m = new (std::nothrow) ws_metrics();
-    if (!m) return fail(WS_ERR_OOM, "ws_metrics_create: host allocation failed");
-    m->ctx = ctx;
-    m->max_images = max_images;
-    const int rc = m->records.alloc(max_images);
-    if (rc != WS_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return WS_OK;
-}
-
-void ws_metrics_destroy(ws_metrics* m) { SyncedDelete()(m); }
-
-int ws_metrics_reset(ws_metrics* m, void* stream_v) {
-    if (!m) return fail(WS_ERR_INVALID, "ws_metrics_reset: null accumulator");
-    // records are written whole by the add that owns them: emptying is the host counter
-    m->count = 0;
-    m->last_stream = static_cast<hipStream_t>(stream_v);
-    return WS_OK;
-}
-
-uint32_t ws_metrics_count(const ws_metrics* m) { return m ? m->count : 0u; }
-
-int ws_metrics_add(ws_metrics* m, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, uint32_t flags,
-                   float* d_ssim_map, size_t map_pitch_bytes, void* stream_v) {
-    if (!m || !a || !b) return fail(WS_ERR_INVALID, "ws_metrics_add: null argument");
-    if (width == 0 || height == 0) return fail(WS_ERR_INVALID, "ws_metrics_add: empty image");
-    if (width > 65536u || height > 65536u) return fail(WS_ERR_INVALID, "ws_metrics_add: image larger than 65536 pixels on a side");
-    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_metrics_add: unknown flag bits");
-    MetricsParams p;
-    int rc = metrics_view(a, width, "a", &p.a);
-    if (rc == WS_OK) rc = metrics_view(b, width, "b", &p.b);
-    if (rc) return rc;
-    if (d_ssim_map && (map_pitch_bytes < (size_t)width * 4 || map_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(d_ssim_map) % 4 != 0))
-        return fail(WS_ERR_INVALID, "ws_metrics_add: map pitch below 4 x width, or map pointer / pitch not 4-B aligned");
-    if (m->count >= m->max_images) return fail(WS_ERR_OVERFLOW, "ws_metrics_add: the accumulator is full");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    const uint32_t tiles = metrics_num_tiles(width, height);
-    // (alloc frees the old slab first, and hipFree waits for the adds that still use it)
-    if (tiles > m->slab.count() && (rc = m->slab.alloc(tiles))) return rc;
-    p.width = width;
-    p.height = height;
-    p.flags = flags;
-    p.map = d_ssim_map;
-    p.map_pitch = map_pitch_bytes;
-    p.slab = m->slab.get();
-    if ((rc = launch_image_metrics(p, m->records.get() + m->count, stream))) return rc;
-    ++m->count;
-    m->last_stream = stream;
-    return WS_OK;
-}
-
-int ws_image_error_plane(ws_context* ctx, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, int kind,
-                         uint32_t flags, float* d_plane, size_t plane_pitch_bytes, void* stream_v) {
-    if (!ctx || !a || !b || !d_plane) return fail(WS_ERR_INVALID, "ws_image_error_plane: null argument");
-    if (width == 0 || height == 0) return fail(WS_ERR_INVALID, "ws_image_error_plane: empty image");
-    if (width > 65536u || height > 65536u) return fail(WS_ERR_INVALID, "ws_image_error_plane: image larger than 65536 pixels on a side");
-    if (flags & ~WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, "ws_image_error_plane: unknown flag bits");
-    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, "ws_image_error_plane: kind must be WS_ERROR_SQ or WS_ERROR_ABS");
-    ImageErrorParams p;
-    int rc = metrics_view(a, width, "a", &p.a, "ws_image_error_plane");
-    if (rc == WS_OK) rc = metrics_view(b, width, "b", &p.b, "ws_image_error_plane");
-    if (rc) return rc;
-    if (plane_pitch_bytes < (size_t)width * 4 || plane_pitch_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(d_plane) % 4 != 0)
-        return fail(WS_ERR_INVALID, "ws_image_error_plane: plane pitch below 4 x width, or plane pointer / pitch not 4-B aligned");
-    p.width = width;
-    p.height = height;
-    p.flags = flags;
-    p.kind = kind;
-    p.plane = d_plane;
-    p.plane_pitch = plane_pitch_bytes;
-    return launch_image_error(p, static_cast<hipStream_t>(stream_v));
-}
-
-int ws_metrics_download(ws_metrics* m, uint32_t capacity, ws_image_metrics* out, uint32_t* count) {
-    if (!m) return fail(WS_ERR_INVALID, "ws_metrics_download: null accumulator");
-    if (count) *count = m->count;
-    if (!out) {  // (the count alone)
-        WS_HIP(hipStreamSynchronize(m->last_stream));
-        return WS_OK;
-    }
-    if (capacity < m->count) return fail(WS_ERR_INVALID, "ws_metrics_download: capacity smaller than the number of records");
-    std::vector<MetricsRecord> recs;
-    try {
-        recs.resize(m->count);
-    } catch (...) {
-        return fail(WS_ERR_OOM, "ws_metrics_download: host allocation failed");
-    }
-    WS_HIP(hipStreamSynchronize(m->last_stream));
-    const int rc = copy_d2h(recs.data(), m->records.get(), (size_t)m->count * sizeof(MetricsRecord), m->last_stream);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < m->count; ++i) {
-        const MetricsRecord& r = recs[i];
-        ws_image_metrics& o = out[i];
-        const double n = 3.0 * (double)r.width * (double)r.height;
-        o.mse = (r.flags & WS_METRICS_QUANTIZE_U8) ? (double)r.sse_u8 / (255.0 * 255.0 * n) : r.sse / n;
-        o.psnr = o.mse == 0.0 ? (double)INFINITY : -10.0 * std::log10(o.mse);
-        o.ssim = r.ssim_sum / n;
-        o.sse_u8 = r.sse_u8;
-        o.width = r.width;
-        o.height = r.height;
-        o.flags = r.flags;
-        o.reserved = 0;
-    }
-    return WS_OK;
-}
-
-}  // extern "C"
-
-// ---- gradients of an image loss (include/websplat.h "Gradients of an image loss"; gradient.hip) ----------------
-struct ws_grad {
-    ws_context* ctx = nullptr;
-    uint32_t num_points = 0;
-    DeviceBuf<unsigned long long> sums;  // [num_points][WS_GRAD_CHANNELS] two's-complement q32 sums
-    uint32_t frames = 0;
-    hipStream_t last_stream = nullptr;
-};
-static_assert(WS_GRAD_CHANNELS == GRAD_CHANNELS, "the ABI's channel count is the kernel's");
-
-// ---- SH gradients (include/websplat.h "SH gradients"; sh_gradient.hip) ----
-struct ws_shgrad {
-    ws_context* ctx = nullptr;
-    uint32_t num_points = 0;
-    uint32_t sh_deg = 0, ncoef = 1;
-    DeviceBuf<unsigned long long> sums;     // [3 ncoef + 1][num_points]: one plane per element, the opacity's last
-    DeviceBuf<unsigned long long> scratch;  // [num_points][WS_GRAD_CHANNELS]: one frame's sums, zero between the calls
-    uint32_t frames = 0;
-    hipStream_t last_stream = nullptr;
-    size_t elements() const { return (size_t)3 * ncoef + 1; }
-};
-
-extern "C" {
-
-int ws_grad_create(ws_context* ctx, uint32_t num_points, ws_grad** out) {
-    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_grad_create: null argument");
-    *out = nullptr;
-    if (num_points == 0) return fail(WS_ERR_INVALID, "ws_grad_create: no points");
-    std::unique_ptr<ws_grad, SyncedDelete> g(new (std::nothrow) ws_grad());
-    if (!g) return fail(WS_ERR_OOM, "ws_grad_create: host allocation failed");
-    g->ctx = ctx;
-    g->num_points = num_points;
-    WS_TRY(g->sums.alloc((size_t)num_points * GRAD_CHANNELS));
-    WS_TRY(ws_grad_reset(g.get(), nullptr));
-    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_grad_create: device sync failed");
-    *out = g.release();
-    return WS_OK;
-}
-
-void ws_grad_destroy(ws_grad* g) { SyncedDelete()(g); }
-
-int ws_grad_reset(ws_grad* g, void* stream_v) {
-    if (!g) return fail(WS_ERR_INVALID, "ws_grad_reset: null accumulator");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    WS_HIP(hipMemsetAsync(g->sums.get(), 0, g->sums.bytes(), stream));
-    g->frames = 0;
-    g->last_stream = stream;
-    return WS_OK;
-}
-
-uint32_t ws_grad_num_points(const ws_grad* g) { return g ? g->num_points : 0u; }
-uint32_t ws_grad_frames(const ws_grad* g) { return g ? g->frames : 0u; }
-
-int ws_grad_download(ws_grad* g, uint32_t capacity, int64_t* q32) {
-    if (!g) return fail(WS_ERR_INVALID, "ws_grad_download: null accumulator");
-    if (q32 && capacity < g->num_points) return fail(WS_ERR_INVALID, "ws_grad_download: capacity smaller than the number of points");
-    WS_HIP(hipStreamSynchronize(g->last_stream));
-    if (!q32) return WS_OK;
-    return copy_d2h(q32, g->sums.get(), g->sums.bytes(), g->last_stream);
-}
-
-int ws_grad_add(ws_grad* g, const int64_t* q32, uint32_t n) {
-    if (!g) return fail(WS_ERR_INVALID, "ws_grad_add: null accumulator");
-    if (n < g->num_points) return fail(WS_ERR_INVALID, "ws_grad_add: fewer values than the accumulator has points");
-    if (!q32) return WS_OK;
-    const size_t words = g->sums.count();
-    DeviceBuf<unsigned long long> d_other;  // (let go at the return, behind the stream sync)
-    hipStream_t stream = g->last_stream;
-    int rc = d_other.alloc(words);
-    if (rc == WS_OK) {
-        const hipError_t e = hipMemcpyAsync(d_other.get(), q32, words * sizeof(int64_t), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_grad_add: upload");
-    }
-    if (rc == WS_OK) rc = launch_grad_merge(g->sums.get(), d_other.get(), words, stream);
-    if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_grad_add: stream sync failed");
-    return rc;
-}
-
-// The descriptor is judged by itself first, then the handles, then the descriptor against the frame; only then the two launches:
-// removal's pass 1 through launch_removal_base, then k_gradient.
-int ws_renderer_accumulate_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream) {
-    return ws_internal_gradient_passes(r, pc, g, p, stream, 3u);
-}
-
-// ... and the same two launches into the accumulator's scratch, then k_sh_spread
-int ws_renderer_accumulate_sh_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream) {
-    return ws_internal_sh_gradient_passes(r, pc, g, p, stream, 3u);
-}
-
-}  // extern "C"
-
-// One sequence for both accumulators: exactly one of g and sh is looked at (sh when `spread`)
-static int gradient_passes(const std::string& who, ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, ws_shgrad* sh, bool spread,
-                           const ws_gradient_params* p, void* stream_v, unsigned passes);
-
-int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    return gradient_passes("ws_renderer_accumulate_gradient", r, pc, g, nullptr, false, p, stream_v, passes);
-}
-
-int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    return gradient_passes("ws_renderer_accumulate_sh_gradient", r, pc, nullptr, g, true, p, stream_v, passes);
-}
-
-static int gradient_passes(const std::string& who, ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, ws_shgrad* sh, bool spread,
-                           const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
-    if (p->reserved0 != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    for (uint32_t w : p->reserved)
-        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    if (!std::isfinite(p->opacity_scale) || !(p->opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
-    for (float b : p->background)
-        if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
-    if (!p->d_grad) return fail(WS_ERR_INVALID, who + ": null d_grad");
-    if (p->grad_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_grad) % 16 != 0)
-        return fail(WS_ERR_INVALID, who + ": d_grad: pointer and grad_pitch_bytes must be multiples of 16");
-    if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
-        return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
-    if (!r || !pc || (spread ? !sh : !g)) return fail(WS_ERR_INVALID, who + ": null argument");
-    const uint32_t acc_points = spread ? sh->num_points : g->num_points;
-    const int state = check_weights_frame(r, pc, who, acc_points == pc->num_points, "the accumulator was created for another number of points");
-    if (state) return state;
-    if (spread && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no SH gradients (its codebooks are shared between Gaussians)");
-    if (spread && sh->sh_deg != pc->sh_deg) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another SH degree");
-    if (p->grad_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_grad: grad_pitch_bytes below 16 x the viewport's width");
-    if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
-    RemovalParams rp;
-    rp.frame = frame_lists(r);
-    if (const int rc = base_plane(r, p->d_base, p->base_pitch_bytes, &rp.base, &rp.base_pitch)) return rc;
-    for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
-    rp.scale = 1.0f;  // (pass 1 reads neither of the three)
-    rp.kind = WS_ERROR_SQ;
-    rp.acc = Accum{nullptr, nullptr, nullptr, 0, 1.0f, 0.0f};
-    GradientParams gp;
-    gp.frame = rp.frame;
-    gp.base = rp.base;
-    gp.base_pitch = rp.base_pitch;
-    gp.grad = reinterpret_cast<const float4*>(p->d_grad);
-    gp.grad_pitch = p->grad_pitch_bytes;
-    gp.scale = p->scale;
-    gp.opacity_scale = p->opacity_scale;
-    gp.sums = spread ? sh->scratch.get() : g->sums.get();
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    KernelMarks* km = launch_begin(r, stream);
-    int rc = (passes & 1u) ? launch_removal_base(rp, stream) : WS_OK;
-    if (rc == WS_OK && (passes & 2u)) rc = launch_gradient(gp, stream);
-    if (rc == WS_OK && (passes & 2u) && spread) {
-        ShSpreadParams sp;
-        sp.planes = pc->planes.get();
-        sp.scratch = sh->scratch.get();
-        sp.sums = sh->sums.get();
-        sp.n = sh->num_points;
-        sp.ncoef = sh->ncoef;
-        sp.nact = sh_active_coefs(r->frame.max_sh_deg, sh->sh_deg);
-        for (int i = 0; i < 3; ++i) sp.cam[i] = r->frame.cam_pos[i];
-        rc = launch_sh_spread(sp, stream);
-    }
-    const char* const marks[2][3] = {{"k_removal_base", "k_gradient", "k_removal_base+k_gradient"},
-                                     {"k_removal_base", "k_gradient+k_sh_spread", "k_removal_base+k_gradient+k_sh_spread"}};
-    rc = launch_done(rc, r, nullptr, stream, km, marks[spread ? 1 : 0][passes == 1u ? 0 : passes == 2u ? 1 : 2]);
-    if (rc == WS_OK && (passes & 2u)) {
-        if (spread) ++sh->frames, sh->last_stream = stream;
-        else ++g->frames, g->last_stream = stream;
-    }
-    return rc;
-}
-
-extern "C" {
-
-int ws_shgrad_create(ws_context* ctx, uint32_t num_points, uint32_t sh_deg, ws_shgrad** out) {
-    if (!ctx || !out) return fail(WS_ERR_INVALID, "ws_shgrad_create: null argument");
-    *out = nullptr;
-    if (num_points == 0) return fail(WS_ERR_INVALID, "ws_shgrad_create: no points");
-    if (sh_deg > 3) return fail(WS_ERR_UNSUPPORTED, "ws_shgrad_create: sh_deg > 3");
-    std::unique_ptr<ws_shgrad, SyncedDelete> g(new (std::nothrow) ws_shgrad());
-    if (!g) return fail(WS_ERR_OOM, "ws_shgrad_create: host allocation failed");
-    g->ctx = ctx;
-    g->num_points = num_points;
-    g->sh_deg = sh_deg;
-    g->ncoef = (sh_deg + 1) * (sh_deg + 1);
-    WS_TRY(g->sums.alloc(g->elements() * num_points));
-    WS_TRY(g->scratch.alloc((size_t)num_points * GRAD_CHANNELS));
-    WS_HIP(hipMemsetAsync(g->scratch.get(), 0, g->scratch.bytes(), nullptr));
-    WS_TRY(ws_shgrad_reset(g.get(), nullptr));
-    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_shgrad_create: device sync failed");
-    *out = g.release();
-    return WS_OK;
-}
-
-void ws_shgrad_destroy(ws_shgrad* g) { SyncedDelete()(g); }
-
-// (the scratch is zero between the calls by k_sh_spread's own doing; a reset leaves it alone)
-int ws_shgrad_reset(ws_shgrad* g, void* stream_v) {
-    if (!g) return fail(WS_ERR_INVALID, "ws_shgrad_reset: null accumulator");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    WS_HIP(hipMemsetAsync(g->sums.get(), 0, g->sums.bytes(), stream));
-    g->frames = 0;
-    g->last_stream = stream;
-    return WS_OK;
-}
-
-uint32_t ws_shgrad_num_points(const ws_shgrad* g) { return g ? g->num_points : 0u; }
-uint32_t ws_shgrad_sh_deg(const ws_shgrad* g) { return g ? g->sh_deg : 0u; }
-uint32_t ws_shgrad_frames(const ws_shgrad* g) { return g ? g->frames : 0u; }
-
-// The device keeps one plane per element; the caller's rows are per Gaussian: the transposes are the host's.
-int ws_shgrad_download(ws_shgrad* g, uint32_t capacity, int64_t* q_sh, int64_t* q_opacity) {
-    if (!g) return fail(WS_ERR_INVALID, "ws_shgrad_download: null accumulator");
-    if ((q_sh || q_opacity) && capacity < g->num_points) return fail(WS_ERR_INVALID, "ws_shgrad_download: capacity smaller than the number of points");
-    WS_HIP(hipStreamSynchronize(g->last_stream));
-    const size_t n = g->num_points, el = (size_t)3 * g->ncoef;
-    if (q_opacity) WS_TRY(copy_d2h(q_opacity, g->sums.get() + el * n, n * sizeof(int64_t), g->last_stream));
-    if (!q_sh) return WS_OK;
-    std::unique_ptr<int64_t[]> st(new (std::nothrow) int64_t[el * n]);
-    if (!st) return fail(WS_ERR_OOM, "ws_shgrad_download: host allocation failed");
-    WS_TRY(copy_d2h(st.get(), g->sums.get(), el * n * sizeof(int64_t), g->last_stream));
-    for (size_t e = 0; e < el; ++e)
-        for (size_t i = 0; i < n; ++i) q_sh[i * el + e] = st[e * n + i];
-    return WS_OK;
-}
-
-int ws_shgrad_add(ws_shgrad* g, const int64_t* q_sh, const int64_t* q_opacity, uint32_t n_rows) {
-    if (!g) return fail(WS_ERR_INVALID, "ws_shgrad_add: null accumulator");
-    if (n_rows < g->num_points) return fail(WS_ERR_INVALID, "ws_shgrad_add: fewer values than the accumulator has points");
-    if (!q_sh && !q_opacity) return WS_OK;
-    const size_t n = g->num_points, el = (size_t)3 * g->ncoef, words = g->sums.count();
-    std::unique_ptr<int64_t[]> st(new (std::nothrow) int64_t[words]());  // (zeros where a pointer is NULL)
-    if (!st) return fail(WS_ERR_OOM, "ws_shgrad_add: host allocation failed");
-    if (q_sh)
-        for (size_t e = 0; e < el; ++e)
-            for (size_t i = 0; i < n; ++i) st[e * n + i] = q_sh[i * el + e];
-    if (q_opacity) std::memcpy(st.get() + el * n, q_opacity, n * sizeof(int64_t));
-    DeviceBuf<unsigned long long> d_other;  // (let go at the return, behind the stream sync)
-    hipStream_t stream = g->last_stream;
-    int rc = d_other.alloc(words);
-    if (rc == WS_OK) {
-        const hipError_t e = hipMemcpyAsync(d_other.get(), st.get(), words * sizeof(int64_t), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) rc = hip_fail(e, "ws_shgrad_add: upload");
-    }
-    if (rc == WS_OK) rc = launch_grad_merge(g->sums.get(), d_other.get(), words, stream);
-    if (hipStreamSynchronize(stream) != hipSuccess && rc == WS_OK) rc = fail(WS_ERR_HIP, "ws_shgrad_add: stream sync failed");
-    return rc;
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int ws_image_error_gradient(ws_context* ctx, const ws_image_view* a, const ws_image_view* b, uint32_t width, uint32_t height, int kind,
-                            uint32_t flags, float* d_grad, size_t grad_pitch_bytes, void* stream_v) {
-    const char* fn = "ws_image_error_gradient";
-    const std::string who(fn);
-    if (!ctx || !a || !b || !d_grad) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (width == 0 || height == 0) return fail(WS_ERR_INVALID, who + ": empty image");
-    if (width > 65536u || height > 65536u) return fail(WS_ERR_INVALID, who + ": image larger than 65536 pixels on a side");
-    if (flags & WS_METRICS_QUANTIZE_U8) return fail(WS_ERR_INVALID, who + ": WS_METRICS_QUANTIZE_U8 has no gradient");
-    if (flags) return fail(WS_ERR_INVALID, who + ": unknown flag bits");
-    if (kind != WS_ERROR_SQ && kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": kind must be WS_ERROR_SQ or WS_ERROR_ABS");
-    ImageErrorParams p;
-    int rc = metrics_view(a, width, "a", &p.a, fn);
-    if (rc == WS_OK) rc = metrics_view(b, width, "b", &p.b, fn);
-    if (rc) return rc;
-    if (grad_pitch_bytes < (size_t)width * 16 || grad_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(d_grad) % 16 != 0)
-        return fail(WS_ERR_INVALID, who + ": gradient pitch below 16 x width, or gradient pointer / pitch not 16-B aligned");
-    p.width = width;
-    p.height = height;
-    p.flags = 0;
-    p.kind = kind;
-    p.plane = d_grad;
-    p.plane_pitch = grad_pitch_bytes;
-    p.gradient = 1;
-    return launch_image_error(p, static_cast<hipStream_t>(stream_v));
-}
-
-}  // extern "C"
-
-// ---- refitting colour and opacity (include/websplat.h "Refitting colour and opacity"; refit.hip) ----------------
-struct ws_refit {
-    ws_context* ctx = nullptr;
-    const ws_pointcloud* pc = nullptr;   // the cloud the masters were widened from: the only one a step accepts
-    const uint4* planes = nullptr;       // (and its planes: a later cloud at the same address is another cloud)
-    uint32_t num_points = 0;
-    DeviceBuf<float4> master, m, v;      // [num_points] each
-    uint32_t steps = 0;
-    double p1 = 1.0, p2 = 1.0;           // beta1^steps, beta2^steps
-    hipStream_t last_stream = nullptr;
-    // ws_refit_enable_sh: the rest coefficients, one plane per element ([3 (ncoef - 1)][num_points]); empty at degree 0
-    uint32_t ncoef = 1;                  // (sh_deg + 1)^2 of the cloud
-    bool sh_enabled = false;
-    DeviceBuf<float> sh_master, sh_m, sh_v;
-};
-static_assert(sizeof(ws_refit_sh_params) == 72 && offsetof(ws_refit_sh_params, lr_sh) == 56 && offsetof(ws_refit_sh_params, reserved) == 60,
-              "ws_refit_sh_params layout (websplat/_lib.py mirrors it)");
-static_assert(sizeof(ws_refit_params) == 56 && offsetof(ws_refit_params, colour_unit) == 24 && offsetof(ws_refit_params, reserved) == 40,
-              "ws_refit_params layout (websplat/_lib.py mirrors it)");
-
-// Everything about a ws_refit_params that can be judged without a handle; units = false: the two unit fields are not looked at
-// (ws_scene_refit computes them per batch).
-int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& who, bool units) {
-    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
-    for (uint32_t w : p->reserved)
-        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    if (!std::isfinite(p->lr_colour) || !(p->lr_colour >= 0.0f)) return fail(WS_ERR_INVALID, who + ": lr_colour must be finite and not below 0");
-    if (!std::isfinite(p->lr_opacity) || !(p->lr_opacity >= 0.0f)) return fail(WS_ERR_INVALID, who + ": lr_opacity must be finite and not below 0");
-    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f)) return fail(WS_ERR_INVALID, who + ": beta1 must lie in [0, 1)");
-    if (!(p->beta2 >= 0.0f && p->beta2 < 1.0f)) return fail(WS_ERR_INVALID, who + ": beta2 must lie in [0, 1)");
-    if (!std::isfinite(p->eps) || !(p->eps > 0.0f)) return fail(WS_ERR_INVALID, who + ": eps must be finite and above 0");
-    if (!(p->opacity_min >= 0.0f && p->opacity_min <= 1.0f)) return fail(WS_ERR_INVALID, who + ": opacity_min must lie in [0, 1]");
-    if (units && (!std::isfinite(p->colour_unit) || !(p->colour_unit > 0.0))) return fail(WS_ERR_INVALID, who + ": colour_unit must be finite and above 0");
-    if (units && (!std::isfinite(p->opacity_unit) || !(p->opacity_unit > 0.0))) return fail(WS_ERR_INVALID, who + ": opacity_unit must be finite and above 0");
-    return WS_OK;
-}
-
-int ws_internal_refit_check_sh_params(const ws_refit_sh_params* p, const std::string& who, bool units) {
-    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
-    if (const int rc = ws_internal_refit_check_params(&p->base, who, units)) return rc;
-    for (uint32_t w : p->reserved)
-        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    if (!std::isfinite(p->lr_sh) || !(p->lr_sh >= 0.0f)) return fail(WS_ERR_INVALID, who + ": lr_sh must be finite and not below 0");
-    return WS_OK;
-}
-
-// The host's share of a step, common to ws_refit_step and ws_refit_step_sh: p1, p2 are the powers AFTER this step (committed by
-// the caller only when the launch went out); `sums` is the caller's.
-static RefitParams refit_kernel_params(const ws_refit* rf, ws_pointcloud* pc, const ws_refit_params* p, double p1, double p2) {
-    RefitParams kp;
-    kp.planes = pc->planes.get();
-    kp.sums = nullptr;
-    kp.master = rf->master.get();
-    kp.m = rf->m.get();
-    kp.v = rf->v.get();
-    kp.n = rf->num_points;
-    kp.lr_colour = p->lr_colour;
-    kp.lr_opacity = p->lr_opacity;
-    kp.beta1 = p->beta1;
-    kp.beta2 = p->beta2;
-    kp.omb1 = 1.0f - p->beta1;
-    kp.omb2 = 1.0f - p->beta2;
-    kp.bc1 = (float)(1.0 - p1);
-    kp.bc2 = (float)(1.0 - p2);
-    kp.eps = p->eps;
-    kp.opacity_min = p->opacity_min;
-    kp.u_colour = p->colour_unit * REFIT_C0_F64;
-    kp.u_opacity = p->opacity_unit;
-    return kp;
-}
-
-extern "C" {
-
-int ws_refit_create(ws_context* ctx, const ws_pointcloud* pc, ws_refit** out) {
-    if (!ctx || !pc || !out) return fail(WS_ERR_INVALID, "ws_refit_create: null argument");
-    *out = nullptr;
-    if (pc->compressed)
-        return fail(WS_ERR_UNSUPPORTED, "ws_refit_create: a compressed cloud cannot be refitted (its codebooks are shared between Gaussians)");
-    std::unique_ptr<ws_refit, SyncedDelete> rf(new (std::nothrow) ws_refit());
-    if (!rf) return fail(WS_ERR_OOM, "ws_refit_create: host allocation failed");
-    rf->ctx = ctx;
-    rf->pc = pc;
-    rf->planes = pc->planes.get();
-    rf->num_points = pc->num_points;
-    rf->ncoef = (pc->sh_deg + 1) * (pc->sh_deg + 1);
-    WS_TRY(rf->master.alloc(rf->num_points));
-    WS_TRY(rf->m.alloc(rf->num_points));
-    WS_TRY(rf->v.alloc(rf->num_points));
-    WS_TRY(launch_refit_init(rf->planes, rf->num_points, rf->master.get(), rf->m.get(), rf->v.get(), nullptr));
-    if (hipDeviceSynchronize() != hipSuccess) return fail(WS_ERR_HIP, "ws_refit_create: device sync failed");
-    *out = rf.release();
-    return WS_OK;
-}
-
-void ws_refit_destroy(ws_refit* rf) { SyncedDelete()(rf); }
-
-uint32_t ws_refit_num_points(const ws_refit* rf) { return rf ? rf->num_points : 0u; }
-uint32_t ws_refit_steps(const ws_refit* rf) { return rf ? rf->steps : 0u; }
-
-// The descriptor is judged by itself first, then the handles; the host's share of the step (the running beta powers, the bias
-// corrections, the units) is committed only when the launch went out.
-int ws_refit_step(ws_refit* rf, ws_pointcloud* pc, const ws_grad* g, const ws_refit_params* p, void* stream_v) {
-    const std::string who("ws_refit_step");
-    if (const int rc = ws_internal_refit_check_params(p, who, true)) return rc;
-    if (!rf || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (pc != rf->pc || pc->planes.get() != rf->planes || pc->compressed || pc->num_points != rf->num_points)
-        return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
-    if (g->num_points != rf->num_points) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another number of points");
-    const double p1 = rf->p1 * (double)p->beta1, p2 = rf->p2 * (double)p->beta2;
-    RefitParams kp = refit_kernel_params(rf, pc, p, p1, p2);
-    kp.sums = g->sums.get();
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (const int rc = launch_refit_step(kp, stream)) return rc;
-    rf->p1 = p1;
-    rf->p2 = p2;
-    ++rf->steps;
-    rf->last_stream = stream;
-    return WS_OK;
-}
-
-// The rest coefficients join: masters and moments of their own, widened from the stored halves.  Refused once a step has been
-// taken: the bias-correction powers are the object's, shared by every element.
-int ws_refit_enable_sh(ws_refit* rf, const ws_pointcloud* pc, void* stream_v) {
-    const std::string who("ws_refit_enable_sh");
-    if (!rf || !pc) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (pc != rf->pc || pc->planes.get() != rf->planes || pc->compressed || pc->num_points != rf->num_points)
-        return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
-    if (rf->sh_enabled) return WS_OK;
-    if (rf->steps > 0) return fail(WS_ERR_INVALID, who + ": steps have been taken already (the bias-correction powers are shared)");
-    const size_t count = (size_t)3 * (rf->ncoef - 1) * rf->num_points;
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (count) {
-        DeviceBuf<float> master, m, v;
-        WS_TRY(master.alloc(count));
-        WS_TRY(m.alloc(count));
-        WS_TRY(v.alloc(count));
-        WS_TRY(launch_refit_init_sh(rf->planes, rf->num_points, rf->ncoef, master.get(), m.get(), v.get(), stream));
-        rf->sh_master = std::move(master);
-        rf->sh_m = std::move(m);
-        rf->sh_v = std::move(v);
-        rf->last_stream = stream;
-    }
-    rf->sh_enabled = true;
-    return WS_OK;
-}
-
-int ws_refit_step_sh(ws_refit* rf, ws_pointcloud* pc, const ws_shgrad* g, const ws_refit_sh_params* p, void* stream_v) {
-    const std::string who("ws_refit_step_sh");
-    if (const int rc = ws_internal_refit_check_sh_params(p, who, true)) return rc;
-    if (!rf || !pc || !g) return fail(WS_ERR_INVALID, who + ": null argument");
-    if (pc != rf->pc || pc->planes.get() != rf->planes || pc->compressed || pc->num_points != rf->num_points)
-        return fail(WS_ERR_INVALID, who + ": not the point cloud this object was created for");
-    if (!rf->sh_enabled) return fail(WS_ERR_INVALID, who + ": ws_refit_enable_sh was not called");
-    if (g->num_points != rf->num_points) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another number of points");
-    if (g->ncoef != rf->ncoef) return fail(WS_ERR_INVALID, who + ": the gradient accumulator was created for another SH degree");
-    const double p1 = rf->p1 * (double)p->base.beta1, p2 = rf->p2 * (double)p->base.beta2;
-    RefitShParams kp;
-    kp.base = refit_kernel_params(rf, pc, &p->base, p1, p2);
-    kp.sh_sums = g->sums.get();
-    kp.sh_master = rf->sh_master.get();
-    kp.sh_m = rf->sh_m.get();
-    kp.sh_v = rf->sh_v.get();
-    kp.ncoef = rf->ncoef;
-    kp.lr_sh = rf->ncoef > 1 ? p->lr_sh : 0.0f;
-    kp.u_sh = p->base.colour_unit;
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (const int rc = launch_refit_step_sh(kp, stream)) return rc;
-    rf->p1 = p1;
-    rf->p2 = p2;
-    ++rf->steps;
-    rf->last_stream = stream;
-    return WS_OK;
-}
-
-int ws_refit_download_sh(ws_refit* rf, uint32_t capacity, float* master, float* m, float* v) {
-    if (!rf) return fail(WS_ERR_INVALID, "ws_refit_download_sh: null object");
-    if (!rf->sh_enabled) return fail(WS_ERR_INVALID, "ws_refit_download_sh: ws_refit_enable_sh was not called");
-    if ((master || m || v) && capacity < rf->num_points) return fail(WS_ERR_INVALID, "ws_refit_download_sh: capacity smaller than the number of points");
-    WS_HIP(hipStreamSynchronize(rf->last_stream));
-    const size_t n = rf->num_points, el = (size_t)3 * (rf->ncoef - 1);
-    if (el == 0 || (!master && !m && !v)) return WS_OK;
-    std::unique_ptr<float[]> st(new (std::nothrow) float[el * n]);
-    if (!st) return fail(WS_ERR_OOM, "ws_refit_download_sh: host allocation failed");
-    const std::pair<float*, const float*> jobs[3] = {{master, rf->sh_master.get()}, {m, rf->sh_m.get()}, {v, rf->sh_v.get()}};
-    for (const auto& job : jobs) {
-        if (!job.first) continue;
-        WS_TRY(copy_d2h(st.get(), job.second, el * n * sizeof(float), rf->last_stream));
-        for (size_t e = 0; e < el; ++e)
-            for (size_t i = 0; i < n; ++i) job.first[i * el + e] = st[e * n + i];
-    }
-    return WS_OK;
-}
-
-int ws_refit_download(ws_refit* rf, uint32_t capacity, float* master, float* m, float* v) {
-    if (!rf) return fail(WS_ERR_INVALID, "ws_refit_download: null object");
-    if ((master || m || v) && capacity < rf->num_points) return fail(WS_ERR_INVALID, "ws_refit_download: capacity smaller than the number of points");
-    WS_HIP(hipStreamSynchronize(rf->last_stream));
-    if (master) WS_TRY(copy_d2h(master, rf->master.get(), rf->master.bytes(), rf->last_stream));
-    if (m) WS_TRY(copy_d2h(m, rf->m.get(), rf->m.bytes(), rf->last_stream));
-    if (v) WS_TRY(copy_d2h(v, rf->v.get(), rf->v.bytes(), rf->last_stream));
     return WS_OK;
 }
 

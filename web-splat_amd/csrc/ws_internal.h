@@ -531,20 +531,20 @@ uint32_t ws_internal_renderer_frames_enqueued(const ws_renderer* r);
 bool ws_internal_renderer_progress(const ws_renderer* r, uint32_t* started_seq);
 // a renderer that runs beside others (a slot of a view batch with several frames in flight): see ws_api.cpp `throughput_mode`
 void ws_internal_renderer_set_throughput_mode(ws_renderer* r, bool on);
-// ws_scene_evaluate gives back the records of a pass it has to repeat (ws_api.cpp): the host counter only
+// ws_scene_evaluate gives back the records of a pass it has to repeat (api_metrics.cpp): the host counter only
 struct ws_metrics;
 void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count);
 // ws_renderer_accumulate_gradient in two steps, for ws_scene_accumulate_gradient, which makes the plane from pass 1's image
-// (ws_api.cpp): passes = 1: the base image only, nothing is accumulated; 2: k_gradient on a base plane already there; 3: the call
+// (api_attrib.cpp): passes = 1: the base image only, nothing is accumulated; 2: k_gradient on a base plane already there; 3: the call
 struct ws_grad;
 struct ws_gradient_params;
 int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream, unsigned passes);
 // what ws_refit_step judges from its descriptor alone, for ws_scene_refit, which fills in the two units itself (units = false:
-// they are not looked at) (ws_api.cpp)
+// they are not looked at) (api_refit.cpp)
 struct ws_refit_params;
 int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& who, bool units);
 // the same two for "SH gradients": ws_renderer_accumulate_sh_gradient in two steps (passes = 2: k_gradient + k_sh_spread), and what
-// ws_refit_step_sh judges from its descriptor alone, for ws_scene_accumulate_sh_gradient and ws_scene_refit_sh (ws_api.cpp)
+// ws_refit_step_sh judges from its descriptor alone, for ws_scene_accumulate_sh_gradient and ws_scene_refit_sh (api_attrib.cpp, api_refit.cpp)
 struct ws_shgrad;
 struct ws_refit_sh_params;
 int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream, unsigned passes);

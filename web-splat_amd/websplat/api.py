@@ -656,31 +656,39 @@ class PointCloud:
         return PointCloud(self.ctx, _handle=h)
 
 
-class Contrib:
-    """Per-Gaussian contribution accumulators over frames (websplat.h "Per-Gaussian contributions"): for every Gaussian of a
-    cloud of num_points, the q32 sum of its blend weights over all pixels of all frames added, and its largest weight."""
+class _GaussianSums:
+    """What Contrib, Grad and ShGrad share (csrc/gaussian_sums.h): the handle's life, reset and the two counters, by the entry
+    points' prefix.  A subclass has its constructor's arguments, download and add."""
+    _prefix = None   # "ws_contrib" | "ws_grad" | "ws_shgrad"
+    _create_args = ()   # what the creator takes between num_points and the handle
 
     def __init__(self, ctx: Context, num_points: int):
         self.ctx = ctx
         h = C.c_void_p()
-        check(lib.ws_contrib_create(ctx.handle, int(num_points), C.byref(h)))
+        check(getattr(lib, self._prefix + "_create")(ctx.handle, int(num_points), *self._create_args, C.byref(h)))
         self.handle = h
 
     def close(self):
         if self.handle:
-            lib.ws_contrib_destroy(self.handle)
+            getattr(lib, self._prefix + "_destroy")(self.handle)
             self.handle = None
 
     def reset(self, stream=None):
-        check(lib.ws_contrib_reset(self.handle, C.c_void_p(stream or 0)))
+        check(getattr(lib, self._prefix + "_reset")(self.handle, C.c_void_p(stream or 0)))
 
     def num_points(self) -> int:
-        return lib.ws_contrib_num_points(self.handle)
+        return getattr(lib, self._prefix + "_num_points")(self.handle)
 
     @property
     def frames(self) -> int:
         """frames added since creation / the last reset"""
-        return lib.ws_contrib_frames(self.handle)
+        return getattr(lib, self._prefix + "_frames")(self.handle)
+
+
+class Contrib(_GaussianSums):
+    """Per-Gaussian contribution accumulators over frames (websplat.h "Per-Gaussian contributions"): for every Gaussian of a
+    cloud of num_points, the q32 sum of its blend weights over all pixels of all frames added, and its largest weight."""
+    _prefix = "ws_contrib"
 
     def download(self):
         """(sum float64 = sum_q32 / 2^32, sum_q32 uint64, max_weight float32), one value per Gaussian (syncs)."""
@@ -699,31 +707,10 @@ class Contrib:
                                  m.ctypes.data_as(C.POINTER(C.c_float)) if m is not None else None, n))
 
 
-class Grad:
+class Grad(_GaussianSums):
     """Per-Gaussian gradient accumulators over frames (websplat.h "Gradients of an image loss"): for every Gaussian of a cloud
     of num_points, four signed q32 sums -- dL/d(colour r, g, b) and dL/d(ln opacity) times 2^32 and the calls' scales."""
-
-    def __init__(self, ctx: Context, num_points: int):
-        self.ctx = ctx
-        h = C.c_void_p()
-        check(lib.ws_grad_create(ctx.handle, int(num_points), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if self.handle:
-            lib.ws_grad_destroy(self.handle)
-            self.handle = None
-
-    def reset(self, stream=None):
-        check(lib.ws_grad_reset(self.handle, C.c_void_p(stream or 0)))
-
-    def num_points(self) -> int:
-        return lib.ws_grad_num_points(self.handle)
-
-    @property
-    def frames(self) -> int:
-        """frames added since creation / the last reset"""
-        return lib.ws_grad_frames(self.handle)
+    _prefix = "ws_grad"
 
     def download(self) -> np.ndarray:
         """(N, 4) int64: the q32 sums of colour r, g, b and ln-opacity per Gaussian (syncs)."""
@@ -743,36 +730,19 @@ class Grad:
 _i64p = C.POINTER(C.c_int64)
 
 
-class ShGrad:
+class ShGrad(_GaussianSums):
     """Per-Gaussian, per-coefficient gradient accumulators over frames (websplat.h "SH gradients"): for every Gaussian of a
     cloud of num_points and degree sh_deg, 3 (sh_deg + 1)^2 signed q32 sums dL/d(sh[k][ch]) -- coefficient 0 holds the plain
     colour sums of a Grad -- and dL/d(ln opacity)."""
+    _prefix = "ws_shgrad"
 
     def __init__(self, ctx: Context, num_points: int, sh_deg: int):
-        self.ctx = ctx
-        h = C.c_void_p()
-        check(lib.ws_shgrad_create(ctx.handle, int(num_points), int(sh_deg), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if self.handle:
-            lib.ws_shgrad_destroy(self.handle)
-            self.handle = None
-
-    def reset(self, stream=None):
-        check(lib.ws_shgrad_reset(self.handle, C.c_void_p(stream or 0)))
-
-    def num_points(self) -> int:
-        return lib.ws_shgrad_num_points(self.handle)
+        self._create_args = (int(sh_deg),)
+        super().__init__(ctx, num_points)
 
     @property
     def sh_deg(self) -> int:
         return lib.ws_shgrad_sh_deg(self.handle)
-
-    @property
-    def frames(self) -> int:
-        """frames added since creation / the last reset"""
-        return lib.ws_shgrad_frames(self.handle)
 
     def download(self) -> dict:
         """{"sh": (N, ncoef, 3) int64, "opacity": (N,) int64}: the q32 sums per Gaussian (syncs)."""
