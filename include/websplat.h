@@ -1038,7 +1038,23 @@ int  ws_scene_accumulate_sh_gradient(ws_context* ctx, const ws_pointcloud* pc, c
  * CLOUD CHANGES: not x, y, z, not the two bytes of padding beside the opacity, not the SH halves behind the DC triple.  A rate of
  * 0 freezes its group: its masters, moments and stored halves are not written.  Consequences that hold to the bit: (a) a Gaussian
  * with q = 0 and m = v = 0 keeps its masters and its stored halves, provided opacity_min is not above its opacity; (b) the result
- * does not depend on the launch geometry.  Denormal intermediates are not pinned.
+ * does not depend on the launch geometry.
+ * THE EDGES OF THE STEP, pinned like the rest (tests/refit_edges.py; profiles/refit/edges.json).  Denormals are honoured in every
+ * operation above -- operands and results, the division and the square root included -- and in both conversions: a subnormal
+ * half widens to its exact f32 master, and f16(x') rounds to nearest even onto subnormal halves (2^-25 stores as 0, 3 * 2^-25 as
+ * 0x0002).  Nothing is flushed: a first moment that decays under zero sums ends at +-4 * 2^-149 (4 * 0.9 rounds back to 4), not
+ * at 0.  A NaN passes both clamps (x' < lo and x' > hi are false) and is stored as a NaN half, its sign and payload the
+ * hardware's; a master of +-inf (an infinite half widened, or an x' that overflowed) is clamped like any other value: +-65504,
+ * opacity_min or 1.  A NaN half that a step only passes through keeps its bits, a signalling one too.  A master of -0 with sum 0
+ * stays -0.  Beyond the f32 range of g * g there are TWO OVERFLOW REGIMES, both permanent:
+ *   g * g = inf with g finite (|g| >= 2^64):  v' = inf, s = m^ / inf = 0, x' = x.  v stays inf under every later sum (beta2 * inf):
+ *                                             the parameter never moves again.
+ *   g = +-inf (|q * u| >= 2^128, or the opacity's g / x):  m' = +-inf, s = inf / inf = NaN: the master and its stored half are
+ *                                             NaN from this step on.
+ * Neither can occur while |q * u| < 2^63 for the colour and rest sums and |q * u / x| < 2^63 for the opacity, x its master (then
+ * g * g < 2^126 and every later intermediate is finite).  The descriptor checks do not enforce this bound: units are only required
+ * to be finite and positive, and an opacity master may lie far below the f16 range (opacity_min = 0 allows it: the master 2^-40
+ * stores as the half 0 and divides a sum by 2^-40).  Keeping the sums inside the bound is the caller's business.
  * ORDER.  ws_refit_step only ENQUEUES on `stream`, behind the accumulations that filled `g` on it.  Frames prepared later on that
  * stream see the new values (K1 reads the planes at every prepare()); frames of the cloud in flight on OTHER streams, prepared
  * or being prepared, are the caller's business -- the step does not wait for them.  ws_refit_download syncs.

@@ -101,26 +101,27 @@ class ShState(refit_ref.State):
         self.sh_m = np.zeros_like(self.sh_master)
         self.sh_v = np.zeros_like(self.sh_master)
 
-    def rest_halves(self):
-        return self.sh_master.astype(np.float16)
+    def rest_halves(self, defect=None):
+        return refit_ref.store16(self.sh_master, defect)
 
 
 def step_sh(st, q_sh, q_o, colour_unit, opacity_unit, lr_sh=0.000125, lr_colour=0.0025, lr_opacity=0.01, beta1=0.9, beta2=0.999, eps=1e-15,
-            opacity_min=0.0, trace=None):
+            opacity_min=0.0, trace=None, defect=None):
     """One ws_refit_step_sh of ShState st along q_sh (N, ncoef, 3) and q_o (N,), in place: refit_ref.step on the DC triple and the
     opacity, then the rest elements with g = (float)((double)q * colour_unit), the rate lr_sh and the clamp at +-65504, under the
     same powers."""
     q_sh, q_o = np.asarray(q_sh), np.asarray(q_o)
     assert q_sh.dtype == np.int64 and q_o.dtype == np.int64 and q_sh.shape[1:] == (st.sh_master.shape[1] + 1, 3)
     refit_ref.step(st, np.concatenate([q_sh[:, 0, :], q_o[:, None]], axis=1), colour_unit, opacity_unit, lr_colour=lr_colour,
-                   lr_opacity=lr_opacity, beta1=beta1, beta2=beta2, eps=eps, opacity_min=opacity_min, trace=trace)
+                   lr_opacity=lr_opacity, beta1=beta1, beta2=beta2, eps=eps, opacity_min=opacity_min, trace=trace, defect=defect)
     lr_sh, beta1, beta2, eps = (F(z) for z in (lr_sh, beta1, beta2, eps))
     if lr_sh != 0 and st.sh_master.shape[1]:
         bc1, bc2 = F(1.0 - st.p1), F(1.0 - st.p2)   # (the powers refit_ref.step has just advanced)
         omb1, omb2 = F(1.0) - beta1, F(1.0) - beta2
         with np.errstate(all="ignore"):
             g = (q_sh[:, 1:, :].astype(np.float64) * float(colour_unit)).astype(F)
-            x1, m1, v1 = refit_ref._adam(g, lr_sh, st.sh_master, st.sh_m, st.sh_v, beta1, beta2, omb1, omb2, bc1, bc2, eps, trace)
-        st.sh_master = refit_ref._clamp(x1, -SH_MAX, SH_MAX)
+            x1, m1, v1 = refit_ref._adam(g, lr_sh, st.sh_master, st.sh_m, st.sh_v, beta1, beta2, omb1, omb2, bc1, bc2, eps, trace,
+                                           defect)
+        st.sh_master = refit_ref._clamp(x1, -SH_MAX, SH_MAX, defect)
         st.sh_m, st.sh_v = m1, v1
     return st

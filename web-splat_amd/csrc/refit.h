@@ -38,6 +38,11 @@ struct RefitParams {
 // correctly rounded).  x', m', v' are stored, and f16(x'), round to nearest even, into the four halves of the planes.  A frozen
 // group's masters, moments and halves are not written.  No other byte of the planes changes: the opacity's word keeps its upper
 // half (the loader's padding), the second DC word its upper half (the first half of SH coefficient 1).
+// THE EDGES (include/websplat.h has them in full; tests/test_gpu_refit_edges.py holds the kernels to them): denormals are honoured
+// in every operation and in both conversions (the file must never be built with a flush-to-zero mode or a fast divide / square
+// root); a NaN passes clamp_to -- both of its comparisons are false -- and is stored as a NaN half; +-inf masters are clamped.
+// g * g = inf with g finite leaves v' = inf, s = 0 and the parameter unmoved for good; g = +-inf leaves m' = +-inf, s = NaN and a NaN
+// master.  Neither can occur while |q * u| < 2^63, for the opacity |q * u / x| < 2^63; nothing here enforces that bound.
 int launch_refit_step(const RefitParams& p, hipStream_t stream);
 
 // master[i] = the four halves widened to f32, m[i] = v[i] = 0
@@ -66,7 +71,8 @@ struct RefitShParams {
 // group whose rate is not 0 takes the same step with g = (float)((double)(int64_t)q[e] * u_sh), lr = lr_sh and the clamp +-65504;
 // x', m', v' go to plane e - 3 of the three arrays, f16(x') to its half.  Each thread loads its 16-B chunk once and, if it stepped
 // any of its halves, stores it once as a whole: the halves it did not step (a frozen group's; the first half of coefficient 1
-// beside a moving DC; the padding) go back with the bits they were read with.  No 2-byte store, no scratch.
+// beside a moving DC; the padding) go back with the bits they were read with -- as integers, never through a float: a signalling
+// NaN there stays signalling.  No 2-byte store, no scratch.  The edges of the step above hold for the rest elements word for word.
 int launch_refit_step_sh(const RefitShParams& p, hipStream_t stream);
 
 // master[e - 3][i] = half e of Gaussian i widened to f32, m = v = 0, for 3 <= e < 3 ncoef
