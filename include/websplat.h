@@ -916,8 +916,8 @@ int  ws_scene_accumulate_removal(ws_context* ctx, const ws_pointcloud* pc, const
  * red is above 0 in the frame -- with E == 1 everywhere, ws_renderer_accumulate_contrib's sum.
  * THE STOPS.  As "Removal effect": F ignores what lies behind a stop, so a pair's opacity term is under-reported by at most
  * r * 2^-14 * colour * |G|.
- * Out of scope: gradients with respect to position and covariance (the higher SH coefficients are "SH gradients" below, the
- * optimiser "Refitting colour and opacity", the writer "Saving a point cloud").
+ * Elsewhere: the higher SH coefficients are "SH gradients" below, position and covariance "Geometry gradients" behind it, the
+ * optimiser "Refitting colour and opacity", the writer "Saving a point cloud".
  * Errors: as ws_renderer_accumulate_removal, judged from the descriptor before a handle is looked at; in addition
  * WS_ERR_INVALID for a null d_grad, a gradient pointer or pitch that is not a multiple of 16, a pitch below 16 * width, a scale
  * or opacity_scale that is not finite and above 0.
@@ -991,8 +991,8 @@ int  ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, cons
  * q4[n][4] one frame's ws_grad-layout sums, xyz[n][3], cam[3]; ADDS to q_sh[n][ncoef][3] and q_opacity[n] (either may be NULL)
  * with active_deg in the place of the prepared frame's max_sh_deg.
  * ws_scene_accumulate_sh_gradient: ws_scene_accumulate_gradient's walk over the cameras with this per-frame call.
- * The optimiser is ws_refit_step_sh ("Refitting colour and opacity" below).  Out of scope: gradients with respect to position
- * and covariance; compressed clouds; a float or compacted accumulator. */
+ * The optimiser is ws_refit_step_sh ("Refitting colour and opacity" below); gradients with respect to position and covariance are
+ * "Geometry gradients" below.  Out of scope: compressed clouds; a float or compacted accumulator. */
 typedef struct ws_shgrad ws_shgrad;             /* 3 (sh_deg + 1)^2 + 1 int64 sums per Gaussian, device memory, zeroed */
 int  ws_shgrad_create(ws_context* ctx, uint32_t num_points, uint32_t sh_deg, ws_shgrad** out);
 void ws_shgrad_destroy(ws_shgrad* g);
@@ -1007,6 +1007,87 @@ int  ws_sh_spread_rows(const int64_t* q4, const float* xyz, const float* cam, ui
                        int64_t* q_sh, int64_t* q_opacity);
 int  ws_scene_accumulate_sh_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                      const char* gt_dir, int kind, float scale, float opacity_scale, ws_shgrad* grad, uint32_t* frames);
+/* ---- Geometry gradients: dL/d(position) and dL/d(covariance) per Gaussian (no counterpart in the reference) ----------------------
+ * The part of a 3DGS parameter set "Gradients of an image loss" and "SH gradients" leave out, and the densification statistic of
+ * the INRIA trainer.  The blend evaluates b = min(0.99, alpha * 2^(-a')), a' = p0^2 + p1^2, p = I' (x - mu), with I' the 2 x 2 map
+ * and mu the pixel centre the blend decodes from the 20-B Splat record: I'^T I' = (log2 e / 2) Sigma^-1, Sigma = (v1 v1^T + v2
+ * v2^T) / 2 in px^2; a pair is kept iff a' <= CUT_A2 (about 6.8), so |p|^2 <= CUT_A2 on every kept pair.
+ * With kappa = G_r d_r + G_g d_g + G_b d_b + G_T r T_end of "Gradients of an image loss" (its a, before opacity_scale):
+ * b dL/db = -kappa and db/da' = -ln2 b off the clamp, so dL/da' = ln2 kappa per pair.  Perturb mu -> mu + dmu and I' -> (1 + E) I':
+ * da' = 2 p^T (E p - I' dmu); the antisymmetric part of E turns the unit disc into itself and drops out.  Hence with
+ *   m_k  = sum_p kappa p_k   (k = 0, 1)        S_kl = sum_p kappa p_k p_l   (00, 01, 11)
+ * five sums per splat, bounded because |p| is:
+ *   dL/dmu    = sum_p ln2 kappa (-2 I'^T p)                          = -2 ln2 I'^T m                (px^-1, x right, y down)
+ *   dL/dSigma = sum_p ln2 kappa (-(log2 e / 2) Sigma^-1 d d^T Sigma^-1) = -2 (ln2)^2 I'^T S I'      (symmetric 2 x 2, px^-2)
+ * the second with d = x - mu and Sigma^-1 d = (2 / log2 e) I'^T p.
+ * ws_renderer_accumulate_geometry_gradient: preconditions and descriptor checks exactly those of ws_renderer_accumulate_gradient
+ * (geometry_scale in the place of opacity_scale: finite, > 0), WS_ERR_INVALID for a ws_geomgrad of another size, WS_ERR_UNSUPPORTED
+ * for a compressed cloud.  Three launches on `stream`, no blend launch, no target changed; counts as a frame of g.
+ * STAGE A, k_removal_base (unchanged) and k_geometry: the pairs, weights and stops of "Per-Gaussian contributions"; per walked pair
+ * Tb, T, P_ch, r, d_ch, u and kappa exactly as "Gradients of an image loss" forms them (one copy of the code), counted under its
+ * opacity rule: kept, w > 0, Tb >= 2^-14, not on the 0.99 clamp.  With p0, p1 the walk's own values, every multiply rounded by itself:
+ *   t = geometry_scale * kappa;  v = (t * p0, t * p1, (t * p0) * p0, (t * p0) * p1, (t * p1) * p1)
+ * each NaN -> 0 and capped silently at +-0x1.fffffep-1f, into five int64 sums per Gaussian under the ACCUMULATION rule of
+ * "Gradients of an image loss" (q = (int64_t)(v * 2^32) toward zero; integer sums commute), in the accumulator's scratch.  Bit for
+ * bit: g and -g give negated sums; a 0/1 mask of the plane and its complement add up to the whole; the launch geometry and
+ * repetition do not show.
+ * STAGE B, k_geom_spread: one thread per store slot i of the prepared frame (slots at or beyond the visible count return), no
+ * atomics.  j = src_index[i]; the five scratch sums of j all 0: nothing else is read or written; else they are zeroed again (the
+ * next frame needs no memset) and, ALL IN F64 with + - x / sqrt and comparisons only, none contracted:
+ *   1. I' from the record's four halves by the blend's decode expressions; m, S = sums / (2^32 geometry_scale); dmu and D = dL/dSigma
+ *      as above.  K1 forms Sigma with y up (its Jacobian's second row is negated), so D_K = diag(1, -1) D diag(1, -1).
+ *   2. from the prepared frame's ws_camera_uniform and ws_settings_uniform, the cloud's f32 position and six f16 covariance halves,
+ *      as K1 states them: cs = view (xyz, 1); clip = proj cs; w; jac(cs) = [fx / z, 0, -fx x / z^2; 0, -fy / z, fy y / z^2]; T = jac
+ *      view3x3; scaling^2 = (gaussian_scaling scale_mod)^2; V = scaling^2 sym(cov); lambda2_raw of T V T^T + kernel_size I.
+ *   3. position.  Through the centre mu_px = ((clip_x / w / 2 + 1/2) W, (1/2 - clip_y / w / 2) H); through the Jacobian,
+ *      dL/dT = 2 D_K T V, on through jac's four non-zero entries to cs; both to the world by view^T.
+ *   4. covariance.  scaling^2 T^T D_K T as six numbers (xx xy xz yy yz zz): the derivatives with respect to the six STORED
+ *      elements, so an off-diagonal is twice the symmetric matrix's entry.
+ *   5. the statistic.  n = sqrt(gx^2 + gy^2) of the NDC gradient (W/2 dmu_x, -H/2 dmu_y) -- the INRIA trainer's
+ *      viewspace_point_tensor.grad -- is added to screen_norm[j], and 1 to seen[j].
+ * LEFT OUT.  A splat whose lambda2_raw < 0.1 has its record's minor axis on K1's clamp: it adds nothing to the covariance sums and
+ * nothing through the Jacobian; its centre path still counts.  The dependence of the colour on the view direction, of the
+ * mip-splatting opacity factor on Sigma and of the fade-in scale_mod on the position are not differentiated.  The record's f16
+ * rounding is treated as the identity.  Compressed clouds are refused (WS_ERR_UNSUPPORTED), as ws_refit refuses them.  No
+ * optimiser step moves positions or covariances.
+ * THE SUMS.  Ten f64 per Gaussian (position 3, covariance 6, screen_norm 1) and one uint64 count, one plane per element on the
+ * device.  They are f64, not q32, because their range is unbounded: a covariance gradient scales with 1 / extent^2.  Each Gaussian
+ * belongs to one thread per frame and the stream orders the frames: the result is reproducible for a given frame order, and it is
+ * in units of the clamped plane G (divide by scale).  Merges across ranks are exact only for seen; ws_geomgrad_add adds in the
+ * order given.  ws_geomgrad_download: any of the four arrays may be NULL; syncs.
+ * ws_geom_spread_rows (host only, no device needed): stage B's per-Gaussian code from the same text, over n rows -- q5[n][5] one
+ * frame's scratch sums, rec[n][4] the record's halves 0..3 as f16 bits, xyz[n][3], cov[n][6] f16 bits; rows whose five sums are
+ * all 0 are skipped; ADDS to the four arrays (any may be NULL). */
+typedef struct ws_geomgrad ws_geomgrad;         /* ten f64 sums and one uint64 count per Gaussian, device memory, zeroed */
+typedef struct ws_geometry_params {
+    float background[3]; float scale; float geometry_scale; uint32_t reserved0;   /* scales finite, > 0; reserved0 zero */
+    const float* d_grad; size_t grad_pitch_bytes;      /* as ws_gradient_params */
+    float* d_base; size_t base_pitch_bytes;            /* may be NULL, as ws_removal_params */
+    uint32_t reserved[4];                              /* zero */
+} ws_geometry_params;
+int  ws_geomgrad_create(ws_context* ctx, uint32_t num_points, ws_geomgrad** out);
+void ws_geomgrad_destroy(ws_geomgrad* g);
+int  ws_geomgrad_reset(ws_geomgrad* g, void* stream);
+uint32_t ws_geomgrad_num_points(const ws_geomgrad* g);
+uint32_t ws_geomgrad_frames(const ws_geomgrad* g);
+int  ws_geomgrad_download(ws_geomgrad* g, uint32_t capacity, double* position /* [capacity][3] */, double* covariance /* [capacity][6] */,
+                          double* screen_norm /* [capacity] */, uint64_t* seen /* [capacity] */);   /* syncs */
+int  ws_geomgrad_add(ws_geomgrad* g, const double* position, const double* covariance, const double* screen_norm, const uint64_t* seen,
+                     uint32_t n);
+int  ws_renderer_accumulate_geometry_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p,
+                                              void* stream); /* enqueues; counts as a frame of g */
+int  ws_geom_spread_rows(const int64_t* q5, const uint16_t* rec, const float* xyz, const uint16_t* cov, const ws_camera_uniform* cam,
+                         const ws_settings_uniform* settings, float geometry_scale, uint32_t n, double* position, double* covariance,
+                         double* screen_norm, uint64_t* seen);
+/* ws_scene_accumulate_gradient's walk over the cameras with this per-frame call (geometry_scale where that has opacity_scale) */
+int  ws_scene_accumulate_geometry_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                                           const char* gt_dir, int kind, float scale, float geometry_scale, ws_geomgrad* grad, uint32_t* frames);
+/* test hook: the scratch of a ws_geomgrad, [capacity][5] int64 (m0, m1, S00, S01, S11); syncs.  Zero between the calls. */
+int  ws_debug_geomgrad_scratch(ws_geomgrad* g, uint32_t capacity, int64_t* q5);
+/* test hooks: stage A alone (k_removal_base + k_geometry) into g's scratch, adding no frame; and the scratch zeroed again, which a
+ * caller of the first owes the next ws_renderer_accumulate_geometry_gradient (stage B would have done it). */
+int  ws_debug_geometry_stage_a(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream);
+int  ws_debug_geomgrad_clear_scratch(ws_geomgrad* g, void* stream);
 /* ---- Refitting colour and opacity: Adam steps on the resident planes, in place (no counterpart in the reference) -----------------
  * What "Gradients of an image loss" is for: its sums say in which direction every colour and opacity of a (pruned) cloud should
  * move; a ws_refit moves them.  It belongs to ONE uncompressed point cloud and holds, per Gaussian, f32 masters of four

@@ -22,6 +22,7 @@
 namespace ws {
 
 constexpr int GRAD_CHANNELS = 4;  // colour r, g, b; ln-opacity
+constexpr int GEOM_CHANNELS = 5;  // m0, m1, S00, S01, S11 (geometry.h)
 
 }  // namespace ws
 
@@ -78,6 +79,56 @@ struct AccumS32 {
             unsigned long long* g = sums + (size_t)src_index[idx] * GRAD_CHANNELS;
 #pragma unroll
             for (int ch = 0; ch < GRAD_CHANNELS; ++ch)
+                if (s[ch] != 0ull) atomicAdd(g + ch, s[ch]);
+        }
+    }
+};
+
+// The five-channel sibling (geometry.hip, GeometrySink): the same q, the same bias, the same three meeting points.  Five low words
+// and three words of high parts (channels 0|1, 2|3, 4): eight wave sums per pair.  AccumS32 above is left as it was, so that
+// k_gradient's code does not depend on this one.
+template <int STAGE>
+struct AccumS32x5 {
+    unsigned long long* sums;   // [num_points][GEOM_CHANNELS], two's complement
+    unsigned long long* s_sum;  // [GEOM_CHANNELS][STAGE]
+    const int lane = threadIdx.x & 63;
+
+    __device__ __forceinline__ void clear(int tid) {
+#pragma unroll
+        for (int ch = 0; ch < GEOM_CHANNELS; ++ch) s_sum[ch * STAGE + tid] = 0ull;
+    }
+    __device__ __forceinline__ void add(uint32_t off, const float (&v)[GEOM_CHANNELS]) {  // off = slot * 16; every lane of the wave
+        BiasedQ u[GEOM_CHANNELS];
+        uint32_t l[GEOM_CHANNELS];
+#pragma unroll
+        for (int ch = 0; ch < GEOM_CHANNELS; ++ch) u[ch] = biased_q(v[ch]);
+#pragma unroll
+        for (int ch = 0; ch < GEOM_CHANNELS; ++ch) l[ch] = wave_add_u32(u[ch].lo26());
+        const uint32_t h01 = wave_add_u32(u[0].hi7() | (u[1].hi7() << 16)), h23 = wave_add_u32(u[2].hi7() | (u[3].hi7() << 16));
+        const uint32_t h4 = wave_add_u32(u[4].hi7());
+        constexpr unsigned long long BIAS = 1ull << 38;  // 64 lanes x 2^32
+        const uint32_t h[GEOM_CHANNELS] = {h01 & 0xFFFFu, h01 >> 16, h23 & 0xFFFFu, h23 >> 16, h4};
+        unsigned long long s[GEOM_CHANNELS], any = 0ull;
+#pragma unroll
+        for (int ch = 0; ch < GEOM_CHANNELS; ++ch) {
+            s[ch] = (unsigned long long)l[ch] + ((unsigned long long)h[ch] << 26) - BIAS;
+            any |= s[ch];
+        }
+        if (any != 0ull && lane == 0) {  // (the sums are wave-uniform)
+            unsigned long long* d = s_sum + (off >> 4);
+#pragma unroll
+            for (int ch = 0; ch < GEOM_CHANNELS; ++ch)
+                if (s[ch] != 0ull) atomicAdd(d + ch * STAGE, s[ch]);
+        }
+    }
+    __device__ __forceinline__ void flush(const uint32_t* src_index, int tid, uint32_t idx) {
+        unsigned long long s[GEOM_CHANNELS], any = 0ull;
+#pragma unroll
+        for (int ch = 0; ch < GEOM_CHANNELS; ++ch) any |= (s[ch] = s_sum[ch * STAGE + tid]);
+        if (any != 0ull) {
+            unsigned long long* g = sums + (size_t)src_index[idx] * GEOM_CHANNELS;
+#pragma unroll
+            for (int ch = 0; ch < GEOM_CHANNELS; ++ch)
                 if (s[ch] != 0ull) atomicAdd(g + ch, s[ch]);
         }
     }

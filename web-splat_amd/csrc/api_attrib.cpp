@@ -1,6 +1,6 @@
 // api_attrib.cpp -- the C ABI's passes over a prepared frame's blend weights and the per-Gaussian accumulators they add to
-// (include/websplat.h): contributions, values, removal effect, gradients, SH gradients.  They read the renderer's prepared
-// frame (api_state.h) and never make one; the three accumulators are one store (gaussian_sums.h).
+// (include/websplat.h): contributions, values, removal effect, gradients, SH gradients, geometry gradients.  They read the
+// renderer's prepared frame (api_state.h) and never make one; the four accumulators are one store (gaussian_sums.h).
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -9,6 +9,8 @@
 #include "api_state.h"
 #include "contrib.h"
 #include "gaussian_sums.h"
+#include "geometry.h"
+#include "geometry_spread.h"
 #include "gradient.h"
 #include "sh_gradient.h"
 #include "values.h"
@@ -163,17 +165,21 @@ static int accumulate_frame(ws_renderer* r, const ws_pointcloud* pc, ws_contrib*
 
 static_assert(WS_GRAD_CHANNELS == GRAD_CHANNELS, "the ABI's channel count is the kernel's");
 
-// One sequence for both gradient accumulators; sh: `acc` again when it is a ws_shgrad, else nullptr.  The descriptor is judged
-// by itself first, then the handles, then the descriptor against the frame; only then the launches: removal's pass 1 through
-// launch_removal_base, then k_gradient -- into the accumulator, or into a ws_shgrad's scratch, then k_sh_spread.
+// One sequence for the three gradient accumulators; sh / geo: `acc` again when it is a ws_shgrad / ws_geomgrad, else nullptr.  The
+// descriptor is judged by itself first, then the handles, then the descriptor against the frame; only then the launches:
+// removal's pass 1 through launch_removal_base, then k_gradient -- into the accumulator, or into a ws_shgrad's scratch, then
+// k_sh_spread -- or, for a ws_geomgrad (whose descriptor carries geometry_scale where opacity_scale is), k_geometry into its
+// scratch, then k_geom_spread (passes & 4; without it the sums stay in the scratch: ws_debug_geometry_stage_a); `geometry` says so
+// where `geo` may still be null.
 static int gradient_passes(const std::string& who, ws_renderer* r, const ws_pointcloud* pc, GaussianSums* acc, ws_shgrad* sh,
-                           const ws_gradient_params* p, void* stream_v, unsigned passes) {
+                           const ws_gradient_params* p, void* stream_v, unsigned passes, ws_geomgrad* geo = nullptr, bool geometry = false) {
     if (!p) return fail(WS_ERR_INVALID, who + ": null params");
     if (p->reserved0 != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
     for (uint32_t w : p->reserved)
         if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
     if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    if (!std::isfinite(p->opacity_scale) || !(p->opacity_scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": opacity_scale must be finite and above 0");
+    if (!std::isfinite(p->opacity_scale) || !(p->opacity_scale > 0.0f))
+        return fail(WS_ERR_INVALID, who + (geometry ? ": geometry_scale" : ": opacity_scale") + " must be finite and above 0");
     for (float b : p->background)
         if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
     if (!p->d_grad) return fail(WS_ERR_INVALID, who + ": null d_grad");
@@ -185,6 +191,7 @@ static int gradient_passes(const std::string& who, ws_renderer* r, const ws_poin
     const int state = check_weights_frame(r, pc, who, acc->num_points == pc->num_points, "the accumulator was created for another number of points");
     if (state) return state;
     if (sh && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no SH gradients (its codebooks are shared between Gaussians)");
+    if (geometry && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no geometry gradients (its covariances are a codebook shared between Gaussians)");
     if (sh && sh->sh_deg != pc->sh_deg) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another SH degree");
     if (p->grad_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_grad: grad_pitch_bytes below 16 x the viewport's width");
     if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
@@ -207,6 +214,33 @@ static int gradient_passes(const std::string& who, ws_renderer* r, const ws_poin
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     KernelMarks* km = launch_begin(r, stream);
     int rc = (passes & 1u) ? launch_removal_base(rp, stream) : WS_OK;
+    if (geometry) {
+        GeometryParams ep;
+        ep.frame = rp.frame;
+        ep.base = rp.base;
+        ep.base_pitch = rp.base_pitch;
+        ep.grad = gp.grad;
+        ep.grad_pitch = gp.grad_pitch;
+        ep.scale = p->scale;
+        ep.geometry_scale = p->opacity_scale;
+        ep.sums = geo->scratch.get();
+        if (rc == WS_OK && (passes & 2u)) rc = launch_geometry(ep, stream);
+        if (rc == WS_OK && (passes & 4u)) {
+            GeomSpreadParams sp{};
+            sp.planes = pc->planes.get();
+            sp.splats = rp.frame.splats;
+            sp.src_index = rp.frame.src_index;
+            sp.counters = rp.frame.counters;
+            sp.scratch = geo->scratch.get();
+            sp.sums = geo->sums.get();
+            sp.n = geo->num_points;
+            sp.frame.cam = r->frame.cam;
+            sp.frame.rs = r->frame.settings;
+            sp.frame.geometry_scale = p->opacity_scale;
+            rc = launch_geom_spread(sp, stream);
+        }
+        return launch_done(rc, r, (passes & 4u) ? acc : nullptr, stream, km, passes == 1u ? "k_removal_base" : passes == 3u ? "k_removal_base+k_geometry" : passes == 6u ? "k_geometry+k_geom_spread" : "k_removal_base+k_geometry+k_geom_spread");
+    }
     if (rc == WS_OK && (passes & 2u)) rc = launch_gradient(gp, stream);
     if (rc == WS_OK && (passes & 2u) && sh) {
         ShSpreadParams sp;
@@ -231,6 +265,11 @@ int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad
 
 int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
     return gradient_passes("ws_renderer_accumulate_sh_gradient", r, pc, g, g, p, stream_v, passes);
+}
+
+// (p->opacity_scale is the geometry_scale here; passes: 1 the base image, 2 k_geometry into the scratch, 4 k_geom_spread)
+int ws_internal_geometry_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
+    return gradient_passes("ws_renderer_accumulate_geometry_gradient", r, pc, g, nullptr, p, stream_v, passes, g, true);
 }
 
 extern "C" {
@@ -452,6 +491,97 @@ int ws_shgrad_add(ws_shgrad* g, const int64_t* q_sh, const int64_t* q_opacity, u
 // ... and ws_renderer_accumulate_gradient's launches into the accumulator's scratch, then k_sh_spread
 int ws_renderer_accumulate_sh_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream) {
     return ws_internal_sh_gradient_passes(r, pc, g, p, stream, 3u);
+}
+
+// ---- ws_geomgrad: ten f64 planes and a count plane of the store, a frame's scratch, and the host's transposes
+static int geometry_passes(const char* who, ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream, unsigned passes) {
+    ws_gradient_params gp{};
+    if (p) {
+        static_assert(sizeof(ws_geometry_params) == sizeof(ws_gradient_params), "the two descriptors differ in the meaning of one float");
+        std::memcpy(&gp, p, sizeof gp);
+    }
+    return gradient_passes(who, r, pc, g, nullptr, p ? &gp : nullptr, stream, passes, g, true);
+}
+
+int ws_geomgrad_create(ws_context* ctx, uint32_t num_points, ws_geomgrad** out) {
+    return create_sums("ws_geomgrad_create", ctx, num_points, out, [num_points](ws_geomgrad* g) {
+        WS_TRY(g->sums.alloc((size_t)GEOM_ELEMENTS * num_points));
+        WS_TRY(g->scratch.alloc((size_t)num_points * GEOM_SCRATCH));
+        WS_HIP(hipMemsetAsync(g->scratch.get(), 0, g->scratch.bytes(), nullptr));
+        return ws_geomgrad_reset(g, nullptr);
+    });
+}
+
+void ws_geomgrad_destroy(ws_geomgrad* g) { SyncedDelete()(g); }
+// (the scratch is zero between the calls by k_geom_spread's own doing; a reset leaves it alone.  All-zero words are 0.0 and 0.)
+int ws_geomgrad_reset(ws_geomgrad* g, void* stream) { return GaussianSums::reset(g, "ws_geomgrad_reset", static_cast<hipStream_t>(stream)); }
+
+uint32_t ws_geomgrad_num_points(const ws_geomgrad* g) { return g ? g->num_points : 0u; }
+uint32_t ws_geomgrad_frames(const ws_geomgrad* g) { return g ? g->frames : 0u; }
+
+// The device keeps one plane per element; the caller's rows are per Gaussian: the transposes are the host's, as ws_shgrad's are.
+int ws_geomgrad_download(ws_geomgrad* g, uint32_t capacity, double* position, double* covariance, double* screen_norm, uint64_t* seen) {
+    const bool wanted = position || covariance || screen_norm || seen;
+    std::unique_ptr<uint64_t[]> st;
+    if (g && wanted) {
+        st.reset(new (std::nothrow) uint64_t[g->sums.count()]);
+        if (!st) return fail(WS_ERR_OOM, "ws_geomgrad_download: host allocation failed");
+    }
+    WS_TRY(GaussianSums::download_words(g, "ws_geomgrad_download", capacity, st != nullptr, st.get()));
+    if (!st) return WS_OK;
+    const size_t n = g->num_points;
+    const double* d = reinterpret_cast<const double*>(st.get());
+    for (size_t i = 0; i < n; ++i) {
+        for (size_t k = 0; position && k < 3; ++k) position[i * 3 + k] = d[k * n + i];
+        for (size_t e = 0; covariance && e < 6; ++e) covariance[i * 6 + e] = d[(3 + e) * n + i];
+    }
+    if (screen_norm) std::memcpy(screen_norm, d + 9 * n, n * sizeof(double));
+    if (seen) std::memcpy(seen, st.get() + 10 * n, n * sizeof(uint64_t));
+    return WS_OK;
+}
+
+int ws_geomgrad_add(ws_geomgrad* g, const double* position, const double* covariance, const double* screen_norm, const uint64_t* seen, uint32_t n_rows) {
+    std::unique_ptr<uint64_t[]> st;
+    if (g && n_rows >= g->num_points && (position || covariance || screen_norm || seen)) {  // (else the store refuses, or there is nothing to add)
+        const size_t n = g->num_points;
+        st.reset(new (std::nothrow) uint64_t[g->sums.count()]());  // (zeros where a pointer is NULL: +0.0 and 0)
+        if (!st) return fail(WS_ERR_OOM, "ws_geomgrad_add: host allocation failed");
+        double* d = reinterpret_cast<double*>(st.get());
+        for (size_t i = 0; i < n; ++i) {
+            for (size_t k = 0; position && k < 3; ++k) d[k * n + i] = position[i * 3 + k];
+            for (size_t e = 0; covariance && e < 6; ++e) d[(3 + e) * n + i] = covariance[i * 6 + e];
+        }
+        if (screen_norm) std::memcpy(d + 9 * n, screen_norm, n * sizeof(double));
+        if (seen) std::memcpy(st.get() + 10 * n, seen, n * sizeof(uint64_t));
+    }
+    const GaussianSums::Merge merge = [g](const unsigned long long* d_words, hipStream_t stream) {
+        return launch_geom_merge(g->sums.get(), d_words, g->num_points, stream);
+    };
+    return GaussianSums::merge_words(g, "ws_geomgrad_add", n_rows, st.get(), st ? merge : GaussianSums::Merge());
+}
+
+int ws_renderer_accumulate_geometry_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream) {
+    return geometry_passes("ws_renderer_accumulate_geometry_gradient", r, pc, g, p, stream, 7u);
+}
+
+int ws_debug_geometry_stage_a(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream) {
+    WS_TRY(geometry_passes("ws_debug_geometry_stage_a", r, pc, g, p, stream, 3u));
+    g->last_stream = static_cast<hipStream_t>(stream);  // (no frame added, but the scratch is read back behind this stream)
+    return WS_OK;
+}
+
+int ws_debug_geomgrad_scratch(ws_geomgrad* g, uint32_t capacity, int64_t* q5) {
+    if (!g || !q5) return fail(WS_ERR_INVALID, "ws_debug_geomgrad_scratch: null argument");
+    if (capacity < g->num_points) return fail(WS_ERR_INVALID, "ws_debug_geomgrad_scratch: capacity smaller than the number of points");
+    WS_HIP(hipStreamSynchronize(g->last_stream));
+    return copy_d2h(q5, g->scratch.get(), g->scratch.bytes(), g->last_stream);
+}
+
+int ws_debug_geomgrad_clear_scratch(ws_geomgrad* g, void* stream) {
+    if (!g) return fail(WS_ERR_INVALID, "ws_debug_geomgrad_clear_scratch: null accumulator");
+    WS_HIP(hipMemsetAsync(g->scratch.get(), 0, g->scratch.bytes(), static_cast<hipStream_t>(stream)));
+    g->last_stream = static_cast<hipStream_t>(stream);
+    return WS_OK;
 }
 
 }  // extern "C"

@@ -51,6 +51,8 @@ struct PreparedFrame {
     float znear = 0.0f, zfar = 0.0f; // K1Params::znear / zfar (the composite's NDC occluder)
     float cam_pos[3] = {0.0f, 0.0f, 0.0f};  // view_inv[12..14] of K1's camera uniform: where K1 takes the SH direction from
     uint32_t max_sh_deg = 0;         // of K1's settings uniform (both read by ws_renderer_accumulate_sh_gradient)
+    ws_camera_uniform cam{};         // K1's two uniforms as the frame was prepared with them (read by
+    ws_settings_uniform settings{};  //   ws_renderer_accumulate_geometry_gradient, which takes the sums back through K1's projection)
     FrameArrays arrays;
     float* k1_depths = nullptr;      // the z plane the prepare() in progress writes (nullptr: depth off)
     unsigned long long* trace_slot = nullptr;  // the frame's slot of ws_renderer::frame_trace (nullptr: not traced)

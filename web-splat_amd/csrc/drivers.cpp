@@ -346,11 +346,13 @@ int refuse_scale(const std::string& who, const char* name, float v) {
 struct GradSink {
     ws_grad* grad = nullptr;
     ws_shgrad* sh = nullptr;
+    ws_geomgrad* geo = nullptr;   // (its descriptor's opacity_scale is the geometry_scale; step 2 is k_geometry + k_geom_spread)
     int passes(ws_renderer* r, const ws_pointcloud* pc, const ws_gradient_params* p, unsigned which) const {
+        if (geo) return ws_internal_geometry_gradient_passes(r, pc, geo, p, nullptr, which == 2u ? 6u : which);
         return sh ? ws_internal_sh_gradient_passes(r, pc, sh, p, nullptr, which) : ws_internal_gradient_passes(r, pc, grad, p, nullptr, which);
     }
-    uint32_t num_points() const { return sh ? ws_shgrad_num_points(sh) : ws_grad_num_points(grad); }
-    int reset() const { return sh ? ws_shgrad_reset(sh, nullptr) : ws_grad_reset(grad, nullptr); }
+    uint32_t num_points() const { return geo ? ws_geomgrad_num_points(geo) : sh ? ws_shgrad_num_points(sh) : ws_grad_num_points(grad); }
+    int reset() const { return geo ? ws_geomgrad_reset(geo, nullptr) : sh ? ws_shgrad_reset(sh, nullptr) : ws_grad_reset(grad, nullptr); }
 };
 
 int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, const GradSink& grad, const ws_gradient_params& gp, int kind, const SceneFrame& f) {
@@ -369,14 +371,14 @@ int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, const GradSink& gra
     return frc;
 }
 
-// ws_scene_accumulate_gradient and ws_scene_accumulate_sh_gradient
+// ws_scene_accumulate_gradient, ws_scene_accumulate_sh_gradient and ws_scene_accumulate_geometry_gradient
 int scene_accumulate_gradient(const std::string& who, ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split,
                               const ws_pointcloud* ref_pc, const char* gt_dir, int kind, float scale, float opacity_scale, bool have_sink,
                               const GradSink& grad, uint32_t* frames) {
     if (frames) *frames = 0;
     if (const int rc = refuse_kind(who, kind)) return rc;
     if (const int rc = refuse_scale(who, "scale", scale)) return rc;
-    if (const int rc = refuse_scale(who, "opacity_scale", opacity_scale)) return rc;
+    if (const int rc = refuse_scale(who, grad.geo ? "geometry_scale" : "opacity_scale", opacity_scale)) return rc;
     if (const int rc = refuse_unless_a_split(who, split)) return rc;
     if (!ctx || !pc || !scene || !have_sink) return fail(WS_ERR_INVALID, who + ": null argument");
     if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
@@ -594,6 +596,14 @@ int ws_scene_accumulate_sh_gradient(ws_context* ctx, const ws_pointcloud* pc, co
     GradSink sink;
     sink.sh = grad;
     return scene_accumulate_gradient("ws_scene_accumulate_sh_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, opacity_scale, grad != nullptr, sink, frames);
+}
+
+// ... and into a ws_geomgrad (websplat.h "Geometry gradients"): geometry_scale where the other two have opacity_scale
+int ws_scene_accumulate_geometry_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
+                                          const char* gt_dir, int kind, float scale, float geometry_scale, ws_geomgrad* grad, uint32_t* frames) {
+    GradSink sink;
+    sink.geo = grad;
+    return scene_accumulate_gradient("ws_scene_accumulate_geometry_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, geometry_scale, grad != nullptr, sink, frames);
 }
 
 // ... and the loops those gradients are for (websplat.h "Refitting colour and opacity"; scene_refit above)

@@ -1,4 +1,4 @@
-// gaussian_sums.h -- the store under the per-Gaussian accumulators of the ABI (ws_contrib, ws_grad, ws_shgrad): a device array
+// gaussian_sums.h -- the store under the per-Gaussian accumulators of the ABI (ws_contrib, ws_grad, ws_shgrad, ws_geomgrad): a device array
 // of 64-bit sums, so many words per Gaussian, with the frames added and the stream of the last launch, and the three things every
 // accumulator does with it.  Host only; the functions are defined in api_attrib.cpp beside the handles' entry points.  They take
 // the handle as the ABI got it and the entry point's name: "<who>: null accumulator" is the first refusal of each.
@@ -43,4 +43,8 @@ struct ws_grad : ws::GaussianSums {};    // sums: [num_points][WS_GRAD_CHANNELS]
 struct ws_shgrad : ws::GaussianSums {    // sums: [3 ncoef + 1][num_points]: one plane per element, the opacity's last
     uint32_t sh_deg = 0, ncoef = 1;
     ws::DeviceBuf<unsigned long long> scratch;  // [num_points][WS_GRAD_CHANNELS]: one frame's sums, zero between the calls
+};
+// ---- geometry gradients (include/websplat.h "Geometry gradients"; geometry.hip, geometry_spread.hip) ----
+struct ws_geomgrad : ws::GaussianSums {  // sums: [11][num_points]: ten planes of f64 bits (position 3, covariance 6, screen_norm), then seen
+    ws::DeviceBuf<unsigned long long> scratch;  // [num_points][5] int64: one frame's screen-space sums, zero between the calls
 };

@@ -10,22 +10,14 @@
 #include <hip/hip_runtime.h>
 
 #include "gradient.h"
+#include "gradient_pair.h"
 
 namespace ws {
 
 namespace {
 
-constexpr float V_CAP = 0x1.fffffep-1f;    // the largest f32 below 1: |v| * 2^32 fits 32 bits
-constexpr float B_CLAMP = 0x1.fae148p-1f;  // 0.99f, the cap of opacity_at (blend_tile.h)
-
-__device__ __forceinline__ float plane_value(float scale, float g) {
-#pragma clang fp contract(off)
-    const float e = scale * g;
-    return (e != e) ? 0.0f : fminf(fmaxf(e, -1.0f), 1.0f);
-}
-
 // gradient.h: four v per walked pair, into the accumulator.  LDS per staged record: its colour words beside the accumulator's
-// four partials.
+// four partials.  What is kept per pair and which pairs count is gradient_pair.h's, the one k_geometry runs too.
 template <int STAGE>
 struct GradientSink {
     static constexpr bool WRITES_EMPTY_TILES = false;
@@ -33,23 +25,12 @@ struct GradientSink {
     const GradientParams& p;
     uint2* s_col;
     AccumS32<STAGE> acc;
-    float F0 = 0.0f, F1 = 0.0f, F2 = 0.0f, Tend = 0.0f;  // base(p)
-    float G0 = 0.0f, G1 = 0.0f, G2 = 0.0f, GT = 0.0f;    // the plane at p
-    float P0 = 0.0f, P1 = 0.0f, P2 = 0.0f;               // the colour accumulated through the pair at hand
-    float T = 0.0f;                                      // the walk's T again
-    bool none = false;                                   // wave-uniform: nothing but zeros in the plane -- no walk to do
+    GradPixel px{};
 
-    __device__ __forceinline__ void begin(uint32_t px, uint32_t py, bool inside) {
-        if (inside) {
-            const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.base) + (size_t)py * p.base_pitch + (size_t)px * 16);
-            const float4 g = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.grad) + (size_t)py * p.grad_pitch + (size_t)px * 16);
-            F0 = b.x, F1 = b.y, F2 = b.z, Tend = b.w;
-            G0 = plane_value(p.scale, g.x), G1 = plane_value(p.scale, g.y), G2 = plane_value(p.scale, g.z), GT = plane_value(p.scale, g.w);
-            T = 1.0f;
-        }
-        none = __ballot(G0 != 0.0f || G1 != 0.0f || G2 != 0.0f || GT != 0.0f) == 0ull;
+    __device__ __forceinline__ void begin(uint32_t x, uint32_t y, bool inside) {
+        px.begin(p.base, p.base_pitch, p.grad, p.grad_pitch, p.scale, x, y, inside);
     }
-    __device__ __forceinline__ bool idle() const { return none; }
+    __device__ __forceinline__ bool idle() const { return px.none; }
     __device__ __forceinline__ void stage(int tid, uint32_t idx, bool live) {
         acc.clear(tid);
         if (live) s_col[tid] = splat_colour_words(p.frame.splats, idx);
@@ -57,31 +38,18 @@ struct GradientSink {
     __device__ __forceinline__ void pair(uint32_t off, float wgt, bool kept) {
         float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f, vo = 0.0f;
         {
-#pragma clang fp contract(off)  // every step below is the separately rounded operation gradient.h names; the fmaf calls stay fused
-            const float Tb = T;
-            T = Tb - wgt;
+#pragma clang fp contract(off)  // one rounded multiply each
+            const float Tb = px.step(wgt);
             if (kept) {
-                const f16x4_t c16 = staged_colour(s_col, off);
-                const float c0 = (float)c16.x, c1 = (float)c16.y, c2 = (float)c16.z;
-                P0 = fmaf(wgt, c0, P0);
-                P1 = fmaf(wgt, c1, P1);
-                P2 = fmaf(wgt, c2, P2);
+                float c[3];
+                px.blend_in(s_col, off, wgt, c);
                 if (wgt > 0.0f) {
-                    if (c0 > 0.0f) v0 = wgt * G0;
-                    if (c1 > 0.0f) v1 = wgt * G1;
-                    if (c2 > 0.0f) v2 = wgt * G2;
-                    if (Tb >= T_MIN && wgt != B_CLAMP * Tb) {  // (T > 0: b <= 0.99)
-                        const float r = wgt / T;
-                        const float d0 = fmaf(r, F0 - P0, -(wgt * c0));
-                        const float d1 = fmaf(r, F1 - P1, -(wgt * c1));
-                        const float d2 = fmaf(r, F2 - P2, -(wgt * c2));
-                        float a = G0 * d0;
-                        a = fmaf(G1, d1, a);
-                        a = fmaf(G2, d2, a);
-                        const float u = r * Tend;
-                        a = fmaf(GT, u, a);
-                        const float sa = p.opacity_scale * a;
-                        vo = (sa != sa) ? 0.0f : -fminf(fmaxf(sa, -V_CAP), V_CAP);
+                    if (c[0] > 0.0f) v0 = wgt * px.G0;
+                    if (c[1] > 0.0f) v1 = wgt * px.G1;
+                    if (c[2] > 0.0f) v2 = wgt * px.G2;
+                    if (px.counts(Tb, wgt)) {
+                        const float sa = p.opacity_scale * px.kappa(wgt, c);
+                        vo = (sa != sa) ? 0.0f : -fminf(fmaxf(sa, -GRAD_V_CAP), GRAD_V_CAP);
                     }
                 }
             }

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "geometry_spread.h"
 #include "ply_encode.h"
 #include "sh_gradient.h"
 #include "ws_internal.h"
@@ -485,6 +486,30 @@ int ws_sh_spread_rows(const int64_t* q4, const float* xyz, const float* cam, uin
         sh_spread_basis(dir[0], dir[1], dir[2], bas);
         for (uint32_t k = 1; k < nact; ++k)
             for (uint32_t ch = 0; ch < 3; ++ch) s[3 * k + ch] += static_cast<uint64_t>(sh_spread_term(q[ch], bas[k]));
+    }
+    return WS_OK;
+}
+
+// The host twin of k_geom_spread: geometry_spread.h's chain, one row per Gaussian.  The sums here are per Gaussian, not per plane.
+int ws_geom_spread_rows(const int64_t* q5, const uint16_t* rec, const float* xyz, const uint16_t* cov, const ws_camera_uniform* cam,
+                        const ws_settings_uniform* settings, float geometry_scale, uint32_t n, double* position, double* covariance,
+                        double* screen_norm, uint64_t* seen) {
+    if (!cam || !settings || ((!q5 || !rec || !xyz || !cov) && n)) return fail(WS_ERR_INVALID, "ws_geom_spread_rows: null argument");
+    if (!std::isfinite(geometry_scale) || !(geometry_scale > 0.0f)) return fail(WS_ERR_INVALID, "ws_geom_spread_rows: geometry_scale must be finite and above 0");
+    GeomSpreadFrame f{};
+    f.cam = *cam;
+    f.rs = *settings;
+    f.geometry_scale = geometry_scale;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t* q = q5 + i * GEOM_SCRATCH;
+        if ((q[0] | q[1] | q[2] | q[3] | q[4]) == 0) continue;
+        const long long ql[GEOM_SCRATCH] = {q[0], q[1], q[2], q[3], q[4]};
+        GeomSpreadRow r;
+        geom_spread_row(ql, rec + i * 4, xyz + i * 3, cov + i * 6, f, &r);
+        for (int k = 0; position && k < 3; ++k) position[i * 3 + k] += r.position[k];
+        for (int e = 0; covariance && e < 6; ++e) covariance[i * 6 + e] += r.covariance[e];
+        if (screen_norm) screen_norm[i] += r.norm;
+        if (seen) seen[i] += 1u;
     }
     return WS_OK;
 }

@@ -60,8 +60,16 @@ namespace tile {
 //                                record, with wgt = 0 and kept = false where the pair is outside the cut-off; false: only the
 //                                lanes of kept pairs call it, inside the branch that made wgt
 //   pair(off, wgt, kept)         one (pixel, record) pair; off = slot * 16
+//   static constexpr bool WANTS_COORDS         optional; true: the call is pair(off, wgt, kept, p0, p1) with the walk's own p0, p1
+//                                (a' = p0^2 + p1^2, formed for every walked pair, kept or not).  A sink without the member is
+//                                called as before: the choice is made at compile time and leaves no trace in its code
 //   flush(tid, idx)              live staging threads, behind the batch's vote (every wave's pair() calls of the batch are done)
 //   finish(px, py, inside)       once, behind the last batch
+template <class Sink, class = void>
+struct wants_coords : std::false_type {};
+template <class Sink>
+struct wants_coords<Sink, std::void_t<decltype(Sink::WANTS_COORDS)>> : std::integral_constant<bool, Sink::WANTS_COORDS> {};
+
 template <int QW, int QH, class Sink>
 __device__ __forceinline__ void walk_weights(const FrameLists& p, Sink& sink) {
     using G = Geometry<QW, QH>;
@@ -126,9 +134,15 @@ __device__ __forceinline__ void walk_weights(const FrameLists& p, Sink& sink) {
                     wgt = b * T;
                     T -= wgt;
                     // (inside the branch the sink's LDS reads issue beside the exp; behind it they wait for the branch to rejoin)
-                    if constexpr (!Sink::PAIR_IS_WAVE_WIDE) sink.pair(off, wgt, true);
+                    if constexpr (!Sink::PAIR_IS_WAVE_WIDE) {
+                        if constexpr (wants_coords<Sink>::value) sink.pair(off, wgt, true, p0, p1);
+                        else sink.pair(off, wgt, true);
+                    }
                 }
-                if constexpr (Sink::PAIR_IS_WAVE_WIDE) sink.pair(off, wgt, kept);
+                if constexpr (Sink::PAIR_IS_WAVE_WIDE) {
+                    if constexpr (wants_coords<Sink>::value) sink.pair(off, wgt, kept, p0, p1);
+                    else sink.pair(off, wgt, kept);
+                }
                 // the quadrant is saturated: nothing behind can add more than T_MIN
                 if ((i & 3u) == 3u && __ballot(T >= T_MIN) == 0ull) break;
             }

@@ -1128,6 +1128,8 @@ static int prepare_setup(ws_renderer* r, const ws_pointcloud* pc, const ws_splat
     r->frame.zfar = kp.zfar;
     for (int i = 0; i < 3; ++i) r->frame.cam_pos[i] = kp.cam.view_inv[12 + i];
     r->frame.max_sh_deg = kp.rs.max_sh_deg;
+    r->frame.cam = kp.cam;
+    r->frame.settings = kp.rs;
     // fade-in (preprocess.wgsl:196-203): once walltime is past (largest possible dd) + 1, smoothstep(walltime - dd) is exactly
     // 1 for every Gaussian and the kernel skips the computation.  One rule, dd = 5 |centre - xyz| / extend bounded two ways:
     //   * every Gaussian that reaches k1_math lies inside the bbox (the default clip box IS the bbox; a user box may admit

@@ -549,6 +549,10 @@ struct ws_shgrad;
 struct ws_refit_sh_params;
 int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream, unsigned passes);
 int ws_internal_refit_check_sh_params(const ws_refit_sh_params* p, const std::string& who, bool units);
+// "Geometry gradients" in steps, for ws_scene_accumulate_geometry_gradient: passes = 1: the base image only; 6: k_geometry and
+// k_geom_spread on a base plane already there; p->opacity_scale holds the geometry_scale (api_attrib.cpp)
+struct ws_geomgrad;
+int ws_internal_geometry_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_gradient_params* p, void* stream, unsigned passes);
 
 // opaque handle definitions -------------------------------------------------------------------------
 // The depth sort of a frame (V keys + store index + footprint word):

@@ -1,6 +1,6 @@
 // websplat_evaluate -- PSNR and SSIM of a scene over a cameras.json split, computed on the device (websplat.h "Image metrics"):
 //   websplat_evaluate <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize]
-//                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]]
+//                     [--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]] [--densify N [--error sq|abs]]
 //                     [--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs] [--refit-sh [--lr-sh Z]]]
 //                     [--save OUT.ply]
 // prints one line per camera and the means of the per-image PSNR and SSIM (the 3DGS convention).  --ref compares against
@@ -13,6 +13,9 @@
 // --gradient N: behind all that, the N Gaussians with the largest |d error / d ln opacity| over the split (websplat.h "Gradients
 // of an image loss"; the error is --blame's, sq or abs, against --ref / --gt): index, opacity gradient, the three colour
 // gradients, then how many drawn Gaussians have all four sums 0.
+// --densify N: behind all that, the N Gaussians with the largest screen_norm / seen over the split (websplat.h "Geometry gradients":
+// the INRIA trainer's densification statistic; the error as --gradient's): index, that mean, seen, |d error / d position|, then how
+// many seen Gaussians have a norm of exactly 0.
 // --refit EPOCHS: behind all that, Adam steps on the scene's DC colours and opacities over the TRAIN split against --ref / --gt
 // (websplat.h "Refitting colour and opacity"; a step after every B views, default: one per epoch), then the first table again,
 // of the refitted scene, under a line "after refit: EPOCHS epochs, S steps".  A compressed scene is refused.
@@ -53,7 +56,7 @@ int main(int argc, char** argv) {
     const char *ref = nullptr, *gt = nullptr, *save = nullptr;
     int split = WS_SPLIT_TEST;
     uint32_t flags = 0;
-    long blame = 0, removal = 0, gradient = 0, refit = 0, views_per_step = 0;
+    long blame = 0, removal = 0, gradient = 0, densify = 0, refit = 0, views_per_step = 0;
     double lr_colour = 0.0025, lr_opacity = 0.01, lr_sh = -1.0;  // (lr_sh < 0: lr_colour / 20)
     bool have_refit_option = false, refit_sh = false;
     int kind = WS_ERROR_SQ;
@@ -71,6 +74,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--blame") && i + 1 < argc) bad = !positive(argv[++i], &blame);
         else if (!std::strcmp(argv[i], "--removal") && i + 1 < argc) bad = !positive(argv[++i], &removal);
         else if (!std::strcmp(argv[i], "--gradient") && i + 1 < argc) bad = !positive(argv[++i], &gradient);
+        else if (!std::strcmp(argv[i], "--densify") && i + 1 < argc) bad = !positive(argv[++i], &densify);
         else if (!std::strcmp(argv[i], "--refit") && i + 1 < argc) bad = !positive(argv[++i], &refit);
         else if (!std::strcmp(argv[i], "--views-per-step") && i + 1 < argc) {
             have_refit_option = true;
@@ -92,15 +96,15 @@ int main(int argc, char** argv) {
             else bad = true;
         } else bad = true;
     }
-    if (have_error && blame == 0 && removal == 0 && gradient == 0 && refit == 0) bad = true;
-    if ((removal > 0 || gradient > 0 || refit > 0) && kind == WS_ERROR_DSSIM) bad = true;
+    if (have_error && blame == 0 && removal == 0 && gradient == 0 && densify == 0 && refit == 0) bad = true;
+    if ((removal > 0 || gradient > 0 || densify > 0 || refit > 0) && kind == WS_ERROR_DSSIM) bad = true;
     if (have_refit_option && refit == 0) bad = true;
     if (lr_sh >= 0.0 && !refit_sh) bad = true;
     const bool compare = ref != nullptr || gt != nullptr;  // (--removal alone needs no second image)
-    if ((blame > 0 || gradient > 0 || refit > 0) && !compare) bad = true;
+    if ((blame > 0 || gradient > 0 || densify > 0 || refit > 0) && !compare) bad = true;
     if (bad || (ref != nullptr && gt != nullptr) || (!compare && removal == 0 && !save)) {
         std::fprintf(stderr, "usage: %s <scene.ply|.npz> <cameras.json> (--ref <other.ply|.npz> | --gt <dir>) [--split train|test] [--quantize] "
-                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]] "
+                             "[--blame N [--error sq|abs|dssim]] [--removal N [--error sq|abs]] [--gradient N [--error sq|abs]] [--densify N [--error sq|abs]] "
                              "[--refit EPOCHS [--lr-colour X] [--lr-opacity Y] [--views-per-step B] [--error sq|abs] [--refit-sh [--lr-sh Z]]] [--save OUT.ply]\n", argv[0]);
         return 2;
     }
@@ -218,6 +222,33 @@ int main(int argc, char** argv) {
             std::printf("gradient: %u of %u drawn Gaussians have all four sums exactly 0\n", zero_n, drawn_n);
         }
     }
+    // the densification statistic of the INRIA trainer: the mean norm of the screen-space positional gradient over the frames that saw
+    // the Gaussian (websplat.h "Geometry gradients")
+    ws_geomgrad* geo = nullptr;
+    if (rc == WS_OK && densify > 0) {
+        const uint32_t np = ws_pointcloud_num_points(pc);
+        std::vector<double> pos((size_t)np * 3), norm(np);
+        std::vector<uint64_t> seen(np);
+        rc = ws_geomgrad_create(ctx, np, &geo);
+        if (rc == WS_OK) rc = ws_scene_accumulate_geometry_gradient(ctx, pc, scene, split, ref_pc, gt, kind, 1.0f, 1.0f, geo, &frames);
+        if (rc == WS_OK) rc = ws_geomgrad_download(geo, np, pos.data(), nullptr, norm.data(), seen.data());
+        if (rc == WS_OK) {
+            const auto mean = [&](uint32_t i) { return seen[i] ? norm[i] / (double)seen[i] : 0.0; };
+            const std::vector<uint32_t> order = top_by(np, densify, mean);
+            std::printf("densify (%s error over %u frames): %zu of %u Gaussians by screen_norm / seen\n", kind == WS_ERROR_SQ ? "sq" : "abs", frames, order.size(), np);
+            std::printf("%10s %16s %8s %16s\n", "index", "screen_norm/seen", "seen", "|d/d position|");
+            for (const uint32_t i : order) {
+                const double* g = &pos[(size_t)i * 3];
+                std::printf("%10u %16.9g %8llu %16.9g\n", i, mean(i), (unsigned long long)seen[i], std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]));
+            }
+            uint32_t seen_n = 0, zero_n = 0;
+            for (uint32_t i = 0; i < np; ++i) {
+                seen_n += seen[i] != 0;
+                zero_n += seen[i] != 0 && norm[i] == 0.0;
+            }
+            std::printf("densify: %u of %u seen Gaussians have a norm of exactly 0\n", zero_n, seen_n);
+        }
+    }
     ws_refit* fit = nullptr;
     if (rc == WS_OK && refit > 0) {
         ws_refit_sh_params sp;
@@ -258,6 +289,7 @@ int main(int argc, char** argv) {
     if (fit) ws_refit_destroy(fit);
     if (grad) ws_grad_destroy(grad);
     if (grad_drawn) ws_contrib_destroy(grad_drawn);
+    if (geo) ws_geomgrad_destroy(geo);
     if (effect) ws_contrib_destroy(effect);
     if (drawn) ws_contrib_destroy(drawn);
     if (err) ws_contrib_destroy(err);

@@ -202,6 +202,12 @@ class ws_gradient_params(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
+class ws_geometry_params(C.Structure):
+    _fields_ = [("background", C.c_float * 3), ("scale", C.c_float), ("geometry_scale", C.c_float), ("reserved0", C.c_uint32),
+                ("d_grad", C.c_void_p), ("grad_pitch_bytes", C.c_size_t), ("d_base", C.c_void_p), ("base_pitch_bytes", C.c_size_t),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class ws_refit_params(C.Structure):
     _fields_ = [("lr_colour", C.c_float), ("lr_opacity", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("opacity_min", C.c_float), ("colour_unit", C.c_double), ("opacity_unit", C.c_double), ("reserved", C.c_uint32 * 4)]
@@ -214,6 +220,7 @@ class ws_refit_sh_params(C.Structure):
 assert C.sizeof(ws_refit_params) == 56
 assert C.sizeof(ws_refit_sh_params) == 72
 assert C.sizeof(ws_gradient_params) == 72
+assert C.sizeof(ws_geometry_params) == 72
 assert C.sizeof(ws_removal_params) == 64
 assert C.sizeof(ws_image_view) == 40
 assert C.sizeof(ws_values_view) == 24
@@ -228,6 +235,9 @@ _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
 _u32p = C.POINTER(C.c_uint32)
 _f32p = C.POINTER(C.c_float)
+_f64p = C.POINTER(C.c_double)
+_u64p = C.POINTER(C.c_uint64)
+_u16p = C.POINTER(C.c_uint16)
 
 # name -> (restype, argtypes): every symbol include/websplat.h declares
 SIGNATURES = {
@@ -411,6 +421,20 @@ SIGNATURES = {
     "ws_refit_download_sh": (C.c_int, [_P, C.c_uint32, _f32p, _f32p, _f32p]),
     "ws_scene_refit_sh": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, _P, C.POINTER(ws_refit_sh_params), C.c_uint32,
                                     C.c_uint32, _u32p]),
+    "ws_geomgrad_create": (C.c_int, [_P, C.c_uint32, _PP]),
+    "ws_geomgrad_destroy": (None, [_P]),
+    "ws_geomgrad_reset": (C.c_int, [_P, _P]),
+    "ws_geomgrad_num_points": (C.c_uint32, [_P]),
+    "ws_geomgrad_frames": (C.c_uint32, [_P]),
+    "ws_geomgrad_download": (C.c_int, [_P, C.c_uint32, _f64p, _f64p, _f64p, _u64p]),
+    "ws_geomgrad_add": (C.c_int, [_P, _f64p, _f64p, _f64p, _u64p, C.c_uint32]),
+    "ws_renderer_accumulate_geometry_gradient": (C.c_int, [_P, _P, _P, C.POINTER(ws_geometry_params), _P]),
+    "ws_geom_spread_rows": (C.c_int, [C.POINTER(C.c_int64), _u16p, _f32p, _u16p, C.POINTER(ws_camera_uniform), C.POINTER(ws_settings_uniform),
+                                      C.c_float, C.c_uint32, _f64p, _f64p, _f64p, _u64p]),
+    "ws_scene_accumulate_geometry_gradient": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_char_p, C.c_int, C.c_float, C.c_float, _P, _u32p]),
+    "ws_debug_geomgrad_scratch": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int64)]),
+    "ws_debug_geometry_stage_a": (C.c_int, [_P, _P, _P, C.POINTER(ws_geometry_params), _P]),
+    "ws_debug_geomgrad_clear_scratch": (C.c_int, [_P, _P]),
 }
 
 

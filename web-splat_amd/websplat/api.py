@@ -787,6 +787,69 @@ def sh_spread_rows(q4, xyz, cam, sh_deg: int, active_deg: int) -> dict:
     return out
 
 
+class GeomGrad(_GaussianSums):
+    """Per-Gaussian geometry gradient accumulators over frames (websplat.h "Geometry gradients"): for every Gaussian of a cloud
+    of num_points, float64 sums of dL/d(position), dL/d(the six stored covariance elements) and the norm of the screen-space
+    positional gradient, and the number of frames that counted a pair of it."""
+    _prefix = "ws_geomgrad"
+    _FIELDS = (("position", (3,), np.float64), ("covariance", (6,), np.float64), ("screen_norm", (), np.float64), ("seen", (), np.uint64))
+
+    def download(self) -> dict:
+        """{"position": (N, 3), "covariance": (N, 6), "screen_norm": (N,) float64, "seen": (N,) uint64} (syncs)."""
+        n = self.num_points()
+        out = {k: np.empty((n,) + shape, dtype=dt) for k, shape, dt in self._FIELDS}
+        check(lib.ws_geomgrad_download(self.handle, n, *(out[k].ctypes.data_as(L._u64p if dt is np.uint64 else L._f64p) for k, _, dt in self._FIELDS)))
+        return out
+
+    def add(self, position=None, covariance=None, screen_norm=None, seen=None):
+        """Add another accumulator's (or rank's) downloaded sums, in the order given (float64 addition: exact only for `seen`);
+        any array may be left out."""
+        given = {"position": position, "covariance": covariance, "screen_norm": screen_norm, "seen": seen}
+        ptrs, rows = [], []
+        for k, shape, dt in self._FIELDS:
+            a = given[k]
+            if a is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape[1:] != shape:
+                raise ValueError(f"GeomGrad.add: want an (N,{' ' + str(shape[0]) if shape else ''}) {np.dtype(dt).name} array for {k}, got {a.shape}")
+            given[k] = a   # (keeps the converted array alive through the call)
+            rows.append(a.shape[0])
+            ptrs.append(a.ctypes.data_as(L._u64p if dt is np.uint64 else L._f64p))
+        if not rows:
+            return
+        check(lib.ws_geomgrad_add(self.handle, *ptrs, min(rows)))
+
+    def _debug_scratch(self) -> np.ndarray:
+        """(N, 5) int64: the scratch sums m0, m1, S00, S01, S11 (tests; syncs)."""
+        q = np.empty((self.num_points(), 5), dtype=np.int64)
+        check(lib.ws_debug_geomgrad_scratch(self.handle, q.shape[0], q.ctypes.data_as(_i64p)))
+        return q
+
+    def _debug_clear_scratch(self, stream=None):
+        check(lib.ws_debug_geomgrad_clear_scratch(self.handle, C.c_void_p(stream or 0)))
+
+
+def geom_spread_rows(q5, rec, xyz, cov, camera_uniform, settings_uniform, geometry_scale=1.0) -> dict:
+    """The host twin of the geometry spread (ws_geom_spread_rows, no GPU needed): one frame's (N, 5) int64 scratch sums, the
+    (N, 4) uint16 halves 0..3 of each Gaussian's Splat record, the (N, 3) float32 positions, the (N, 6) uint16 covariance halves
+    and the frame's two uniforms -> a dict as GeomGrad.download() gives it."""
+    q5 = np.ascontiguousarray(q5, dtype=np.int64)
+    rec = np.ascontiguousarray(rec, dtype=np.uint16)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    cov = np.ascontiguousarray(cov, dtype=np.uint16)
+    n = q5.shape[0]
+    if q5.shape != (n, 5) or rec.shape != (n, 4) or xyz.shape != (n, 3) or cov.shape != (n, 6):
+        raise ValueError("geom_spread_rows: want (N, 5) sums, (N, 4) record halves, (N, 3) positions and (N, 6) covariance halves")
+    out = {k: np.zeros((n,) + shape, dtype=dt) for k, shape, dt in GeomGrad._FIELDS}
+    check(lib.ws_geom_spread_rows(q5.ctypes.data_as(_i64p), rec.ctypes.data_as(L._u16p), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                  cov.ctypes.data_as(L._u16p), C.byref(camera_uniform), C.byref(settings_uniform), float(geometry_scale), n,
+                                  out["position"].ctypes.data_as(L._f64p), out["covariance"].ctypes.data_as(L._f64p),
+                                  out["screen_norm"].ctypes.data_as(L._f64p), out["seen"].ctypes.data_as(L._u64p)))
+    return out
+
+
 def _refit_params(lr_colour=0.0025, lr_opacity=0.01, beta1=0.9, beta2=0.999, eps=1e-15, opacity_min=0.0, colour_unit=1.0,
                   opacity_unit=1.0):
     p = L.ws_refit_params()
@@ -1086,6 +1149,17 @@ def accumulate_sh_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene,
     check(lib.ws_scene_accumulate_sh_gradient(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
                                               None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(scale),
                                               float(opacity_scale), shgrad.handle, C.byref(n)))
+    return n.value
+
+
+def accumulate_geometry_gradient_scene(ctx: "Context", pc: "PointCloud", scene: Scene, split: str, geomgrad: "GeomGrad",
+                                       ref: "PointCloud" = None, gt_dir: str = None, kind="sq", scale=1.0, geometry_scale=1.0) -> int:
+    """accumulate_gradient_scene's frames into a GeomGrad: per Gaussian the gradients with respect to position and covariance and
+    the densification statistic (ws_scene_accumulate_geometry_gradient).  Returns the frames added."""
+    n = C.c_uint32()
+    check(lib.ws_scene_accumulate_geometry_gradient(ctx.handle, pc.handle, scene.handle, _SPLITS[split], ref.handle if ref is not None else None,
+                                                    None if gt_dir is None else str(gt_dir).encode(), ERROR_KINDS[kind], float(scale),
+                                                    float(geometry_scale), geomgrad.handle, C.byref(n)))
     return n.value
 
 
@@ -1401,12 +1475,23 @@ class GaussianRenderer:
         self._accumulate_gradient(lib.ws_renderer_accumulate_sh_gradient, pc, shgrad, plane, background, scale, opacity_scale, base,
                                   stream, plane_pitch, base_ptr, base_pitch)
 
+    def accumulate_geometry_gradient(self, pc: PointCloud, geomgrad: "GeomGrad", plane, background=(0.0, 0.0, 0.0), scale=1.0,
+                                     geometry_scale=1.0, base=False, stream=None, plane_pitch=None, base_ptr=None, base_pitch=None,
+                                     _stage_a_only=False):
+        """Add to `geomgrad`, per Gaussian, dL/d(position), dL/d(covariance) and the norm of the screen-space positional gradient
+        of an image loss over the prepared frame (ws_renderer_accumulate_geometry_gradient).  `plane` and the other arguments as
+        accumulate_gradient; geometry_scale scales the five screen-space sums before they are made fixed-point (finite, > 0)."""
+        call = lib.ws_debug_geometry_stage_a if _stage_a_only else lib.ws_renderer_accumulate_geometry_gradient
+        self._accumulate_gradient(call, pc, geomgrad, plane, background, scale, geometry_scale, base, stream, plane_pitch, base_ptr,
+                                  base_pitch, params=L.ws_geometry_params)
+
     def _accumulate_gradient(self, call, pc, grad, plane, background, scale, opacity_scale, base, stream, plane_pitch, base_ptr,
-                             base_pitch):
-        p = L.ws_gradient_params()
+                             base_pitch, params=L.ws_gradient_params):
+        p = params()
         for i in range(3):
             p.background[i] = float(background[i])
-        p.scale, p.opacity_scale = float(scale), float(opacity_scale)
+        p.scale = float(scale)
+        setattr(p, "geometry_scale" if params is L.ws_geometry_params else "opacity_scale", float(opacity_scale))
         w, h = self._viewport
         self._set_base(p, base, base_ptr, base_pitch)
         host = None
