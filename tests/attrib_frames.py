@@ -87,6 +87,18 @@ def _stack_frame(ws, c, k, opacity, viewport=(32, 32)):
     return _Frame(ws, c, *blend_ref.device_scene(ws, _stack(k, opacity), viewport))
 
 
+def _cloud_rows(n=3000, seed=17):
+    """The general cloud of test_gpu_removal, test_gpu_gradient and the geometry tests: anisotropic Gaussians of random rotation
+    and random colours in the unit cube, scales 0.01 - 0.08, opacities 0.02 - 0.3."""
+    rng = np.random.default_rng(seed)
+    xyz = rng.uniform(-1.0, 1.0, size=(n, 3)).astype(F)
+    log_scale = rng.uniform(np.log(0.01), np.log(0.08), size=(n, 3)).astype(F)
+    rot = rng.standard_normal(size=(n, 4)).astype(F)
+    op = rng.uniform(0.02, 0.3, size=n)
+    f_dc = rng.uniform(-1.5, 1.5, size=(n, 3)).astype(F)
+    return synth._rows(xyz, f_dc, np.zeros((n, 45), F), np.log(op / (1.0 - op)).astype(F), log_scale, rot)
+
+
 def _c1_frame(ws, oracle, c, seed=0, viewport=VIEW):
     sc = scenes.c1(ws, oracle, n=10_000, viewport=viewport, seed=seed)
     return _Frame(ws, c, sc.gpc, sc.args)

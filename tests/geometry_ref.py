@@ -23,7 +23,32 @@ bounds() of (a): DERIVED, per counted pair, for a device that follows geometry.h
   v_Skl : |p_k p_l| e_t + |t| (|p_l| e_pk + |p_k| e_pl + e_pk e_pl) + 2 2^-24 |v| + 2^-32      two roundings
   a pair in the band (Tb in [2^-15, 2^-13], or b within 2e-5 relative of 0.99) may count on one side and not on the other: it gets
   its whole |v| on top, as in gradient_ref.  Pixels with an undecided cut-off pair carry no bound: the tests mask them out of the
-  plane and assert U == 0."""
+  plane and assert U == 0.
+
+THE CAP.  geom_value (geometry.hip) turns the f32 value v' of a channel into clamp(v', +-V_CAP), V_CAP = 1 - 2^-24, and the
+accumulator into q = trunc(|.| 2^32) with the value's sign: a capped value is the integer +-(2^32 - 256), whatever v' was.  With
+v the float64 value of the pair and channel, e = errs[k] the error of the product's factors above and n the product's own
+roundings (1 for m, 2 for S), the device's v' = v~ (1 + d_1) .. (1 + d_n) with |v~ - v| <= e, |d_i| <= 2^-24, hence
+  |v'| >= (|v| - e) (1 - 2^-24)^n >= |v| - e - n 2^-24 |v|  =: lower            |v'| <= |v| + e + n 2^-24 |v|  =: upper
+(to first order in 2^-24, as every term here).  A pair and channel is
+  DECIDEDLY CAPPED  iff the pair counts on both sides (counted, and not in the band) and lower >= V_CAP: v' has v's sign (lower >
+              0) and |v'| >= V_CAP, so fminf / fmaxf return +-V_CAP exactly; V_CAP 2^32 = 2^32 - 256 is an integer, the truncation
+              drops nothing.  The reference adds sign(v) V_CAP, the tolerance of the pair is 0 -- no 2^-32 either.
+  STRADDLING        iff it may count, is not decidedly capped, and upper >= V_CAP: either side may or may not be capped.  It keeps
+              the treatment of an uncapped pair -- the clamp is a contraction, |clamp(v') - clamp(v)| <= |v' - v| -- and since
+              both clamped values lie in [-V_CAP, V_CAP] its tolerance is at most 2 V_CAP.
+  any other pair has upper < V_CAP: neither side is capped, nothing changes.
+capped[j][k] and straddling[j][k] count them; net[j][k] is the signed count of the decidedly capped (positive minus negative).
+A Gaussian and channel whose pairs are all decidedly capped has tol == 0 and sum == net V_CAP exactly (a multiple of 2^-24 below
+2^11: exact in float64), and the device's q must be the integer net (2^32 - 256).  Where nothing is capped or straddling, sum and
+tol are what they were before this rule to the last bit: the same operations in the same order (test_geometry_ref.py pins them).
+
+STAGE_A_MUTATIONS: the defective walks the bounds have to tell from the right one (mutate=):
+  p_swapped              p0 and p1 exchanged before the five products (their errors with them)
+  iprime_transposed      I' transposed, in p and in its error
+  s01_negated            the sign of the S01 channel
+  clamped_pairs_counted  a pair on the 0.99 clamp counts, with the kappa its w gives (gradient_ref's mutant of that name)
+  cap_ignored            no clamp to +-V_CAP: every pair keeps the uncapped treatment"""
 import numpy as np
 
 import contrib_ref
@@ -40,6 +65,8 @@ B_CLAMP = 0.99
 CUT_A = 2.0 * 2.3539888583335364          # natural-exponent domain: a pair is kept iff a <= CUT_A (a' = a log2 e)
 C_0P1 = float(np.float32(0.1))
 MUTATIONS = ("no_jacobian", "offdiag_not_doubled", "dmu_y_not_flipped", "ln2_once")
+STAGE_A_MUTATIONS = ("p_swapped", "iprime_transposed", "s01_negated", "clamped_pairs_counted", "cap_ignored")
+Q_CAP = 2 ** 32 - 256                      # V_CAP 2^32: what a capped value adds to a q32 sum
 E24 = 2.0 ** -24
 
 
@@ -62,9 +89,12 @@ def p_error(I, dx, dy, cx, cy, W, H):
     return out
 
 
-def stage_a_f64(frame, width, height, num_points, G, background=(0.0, 0.0, 0.0), geometry_scale=1.0, saturating=False):
+def stage_a_f64(frame, width, height, num_points, G, background=(0.0, 0.0, 0.0), geometry_scale=1.0, saturating=False, mutate=None):
     """See the module text.  G: the H x W x 4 clamped plane (gradient_ref.plane_G).  Returns sum[j][5] (in units of v: s kappa p..),
-    tol[j][5], and per Gaussian pairs, U, band, clamped as gradient_ref.gradient_f64 does."""
+    tol[j][5], per Gaussian pairs, U, band, clamped as gradient_ref.gradient_f64 does and counted (the pairs that count), and per
+    Gaussian and channel capped, net, straddling (THE CAP); open_px [H, W]: the pixels with a pair and channel that may count and
+    is not decidedly capped (masked out of the plane, nothing but exact integers is left).  mutate: one of STAGE_A_MUTATIONS."""
+    assert mutate is None or mutate in STAGE_A_MUTATIONS
     recs = list(weight_ref.records(frame, width, height))
     bg = np.asarray(background, dtype=np.float32).astype(F64)
     base = removal_ref.base_f64(frame, width, height, bg, records=recs)
@@ -83,7 +113,9 @@ def stage_a_f64(frame, width, height, num_points, G, background=(0.0, 0.0, 0.0),
     T = np.ones((height, width))
     P = np.zeros((height, width, 3))
     out = {"sum": np.zeros((num_points, 5)), "tol": np.zeros((num_points, 5))}
-    out.update({k: np.zeros(num_points, dtype=np.int64) for k in ("pairs", "U", "band", "clamped")})
+    out.update({k: np.zeros(num_points, dtype=np.int64) for k in ("pairs", "U", "band", "clamped", "counted")})
+    out.update({k: np.zeros((num_points, 5), dtype=np.int64) for k in ("capped", "net", "straddling")})
+    out["open_px"] = np.zeros((height, width), dtype=bool)   # pixels with a judged pair and channel that is not decidedly capped
     s = float(geometry_scale)
     for j, blk, a, keep, und, alpha in recs:
         Tb = T[blk]
@@ -99,8 +131,11 @@ def stage_a_f64(frame, width, height, num_points, G, background=(0.0, 0.0, 0.0),
             clamped = keep & (b_raw >= B_CLAMP)
             near_clamp = drawn & (np.abs(b_raw - B_CLAMP) <= 2e-5 * B_CLAMP)
             out["clamped"][j] += int((clamped & drawn).sum())
-            may = drawn & (Tb >= 2.0 ** -15) & (~clamped | near_clamp)
-            counted = drawn & (Tb >= T_MIN) & ~clamped
+            may = drawn & (Tb >= 2.0 ** -15)
+            counted = drawn & (Tb >= T_MIN)
+            if mutate != "clamped_pairs_counted":
+                may = may & (~clamped | near_clamp)
+                counted = counted & ~clamped
             with np.errstate(divide="ignore", invalid="ignore"):
                 r = np.where(may, w / Ta, 0.0)
             d = r[..., None] * (F[blk] - Pa) - w[..., None] * c
@@ -114,24 +149,48 @@ def stage_a_f64(frame, width, height, num_points, G, background=(0.0, 0.0, 0.0),
             e_t = e_t + E24 * np.abs(t)
             # the pair's coordinates, exp2 domain
             I, (cx, cy) = _iprime(halves[slot_of[int(j)]], W, H)
+            if mutate == "iprime_transposed":
+                I = I.T
             dx = np.arange(blk[1].start, blk[1].stop)[None, :] + 0.5 - cx
             dy = np.arange(blk[0].start, blk[0].stop)[:, None] + 0.5 - cy
             p0 = I[0, 0] * dx + I[0, 1] * dy
             p1 = I[1, 0] * dx + I[1, 1] * dy
             e0, e1 = p_error(I, dx, dy, cx, cy, W, H)
+            if mutate == "p_swapped":
+                p0, p1, e0, e1 = p1, p0, e1, e0
             in_band = may & live_px[blk] & (((Tb >= 2.0 ** -15) & (Tb <= 2.0 ** -13)) | near_clamp)
             vals = (t * p0, t * p1, t * p0 * p0, t * p0 * p1, t * p1 * p1)
             at = np.abs(t)
             errs = (np.abs(p0) * e_t + at * e0, np.abs(p1) * e_t + at * e1,
                     p0 * p0 * e_t + at * (2 * np.abs(p0) * e0 + e0 * e0), np.abs(p0 * p1) * e_t + at * (np.abs(p1) * e0 + np.abs(p0) * e1 + e0 * e1),
                     p1 * p1 * e_t + at * (2 * np.abs(p1) * e1 + e1 * e1))
+            if mutate == "s01_negated":
+                vals = vals[:3] + (-vals[3],) + vals[4:]
+            judged = may & live_px[blk]
             for k in range(5):
-                v = np.clip(vals[k], -V_CAP, V_CAP)
-                tol = errs[k] + (1 if k < 2 else 2) * E24 * np.abs(v) + 2.0 ** -32
-                tol = np.where(may & live_px[blk], tol + np.where(in_band, np.abs(v), 0.0), 0.0)
+                n_round = 1 if k < 2 else 2
+                if mutate == "cap_ignored":
+                    v = vals[k]
+                    decided = straddle = np.zeros(v.shape, dtype=bool)
+                else:
+                    v = np.clip(vals[k], -V_CAP, V_CAP)
+                    slack = errs[k] + n_round * E24 * np.abs(vals[k])
+                    decided = counted & live_px[blk] & ~in_band & (np.abs(vals[k]) - slack >= V_CAP)
+                    straddle = judged & ~decided & (np.abs(vals[k]) + slack >= V_CAP)
+                tol = errs[k] + n_round * E24 * np.abs(v) + 2.0 ** -32
+                tol = np.where(judged, tol + np.where(in_band, np.abs(v), 0.0), 0.0)
+                if straddle.any():
+                    tol = np.where(straddle, np.minimum(tol, 2.0 * V_CAP), tol)
+                if decided.any():
+                    tol = np.where(decided, 0.0, tol)
+                    out["capped"][j, k] += int(decided.sum())
+                    out["net"][j, k] += int((decided & (v > 0)).sum()) - int((decided & (v < 0)).sum())
+                out["straddling"][j, k] += int(straddle.sum())
+                out["open_px"][blk] |= judged & ~decided
                 out["sum"][j, k] += np.where(counted, v, 0.0).sum()
                 out["tol"][j, k] += tol.sum()
             out["pairs"][j] += int(live.sum())
+            out["counted"][j] += int((counted & live_px[blk]).sum())
             out["U"][j] += int((live & (base["und"][blk] > 0)).sum())
             out["band"][j] += int(in_band.sum())
         P[blk] = Pa

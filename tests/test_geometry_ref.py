@@ -4,6 +4,10 @@
    2. four defective chains each fail that check                     4. ws_geom_spread_rows against spread_f64
    3. a Gaussian on K1's lambda2 clamp has covariance sums of 0       5. the p0, p1 error term of bounds() against ws_debug_stage_splat
 
+   6. stage_a_f64 on oracle frames (blend_ref.oracle_frame: no device), the frames of geometry_frames.py: the cap rule leaves the
+      uncapped cases' sums and bounds where they were; the general anisotropic cloud at 96 x 72 has bounds that say something; each
+      stage-A mutant is told from the right walk on the frame meant for it; the clamped core; the cap frame is exact
+
 The finite differences.  A cloud of 12 Gaussians of SH degree 0 (the colour does not depend on the position), mip off, walltime far
 past the fade-in, under two cameras on a 64 x 48 viewport; L = sum G . F + G_T T_end for gradient_frames.signed_ramp.  Central
 differences at a relative step of 1e-6 leave about 1e-10 of the gradient (truncation h^2, rounding 1e-16 |L| / h); the bound is 1e-5
@@ -11,12 +15,19 @@ of the Gaussian's gradient norm (position and covariance each against their own 
 cloud is chosen so that no pair's kept verdict and no pair's clamp verdict differs between -h and +h: asserted for every step."""
 import ctypes as C
 import functools
+import os
+import time
 
 import numpy as np
 
+import blend_ref
+import geometry_frames as gf
 import geometry_ref as ref
+import gradient_ref
 import k1_edges
 import oracle_lib as oracle
+import removal_ref
+from attrib_frames import _stack
 from gradient_frames import signed_ramp
 from websplat import synth
 
@@ -217,3 +228,135 @@ def test_p_error_bound_against_the_host_decode(ws):
             worst = max(worst, float(frac.max()))
     print(f"largest |p(f32 record) - p(f64)| as a fraction of e_p: {worst:.3f}")
     assert worst <= 1.0
+
+
+# ---- 6. stage_a_f64 on oracle frames: the cap rule, the general cloud, the mutants ------------------------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geometry_stage_a_uncapped.npz")
+UNCAPPED = {"tile": (24, 0.03, 8.0, False), "long": (513, 0.002, 64.0, False), "saturating": (513, 0.9, 1.0 / 128, True)}
+
+
+def test_cap_rule_leaves_the_uncapped_cases_where_they_were():
+    """The stacks of test_gpu_geometry's existing cases (one tile of 24 layers, the 513-entry list, the saturating stack) on oracle
+    frames: sum and tol as stage_a_f64 gave them before it knew of the cap (golden/geometry_stage_a_uncapped.npz, recorded with
+    that version; 1e-12 relative, for a libm that rounds exp differently -- on the recording machine the arrays are equal)."""
+    gold = np.load(GOLDEN)
+    for name, (k, opacity, s, sat) in UNCAPPED.items():
+        frame = blend_ref.oracle_frame(oracle, _stack(k, opacity), gf.TILE)
+        base = removal_ref.base_f64(frame, 32, 32, BG)
+        ok = (base["und"] == 0) if sat else ~removal_ref.undecided_mask(base)
+        g = (signed_ramp(32, 32) * ok[..., None]).astype(np.float32)
+        got = ref.stage_a_f64(frame, 32, 32, k, gradient_ref.plane_G(g), BG, geometry_scale=s, saturating=sat)
+        assert not got["capped"].any() and not got["straddling"].any() and not got["net"].any()
+        assert np.array_equal(got["counted"] > 0, (got["sum"] != 0).any(axis=1)) and got["open_px"].any()
+        for key in ("sum", "tol"):
+            want = gold[f"{name}_{key}"]
+            assert np.abs(want).max() > 0 and np.allclose(got[key], want, rtol=1e-12, atol=0), (name, key)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_case(name):
+    """(frame, n, view, plane, plane scale, geometry_scale, reference) of one of geometry_frames' frames, computed once."""
+    if name == "general":
+        rows, view, s, ps = gf.general_rows(), gf.GENERAL_VIEW, gf.GENERAL_S, gf.GENERAL_PLANE_SCALE
+    elif name.startswith("clamped"):
+        rows, view, s, ps = gf.clamped_rows(), gf.TILE, gf.CLAMPED_S[int(name[-1])], 1.0
+    else:
+        rows, view, s, ps = gf.cap_rows(), gf.TILE, gf.CAP_S, 1.0
+    frame = blend_ref.oracle_frame(oracle, rows, view)
+    g, share = gf.masked_ramp(frame, view, gf.MASK_CAP_GENERAL)
+    t0 = time.perf_counter()
+    want = gf.stage_a(frame, view, len(rows), g, s, ps)
+    print(f"{name}: {len(frame['src_index'])} visible of {len(rows)}, {100 * share:.2f} % of the pixels masked, reference in {time.perf_counter() - t0:.2f} s")
+    return frame, len(rows), view, g, ps, s, want
+
+
+def test_general_frame_has_bounds_that_say_something():
+    frame, n, view, g, ps, s, want = _oracle_case("general")
+    tol = ref.bounds(want)
+    drawn = want["pairs"] > 0
+    halves = np.ascontiguousarray(frame["splats"]).view(np.float16).reshape(-1, 10).astype(np.float64)[: len(frame["src_index"])]
+    cx, cy = (halves[:, 4] * 0.5 + 0.5) * view[0], (0.5 - halves[:, 5] * 0.5) * view[1]
+    outside = (cx < 0) | (cx > view[0]) | (cy < 0) | (cy > view[1])
+    nz = np.abs(want["sum"]) > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        over = [float(np.median((tol[:, k] / np.abs(want["sum"][:, k]))[nz[:, k]])) for k in range(5)]
+    big = (np.abs(want["sum"]) > 4 * tol)[drawn].mean(axis=0)
+    print(f"general: {int(drawn.sum())} Gaussians with pairs, {int(outside.sum())} centres outside the viewport ({int((cx < 0).sum())} left, "
+          f"{int((cx > view[0]).sum())} right), band {int(want['band'].sum())}, clamped {int(want['clamped'].sum())}, T_end >= {want['T'].min():.3f}, "
+          f"median bound / value {['%.2e' % v for v in over]}, |sum| > 4 tol {np.round(big, 3).tolist()}")
+    assert n - len(frame["src_index"]) > 2000 and drawn.sum() >= 500
+    assert (cx < 0).sum() >= 10 and (cx > view[0]).sum() >= 10 and (cy < 0).sum() >= 10 and (cy > view[1]).sum() >= 10
+    assert int(want["U"].sum()) == 0 and int(want["band"].sum()) == 0 and int(want["clamped"].sum()) == 0
+    assert not want["capped"].any() and not want["straddling"].any()
+    assert (big > 0.9).all(), big
+
+
+def test_each_stage_a_mutant_is_told_apart():
+    """Under every mutant the UNMUTATED float64 sums lie outside the mutant's bounds (in at least one of the five channels) for at
+    least half of the Gaussians it can touch.  clamped_pairs_counted: under the plane of geometry_frames.clamped_corner -- under
+    the whole signed ramp the twelve clamped pairs move layer 0's sums by 0.35 to 0.54 of the bound (S01: 0.001), see there."""
+    shares = {}
+    frame, n, view, g, ps, s, want = _oracle_case("general")
+    for m in gf.GENERAL_MUTANTS:
+        wrong = gf.stage_a(frame, view, n, g, s, ps, mutate=m)
+        shares[m], count, outside = gf.told_apart(want["sum"], wrong)
+        print(f"{m}: {100 * shares[m]:.1f} % of {count} Gaussians out of bounds; per channel {np.round(outside[wrong['pairs'] > 0].mean(axis=0), 3).tolist()}")
+        assert count >= 500
+    for i, s in enumerate(gf.CLAMPED_S):
+        frame, n, view, g, ps, _, whole = _oracle_case(f"clamped{i}")
+        wrong = gf.stage_a(frame, view, n, g, s, mutate="clamped_pairs_counted")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            print(f"clamped core, whole ramp, geometry_scale {s}: layer 0 moves by {np.round(np.abs(whole['sum'] - wrong['sum'])[0] / ref.bounds(wrong)[0], 4).tolist()} of the bound")
+        corner = gf.clamped_corner(frame, view)
+        gc = (signed_ramp(*view) * corner[..., None]).astype(np.float32)
+        right, wrong = gf.stage_a(frame, view, n, gc, s), gf.stage_a(frame, view, n, gc, s, mutate="clamped_pairs_counted")
+        touched = right["clamped"] > 0
+        assert corner.sum() >= 2 and int(right["pairs"][0]) == int(corner.sum()) and int(right["counted"][0]) == 0 and int(right["band"].sum()) == 0
+        assert 4 <= right["clamped"][0] <= 16 and not right["clamped"][1:].any()
+        assert not right["sum"][0].any() and not ref.bounds(right)[0].any(), "every pair of layer 0 under this plane is clamped: exactly 0"
+        share, count, outside = gf.told_apart(right["sum"], wrong, touched=touched)
+        print(f"clamped_pairs_counted, corner plane of {int(corner.sum())} pixels, geometry_scale {s}: {100 * share:.0f} % of {count}, channels {outside[0].tolist()}")
+        assert count == 1 and outside[0].all()
+        shares["clamped_pairs_counted"] = min(share, shares.get("clamped_pairs_counted", 1.0))
+    frame, n, view, _, _, s, _ = _oracle_case("cap")
+    for plane in (gf.red_plane(*view), gf.masked_ramp(frame, view, gf.MASK_CAP_GENERAL)[0]):
+        right, wrong = gf.stage_a(frame, view, n, plane, s), gf.stage_a(frame, view, n, plane, s, mutate="cap_ignored")
+        share, count, _ = gf.told_apart(right["sum"], wrong)
+        shares["cap_ignored"] = min(share, shares.get("cap_ignored", 1.0))
+        assert count == n
+    print(shares)
+    assert set(shares) == set(ref.STAGE_A_MUTATIONS) and all(v >= 0.5 for v in shares.values()), shares
+
+
+def test_clamped_core_frame():
+    for i, s in enumerate(gf.CLAMPED_S):
+        frame, n, view, g, ps, _, want = _oracle_case(f"clamped{i}")
+        tol = ref.bounds(want)
+        print(f"geometry_scale {s}: clamped pairs per layer {want['clamped'].tolist()}, band {int(want['band'].sum())}, capped {int(want['capped'].sum())}, "
+              f"straddling {int(want['straddling'].sum())}, largest bound / value {float((tol / np.abs(want['sum'])).max()):.3e}")
+        assert 4 <= want["clamped"][0] <= 16 and not want["clamped"][1:].any()
+        assert int(want["band"].sum()) == 0 and int(want["U"].sum()) == 0 and (np.abs(want["sum"]) > 4 * tol).all()
+    assert int(_oracle_case("clamped0")[6]["capped"].sum()) == 0 and int(_oracle_case("clamped1")[6]["capped"].sum()) > 0
+
+
+def test_cap_frame_is_exact():
+    """_stack(3, 0.3) under (1, 0, 0, 0) at geometry_scale 2^20: every pair of every layer counts and all five values of every pair
+    are decidedly capped, so the sums are integers times 2^-32 -- net (2^32 - 256) -- and the tolerance is exactly 0.  Under the
+    signed ramp kappa changes sign inside the view: a pair or two per layer straddle."""
+    frame, n, view, _, _, s, ramp = _oracle_case("cap")
+    g, want, share = gf.exact_cap_plane(frame, view, n, gf.red_plane(*view))
+    assert share == 0.0 and want["counted"].tolist() == [1024] * 3 and (want["capped"] == 1024).all()
+    assert not ref.bounds(want).any() and not want["straddling"].any()
+    q = want["net"] * ref.Q_CAP
+    assert np.array_equal(want["sum"] * 2.0 ** 32, q.astype(np.float64)) and np.array_equal(np.abs(want["net"][:, [2, 4]]), np.full((3, 2), 1024))
+    assert ref.Q_CAP == int(ref.V_CAP * 2.0 ** 32) and ref.V_CAP == float(np.float32(ref.V_CAP))
+    # the ramp: 1 - 2 straddling pairs in some layer and channel; a straddling pair carries at most 2 V_CAP, a pair that is neither
+    # straddling nor capped has |v| + slack < V_CAP, a capped one nothing
+    tol = ref.bounds(ramp)
+    print(f"cap frame under the ramp: straddling {ramp['straddling'].tolist()}, capped {ramp['capped'].tolist()}, bounds {np.round(tol, 4).tolist()}")
+    assert 1 <= ramp["straddling"].max() <= 2 and int(ramp["band"].sum()) == 0 and (ramp["capped"] >= 1020).all()
+    loose = ramp["counted"][:, None] - ramp["capped"] - ramp["straddling"]
+    assert (loose >= 0).all() and (tol <= ref.V_CAP * (2 * ramp["straddling"] + loose) + 2.0 ** -32 * loose).all() and not tol[(ramp["straddling"] + loose) == 0].any()
+    # ... and masked where a pair is open, the ramp's sums are exact too, and not symmetric: m0, m1 and S01 are not 0
+    g, want, share = gf.exact_cap_plane(frame, view, n, gf.masked_ramp(frame, view, gf.MASK_CAP_GENERAL)[0])
+    assert 0 < share <= gf.MASK_CAP_OPEN and (want["net"] != 0).all() and np.array_equal(want["sum"] * 2.0 ** 32, (want["net"] * ref.Q_CAP).astype(np.float64))

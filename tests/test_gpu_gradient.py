@@ -24,7 +24,7 @@ import gradient_ref
 import removal_ref
 import scenes
 import weight_ref
-from attrib_frames import BG, VIEW, F, _compressed, _ctx, _Frame, _stack, _stack_frame, _u32
+from attrib_frames import BG, VIEW, F, _cloud_rows, _compressed, _ctx, _Frame, _stack, _stack_frame, _u32
 from gradient_frames import gradient, signed_ramp, splat_halves
 from websplat import _lib as L
 from websplat import synth
@@ -118,17 +118,6 @@ def test_against_f64_faint_stacks_at_staging_boundaries(ws, cfg, k):
 
 
 # ---- 2. a general cloud --------------------------------------------------------------------------------------------------------
-def _cloud_rows(n=3000, seed=17):
-    """test_gpu_removal._cloud_rows: anisotropic Gaussians of random colours in the unit cube, opacities 0.02 - 0.3."""
-    rng = np.random.default_rng(seed)
-    xyz = rng.uniform(-1.0, 1.0, size=(n, 3)).astype(F)
-    log_scale = rng.uniform(np.log(0.01), np.log(0.08), size=(n, 3)).astype(F)
-    rot = rng.standard_normal(size=(n, 4)).astype(F)
-    op = rng.uniform(0.02, 0.3, size=n)
-    f_dc = rng.uniform(-1.5, 1.5, size=(n, 3)).astype(F)
-    return synth._rows(xyz, f_dc, np.zeros((n, 45), F), np.log(op / (1.0 - op)).astype(F), log_scale, rot)
-
-
 OPACITY_COLUMN = 9 + 45
 _REF = {}  # K1 and the depth sort do not depend on the tile configuration: one float64 walk serves the cases that share a frame
 
