@@ -1,8 +1,11 @@
 // api_attrib.cpp -- the C ABI's passes over a prepared frame's blend weights and the per-Gaussian accumulators they add to
 // (include/websplat.h): contributions, values, removal effect, gradients, SH gradients, geometry gradients.  They read the
-// renderer's prepared frame (api_state.h) and never make one; the four accumulators are one store (gaussian_sums.h).
+// renderer's prepared frame (api_state.h) and never make one; the four accumulators are one store (gaussian_sums.h).  The three
+// gradient accumulators share one pass (ws_internal_gradient_passes: a target, named steps, one descriptor) and, with removal,
+// one set of descriptor checks; the handles with per-Gaussian rows share one transpose.
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <new>
 
@@ -127,20 +130,21 @@ static int launch_done(int rc, ws_renderer* r, GaussianSums* acc, hipStream_t st
     return WS_OK;
 }
 
-// The base plane (F, T_end) of ws_renderer_accumulate_removal and ws_renderer_accumulate_gradient: the caller's, or the
-// renderer's scratch, grown on demand
-static int base_plane(ws_renderer* r, float* d_base, size_t pitch, float4** base, size_t* base_pitch) {
-    if (d_base) {
-        *base = reinterpret_cast<float4*>(d_base);
-        *base_pitch = pitch;
-        return WS_OK;
-    }
-    if (!r->scratch.removal_base.get()) {  // (one viewport per scratch: the plane is freed with it)
+// Removal's launch parameters, for ws_renderer_accumulate_removal and for the gradient pass, whose first step is removal's pass 1.
+// The base plane (F, T_end) is the caller's, or the renderer's scratch, grown on demand.
+static int removal_params(ws_renderer* r, const float background[3], float* d_base, size_t pitch, float scale, int kind, const Accum& acc,
+                          RemovalParams* rp) {
+    if (!d_base && !r->scratch.removal_base.get()) {  // (one viewport per scratch: the plane is freed with it)
         WS_HIP(hipDeviceSynchronize());
         WS_TRY(r->scratch.removal_base.alloc(r->scratch.layout.removal_base));
     }
-    *base = r->scratch.removal_base.get();
-    *base_pitch = (size_t)r->vw * 16;
+    rp->frame = frame_lists(r);
+    rp->base = d_base ? reinterpret_cast<float4*>(d_base) : r->scratch.removal_base.get();
+    rp->base_pitch = d_base ? pitch : (size_t)r->vw * 16;
+    for (int i = 0; i < 3; ++i) rp->background[i] = background[i];
+    rp->scale = scale;
+    rp->kind = kind;
+    rp->acc = acc;
     return WS_OK;
 }
 
@@ -165,84 +169,74 @@ static int accumulate_frame(ws_renderer* r, const ws_pointcloud* pc, ws_contrib*
 
 static_assert(WS_GRAD_CHANNELS == GRAD_CHANNELS, "the ABI's channel count is the kernel's");
 
-// One sequence for the three gradient accumulators; sh / geo: `acc` again when it is a ws_shgrad / ws_geomgrad, else nullptr.  The
-// descriptor is judged by itself first, then the handles, then the descriptor against the frame; only then the launches:
-// removal's pass 1 through launch_removal_base, then k_gradient -- into the accumulator, or into a ws_shgrad's scratch, then
-// k_sh_spread -- or, for a ws_geomgrad (whose descriptor carries geometry_scale where opacity_scale is), k_geometry into its
-// scratch, then k_geom_spread (passes & 4; without it the sums stay in the scratch: ws_debug_geometry_stage_a); `geometry` says so
-// where `geo` may still be null.
-static int gradient_passes(const std::string& who, ws_renderer* r, const ws_pointcloud* pc, GaussianSums* acc, ws_shgrad* sh,
-                           const ws_gradient_params* p, void* stream_v, unsigned passes, ws_geomgrad* geo = nullptr, bool geometry = false) {
-    if (!p) return fail(WS_ERR_INVALID, who + ": null params");
-    if (p->reserved0 != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    for (uint32_t w : p->reserved)
-        if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
-    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    if (!std::isfinite(p->opacity_scale) || !(p->opacity_scale > 0.0f))
-        return fail(WS_ERR_INVALID, who + (geometry ? ": geometry_scale" : ": opacity_scale") + " must be finite and above 0");
-    for (float b : p->background)
-        if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
-    if (!p->d_grad) return fail(WS_ERR_INVALID, who + ": null d_grad");
-    if (p->grad_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_grad) % 16 != 0)
-        return fail(WS_ERR_INVALID, who + ": d_grad: pointer and grad_pitch_bytes must be multiples of 16");
-    if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
-        return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
-    if (!r || !pc || !acc) return fail(WS_ERR_INVALID, who + ": null argument");
-    const int state = check_weights_frame(r, pc, who, acc->num_points == pc->num_points, "the accumulator was created for another number of points");
-    if (state) return state;
+// What ws_renderer_accumulate_removal and the gradient pass refuse in the same words.  Each entry point calls them in its own
+// order: the descriptor alone, then the handles, then the descriptor against the frame.
+static int check_scale(const std::string& who, const char* name, float v) {
+    return std::isfinite(v) && v > 0.0f ? (int)WS_OK : fail(WS_ERR_INVALID, who + ": " + name + " must be finite and above 0");
+}
+static int check_background(const std::string& who, const float bg[3]) {
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(bg[i])) return fail(WS_ERR_INVALID, who + ": background must be finite");
+    return WS_OK;
+}
+// A caller's plane of float4, d_<name> with <name>_pitch_bytes (nullptr: nothing to judge).  r == nullptr: by itself, pointer and
+// pitch; else against r's prepared frame, the pitch.
+static int check_plane16(const ws_renderer* r, const std::string& who, const std::string& name, const void* ptr, size_t pitch) {
+    if (ptr && !r && (pitch % 16 != 0 || reinterpret_cast<uintptr_t>(ptr) % 16 != 0))
+        return fail(WS_ERR_INVALID, who + ": d_" + name + ": pointer and " + name + "_pitch_bytes must be multiples of 16");
+    if (ptr && r && pitch < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_" + name + ": " + name + "_pitch_bytes below 16 x the viewport's width");
+    return WS_OK;
+}
+
+// The timers' label of a gradient pass, by the target's kind and the steps: the kernels that ran, joined by '+'.  String literals
+// (KernelMarks::mark keeps the pointer), and scripts/*_cost.py select on them.  A ws_grad has no spread.
+static const char* const GRAD_LABELS[3][GRAD_ALL + 1] = {
+    {"", "k_removal_base", "k_gradient", "k_removal_base+k_gradient", "", "k_removal_base", "k_gradient", "k_removal_base+k_gradient"},
+    {"", "k_removal_base", "k_gradient", "k_removal_base+k_gradient", "k_sh_spread", "k_removal_base+k_sh_spread", "k_gradient+k_sh_spread",
+     "k_removal_base+k_gradient+k_sh_spread"},
+    {"", "k_removal_base", "k_geometry", "k_removal_base+k_geometry", "k_geom_spread", "k_removal_base+k_geom_spread", "k_geometry+k_geom_spread",
+     "k_removal_base+k_geometry+k_geom_spread"}};
+
+static const char* const GRAD_ENTRY[3] = {"ws_renderer_accumulate_gradient", "ws_renderer_accumulate_sh_gradient",
+                                          "ws_renderer_accumulate_geometry_gradient"};
+
+// One sequence for the three gradient accumulators (GradTarget, GradSteps, GradDesc: gaussian_sums.h).  The descriptor is judged by
+// itself first, then the handles, then the descriptor against the frame; only then the launches: GRAD_BASE is removal's pass 1;
+// GRAD_SUMS the walk, k_gradient into a ws_grad's sums or a ws_shgrad's scratch, k_geometry into a ws_geomgrad's scratch;
+// GRAD_SPREAD the target's own kernel from its scratch into its sums (without it the sums stay in the scratch:
+// ws_debug_geometry_stage_a).  who: the entry point, for messages; nullptr: the target's own ws_renderer_accumulate_* one.
+int ws_internal_gradient_passes(const char* who_c, ws_renderer* r, const ws_pointcloud* pc, const GradTarget& t, const GradDesc& d, void* stream_v,
+                                unsigned steps) {
+    const std::string who(who_c ? who_c : GRAD_ENTRY[t.kind]);
+    ws_shgrad* const sh = t.sh();
+    ws_geomgrad* const geo = t.geo();
+    WS_TRY(check_scale(who, "scale", d.scale));
+    WS_TRY(check_scale(who, t.kind == GRAD_GEOMETRY ? "geometry_scale" : "opacity_scale", d.second_scale));
+    WS_TRY(check_background(who, d.background));
+    if (!d.d_grad) return fail(WS_ERR_INVALID, who + ": null d_grad");
+    WS_TRY(check_plane16(nullptr, who, "grad", d.d_grad, d.grad_pitch_bytes));
+    WS_TRY(check_plane16(nullptr, who, "base", d.d_base, d.base_pitch_bytes));
+    if (!r || !pc || !t.acc) return fail(WS_ERR_INVALID, who + ": null argument");
+    WS_TRY(check_weights_frame(r, pc, who, t.acc->num_points == pc->num_points, "the accumulator was created for another number of points"));
     if (sh && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no SH gradients (its codebooks are shared between Gaussians)");
-    if (geometry && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no geometry gradients (its covariances are a codebook shared between Gaussians)");
+    if (geo && pc->compressed) return fail(WS_ERR_UNSUPPORTED, who + ": a compressed cloud has no geometry gradients (its covariances are a codebook shared between Gaussians)");
     if (sh && sh->sh_deg != pc->sh_deg) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another SH degree");
-    if (p->grad_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_grad: grad_pitch_bytes below 16 x the viewport's width");
-    if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
-    RemovalParams rp;
-    rp.frame = frame_lists(r);
-    if (const int rc = base_plane(r, p->d_base, p->base_pitch_bytes, &rp.base, &rp.base_pitch)) return rc;
-    for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
-    rp.scale = 1.0f;  // (pass 1 reads neither of the three)
-    rp.kind = WS_ERROR_SQ;
-    rp.acc = Accum{nullptr, nullptr, nullptr, 0, 1.0f, 0.0f};
-    GradientParams gp;
-    gp.frame = rp.frame;
-    gp.base = rp.base;
-    gp.base_pitch = rp.base_pitch;
-    gp.grad = reinterpret_cast<const float4*>(p->d_grad);
-    gp.grad_pitch = p->grad_pitch_bytes;
-    gp.scale = p->scale;
-    gp.opacity_scale = p->opacity_scale;
-    gp.sums = sh ? sh->scratch.get() : acc->sums.get();
+    WS_TRY(check_plane16(r, who, "grad", d.d_grad, d.grad_pitch_bytes));
+    WS_TRY(check_plane16(r, who, "base", d.d_base, d.base_pitch_bytes));
+    RemovalParams rp;  // (pass 1 reads neither scale, kind nor accumulator)
+    WS_TRY(removal_params(r, d.background, d.d_base, d.base_pitch_bytes, 1.0f, WS_ERROR_SQ, Accum{nullptr, nullptr, nullptr, 0, 1.0f, 0.0f}, &rp));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     KernelMarks* km = launch_begin(r, stream);
-    int rc = (passes & 1u) ? launch_removal_base(rp, stream) : WS_OK;
-    if (geometry) {
-        GeometryParams ep;
-        ep.frame = rp.frame;
-        ep.base = rp.base;
-        ep.base_pitch = rp.base_pitch;
-        ep.grad = gp.grad;
-        ep.grad_pitch = gp.grad_pitch;
-        ep.scale = p->scale;
-        ep.geometry_scale = p->opacity_scale;
-        ep.sums = geo->scratch.get();
-        if (rc == WS_OK && (passes & 2u)) rc = launch_geometry(ep, stream);
-        if (rc == WS_OK && (passes & 4u)) {
-            GeomSpreadParams sp{};
-            sp.planes = pc->planes.get();
-            sp.splats = rp.frame.splats;
-            sp.src_index = rp.frame.src_index;
-            sp.counters = rp.frame.counters;
-            sp.scratch = geo->scratch.get();
-            sp.sums = geo->sums.get();
-            sp.n = geo->num_points;
-            sp.frame.cam = r->frame.cam;
-            sp.frame.rs = r->frame.settings;
-            sp.frame.geometry_scale = p->opacity_scale;
-            rc = launch_geom_spread(sp, stream);
-        }
-        return launch_done(rc, r, (passes & 4u) ? acc : nullptr, stream, km, passes == 1u ? "k_removal_base" : passes == 3u ? "k_removal_base+k_geometry" : passes == 6u ? "k_geometry+k_geom_spread" : "k_removal_base+k_geometry+k_geom_spread");
-    }
-    if (rc == WS_OK && (passes & 2u)) rc = launch_gradient(gp, stream);
-    if (rc == WS_OK && (passes & 2u) && sh) {
+    int rc = (steps & GRAD_BASE) ? launch_removal_base(rp, stream) : WS_OK;
+    // (the two walks' params: frame, base, base_pitch, grad, grad_pitch, scale, the second scale under its own name, sums)
+    const float4* grad = reinterpret_cast<const float4*>(d.d_grad);
+    if (rc == WS_OK && (steps & GRAD_SUMS) && !geo)
+        rc = launch_gradient(GradientParams{rp.frame, rp.base, rp.base_pitch, grad, d.grad_pitch_bytes, d.scale, /*opacity_scale*/ d.second_scale,
+                                            sh ? sh->scratch.get() : t.acc->sums.get()}, stream);
+    if (rc == WS_OK && (steps & GRAD_SUMS) && geo)
+        rc = launch_geometry(GeometryParams{rp.frame, rp.base, rp.base_pitch, grad, d.grad_pitch_bytes, d.scale, /*geometry_scale*/ d.second_scale,
+                                            geo->scratch.get()}, stream);
+    if (rc == WS_OK && (steps & GRAD_SPREAD) && sh) {
         ShSpreadParams sp;
         sp.planes = pc->planes.get();
         sp.scratch = sh->scratch.get();
@@ -253,23 +247,89 @@ static int gradient_passes(const std::string& who, ws_renderer* r, const ws_poin
         for (int i = 0; i < 3; ++i) sp.cam[i] = r->frame.cam_pos[i];
         rc = launch_sh_spread(sp, stream);
     }
-    const char* const marks[2][3] = {{"k_removal_base", "k_gradient", "k_removal_base+k_gradient"},
-                                     {"k_removal_base", "k_gradient+k_sh_spread", "k_removal_base+k_gradient+k_sh_spread"}};
-    // (pass 1 alone adds no frame)
-    return launch_done(rc, r, (passes & 2u) ? acc : nullptr, stream, km, marks[sh ? 1 : 0][passes == 1u ? 0 : passes == 2u ? 1 : 2]);
+    if (rc == WS_OK && (steps & GRAD_SPREAD) && geo) {
+        GeomSpreadParams sp{};
+        sp.planes = pc->planes.get();
+        sp.splats = rp.frame.splats;
+        sp.src_index = rp.frame.src_index;
+        sp.counters = rp.frame.counters;
+        sp.scratch = geo->scratch.get();
+        sp.sums = geo->sums.get();
+        sp.n = geo->num_points;
+        sp.frame.cam = r->frame.cam;
+        sp.frame.rs = r->frame.settings;
+        sp.frame.geometry_scale = d.second_scale;
+        rc = launch_geom_spread(sp, stream);
+    }
+    // (the frame is counted by the step that completes it)
+    const bool counted = steps & (t.kind == GRAD_COLOUR ? GRAD_SUMS : GRAD_SPREAD);
+    return launch_done(rc, r, counted ? t.acc : nullptr, stream, km, GRAD_LABELS[t.kind][steps & GRAD_ALL]);
 }
 
-int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    return gradient_passes("ws_renderer_accumulate_gradient", r, pc, g, nullptr, p, stream_v, passes);
+// An ABI descriptor under the pass's names, read through its own: P is ws_gradient_params with its opacity_scale, or
+// ws_geometry_params with its geometry_scale.  What needs no more than the descriptor's own words is refused here, first.
+template <typename P>
+static int gradient_entry(const char* who, ws_renderer* r, const ws_pointcloud* pc, const GradTarget& t, const P* p, float P::*second_scale,
+                          void* stream, unsigned steps) {
+    if (!p) return fail(WS_ERR_INVALID, std::string(who) + ": null params");
+    if (p->reserved0 | p->reserved[0] | p->reserved[1] | p->reserved[2] | p->reserved[3]) return fail(WS_ERR_INVALID, std::string(who) + ": reserved words must be zero");
+    GradDesc d;
+    for (int i = 0; i < 3; ++i) d.background[i] = p->background[i];
+    d.scale = p->scale;
+    d.second_scale = p->*second_scale;
+    d.d_grad = p->d_grad;
+    d.grad_pitch_bytes = p->grad_pitch_bytes;
+    d.d_base = p->d_base;
+    d.base_pitch_bytes = p->base_pitch_bytes;
+    return ws_internal_gradient_passes(who, r, pc, t, d, stream, steps);
 }
 
-int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    return gradient_passes("ws_renderer_accumulate_sh_gradient", r, pc, g, g, p, stream_v, passes);
+// The host's transposes under ws_shgrad and ws_geomgrad.  The device keeps one plane per element, [elements][n] 8-B words; the
+// caller's arrays are rows per Gaussian.  A column: the caller's array of n rows of `width` words (nullptr: not given) and the
+// first of the `width` planes they are.
+struct RowColumn {
+    const void* rows;
+    size_t first, width;
+};
+using RowColumns = std::initializer_list<RowColumn>;
+static bool any_rows(RowColumns cols) {
+    for (const RowColumn& c : cols)
+        if (c.rows) return true;
+    return false;
 }
-
-// (p->opacity_scale is the geometry_scale here; passes: 1 the base image, 2 k_geometry into the scratch, 4 k_geom_spread)
-int ws_internal_geometry_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_gradient_params* p, void* stream_v, unsigned passes) {
-    return gradient_passes("ws_renderer_accumulate_geometry_gradient", r, pc, g, nullptr, p, stream_v, passes, g, true);
+// to_rows: planes -> the caller's arrays (which are then not const: ws_*_download); else the caller's arrays -> planes
+static void transpose_rows(uint64_t* planes, size_t n, RowColumns cols, bool to_rows) {
+    for (const RowColumn& c : cols) {
+        char* rows = static_cast<char*>(const_cast<void*>(c.rows));
+        for (size_t e = 0; rows && e < c.width; ++e)
+            for (size_t i = 0; i < n; ++i) {
+                char* row = rows + (i * c.width + e) * 8;  // (bytes: the rows are int64, double or uint64)
+                uint64_t* word = planes + (c.first + e) * n + i;
+                to_rows ? std::memcpy(row, word, 8) : std::memcpy(word, row, 8);
+            }
+    }
+}
+// Through one staging array of every word, sized by the accumulator, so it may be made before the store has judged the handle
+// and the capacity.
+static int download_rows(GaussianSums* g, const char* who, uint32_t capacity, RowColumns cols) {
+    std::unique_ptr<uint64_t[]> st;
+    if (g && any_rows(cols)) {
+        st.reset(new (std::nothrow) uint64_t[g->sums.count()]);
+        if (!st) return fail(WS_ERR_OOM, std::string(who) + ": host allocation failed");
+    }
+    WS_TRY(GaussianSums::download_words(g, who, capacity, st != nullptr, st.get()));
+    if (st) transpose_rows(st.get(), g->num_points, cols, true);
+    return WS_OK;
+}
+// merge: the handle's own, used when there is something to add (an empty one: the store's k_grad_merge)
+static int add_rows(GaussianSums* g, const char* who, uint32_t n_rows, RowColumns cols, const GaussianSums::Merge& merge) {
+    std::unique_ptr<uint64_t[]> st;
+    if (g && n_rows >= g->num_points && any_rows(cols)) {  // (else the store refuses, or there is nothing to add)
+        st.reset(new (std::nothrow) uint64_t[g->sums.count()]());  // (zeros where a pointer is NULL: 0, +0.0)
+        if (!st) return fail(WS_ERR_OOM, std::string(who) + ": host allocation failed");
+        transpose_rows(st.get(), g->num_points, cols, false);
+    }
+    return GaussianSums::merge_words(g, who, n_rows, st.get(), st ? merge : GaussianSums::Merge());
 }
 
 extern "C" {
@@ -390,25 +450,17 @@ int ws_renderer_accumulate_removal(ws_renderer* r, const ws_pointcloud* pc, ws_c
         if (w != 0) return fail(WS_ERR_INVALID, who + ": reserved words must be zero");
     if (p->kind == WS_ERROR_DSSIM) return fail(WS_ERR_INVALID, who + ": kind WS_ERROR_DSSIM has no removal effect (sq or abs)");
     if (p->kind != WS_ERROR_SQ && p->kind != WS_ERROR_ABS) return fail(WS_ERR_INVALID, who + ": unknown kind");
-    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return fail(WS_ERR_INVALID, who + ": scale must be finite and above 0");
-    for (float b : p->background)
-        if (!std::isfinite(b)) return fail(WS_ERR_INVALID, who + ": background must be finite");
+    WS_TRY(check_scale(who, "scale", p->scale));
+    WS_TRY(check_background(who, p->background));
     if (p->weight && !p->weight->d_values) return fail(WS_ERR_INVALID, who + ": weight: null d_values");
-    if (const int rc = check_plane_view(nullptr, who + ": weight", p->weight)) return rc;
-    if (p->d_base && (p->base_pitch_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(p->d_base) % 16 != 0))
-        return fail(WS_ERR_INVALID, who + ": d_base: pointer and base_pitch_bytes must be multiples of 16");
+    WS_TRY(check_plane_view(nullptr, who + ": weight", p->weight));
+    WS_TRY(check_plane16(nullptr, who, "base", p->d_base, p->base_pitch_bytes));
     if (!r || !pc || !c) return fail(WS_ERR_INVALID, who + ": null argument");
-    const int state = check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points");
-    if (state) return state;
-    if (const int rc = check_plane_view(r, who + ": weight", p->weight)) return rc;
-    if (p->d_base && p->base_pitch_bytes < (size_t)r->vw * 16) return fail(WS_ERR_INVALID, who + ": d_base: base_pitch_bytes below 16 x the viewport's width");
+    WS_TRY(check_weights_frame(r, pc, who, c->num_points == pc->num_points, "the accumulator was created for another number of points"));
+    WS_TRY(check_plane_view(r, who + ": weight", p->weight));
+    WS_TRY(check_plane16(r, who, "base", p->d_base, p->base_pitch_bytes));
     RemovalParams rp;
-    rp.frame = frame_lists(r);
-    if (const int rc = base_plane(r, p->d_base, p->base_pitch_bytes, &rp.base, &rp.base_pitch)) return rc;
-    for (int i = 0; i < 3; ++i) rp.background[i] = p->background[i];
-    rp.scale = p->scale;
-    rp.kind = p->kind;
-    rp.acc = accum_arg(c, p->weight);
+    WS_TRY(removal_params(r, p->background, p->d_base, p->base_pitch_bytes, p->scale, p->kind, accum_arg(c, p->weight), &rp));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     KernelMarks* km = launch_begin(r, stream);
     return launch_done(launch_removal(rp, stream), r, c, stream, km, "k_removal_base+k_removal");
@@ -435,7 +487,7 @@ int ws_grad_download(ws_grad* g, uint32_t capacity, int64_t* q32) {
 int ws_grad_add(ws_grad* g, const int64_t* q32, uint32_t n) { return GaussianSums::merge_words(g, "ws_grad_add", n, q32); }
 
 int ws_renderer_accumulate_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream) {
-    return ws_internal_gradient_passes(r, pc, g, p, stream, 3u);
+    return gradient_entry("ws_renderer_accumulate_gradient", r, pc, g, p, &ws_gradient_params::opacity_scale, stream, GRAD_ALL);
 }
 
 // ---- ws_shgrad: one plane of the store per element, a frame's scratch, and the host's transposes
@@ -458,51 +510,23 @@ uint32_t ws_shgrad_num_points(const ws_shgrad* g) { return g ? g->num_points : 0
 uint32_t ws_shgrad_sh_deg(const ws_shgrad* g) { return g ? g->sh_deg : 0u; }
 uint32_t ws_shgrad_frames(const ws_shgrad* g) { return g ? g->frames : 0u; }
 
-// The device keeps one plane per element; the caller's rows are per Gaussian: the transposes are the host's, through one staging
-// array of every word (sized by the accumulator, so it may be made before the store has judged the handle and the capacity).
+// rows of 3 ncoef words per Gaussian, and the opacity's plane as it is
 int ws_shgrad_download(ws_shgrad* g, uint32_t capacity, int64_t* q_sh, int64_t* q_opacity) {
-    std::unique_ptr<int64_t[]> st;
-    if (g && (q_sh || q_opacity)) {
-        st.reset(new (std::nothrow) int64_t[g->sums.count()]);
-        if (!st) return fail(WS_ERR_OOM, "ws_shgrad_download: host allocation failed");
-    }
-    WS_TRY(GaussianSums::download_words(g, "ws_shgrad_download", capacity, st != nullptr, st.get()));
-    if (!st) return WS_OK;
-    const size_t n = g->num_points, el = (size_t)3 * g->ncoef;
-    if (q_opacity) std::memcpy(q_opacity, st.get() + el * n, n * sizeof(int64_t));
-    for (size_t e = 0; q_sh && e < el; ++e)
-        for (size_t i = 0; i < n; ++i) q_sh[i * el + e] = st[e * n + i];
-    return WS_OK;
+    const size_t el = g ? (size_t)3 * g->ncoef : 0;
+    return download_rows(g, "ws_shgrad_download", capacity, {{q_sh, 0, el}, {q_opacity, el, 1}});
 }
 
 int ws_shgrad_add(ws_shgrad* g, const int64_t* q_sh, const int64_t* q_opacity, uint32_t n_rows) {
-    std::unique_ptr<int64_t[]> st;
-    if (g && n_rows >= g->num_points && (q_sh || q_opacity)) {  // (else the store refuses, or there is nothing to add)
-        const size_t n = g->num_points, el = (size_t)3 * g->ncoef;
-        st.reset(new (std::nothrow) int64_t[g->sums.count()]());  // (zeros where a pointer is NULL)
-        if (!st) return fail(WS_ERR_OOM, "ws_shgrad_add: host allocation failed");
-        for (size_t e = 0; q_sh && e < el; ++e)
-            for (size_t i = 0; i < n; ++i) st[e * n + i] = q_sh[i * el + e];
-        if (q_opacity) std::memcpy(st.get() + el * n, q_opacity, n * sizeof(int64_t));
-    }
-    return GaussianSums::merge_words(g, "ws_shgrad_add", n_rows, st.get());
+    const size_t el = g ? (size_t)3 * g->ncoef : 0;
+    return add_rows(g, "ws_shgrad_add", n_rows, {{q_sh, 0, el}, {q_opacity, el, 1}}, GaussianSums::Merge());
 }
 
 // ... and ws_renderer_accumulate_gradient's launches into the accumulator's scratch, then k_sh_spread
 int ws_renderer_accumulate_sh_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream) {
-    return ws_internal_sh_gradient_passes(r, pc, g, p, stream, 3u);
+    return gradient_entry("ws_renderer_accumulate_sh_gradient", r, pc, g, p, &ws_gradient_params::opacity_scale, stream, GRAD_ALL);
 }
 
 // ---- ws_geomgrad: ten f64 planes and a count plane of the store, a frame's scratch, and the host's transposes
-static int geometry_passes(const char* who, ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream, unsigned passes) {
-    ws_gradient_params gp{};
-    if (p) {
-        static_assert(sizeof(ws_geometry_params) == sizeof(ws_gradient_params), "the two descriptors differ in the meaning of one float");
-        std::memcpy(&gp, p, sizeof gp);
-    }
-    return gradient_passes(who, r, pc, g, nullptr, p ? &gp : nullptr, stream, passes, g, true);
-}
-
 int ws_geomgrad_create(ws_context* ctx, uint32_t num_points, ws_geomgrad** out) {
     return create_sums("ws_geomgrad_create", ctx, num_points, out, [num_points](ws_geomgrad* g) {
         WS_TRY(g->sums.alloc((size_t)GEOM_ELEMENTS * num_points));
@@ -519,53 +543,24 @@ int ws_geomgrad_reset(ws_geomgrad* g, void* stream) { return GaussianSums::reset
 uint32_t ws_geomgrad_num_points(const ws_geomgrad* g) { return g ? g->num_points : 0u; }
 uint32_t ws_geomgrad_frames(const ws_geomgrad* g) { return g ? g->frames : 0u; }
 
-// The device keeps one plane per element; the caller's rows are per Gaussian: the transposes are the host's, as ws_shgrad's are.
+// rows of 3 and of 6 f64 per Gaussian, then the two planes that are per Gaussian as they are
 int ws_geomgrad_download(ws_geomgrad* g, uint32_t capacity, double* position, double* covariance, double* screen_norm, uint64_t* seen) {
-    const bool wanted = position || covariance || screen_norm || seen;
-    std::unique_ptr<uint64_t[]> st;
-    if (g && wanted) {
-        st.reset(new (std::nothrow) uint64_t[g->sums.count()]);
-        if (!st) return fail(WS_ERR_OOM, "ws_geomgrad_download: host allocation failed");
-    }
-    WS_TRY(GaussianSums::download_words(g, "ws_geomgrad_download", capacity, st != nullptr, st.get()));
-    if (!st) return WS_OK;
-    const size_t n = g->num_points;
-    const double* d = reinterpret_cast<const double*>(st.get());
-    for (size_t i = 0; i < n; ++i) {
-        for (size_t k = 0; position && k < 3; ++k) position[i * 3 + k] = d[k * n + i];
-        for (size_t e = 0; covariance && e < 6; ++e) covariance[i * 6 + e] = d[(3 + e) * n + i];
-    }
-    if (screen_norm) std::memcpy(screen_norm, d + 9 * n, n * sizeof(double));
-    if (seen) std::memcpy(seen, st.get() + 10 * n, n * sizeof(uint64_t));
-    return WS_OK;
+    return download_rows(g, "ws_geomgrad_download", capacity, {{position, 0, 3}, {covariance, 3, 6}, {screen_norm, 9, 1}, {seen, 10, 1}});
 }
 
 int ws_geomgrad_add(ws_geomgrad* g, const double* position, const double* covariance, const double* screen_norm, const uint64_t* seen, uint32_t n_rows) {
-    std::unique_ptr<uint64_t[]> st;
-    if (g && n_rows >= g->num_points && (position || covariance || screen_norm || seen)) {  // (else the store refuses, or there is nothing to add)
-        const size_t n = g->num_points;
-        st.reset(new (std::nothrow) uint64_t[g->sums.count()]());  // (zeros where a pointer is NULL: +0.0 and 0)
-        if (!st) return fail(WS_ERR_OOM, "ws_geomgrad_add: host allocation failed");
-        double* d = reinterpret_cast<double*>(st.get());
-        for (size_t i = 0; i < n; ++i) {
-            for (size_t k = 0; position && k < 3; ++k) d[k * n + i] = position[i * 3 + k];
-            for (size_t e = 0; covariance && e < 6; ++e) d[(3 + e) * n + i] = covariance[i * 6 + e];
-        }
-        if (screen_norm) std::memcpy(d + 9 * n, screen_norm, n * sizeof(double));
-        if (seen) std::memcpy(st.get() + 10 * n, seen, n * sizeof(uint64_t));
-    }
     const GaussianSums::Merge merge = [g](const unsigned long long* d_words, hipStream_t stream) {
         return launch_geom_merge(g->sums.get(), d_words, g->num_points, stream);
     };
-    return GaussianSums::merge_words(g, "ws_geomgrad_add", n_rows, st.get(), st ? merge : GaussianSums::Merge());
+    return add_rows(g, "ws_geomgrad_add", n_rows, {{position, 0, 3}, {covariance, 3, 6}, {screen_norm, 9, 1}, {seen, 10, 1}}, merge);
 }
 
 int ws_renderer_accumulate_geometry_gradient(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream) {
-    return geometry_passes("ws_renderer_accumulate_geometry_gradient", r, pc, g, p, stream, 7u);
+    return gradient_entry("ws_renderer_accumulate_geometry_gradient", r, pc, g, p, &ws_geometry_params::geometry_scale, stream, GRAD_ALL);
 }
 
 int ws_debug_geometry_stage_a(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_geometry_params* p, void* stream) {
-    WS_TRY(geometry_passes("ws_debug_geometry_stage_a", r, pc, g, p, stream, 3u));
+    WS_TRY(gradient_entry("ws_debug_geometry_stage_a", r, pc, g, p, &ws_geometry_params::geometry_scale, stream, GRAD_BASE | GRAD_SUMS));
     g->last_stream = static_cast<hipStream_t>(stream);  // (no frame added, but the scratch is read back behind this stream)
     return WS_OK;
 }

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "gaussian_sums.h"
 #include "scene_frames.h"
 #include "ws_internal.h"
 
@@ -341,106 +342,89 @@ int refuse_scale(const std::string& who, const char* name, float v) {
 // One frame of ws_scene_accumulate_gradient and ws_scene_refit: image a is the frame's f32 base plane over the cloud's background,
 // the first half of the scratch plane; the loss gradient is the second half.  ws_renderer_accumulate_gradient in its two steps,
 // the plane made of pass 1's image.
-// Where the frames of the gradient drivers go: a ws_grad, or a ws_shgrad (websplat.h "SH gradients"); the per-frame call differs,
-// the frame does not.
-struct GradSink {
-    ws_grad* grad = nullptr;
-    ws_shgrad* sh = nullptr;
-    ws_geomgrad* geo = nullptr;   // (its descriptor's opacity_scale is the geometry_scale; step 2 is k_geometry + k_geom_spread)
-    int passes(ws_renderer* r, const ws_pointcloud* pc, const ws_gradient_params* p, unsigned which) const {
-        if (geo) return ws_internal_geometry_gradient_passes(r, pc, geo, p, nullptr, which == 2u ? 6u : which);
-        return sh ? ws_internal_sh_gradient_passes(r, pc, sh, p, nullptr, which) : ws_internal_gradient_passes(r, pc, grad, p, nullptr, which);
-    }
-    uint32_t num_points() const { return geo ? ws_geomgrad_num_points(geo) : sh ? ws_shgrad_num_points(sh) : ws_grad_num_points(grad); }
-    int reset() const { return geo ? ws_geomgrad_reset(geo, nullptr) : sh ? ws_shgrad_reset(sh, nullptr) : ws_grad_reset(grad, nullptr); }
-};
-
-int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, const GradSink& grad, const ws_gradient_params& gp, int kind, const SceneFrame& f) {
+// Where the frames go is a GradTarget (gaussian_sums.h): the steps are the same for a ws_grad, a ws_shgrad and a ws_geomgrad.
+// (the pass speaks under the name of the target's own ws_renderer_accumulate_* entry point, as it always has)
+int gradient_frame(ws_context* ctx, const ws_pointcloud* pc, const GradTarget& grad, GradDesc d, int kind, const SceneFrame& f) {
     const size_t pitch = (size_t)f.w * 16;
     float* base = static_cast<float*>(f.plane);
     float* g = base + (size_t)f.w * f.h * 4;
-    ws_gradient_params p = gp;
-    p.d_base = base;
-    p.base_pitch_bytes = pitch;
-    p.d_grad = g;
-    p.grad_pitch_bytes = pitch;
-    int frc = grad.passes(f.r, pc, &p, 1u);
+    d.d_base = base;
+    d.d_grad = g;
+    d.base_pitch_bytes = d.grad_pitch_bytes = pitch;
+    int frc = ws_internal_gradient_passes(nullptr, f.r, pc, grad, d, nullptr, GRAD_BASE);
     const ws_image_view va = view_of(base, WS_FORMAT_RGBA32_FLOAT, pitch, nullptr);  // (the alpha slot holds T_end: ignored)
     if (frc == WS_OK) frc = ws_image_error_gradient(ctx, &va, &f.vb, f.w, f.h, kind, 0, g, pitch, nullptr);
-    if (frc == WS_OK) frc = grad.passes(f.r, pc, &p, 2u);
+    if (frc == WS_OK) frc = ws_internal_gradient_passes(nullptr, f.r, pc, grad, d, nullptr, GRAD_SUMS | GRAD_SPREAD);
     return frc;
 }
 
 // ws_scene_accumulate_gradient, ws_scene_accumulate_sh_gradient and ws_scene_accumulate_geometry_gradient
 int scene_accumulate_gradient(const std::string& who, ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split,
-                              const ws_pointcloud* ref_pc, const char* gt_dir, int kind, float scale, float opacity_scale, bool have_sink,
-                              const GradSink& grad, uint32_t* frames) {
+                              const ws_pointcloud* ref_pc, const char* gt_dir, int kind, float scale, float second_scale, const GradTarget& grad,
+                              uint32_t* frames) {
     if (frames) *frames = 0;
     if (const int rc = refuse_kind(who, kind)) return rc;
     if (const int rc = refuse_scale(who, "scale", scale)) return rc;
-    if (const int rc = refuse_scale(who, grad.geo ? "geometry_scale" : "opacity_scale", opacity_scale)) return rc;
+    if (const int rc = refuse_scale(who, grad.kind == GRAD_GEOMETRY ? "geometry_scale" : "opacity_scale", second_scale)) return rc;
     if (const int rc = refuse_unless_a_split(who, split)) return rc;
-    if (!ctx || !pc || !scene || !have_sink) return fail(WS_ERR_INVALID, who + ": null argument");
+    if (!ctx || !pc || !scene || !grad.acc) return fail(WS_ERR_INVALID, who + ": null argument");
     if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
-    if (grad.num_points() != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
+    if (grad.acc->num_points != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the accumulator was created for another number of points");
     if (const int rc = refuse_debug_cut(who, ctx)) return rc;
-    ws_gradient_params gp;
-    std::memset(&gp, 0, sizeof gp);
-    eval_background(pc, gp.background);
-    gp.scale = scale;
-    gp.opacity_scale = opacity_scale;
+    GradDesc d;
+    eval_background(pc, d.background);
+    d.scale = scale;
+    d.second_scale = second_scale;
     return walk_once(ctx, {who.c_str(), pc, scene, split, ref_pc, gt_dir, true, false, 32, OVERFLOW_FAILS, "the accumulators are incomplete"}, frames,
-                     [&](const SceneFrame& f) { return gradient_frame(ctx, pc, grad, gp, kind, f); });
+                     [&](const SceneFrame& f) { return gradient_frame(ctx, pc, grad, d, kind, f); });
 }
 
-// ws_scene_refit (shp == nullptr) and ws_scene_refit_sh: per epoch the frames of the gradient driver into an accumulator of the
-// driver's own, an Adam step and a reset after every batch.  Everything is enqueued on one stream, so the next frame's K1 reads the
-// planes the step before it wrote; a walk of its own per epoch brings the one sync and the one look at the error bits per epoch.
+// ws_scene_refit (sh false: params->base is the caller's ws_refit_params, the rest is not looked at) and ws_scene_refit_sh: per
+// epoch the frames of the gradient driver into an accumulator of the driver's own, an Adam step and a reset after every batch.
+// Everything is enqueued on one stream, so the next frame's K1 reads the planes the step before it wrote; a walk of its own per
+// epoch brings the one sync and the one look at the error bits per epoch.
 int scene_refit(const std::string& who, ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
-                const char* gt_dir, int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params,
-                const ws_refit_sh_params* shp, bool sh, uint32_t epochs, uint32_t views_per_step, uint32_t* steps) {
+                const char* gt_dir, int kind, float opacity_scale, ws_refit* refit, const ws_refit_sh_params* params, bool sh,
+                uint32_t epochs, uint32_t views_per_step, uint32_t* steps) {
     if (steps) *steps = 0;
     if (const int rc = refuse_kind(who, kind)) return rc;
     if (const int rc = refuse_scale(who, "opacity_scale", opacity_scale)) return rc;
     if (const int rc = refuse_unless_a_split(who, split)) return rc;
-    if (const int rc = sh ? ws_internal_refit_check_sh_params(shp, who, false) : ws_internal_refit_check_params(params, who, false)) return rc;
+    if (const int rc = sh ? ws_internal_refit_check_sh_params(params, who, false) : ws_internal_refit_check_params(params ? &params->base : nullptr, who, false)) return rc;
     if (!ctx || !pc || !scene || !refit) return fail(WS_ERR_INVALID, who + ": null argument");
     if (const int rc = refuse_unless_one_image_b(who, ref_pc, gt_dir)) return rc;
     if (ref_pc == pc) return fail(WS_ERR_INVALID, who + ": ref_pc is the cloud being refitted");
     if (ws_refit_num_points(refit) != ws_pointcloud_num_points(pc)) return fail(WS_ERR_INVALID, who + ": the refit object was created for another number of points");
     if (const int rc = refuse_debug_cut(who, ctx)) return rc;
-    GradSink grad;
+    ws_grad* colour = nullptr;
+    ws_shgrad* rest = nullptr;
     int rc = sh ? ws_refit_enable_sh(refit, pc, nullptr) : (int)WS_OK;
     if (rc == WS_OK)
-        rc = sh ? ws_shgrad_create(ctx, ws_pointcloud_num_points(pc), ws_pointcloud_sh_deg(pc), &grad.sh) : ws_grad_create(ctx, ws_pointcloud_num_points(pc), &grad.grad);
-    ws_gradient_params gp;
-    std::memset(&gp, 0, sizeof gp);
-    eval_background(pc, gp.background);
-    gp.scale = 1.0f;
-    gp.opacity_scale = opacity_scale;
+        rc = sh ? ws_shgrad_create(ctx, ws_pointcloud_num_points(pc), ws_pointcloud_sh_deg(pc), &rest) : ws_grad_create(ctx, ws_pointcloud_num_points(pc), &colour);
+    const GradTarget grad = sh ? GradTarget(rest) : GradTarget(colour);
+    GradDesc d;  // (scale 1)
+    eval_background(pc, d.background);
+    d.second_scale = opacity_scale;
     uint32_t taken = 0;
     for (uint32_t epoch = 0; epoch < epochs && rc == WS_OK; ++epoch) {
         uint32_t in_batch = 0;
         rc = walk_once(ctx, {who.c_str(), pc, scene, split, ref_pc, gt_dir, true, false, 32, OVERFLOW_FAILS, "the accumulators are incomplete"}, nullptr,
                        [&](const SceneFrame& f) {
-                           int frc = gradient_frame(ctx, pc, grad, gp, kind, f);
+                           int frc = gradient_frame(ctx, pc, grad, d, kind, f);
                            if (frc != WS_OK) return frc;
                            ++in_batch;
                            if (in_batch < (views_per_step ? views_per_step : f.count) && f.index + 1 < f.count) return frc;
-                           ws_refit_sh_params sp;
-                           std::memset(&sp, 0, sizeof sp);
-                           if (sh) sp = *shp;
-                           else sp.base = *params;
+                           ws_refit_sh_params sp = *params;
                            sp.base.colour_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)in_batch);
                            sp.base.opacity_unit = 1.0 / (WS_GRAD_SUM_SCALE * (double)opacity_scale * (double)in_batch);
-                           frc = sh ? ws_refit_step_sh(refit, pc, grad.sh, &sp, nullptr) : ws_refit_step(refit, pc, grad.grad, &sp.base, nullptr);
-                           if (frc == WS_OK) ++taken, in_batch = 0, frc = grad.reset();
+                           frc = sh ? ws_refit_step_sh(refit, pc, rest, &sp, nullptr) : ws_refit_step(refit, pc, colour, &sp.base, nullptr);
+                           if (frc == WS_OK) ++taken, in_batch = 0, frc = GaussianSums::reset(grad.acc, who.c_str(), nullptr);
                            return frc;
                        });
     }
     if (steps) *steps = taken;
-    if (grad.grad) ws_grad_destroy(grad.grad);
-    if (grad.sh) ws_shgrad_destroy(grad.sh);
+    if (colour) ws_grad_destroy(colour);
+    if (rest) ws_shgrad_destroy(rest);
     return rc;
 }
 
@@ -585,38 +569,35 @@ int ws_scene_accumulate_error(ws_context* ctx, const ws_pointcloud* pc, const ws
 // the Rgba16Float render of `pc`, a plane of two float4 per pixel (gradient_frame).
 int ws_scene_accumulate_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                  const char* gt_dir, int kind, float scale, float opacity_scale, ws_grad* grad, uint32_t* frames) {
-    GradSink sink;
-    sink.grad = grad;
-    return scene_accumulate_gradient("ws_scene_accumulate_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, opacity_scale, grad != nullptr, sink, frames);
+    return scene_accumulate_gradient("ws_scene_accumulate_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, opacity_scale, grad, frames);
 }
 
 // ... the same frames into a ws_shgrad (websplat.h "SH gradients")
 int ws_scene_accumulate_sh_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                     const char* gt_dir, int kind, float scale, float opacity_scale, ws_shgrad* grad, uint32_t* frames) {
-    GradSink sink;
-    sink.sh = grad;
-    return scene_accumulate_gradient("ws_scene_accumulate_sh_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, opacity_scale, grad != nullptr, sink, frames);
+    return scene_accumulate_gradient("ws_scene_accumulate_sh_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, opacity_scale, grad, frames);
 }
 
 // ... and into a ws_geomgrad (websplat.h "Geometry gradients"): geometry_scale where the other two have opacity_scale
 int ws_scene_accumulate_geometry_gradient(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc,
                                           const char* gt_dir, int kind, float scale, float geometry_scale, ws_geomgrad* grad, uint32_t* frames) {
-    GradSink sink;
-    sink.geo = grad;
-    return scene_accumulate_gradient("ws_scene_accumulate_geometry_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, geometry_scale, grad != nullptr, sink, frames);
+    return scene_accumulate_gradient("ws_scene_accumulate_geometry_gradient", ctx, pc, scene, split, ref_pc, gt_dir, kind, scale, geometry_scale, grad, frames);
 }
 
 // ... and the loops those gradients are for (websplat.h "Refitting colour and opacity"; scene_refit above)
 int ws_scene_refit(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
                    int kind, float opacity_scale, ws_refit* refit, const ws_refit_params* params, uint32_t epochs, uint32_t views_per_step,
                    uint32_t* steps) {
-    return scene_refit("ws_scene_refit", ctx, pc, scene, split, ref_pc, gt_dir, kind, opacity_scale, refit, params, nullptr, false, epochs, views_per_step, steps);
+    ws_refit_sh_params block;
+    std::memset(&block, 0, sizeof block);
+    if (params) block.base = *params;
+    return scene_refit("ws_scene_refit", ctx, pc, scene, split, ref_pc, gt_dir, kind, opacity_scale, refit, params ? &block : nullptr, false, epochs, views_per_step, steps);
 }
 
 int ws_scene_refit_sh(ws_context* ctx, ws_pointcloud* pc, const ws_scene* scene, int split, const ws_pointcloud* ref_pc, const char* gt_dir,
                       int kind, float opacity_scale, ws_refit* refit, const ws_refit_sh_params* params, uint32_t epochs, uint32_t views_per_step,
                       uint32_t* steps) {
-    return scene_refit("ws_scene_refit_sh", ctx, pc, scene, split, ref_pc, gt_dir, kind, opacity_scale, refit, nullptr, params, true, epochs, views_per_step, steps);
+    return scene_refit("ws_scene_refit_sh", ctx, pc, scene, split, ref_pc, gt_dir, kind, opacity_scale, refit, params, true, epochs, views_per_step, steps);
 }
 
 int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, uint32_t num_samples,

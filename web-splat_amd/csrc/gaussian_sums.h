@@ -48,3 +48,41 @@ struct ws_shgrad : ws::GaussianSums {    // sums: [3 ncoef + 1][num_points]: one
 struct ws_geomgrad : ws::GaussianSums {  // sums: [11][num_points]: ten planes of f64 bits (position 3, covariance 6, screen_norm), then seen
     ws::DeviceBuf<unsigned long long> scratch;  // [num_points][5] int64: one frame's screen-space sums, zero between the calls
 };
+
+// ---- a gradient pass over a prepared frame (ws_internal_gradient_passes: ws_internal.h, api_attrib.cpp), as its callers describe it
+namespace ws {
+
+// Where the pass adds: one of the three gradient accumulators, as the store every one of them is.  acc may be null (the ABI's
+// caller passed it so): the pass refuses that in its turn.
+enum GradKind { GRAD_COLOUR = 0, GRAD_SH = 1, GRAD_GEOMETRY = 2 };
+struct GradTarget {
+    GradKind kind;
+    GaussianSums* acc;
+    GradTarget(ws_grad* g) : kind(GRAD_COLOUR), acc(g) {}
+    GradTarget(ws_shgrad* g) : kind(GRAD_SH), acc(g) {}
+    GradTarget(ws_geomgrad* g) : kind(GRAD_GEOMETRY), acc(g) {}
+    ws_shgrad* sh() const { return kind == GRAD_SH ? static_cast<ws_shgrad*>(acc) : nullptr; }
+    ws_geomgrad* geo() const { return kind == GRAD_GEOMETRY ? static_cast<ws_geomgrad*>(acc) : nullptr; }
+};
+
+// Which launches, the same for every target.  A frame is counted by the step that completes it: a ws_grad's by GRAD_SUMS, a
+// target's with a spread by GRAD_SPREAD.
+enum GradSteps : unsigned {
+    GRAD_BASE = 1u,    // k_removal_base: the base image (F, T_end)
+    GRAD_SUMS = 2u,    // the walk, k_gradient or k_geometry, into a ws_grad's sums or the target's scratch
+    GRAD_SPREAD = 4u,  // k_sh_spread or k_geom_spread from the scratch into the sums; nothing for a ws_grad
+    GRAD_ALL = 7u,
+};
+
+// What ws_gradient_params and ws_geometry_params say, under one set of names
+struct GradDesc {
+    float background[3] = {0.0f, 0.0f, 0.0f};
+    float scale = 1.0f;
+    float second_scale = 1.0f;  // opacity_scale; geometry_scale for a GRAD_GEOMETRY target
+    const float* d_grad = nullptr;
+    size_t grad_pitch_bytes = 0;
+    float* d_base = nullptr;  // may be null: the renderer's scratch plane
+    size_t base_pitch_bytes = 0;
+};
+
+}  // namespace ws

@@ -534,25 +534,24 @@ void ws_internal_renderer_set_throughput_mode(ws_renderer* r, bool on);
 // ws_scene_evaluate gives back the records of a pass it has to repeat (api_metrics.cpp): the host counter only
 struct ws_metrics;
 void ws_internal_metrics_truncate(ws_metrics* m, uint32_t count);
-// ws_renderer_accumulate_gradient in two steps, for ws_scene_accumulate_gradient, which makes the plane from pass 1's image
-// (api_attrib.cpp): passes = 1: the base image only, nothing is accumulated; 2: k_gradient on a base plane already there; 3: the call
-struct ws_grad;
-struct ws_gradient_params;
-int ws_internal_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_grad* g, const ws_gradient_params* p, void* stream, unsigned passes);
+// One pass of the gradient family over r's prepared frame, for the ABI's entry points and for the scene drivers, which make
+// the plane between two calls from the first one's base image (api_attrib.cpp).  target: which accumulator; desc: the ABI
+// descriptor's content; steps: which launches, GRAD_BASE | GRAD_SUMS | GRAD_SPREAD, the same for every target (all three:
+// gaussian_sums.h).  The descriptor is judged by itself first, then the handles, then the descriptor against the frame.  who: the
+// entry point, for messages; nullptr: the target's own ws_renderer_accumulate_* one.
+namespace ws {
+struct GradTarget;
+struct GradDesc;
+}
+int ws_internal_gradient_passes(const char* who, ws_renderer* r, const ws_pointcloud* pc, const ws::GradTarget& target, const ws::GradDesc& desc,
+                                void* stream, unsigned steps);
 // what ws_refit_step judges from its descriptor alone, for ws_scene_refit, which fills in the two units itself (units = false:
 // they are not looked at) (api_refit.cpp)
 struct ws_refit_params;
 int ws_internal_refit_check_params(const ws_refit_params* p, const std::string& who, bool units);
-// the same two for "SH gradients": ws_renderer_accumulate_sh_gradient in two steps (passes = 2: k_gradient + k_sh_spread), and what
-// ws_refit_step_sh judges from its descriptor alone, for ws_scene_accumulate_sh_gradient and ws_scene_refit_sh (api_attrib.cpp, api_refit.cpp)
-struct ws_shgrad;
+// ... and what ws_refit_step_sh judges from its descriptor alone, for ws_scene_refit_sh
 struct ws_refit_sh_params;
-int ws_internal_sh_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_shgrad* g, const ws_gradient_params* p, void* stream, unsigned passes);
 int ws_internal_refit_check_sh_params(const ws_refit_sh_params* p, const std::string& who, bool units);
-// "Geometry gradients" in steps, for ws_scene_accumulate_geometry_gradient: passes = 1: the base image only; 6: k_geometry and
-// k_geom_spread on a base plane already there; p->opacity_scale holds the geometry_scale (api_attrib.cpp)
-struct ws_geomgrad;
-int ws_internal_geometry_gradient_passes(ws_renderer* r, const ws_pointcloud* pc, ws_geomgrad* g, const ws_gradient_params* p, void* stream, unsigned passes);
 
 // opaque handle definitions -------------------------------------------------------------------------
 // The depth sort of a frame (V keys + store index + footprint word):
