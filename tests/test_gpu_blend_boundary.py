@@ -55,7 +55,7 @@ U8_K = (32, 64, 96, 128)
 # (blend_split = -1) a frame with fewer tiles than twice the CUs -- every frame here -- is composited by two 512-thread workgroups
 # per tile (k_blend<4, 2> on 32 x 16 halves of the tile's list).  So "4x4" pins blend_split = 0, "split" pins 1 (the frames and
 # lists of 4x4), and "auto" is the context's default, used only as the image the settings of e are compared with.  The API does
-# not report which form a launch took (the kernel timers label every form "k_blend"); the pinning follows ws_api.cpp
+# not report which form a launch took (the kernel timers label every form "k_blend"); the pinning follows api_renderer.cpp
 # render_frame / blend_form.h blend_frame_choice.
 CFG = {"4x4": {"blend_split": 0}, "split": {"blend_split": 1}, "auto": {}, "4x2": {"tile_qw": 4, "tile_qh": 2}, "2x2": {"tile_qw": 2, "tile_qh": 2}}
 FRAMES_OF = {"4x4": "4x4", "split": "4x4", "auto": "4x4", "4x2": "4x2", "2x2": "2x2"}  # launch -> the shape whose frames and lists it has

@@ -1,4 +1,4 @@
-"""One renderer through every call that makes it let device memory go or take new memory (ws_api.cpp renderer_ensure_scratch and
+"""One renderer through every call that makes it let device memory go or take new memory (api_renderer.cpp renderer_ensure_scratch and
 the arrays allocated on first use: frame_scratch.h), in turn.  After each step the frame it draws is error-free and byte-equal to
 what a fresh renderer draws for that cloud and viewport: a frame is a pure function of scene and camera
 (test_gpu_render.py test_determinism_and_reuse), so an array that a reallocation left too short, stale or uninitialised shows here.

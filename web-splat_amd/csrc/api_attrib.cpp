@@ -87,7 +87,7 @@ static FrameLists frame_lists(const ws_renderer* r) {
     f.qh = r->ctx->tile_qh;
     f.counters = r->scratch.counters();
     f.sticky = r->sticky.get();
-    f.demand_mailbox = r->demand_mailbox_dev;
+    f.demand_mailbox = r->mailbox.dev();
     return f;
 }
 

@@ -1,8 +1,10 @@
 // api_state.h -- what the translation units of the C ABI share: the renderer with its prepared frame, and how a handle's data is
-// read back and a handle destroyed.  Host only: included by ws_api.cpp (the object model) and by api_attrib.cpp, api_metrics.cpp
-// and api_refit.cpp (the passes that read a prepared frame, and the objects they fill), never by a .hip.
+// read back and a handle destroyed.  Host only: included by the units of the object model (api_pointcloud.cpp, api_renderer.cpp,
+// api_readback.cpp, api_sorter.cpp) and by api_attrib.cpp, api_metrics.cpp and api_refit.cpp (the passes that read a prepared frame,
+// and the objects they fill), never by a .hip.
 #pragma once
 
+#include "frame_graph.h"
 #include "frame_scratch.h"
 #include "ws_internal.h"
 
@@ -32,16 +34,6 @@ struct SyncedDelete {
 
 }  // namespace ws
 
-// Where the prepared frame's arrays are: one value, so that the frame graph's capture and replay cannot forget a member.
-struct FrameArrays {
-    // the depth sort's result: vals = the draw-ordered store indices, aux = their footprint words; the *_skipped members are
-    // where they are when the sort's last pass had nothing to do (FrameCounters::depth_skip_top, decided on the device per
-    // frame), nullptr: this frame's sort cannot skip
-    ws::SortResult depth;
-    uint32_t* entries = nullptr;     // the tile-sorted entry values (store indices)
-    bool blend_order_valid = false;  // the frame wrote FrameScratch::blend_order (it ran k_blend_order)
-};
-
 // The last prepared frame.  Reset as a whole wherever it stops being one: every reader asks `prepared` first.
 struct PreparedFrame {
     bool prepared = false;
@@ -58,7 +50,29 @@ struct PreparedFrame {
     unsigned long long* trace_slot = nullptr;  // the frame's slot of ws_renderer::frame_trace (nullptr: not traced)
 };
 
-struct ws_renderer {
+// FOUR pinned host words the blend posts to, read here without a sync and without a runtime call.  A renderer whose pinned
+// allocation failed has an empty one: every reader below then gives its "no mailbox" answer.
+class __attribute__((visibility("hidden"))) Mailbox {
+public:
+    int create() { return words_.create(4); }
+    bool present() const { return words_.get() != nullptr; }
+    // [0] the largest entries_needed of an overflowed frame (ws_renderer::sticky [1]) -- prepare() reads it, so the automatic
+    // capacity grows without anyone polling (0: none, or no mailbox)
+    uint32_t demand() const { return present() ? word(0) : 0u; }
+    void clear_demand() { word(0) = 0u; }  // present() only
+    // [1] the number of the last frame whose blend has started (present() only: ws_internal_renderer_progress)
+    uint32_t started_seq() const { return word(1); }
+    // [2] FrameCounters::depth_span_class of that frame -> the next frame's digit width (0: none yet, or no mailbox)
+    uint32_t span_class() const { return present() ? word(2) : 0u; }
+    // what the blend is given: the device's address of [0], the progress word behind it (nullptr: no mailbox)
+    uint32_t* dev() const { return words_.dev(); }
+
+private:
+    volatile uint32_t& word(int k) const { return *reinterpret_cast<volatile uint32_t*>(words_.get() + k); }
+    ws::PinnedWords words_;
+};
+
+struct __attribute__((visibility("hidden"))) ws_renderer {  // (its destructor is the renderer's free list: not a dynamic symbol)
     // ---- fixed configuration and switches ----
     ws_context* ctx = nullptr;
     ws_color_format format = WS_FORMAT_RGBA32_FLOAT;
@@ -79,26 +93,8 @@ struct ws_renderer {
     ws::FramePlan plan{};                // of the last prepare(): the scratch is sized by it, the frame's launches are filled from it (frame_plan.h)
     uint32_t epoch = 0;              // look-back epoch of the last frame (lookback.h); 0 with fresh (zeroed) status arrays
     uint64_t scratch_generation = 0;
-    // The frame's launch sequence of prepare() (memset + 21 kernels), captured once per (point cloud, scratch) and replayed:
-    // only K1's arguments change from frame to frame (camera / settings uniforms, epoch).  A ring of executable graphs,
-    // because updating an executable graph's kernel arguments while an earlier launch of it has not run yet would change
-    // that earlier frame: slot i is reused only after the event recorded behind its last launch has completed.
-    static constexpr int GRAPH_RING = 4;
-    struct FrameGraph {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec[GRAPH_RING] = {};
-        hipEvent_t done[GRAPH_RING] = {};
-        bool used[GRAPH_RING] = {};
-        hipGraphNode_t k1_node = nullptr;
-        hipKernelNodeParams k1_params{};
-        const ws_pointcloud* pc = nullptr;
-        uint64_t generation = 0;   // scratch generation the graph was captured for
-        uint32_t next = 0;
-        bool valid = false;
-        FrameArrays arrays;              // of the captured frame
-        int order_mode = 0;              // decide_blend_order() of the captured frame: a change re-captures
-        int depth_bits = 0;              // != 0 while the graph is valid: the digit width its depth sort was captured with
-    } fg;
+    ws::FrameGraph fg;               // the frame's launch sequence of prepare(), captured and replayed (frame_graph.h); dropped by
+                                     //   renderer_free_graph alone (api_renderer.cpp)
 
     // ---- the last prepared frame ----
     PreparedFrame frame;
@@ -109,18 +105,15 @@ struct ws_renderer {
     ws::DeviceBuf<uint32_t> sticky;      // two device words that survive the per-frame memset (ws_renderer_errors): [0] error bits
                                      // of all frames since the last reset, [1] the largest entries_needed of an overflowed frame
     uint32_t needed_seen = 0;        // host copy of [1]: the automatic entry capacity grows to it at the next prepare()
-    uint32_t* demand_mailbox = nullptr;      // FOUR pinned host words the blend posts to (device-visible address: demand_mailbox_dev):
-    uint32_t* demand_mailbox_dev = nullptr;  //   [0] the demand [1] above -- prepare() reads it without a sync, so the capacity grows
-                                             //   without anyone polling; [1] the number of the last frame whose blend has started;
-                                             //   [2] depth_span_class of that frame -> the next frame's digit width
-    uint32_t frames_enqueued = 0;            // render() calls so far (the sequence number the blend posts)
+    Mailbox mailbox;                 // what the blend posts to the host (optional: empty without pinned memory)
+    uint32_t frames_enqueued = 0;    // render() calls so far (the sequence number the blend posts)
 
     // ---- instrumentation ----
     ws::DeviceBuf<unsigned long long> frame_trace;  // [frames][4]: {K1 start, K1 end, blend start, blend end} per frame (ws_renderer_enable_frame_trace)
     uint32_t trace_count = 0;        // slots handed out so far
     bool timers = false;
     ws::KernelMarks marks;               // per-kernel events, timers level 2
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_group[2] = {nullptr, nullptr};  // grouped prepare of a view batch: "arena cleared" / "shared K1 done"
+    ws::Event ev[6];                     // the stage timers (ws_renderer_stage_times), created with the renderer
+    ws::Event ev_group[2];               // grouped prepare of a view batch: "arena cleared" / "shared K1 done"; created there, on first use
     bool ev_prepare_valid = false, ev_render_valid = false;
 };

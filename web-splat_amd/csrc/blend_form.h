@@ -1,6 +1,6 @@
 // blend_form.h -- what one launch of the blend IS: every compile-time choice of k_blend and its sibling kernels by name, the rules
 // that say which combinations exist, and the mapping from a request to its form.  Plain C++ (no HIP include): raster.hip
-// instantiates exactly the legal forms from the table below, ws_api.cpp asks the same predicate, and a CPU test enumerates both.
+// instantiates exactly the legal forms from the table below, api_renderer.cpp asks the same predicate, and a CPU test enumerates both.
 #pragma once
 
 #include <stdint.h>
@@ -110,7 +110,7 @@ constexpr bool blend_production_launch(const BlendLaunchMode& m) {
     return !m.capture && !m.timing && !m.dma && m.variant == 0 && !m.exact_cut && !m.async_staging && !m.debug_cut;
 }
 
-// The renderer's part of the decision (ws_api.cpp render_frame), from its blend mode and the context's switches: which kernel
+// The renderer's part of the decision (api_renderer.cpp render_frame), from its blend mode and the context's switches: which kernel
 // family, whether the exact cut applies, whether 4x4 tiles are composited as two 4x2 halves, whether the order table is used.
 struct BlendFrameRequest {
     bool target_precision, exact_mode;  // WS_BLEND_TARGET_PRECISION, WS_BLEND_FAST_EXACT_CUT (neither: WS_BLEND_FAST)

@@ -612,14 +612,13 @@ int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, 
     const uint32_t W = 2048, H = 2048;  // bin/measure.rs:34
     std::vector<ws_renderer*> rs(frames_in_flight, nullptr);
     std::vector<void*> targets(frames_in_flight, nullptr);
-    std::vector<hipStream_t> streams(frames_in_flight, nullptr);
+    std::vector<Stream> streams(frames_in_flight);  // slot 0 stays empty: the null stream
     int rc = WS_OK;
     for (uint32_t k = 0; k < frames_in_flight && rc == WS_OK; ++k) {
         rc = ws_renderer_create(ctx, WS_FORMAT_RGBA8_UNORM, ws_pointcloud_sh_deg(pc), ws_pointcloud_compressed(pc), &rs[k]);
         if (rc == WS_OK) ws_internal_renderer_set_throughput_mode(rs[k], frames_in_flight > 1);
         if (rc == WS_OK) rc = ws_device_malloc(ctx, (size_t)W * H * 4, &targets[k]);
-        if (rc == WS_OK && k > 0 && hipStreamCreateWithFlags(&streams[k], hipStreamNonBlocking) != hipSuccess)
-            rc = fail(WS_ERR_HIP, "ws_measure: hipStreamCreate failed");
+        if (rc == WS_OK && k > 0 && streams[k].create() != WS_OK) rc = fail(WS_ERR_HIP, "ws_measure: hipStreamCreate failed");
     }
     const float clear[4] = {0, 0, 0, 0};
     // The measurement, at most three times: a run whose frames overflowed the (automatic) tile-entry capacity is not a rate --
@@ -629,15 +628,15 @@ int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, 
         const auto start = std::chrono::steady_clock::now();  // before the warm-up frame (bin/measure.rs:50)
         ws_splatting_args a;
         offline_args(cams[0], pc, W, H, &a);
-        rc = ws_renderer_prepare(rs[0], pc, &a, streams[0]);  // "first render to lazy init sorter stuff"
-        if (rc == WS_OK) rc = ws_renderer_render(rs[0], pc, clear, targets[0], (size_t)W * 4, streams[0]);
+        rc = ws_renderer_prepare(rs[0], pc, &a, streams[0].get());  // "first render to lazy init sorter stuff"
+        if (rc == WS_OK) rc = ws_renderer_render(rs[0], pc, clear, targets[0], (size_t)W * 4, streams[0].get());
         uint32_t f = 0;
         for (uint32_t i = 0; i < n && rc == WS_OK; ++i) {
             offline_args(cams[i], pc, W, H, &a);
             for (uint32_t s = 0; s < num_samples && rc == WS_OK; ++s, ++f) {
                 const uint32_t k = f % frames_in_flight;
-                rc = ws_renderer_prepare(rs[k], pc, &a, streams[k]);
-                if (rc == WS_OK) rc = ws_renderer_render(rs[k], pc, clear, targets[k], (size_t)W * 4, streams[k]);
+                rc = ws_renderer_prepare(rs[k], pc, &a, streams[k].get());
+                if (rc == WS_OK) rc = ws_renderer_render(rs[k], pc, clear, targets[k], (size_t)W * 4, streams[k].get());
             }
         }
         if (rc == WS_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(WS_ERR_HIP, "ws_measure: device sync failed");  // device.poll(Wait)
@@ -661,9 +660,8 @@ int ws_measure(ws_context* ctx, const ws_pointcloud* pc, const ws_scene* scene, 
     for (uint32_t k = 0; k < frames_in_flight; ++k) {
         if (rs[k]) ws_renderer_destroy(rs[k]);
         if (targets[k]) ws_device_free(ctx, targets[k]);
-        if (streams[k]) (void)hipStreamDestroy(streams[k]);
     }
-    return rc;
+    return rc;  // (the streams go here, behind their renderers)
 }
 
 // ---- view batches: several frames in flight ---------------------------------------------------------------------
@@ -700,8 +698,8 @@ struct SlotWindow {
 };
 struct ws_view_batch {
     ws_context* ctx = nullptr;
-    std::vector<ws_renderer*> renderers;
-    std::vector<hipStream_t> streams;
+    std::vector<ws_renderer*> renderers;  // destroyed by ws_view_batch_destroy, in front of ...
+    std::vector<Stream> streams;          // ... their streams, which go with the batch itself (the member's destructor)
     std::vector<SlotWindow> windows;
     uint32_t queue_depth = 5;
     bool threads_disabled = false;  // a host that could not start the submission threads: this batch enqueues from the caller's
@@ -774,8 +772,8 @@ void batch_worker(ws_view_batch* b, size_t slot) {
         for (uint32_t i = 0; i < j.num_views && rc == WS_OK; ++i) {
             if ((j.first + i) % slots != slot) continue;
             rc = slot_window_admit(b, slot);
-            if (rc == WS_OK) rc = ws_renderer_prepare(b->renderers[slot], j.pc, &j.views[i], b->streams[slot]);
-            if (rc == WS_OK) rc = ws_renderer_render(b->renderers[slot], j.pc, j.background, j.targets[i], j.pitch, b->streams[slot]);
+            if (rc == WS_OK) rc = ws_renderer_prepare(b->renderers[slot], j.pc, &j.views[i], b->streams[slot].get());
+            if (rc == WS_OK) rc = ws_renderer_render(b->renderers[slot], j.pc, j.background, j.targets[i], j.pitch, b->streams[slot].get());
         }
         b->workers[slot].rc = rc;
         if (rc) b->workers[slot].err = ws_last_error();  // (the error text is thread-local: hand it to the caller)
@@ -801,18 +799,18 @@ int ws_view_batch_create(ws_context* ctx, ws_color_format format, uint32_t sh_de
         rc = ws_renderer_create(ctx, format, sh_deg, compressed, &r);
         if (rc) break;
         b->renderers.push_back(r);
-        hipStream_t s = nullptr;
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+        Stream s;
+        if (s.create() != WS_OK) {
             rc = fail(WS_ERR_HIP, "ws_view_batch_create: hipStreamCreate failed");
             break;
         }
-        b->streams.push_back(s);
+        b->streams.push_back(std::move(s));
     }
     if (rc == WS_OK) {
         if (ctx->batch_queue_depth >= 0) b->queue_depth = (uint32_t)ctx->batch_queue_depth;
         if (b->queue_depth > 64u) b->queue_depth = 64u;
         b->windows.resize(b->renderers.size());
-        // several frames in flight: the slots' blends keep the image order of their workgroups (ws_api.cpp)
+        // several frames in flight: the slots' blends keep the image order of their workgroups (api_renderer.cpp)
         for (ws_renderer* r : b->renderers) ws_internal_renderer_set_throughput_mode(r, b->renderers.size() > 1);
     }
     if (rc != WS_OK) {
@@ -834,8 +832,7 @@ void ws_view_batch_destroy(ws_view_batch* b) {
         if (w.th.joinable()) w.th.join();
     (void)hipDeviceSynchronize();
     for (ws_renderer* r : b->renderers) ws_renderer_destroy(r);
-    for (hipStream_t s : b->streams) (void)hipStreamDestroy(s);
-    delete b;
+    delete b;  // (the streams, behind their renderers)
 }
 
 uint32_t ws_view_batch_frames_in_flight(const ws_view_batch* b) { return b ? (uint32_t)b->renderers.size() : 0u; }
@@ -905,7 +902,7 @@ int ws_view_batch_render(ws_view_batch* b, const ws_pointcloud* pc, const ws_spl
             hipStream_t ss[K1_MAX_VIEWS];
             for (size_t j = 0; j < group; ++j) {
                 rs[j] = b->renderers[k + j];
-                ss[j] = b->streams[k + j];
+                ss[j] = b->streams[k + j].get();
             }
             int rc = WS_OK;
             for (size_t j = 0; j < group && rc == WS_OK; ++j) rc = slot_window_admit(b, k + j);
@@ -927,8 +924,8 @@ int ws_view_batch_render(ws_view_batch* b, const ws_pointcloud* pc, const ws_spl
         // a ragged head (the ring is not at a group boundary) or tail, or no grouping: frame by frame
         // a target that an earlier frame of this call still writes must be on the same slot (same stream: ordered)
         int rc = slot_window_admit(b, k);
-        if (rc == WS_OK) rc = ws_renderer_prepare(b->renderers[k], pc, &views[i], b->streams[k]);
-        if (rc == WS_OK) rc = ws_renderer_render(b->renderers[k], pc, background, d_targets[i], row_pitch_bytes, b->streams[k]);
+        if (rc == WS_OK) rc = ws_renderer_prepare(b->renderers[k], pc, &views[i], b->streams[k].get());
+        if (rc == WS_OK) rc = ws_renderer_render(b->renderers[k], pc, background, d_targets[i], row_pitch_bytes, b->streams[k].get());
         if (rc) return rc;
         ++b->next;
         ++i;
@@ -938,7 +935,7 @@ int ws_view_batch_render(ws_view_batch* b, const ws_pointcloud* pc, const ws_spl
 
 int ws_view_batch_sync(ws_view_batch* b) {
     if (!b) return fail(WS_ERR_INVALID, "ws_view_batch_sync: null batch");
-    for (hipStream_t s : b->streams) WS_HIP(hipStreamSynchronize(s));
+    for (const Stream& s : b->streams) WS_HIP(hipStreamSynchronize(s.get()));
     return WS_OK;
 }
 

@@ -1,7 +1,7 @@
 // frame_plan.h -- how one frame is laid out and which launch sequence it gets: the tile grid, the footprint form, the entry
 // capacity, the tile-id sort's shape, the depth sort's digit width, the blend's order table and split.  Every rule is a pure
 // function of the context's switches, the point count, the viewport and the capacity request, stated ONCE here.  Plain C++ (no
-// HIP include): ws_api.cpp asks frame_plan() once per prepare(), sizes the scratch by it (frame_scratch.h), fills the kernels'
+// HIP include): api_renderer.cpp asks frame_plan() once per prepare(), sizes the scratch by it (frame_scratch.h), fills the kernels'
 // parameter blocks and the sort jobs from the one answer; a CPU test (tests/test_frame_plan.py) enumerates it at every boundary.
 #pragma once
 

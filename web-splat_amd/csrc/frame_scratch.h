@@ -1,7 +1,7 @@
 // frame_scratch.h -- a renderer's per-frame device memory: how large every array is (scratch_layout, a pure function of the
 // frame's plan, in the style of frame_plan.h) and the one object that owns them (FrameScratch).  A new per-frame array is one
 // line in scratch_layout, one member and one alloc line below.  What the arrays are initialised with, and the syncs around a
-// reallocation, stay with the caller (ws_api.cpp renderer_ensure_scratch).  Host code; tests/test_scratch_layout.py enumerates
+// reallocation, stay with the caller (api_renderer.cpp renderer_ensure_scratch).  Host code; tests/test_scratch_layout.py enumerates
 // the layout against the sizes the call sites used to spell out, tests/test_frame_scratch.py runs the ownership on the CPU.
 #pragma once
 

@@ -11,6 +11,7 @@
 #include "blend_form.h"
 #include "device_buf.h"
 #include "frame_plan.h"
+#include "hip_handles.h"
 #include "websplat.h"
 
 #if defined(_OPENMP) && !defined(__HIP_DEVICE_COMPILE__)
@@ -120,7 +121,7 @@ struct FrameCounters {
     uint32_t depth_key_base; // written with it: passes 1..3 take their digits from (key - depth_key_base) (depth_range_decide)
     uint32_t depth_span_class; // written with them: 0 = no key reported, 1 = the frame's keys span < 2^24 above their 256-aligned minimum (three
                                // 8-bit passes sort them), 2 = they do not (three 9-bit passes do, below 2^27).  The blend posts it to the host:
-                               // the NEXT frame of the renderer picks its digit width by it (ws_api.cpp; either width gives the same order)
+                               // the NEXT frame of the renderer picks its digit width by it (api_renderer.cpp; either width gives the same order)
     uint32_t _pad[12];
     // --- the frame's footprint totals, summed by K1: TILE_SUM_SLOTS x {sum at the blend's tile size, sum at twice that
     // size}, one 64-B line per slot.  Workgroup b adds its partial sums to slot b % 16 with two returnless atomics; all
@@ -255,16 +256,15 @@ constexpr int PC_PLANES = 8;
 // ---- per-launch GPU timestamps (the reference's GPUStopwatch, utils.rs:26-134, at kernel granularity) --------
 // HIP events recorded on the launch stream between the kernels of one frame; only when the caller asked for
 // per-kernel times (ws_renderer_enable_timers(r, 2)): the events themselves perturb a throughput run.
-struct KernelMarks {
+struct __attribute__((visibility("hidden"))) KernelMarks {  // (it holds owners, hip_handles.h: between the library's units)
     static constexpr int MAX = 48;
-    hipEvent_t ev[MAX + 1] = {};
+    Event ev[MAX + 1];
     const char* label[MAX] = {};
     int n = 0;
     bool created = false;
     bool active = false;
     hipStream_t stream = nullptr;
-    int create();
-    void destroy();
+    int create();  // idempotent
     void begin(hipStream_t s, bool restart);
     void mark(const char* what);
 };
@@ -516,20 +516,20 @@ float host_f16_to_f32(uint16_t h);
 
 }  // namespace ws
 
-// grouped prepare of a view batch (ws_api.cpp): K1 once for up to K1_MAX_VIEWS renderers / views of one scene
+// grouped prepare of a view batch (api_renderer.cpp): K1 once for up to K1_MAX_VIEWS renderers / views of one scene
 struct ws_renderer;
 struct ws_pointcloud;
 int ws_internal_prepare_group(ws_renderer* const* rs, uint32_t n, const ws_pointcloud* pc, const ws_splatting_args* views,
                               hipStream_t const* streams);
 // the largest tile-entry demand an overflowed frame of this renderer has left so far (0 = none), as last seen by
-// ws_renderer_errors or a prepare() (ws_api.cpp)
+// ws_renderer_errors or a prepare() (api_renderer.cpp)
 uint32_t ws_internal_renderer_demand(const ws_renderer* r);
 // Frames this renderer has enqueued (render() calls) and the number of the last one whose compositing kernel has STARTED on
 // the device (posted by that kernel to pinned host memory: reading it costs a load, no runtime call).  A view batch keeps a
 // slot's host side at most queue_depth frames ahead of it.  renderer_progress returns false when the renderer has no mailbox.
 uint32_t ws_internal_renderer_frames_enqueued(const ws_renderer* r);
 bool ws_internal_renderer_progress(const ws_renderer* r, uint32_t* started_seq);
-// a renderer that runs beside others (a slot of a view batch with several frames in flight): see ws_api.cpp `throughput_mode`
+// a renderer that runs beside others (a slot of a view batch with several frames in flight): see api_renderer.cpp `throughput_mode`
 void ws_internal_renderer_set_throughput_mode(ws_renderer* r, bool on);
 // ws_scene_evaluate gives back the records of a pass it has to repeat (api_metrics.cpp): the host counter only
 struct ws_metrics;
@@ -595,7 +595,7 @@ struct ws_context {
     int depth_tile_kpt = 0;        // ws_context_config::depth_tile_kpt (9-bit digits, A/B): 0 = by input size, 4 / 8 keys per thread
     // Is this context drawing on several streams in turn (a hand-rolled pipeline of renderers with frames in flight), or one
     // frame at a time?  The stream of the latest prepare() and how many consecutive prepare() calls used that same stream;
-    // read by the automatic choice of the blend's workgroup order (ws_api.cpp).  Relaxed atomics: renderers of one context
+    // read by the automatic choice of the blend's workgroup order (api_renderer.cpp).  Relaxed atomics: renderers of one context
     // may be driven from several host threads (the submission threads of a view batch).
     std::atomic<void*> last_prepare_stream{nullptr};
     std::atomic<uint32_t> same_stream_run{0};
